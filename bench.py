@@ -7,6 +7,13 @@ rollup-shaped circuit with 73 public inputs (BASELINE.json configs[1]); witnesse
 HBM when the timed region starts.  N>1: the key is generated on rank 0 and broadcast over RCCL, each
 rank proves its own K witnesses (weak scaling, no data-path collective).  Prints ONE JSON line.
 
+A plain run does only what the headline needs: set-up, W warm-up steps, K timed steps, the result line (metric, value,
+unit, higher_is_better, dtype, ms_per_step = milliseconds of one timed step).  --full adds everything else the line has
+carried: stage profile and roofline, sampled clock and power, the native check of every timed proof, the calling-pattern
+boundary, the CPU baselines, the replication, sharding, other-size and other-circuit legs (the --no-* options trim it).
+--dump-outputs DIR writes the proofs of the last timed step as DIR/pi_a.npy, pi_b.npy, pi_c.npy (dump_outputs); the
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
+
 Other forms (same JSON shape):  --gpus N --inproc [--devices 0,0]   N devices from ONE process through zkr_key_replicate +
 zkr_prove_batch_multi_device (no torch.distributed: the shape of the reference's Node host);  --shards P   (default 8; 0 skips) is the
 intra-proof sharding leg (one proof cut into P shards, each timed alone: projected one-shard-per-GPU latency);
@@ -1048,6 +1055,26 @@ def public_signals_of(wit_tensor):
     return [int.from_bytes(head[32 * j:32 * j + 32], "little") for j in range(1, N_PUBLIC + 1)]
 
 
+def dump_outputs(dirname, proofs):
+    """--dump-outputs: the proofs of the last timed step as the caller receives them (zkr_prove's 256 bytes: pi_a (x, y) |
+    pi_b (x.re, x.im, y.re, y.im) | pi_c (x, y), 32 bytes per coordinate), one byte per float32 element:
+    pi_a.npy and pi_c.npy (proofs, 2, 32), pi_b.npy (proofs, 4, 32)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    b = np.frombuffer(b"".join(proofs), dtype=np.uint8).reshape(len(proofs), 8, 32).astype(np.float32)
+    for name, rows in (("pi_a", slice(0, 2)), ("pi_b", slice(2, 6)), ("pi_c", slice(6, 8))):
+        np.save(os.path.join(dirname, name + ".npy"), b[:, rows])
+
+
+def result_head(args, value, elapsed, n_gpus, info):
+    """The keys every line starts with, plain or --full: the headline figure and the workload it was measured on."""
+    return {"metric": "Groth16 proofs/sec (rollup batch circuit)", "value": value, "unit": "proofs/s", "n_gpus": n_gpus,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": DTYPE, "data": "synthetic",
+            "config": {"workload": "2^%d-constraint synthetic %s, 1 proof per step per GPU" % (args.log_m, "rollup circuit" if args.shape == "rollup" else "dense random R1CS"),
+                       "log_m": args.log_m, "n_public": N_PUBLIC, "nVars": info["nVars"], "nnzA": info["nnzA"], "nnzB": info["nnzB"]}}
+
+
 def inproc_main(args):
     """`python bench.py --gpus N --inproc`: the same measurement from ONE process without torch.distributed -- the form the
     reference's Node host takes (operator/src/snarks/common.ts:23-29 awaits its proofs from one process): the key is made on
@@ -1068,8 +1095,8 @@ def inproc_main(args):
     rehearsal = len(set(devices)) < len(devices)
     zkr_hip.synth_set_shape(1 if args.shape == "dense" else 0)
     t_setup = time.time()
-    key0, w0, aux = zkr_hip.ProvingKey.synth(args.log_m, N_PUBLIC, CIRCUIT_SEED, TOXIC_SEED, device=devices[0], want_aux=True)
-    vk_bin = key0.synth_vk(aux)
+    key0, w0, aux = zkr_hip.ProvingKey.synth(args.log_m, N_PUBLIC, CIRCUIT_SEED, TOXIC_SEED, device=devices[0], want_aux=args.full)
+    vk_bin = key0.synth_vk(aux) if args.full else None
     del aux
     info = key0.info()
     arena_bytes = key0.arena()[1]
@@ -1098,9 +1125,10 @@ def inproc_main(args):
                                                 [1000003 + st * n + j for st, j in idx], [2000003 + st * n + j for st, j in idx])
 
     run(0, args.warmup)
-    keys[0].prof_enable(True)
-    keys[0].prof_reset()
-    sampler = GpuSampler(devices[0]).start()
+    if args.full:
+        keys[0].prof_enable(True)
+        keys[0].prof_reset()
+    sampler = GpuSampler(devices[0]).start() if args.full else None
     for d in set(devices):
         torch.cuda.synchronize(d)
     t0 = time.perf_counter()
@@ -1108,30 +1136,31 @@ def inproc_main(args):
     for d in set(devices):
         torch.cuda.synchronize(d)
     elapsed = time.perf_counter() - t0
-    device_state = sampler.stop()
+    device_state = sampler.stop() if sampler else None
+    assert len(proofs) == args.steps * n
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, proofs[-n:])
+    out = result_head(args, len(proofs) / elapsed, elapsed, n, info)
+    out["config"].update({"parallelism": "proof-sharded x%d from ONE process (zkr_prove_batch_multi_device: one host thread per device; key copied device to device, zkr_key_replicate)%s"
+                                         % (n, "; REHEARSAL: devices %s repeat one GPU" % devices if rehearsal else ""),
+                          "devices": devices, "proofs_in_flight": 2})
+    if not args.full:
+        print(json.dumps(out))
+        return
     prof = keys[0].prof()
     keys[0].prof_enable(False)
-    assert len(proofs) == args.steps * n
     pubs = [[public_signals_of(w) for w in row] for row in wits]
     verify_ms = verify_timed_proofs(vk_bin, proofs, lambda q: pubs[q % n][(q // n) % n_wit])
     # per device: its share of the steps over the whole region (the shares run concurrently and end together)
     roofline, whole = roofline_record(keys[0], info, prof, elapsed / args.steps, device_state, args.log_m, args.shape, devices[0])
-    out = {
-        "metric": "Groth16 proofs/sec (rollup batch circuit)", "value": len(proofs) / elapsed, "unit": "proofs/s", "n_gpus": n,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": DTYPE, "data": "synthetic",
-        "config": {"workload": "2^%d-constraint synthetic %s, 1 proof per step per GPU" % (args.log_m, "rollup circuit" if args.shape == "rollup" else "dense random R1CS"),
-                   "log_m": args.log_m, "n_public": N_PUBLIC, "nVars": info["nVars"], "nnzA": info["nnzA"], "nnzB": info["nnzB"],
-                   "parallelism": "proof-sharded x%d from ONE process (zkr_prove_batch_multi_device: one host thread per device; key copied device to device, zkr_key_replicate)%s"
-                                  % (n, "; REHEARSAL: devices %s repeat one GPU" % devices if rehearsal else ""),
-                   "devices": devices, "proofs_in_flight": 2},
+    out.update({
         "roofline": roofline,
         "stage_ms_per_proof": {k: (v[0] / args.steps) for k, v in prof.items()},
         "key": {"arena_bytes": arena_bytes, "setup_s": setup_s, "replication": "peer-copy (zkr_key_replicate, mode %s)" % args.replicate_mode,
                 "replicas": repl, "xgmi_link_GBps": 153.0},
         "proofs_verified": len(proofs), "verify_ms_per_proof_host": verify_ms,
         "device_state_during_timed_region": device_state, "hbm_whole_proof": whole,
-    }
+    })
     modes = [k.replication() for k in keys[1:]]
     out["key"]["replica_modes"] = modes
     out["config"].update({"key_replication": "peer-copy: " + (",".join(sorted(set("%s%s" % (m["mode"], "" if m["peer_direct"] else " (staged through the host)") for m in modes))) or "none"),
@@ -1173,7 +1202,11 @@ def main():
     ap.add_argument("--no-2-22", action="store_true", help="skip the BASELINE configs[2] leg (one 2^22 key, 6 timed proofs; about 20 s)")
     ap.add_argument("--with-2-24-dense", action="store_true", help="add the BASELINE configs[4] leg (2^24 dense random R1CS: setup about 150 s)")
     ap.add_argument("--no-withdraw", action="store_true", help="skip the withdraw-circuit leg (withdraw.ts:6-10)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure (see the module docstring); the --no-* / --with-* / --shards options select within it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the proofs of the last timed step to DIR/pi_a.npy, pi_b.npy, pi_c.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py needs --steps >= 1 and --warmup >= 0")
 
     if args.inproc:
         return inproc_main(args)
@@ -1225,8 +1258,8 @@ def main():
     w0 = None
     synth = lambda want_aux: zkr_hip.ProvingKey.synth(args.log_m, N_PUBLIC, CIRCUIT_SEED, TOXIC_SEED, device=local, want_aux=want_aux)
     if rank == 0:
-        key, w0, aux = synth(True)
-        vk_bin = key.synth_vk(aux)  # for the native acceptance check after the timed region
+        key, w0, aux = synth(args.full)
+        vk_bin = key.synth_vk(aux) if args.full else None  # for the native acceptance check after the timed region
         del aux
     t_bcast = time.time()
     # fallback ("replicas only"): every rank derives the key from the seeds itself -- in production: from the
@@ -1259,9 +1292,10 @@ def main():
         return key.prove_batch_device([wits[i % n_wit].data_ptr() for i in idx], [1000003 + i for i in idx], [2000003 + i for i in idx], stream)
 
     run(0, args.warmup)
-    key.prof_enable(True)
-    key.prof_reset()
-    sampler = GpuSampler(local).start() if rank == 0 else None
+    if args.full:
+        key.prof_enable(True)
+        key.prof_reset()
+    sampler = GpuSampler(local).start() if rank == 0 and args.full else None
     barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -1279,6 +1313,21 @@ def main():
         parts = [None] * world
         dist.all_gather_object(parts, per_rank[0], group=side)  # outside the timed region: what every rank did, for the SCALE record
         per_rank = parts
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, proofs[-1:])
+    parallelism = "proof-sharded x%d (key arena replicated once: %s)" % (world, "RCCL broadcast" if replication == "nccl" else
+                                                                        replication + (", rehearsal on one GPU" if one_gpu else ""))
+    if not args.full:
+        if rank == 0:
+            out = result_head(args, sum(p["proofs"] for p in per_rank) / elapsed, elapsed, world, info)
+            out["config"].update({"parallelism": parallelism, "proofs_in_flight": 1 if args.no_pipeline else 2})
+            if world > 1:
+                out["per_rank"] = per_rank
+            print(json.dumps(out))
+        if dist:
+            barrier()
+            dist.destroy_process_group()
+        return
     prof = key.prof()
     key.prof_enable(False)
 
@@ -1336,16 +1385,11 @@ def main():
         value = total_proofs / elapsed
         roofline, whole = roofline_record(key, info, prof, elapsed / args.steps, device_state, args.log_m, args.shape, local)
         per_proof_ms = {k: (v[0] / args.steps) for k, v in prof.items()}
-        out = {
-            "metric": "Groth16 proofs/sec (rollup batch circuit)", "value": value, "unit": "proofs/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": DTYPE, "data": "synthetic",
-            "config": {"workload": "2^%d-constraint synthetic %s, 1 proof per step per GPU" % (args.log_m, "rollup circuit" if args.shape == "rollup" else "dense random R1CS"),
-                       "log_m": args.log_m, "n_public": N_PUBLIC, "nVars": info["nVars"], "nnzA": info["nnzA"], "nnzB": info["nnzB"],
-                       "parallelism": "proof-sharded x%d (key arena replicated once: %s)" % (world, "RCCL broadcast" if replication == "nccl" else
-                                      replication + (", rehearsal on one GPU" if one_gpu else "")),
-                       "proofs_in_flight": 1 if args.no_pipeline else 2,
-                       "boundary": boundary},
+        out = result_head(args, value, elapsed, world, info)
+        out["config"].update({"parallelism": parallelism,
+                              "proofs_in_flight": 1 if args.no_pipeline else 2,
+                              "boundary": boundary})
+        out.update({
             "roofline": roofline,
             "stage_ms_per_proof": per_proof_ms,
             "per_rank": per_rank,
@@ -1362,7 +1406,7 @@ def main():
             "proofs_verified": verified, "verify_ms_per_proof_host": verify_ms,
             "device_state_during_timed_region": device_state,
             "hbm_whole_proof": whole,
-        }
+        })
         if world == 1 and not args.no_cpu_baseline:  # before the key goes: the GPU proof of the CPU leg's witness is compared with the CPU proofs
             cpu_lm = args.cpu_sample_log_m if args.cpu_sample_log_m is not None else min(args.log_m, 20)
             out["cpu_baseline"] = cpu_baseline(cpu_lm, args.log_m, gpu_key=key if args.shape == "rollup" else None)

@@ -134,3 +134,17 @@ def test_round_6_default_line_carries_ratios_counters_and_denominators():
     for k in ("sync_latency_ms", "host_buffer_sync_proofs_per_s", "rate_2_22_proofs_per_s", "tx_single_proof_ms", "tx_fused_proofs_per_s", "withdraw_single_proof_ms", "sharded_ms"):
         assert isinstance(cfg.get(k), float), k
     assert d["metric"].startswith("Groth16 proofs/sec") and d["unit"] == "proofs/s" and d["dtype"] and d["vs_baseline"] is None and d["scaling"] == "weak"
+
+
+def test_dump_outputs_writes_the_last_steps_proof_bytes(tmp_path):
+    """--dump-outputs: pi_a / pi_b / pi_c of every proof of the last step as float32 arrays, one byte per element, that put
+    back together are the 256 bytes the caller received."""
+    import numpy as np
+    b = _bench()
+    proofs = [bytes((7 * i + j) % 256 for i in range(256)) for j in range(2)]
+    b.dump_outputs(str(tmp_path / "out"), proofs)
+    arrs = {n: np.load(tmp_path / "out" / (n + ".npy")) for n in ("pi_a", "pi_b", "pi_c")}
+    assert {n: a.shape for n, a in arrs.items()} == {"pi_a": (2, 2, 32), "pi_b": (2, 4, 32), "pi_c": (2, 2, 32)}
+    assert all(a.dtype == np.float32 for a in arrs.values())
+    back = np.concatenate([arrs["pi_a"], arrs["pi_b"], arrs["pi_c"]], axis=1).astype(np.uint8)
+    assert [bytes(p.reshape(-1)) for p in back] == proofs

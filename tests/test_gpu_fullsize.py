@@ -337,7 +337,7 @@ def test_bench_two_rank_path_rehearsal_on_one_gpu(launcher):
             sk.bind(("127.0.0.1", 0))
             port = sk.getsockname()[1]
         cmd += ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port)]
-    r = subprocess.run(cmd + [os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "1", "--log-m", "14"],
+    r = subprocess.run(cmd + [os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "1", "--log-m", "14", "--full"],
                        capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -369,7 +369,7 @@ def test_bench_two_rank_rehearsal_survives_a_failed_broadcast():
     env = dict(os.environ, ZKR_BENCH_BACKEND="gloo", ZKR_BENCH_ONE_GPU="1", ZKR_FORCE_BCAST_FAIL="1")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--log-m", "13"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--log-m", "13", "--full"],
                        capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
@@ -390,7 +390,7 @@ def test_bench_inproc_multi_device_rehearsal_on_one_gpu(mode):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--inproc", "--devices", "0,0", "--replicate-mode", mode,
-                        "--steps", "5", "--warmup", "1", "--log-m", "14"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
+                        "--steps", "5", "--warmup", "1", "--log-m", "14", "--full"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -434,3 +434,36 @@ def test_multi_gpu_preflight_rehearsal_on_one_gpu():
     assert run["parts"] == 2 and run["identical_to_whole_key"] and run["verifies"] and run["form"] == "split"
     assert rows["summary"]["ok"] is True and rows["summary"]["rehearsal"] is True
     assert "key_replication_would_use" in rows["summary"]     # rccl or the per-rank fallback: either way a diagnosis
+
+
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """`python bench.py --gpus 1` without --full: only the headline line, and --dump-outputs writes the proof of the last
+    timed step -- the same bytes in two runs of the same arguments, and the proof this key, witness and blinding give."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import numpy as np
+    import zkr_hip
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    lines, dumps = [], []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--log-m", "12",
+                            "--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, timeout=600, env=env, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(out) == 1
+        lines.append(json.loads(out[0]))
+        dumps.append({n: np.load(tmp_path / run / (n + ".npy")) for n in ("pi_a", "pi_b", "pi_c")})
+    d = lines[0]
+    assert d["steps"] == 3 and d["n_gpus"] == 1 and d["unit"] == "proofs/s" and d["higher_is_better"] is True and d["dtype"]
+    assert abs(d["value"] - 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]                 # one proof per step
+    assert not {"roofline", "cpu_baseline", "stage_ms_per_proof", "proofs_verified"} & set(d)    # those are --full
+    for n in ("pi_a", "pi_b", "pi_c"):
+        assert dumps[0][n].dtype == np.float32 and np.array_equal(dumps[0][n], dumps[1][n])
+    # the last timed step is step 2: witness 2 of the run's three, blinding 1000003 + 2 / 2000003 + 2
+    key, _, _ = zkr_hip.ProvingKey.synth(12, 73, 0x5A4B0001, 0x5A4B00FF, want_aux=False)
+    proof = key.prove(zkr_hip.synth_witness(12, 73, 0x5A4B0001, 0x5A4B0001 + 2), 1000003 + 2, 2000003 + 2)
+    got = np.concatenate([dumps[0]["pi_a"], dumps[0]["pi_b"], dumps[0]["pi_c"]], axis=1).astype(np.uint8)
+    assert got.shape == (1, 8, 32) and bytes(got.reshape(-1)) == proof

@@ -9,7 +9,7 @@ LIGHT="--no-cpu-baseline --no-js-baseline --no-tx-circuit --no-bcast-modes --no-
 run() { # name, env...
   local name=$1; shift
   ( for kv in "$@"; do export "$kv"; done
-    python3 bench.py --steps 40 --warmup 5 $LIGHT 2>/dev/null | python3 -c "
+    python3 bench.py --full --steps 40 --warmup 5 $LIGHT 2>/dev/null | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read()); b=d['config']
 print('%-14s %.2f proofs/s  %.3f ms  sync %.2f ms  hostbuf %.1f/s  sclk %s  acc_g1 launch %.1f us' % ('$name', d['value'], d['ms_per_step'], b.get('sync_latency_ms') or 0, b.get('host_buffer_sync_proofs_per_s') or 0, d['device_state_during_timed_region']['sclk_mhz_mean'], 1e3 * d['roofline']['avg_launch_ms']))" ) | tee -a $O/ab_merged_launch.txt
 }

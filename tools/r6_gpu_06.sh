@@ -7,7 +7,7 @@ O=gpurun_out/r6_06; mkdir -p $O
 LIGHT="--no-cpu-baseline --no-js-baseline --no-tx-circuit --no-bcast-modes --no-2-22 --no-withdraw --shards 0"
 for v in r5 cur nopin oldloop nopin_oldloop; do
   ( [ $v != cur ] && export ZKR_HIP_LIB=$PWD/tools/bin/libzkr_hip_$v.so; export ZKR_EXP_MERGE=0 ZKR_SERIAL=1
-    rocprofv3 --kernel-trace --stats -d $O/s_$v -- python3 bench.py --steps 4 --warmup 1 --no-pipeline $LIGHT > /dev/null 2>$O/s_$v.err )
+    rocprofv3 --kernel-trace --stats -d $O/s_$v -- python3 bench.py --full --steps 4 --warmup 1 --no-pipeline $LIGHT > /dev/null 2>$O/s_$v.err )
   python3 profiles/summarize_rocpd.py $(find $O/s_$v -name "*.db" | head -1) 0 > $O/serial_$v.md; rm -rf $O/s_$v
   echo "== $v"; grep -E 'msm_accum_kernel|msm_reduce1' $O/serial_$v.md | awk -F'|' '{printf "%-60s calls %s avg us %s\n", substr($2,1,60), $3, $5}'
 done | tee $O/isolated_accum.txt
