@@ -65,6 +65,32 @@ int zkr_key_info(const zkr_key *key, uint64_t out[10]);
 int zkr_key_save(const zkr_key *key, const char *path);
 int zkr_key_load_file(const char *path, int device, zkr_key **out);
 
+/* What a device key's arena CONTAINS, not only its header.  level 0: structure (every index a kernel follows stays
+ * inside its section); level 1: level 0 + values (points on their curves at every window level, twiddles, canonical
+ * coefficients, shared rank maps, header constants).  report (may be null): [0] faulty entries found, [1] section
+ * (ZKR_KEYSEC_*), [2] QAP side or table, [3] smallest faulty index.  ZKR_OK, or ZKR_ERR_BAD_KEY with zkr_last_error
+ * "key check: <section> <side/table>: <count> bad, first at <index>".
+ * Sections, in the order a fault is reported (the first faulty one; structure before values), with what [2] and [3] count:
+ *   ROWPTR  CSR row pointers of QAP side [2] (0 = A, 1 = B): row_ptr[0] == 0, non-decreasing, row_ptr[m] == nnz; index = row
+ *   COL     column indices of side [2] below nVars; index = term
+ *   WIDE    the list of rows wider than the one-thread row kernel takes: strictly increasing, below m, exactly the wide
+ *           rows; index = position in the list, or the row for a wide row the list lacks
+ *   RANK    rank map of table [2] (0..4 = A, B1, B2, C, H): every entry below the table's point count or "none"; index = scalar
+ *   HEADER  a table [2] flagged as identity-ranked whose point count ([3]) differs from its scalar count
+ *   POINTS  a stored point of table [2] (any window level) off its curve or not canonical; index = stored point
+ *   TWIDDLES [2] = 0: the m-entry table, 1: the local table; an entry differs from the powers of the root; index = entry
+ *   COEF    a QAP coefficient of side [2] not below r; index = term
+ *   SHARED RANK  the rank map of table [2] is not the identity its header claims, or differs from the map of the table it
+ *           shares a digit sort with (B2 with B1, C with A); index = scalar
+ *   CONSTS  [2] = 0..4: alfa1, beta1, delta1 (on G1), beta2, delta2 (on the twist and in G2)
+ * Level 0 runs by itself on every arena that comes from outside the process: zkr_key_load_file, zkr_key_adopt_arena,
+ * zkr_key_adopt_base_arena (and so zkr_key_replicate and zkr_key_shard) refuse an arena that fails it with ZKR_ERR_BAD_KEY. */
+enum {
+  ZKR_KEYSEC_NONE = 0, ZKR_KEYSEC_ROWPTR = 1, ZKR_KEYSEC_COL = 2, ZKR_KEYSEC_WIDE = 3, ZKR_KEYSEC_RANK = 4, ZKR_KEYSEC_HEADER = 5,
+  ZKR_KEYSEC_POINTS = 6, ZKR_KEYSEC_TWIDDLES = 7, ZKR_KEYSEC_COEF = 8, ZKR_KEYSEC_SHARED_RANK = 9, ZKR_KEYSEC_CONSTS = 10
+};
+int zkr_key_check(const zkr_key *key, int level, uint64_t report[4]);
+
 /* MSM geometry of the device key: window bits c and window count K = ceil(255/c) of the A,B1,B2,C,H tables.  Each
  * table holds K levels per base point (2^(ck) P), so an MSM costs K mixed additions per point. */
 int zkr_key_windows(const zkr_key *key, uint32_t c_out[5], uint32_t k_out[5]);

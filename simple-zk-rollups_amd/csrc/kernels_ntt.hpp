@@ -304,16 +304,21 @@ static __global__ void twiddle261_kernel(const Fr *T, uint32_t n, Tw29 *out) {
   for (int i = 0; i < 9; i++) out[k].v[i] = l.v[i];
 }
 
-// T[k] = g^k (Montgomery), k < n, g given in Montgomery form: thread k does square-and-multiply
-static __global__ void twiddle_table_kernel(Fr *T, uint32_t n, Fr g) {
-  uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= n) return;
+// g^k (Montgomery) by square-and-multiply: entry k of a twiddle table, as the table build and the key check
+// (zkr_key_check.hip) compute it
+static __device__ Fr twiddle_pow(Fr g, uint32_t k) {
   Fr r = Fr::one(), b = g;
   for (uint32_t e = k; e; e >>= 1) {
     if (e & 1) r = mul(r, b);
     b = sqr(b);
   }
-  store_fr(T + k, r);
+  return r;
+}
+// T[k] = g^k (Montgomery), k < n, g given in Montgomery form: thread k does square-and-multiply
+static __global__ void twiddle_table_kernel(Fr *T, uint32_t n, Fr g) {
+  uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  store_fr(T + k, twiddle_pow(g, k));
 }
 
 // witness ingest: reduce every 256-bit word below r (values from calculateWitness already are; this

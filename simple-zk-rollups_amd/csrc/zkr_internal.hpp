@@ -238,6 +238,8 @@ int fused_capacity(const ArenaHeader &h, const MsmPlan plan[N_TABLES]);
 void arena_layout(ArenaHeader &h);  // section offsets and total_len from the sizes in the header (n, p, m, nnz, n_wide, npts, win_c, sc_n): THE layout, whoever builds an arena
 const char *arena_header_fault(const ArenaHeader &h, size_t len);  // null when a full arena's header is consistent with its sizes
 void base_layout(const ArenaHeader &full, ArenaHeader &b);  // the same for the compact form (zkr_key_base_arena)
+// zkr_key_check.hip: what an arena whose header passed arena_header_fault CONTAINS (zkr_key_check; level 0 structure, 1 values)
+int key_arena_check(int device, const unsigned char *arena, const ArenaHeader &h, int level, uint64_t report[4]);
 MsmPlan msm_plan(size_t n_scalars, size_t n_points, int c_fixed = 0);
 uint32_t big_threshold(size_t n_points, int K, uint32_t nbw, int nbat);  // occupancy above which a bucket goes to msm_big_kernel (zkr_key.hip)
 int digit_lists_alloc(DigitLists &dl, size_t n_scalars, const MsmPlan &pl);

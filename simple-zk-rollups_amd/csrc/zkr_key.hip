@@ -135,8 +135,10 @@ void arena_layout(ArenaHeader &h) {
   h.total_len = off;
 }
 
-// A full arena's header against the layout its own sizes imply (arena_layout is the only producer): a damaged file or a foreign
-// buffer must be refused here, not found by a kernel reading past a section.  Null when consistent, else what is wrong.
+// A full arena's header against the layout its own sizes imply (arena_layout is the only producer): null when consistent, else
+// what is wrong.  The sections' CONTENTS -- every index a kernel follows (row pointers, columns, wide rows, rank maps) -- are
+// checked next, on the device, by key_arena_check (zkr_key_check.hip) before a loaded or adopted arena becomes a key: a damaged
+// file or a foreign buffer is refused there, not found by a kernel reading past a section.
 const char *arena_header_fault(const ArenaHeader &h, size_t len) {
   if (h.magic != ARENA_MAGIC) return "not a packed zkr key of this version (magic)";
   if (h.total_len != len) return "header total length differs from the bytes handed over";
@@ -157,17 +159,6 @@ const char *arena_header_fault(const ArenaHeader &h, size_t len) {
     same = same && want.off_rowptr[s] == h.off_rowptr[s] && want.off_col[s] == h.off_col[s] && want.off_coef[s] == h.off_coef[s] && want.off_wide[s] == h.off_wide[s];
   for (int t = 0; t < N_TABLES; t++) same = same && want.off_pts[t] == h.off_pts[t] && want.off_rank[t] == h.off_rank[t];
   return same ? nullptr : "section offsets differ from the layout the sizes imply";
-}
-
-// ... and the one size the layout rounds away: the CSR row pointers of both QAP sides end at the header's term counts
-static int arena_rows_check(const unsigned char *arena, const ArenaHeader &h) {
-  for (int s = 0; s < 2; s++) {
-    uint32_t last = 0;
-    ZKR_HIP_CHECK(hipMemcpy(&last, arena + h.off_rowptr[s] + (size_t)h.m * 4, 4, hipMemcpyDeviceToHost));
-    const uint32_t nnz = s == 0 ? h.nnzA : h.nnzB;
-    if (last != nnz) { set_error("arena: QAP side %d has %u terms by its row pointers, %u by the header", s, last, nnz); return ZKR_ERR_BAD_KEY; }
-  }
-  return 0;
 }
 
 // cap: proofs a fused batch can hold (cap bucket sets end to end; kernels_msm.hpp msm_digits_count_kernel)
@@ -773,7 +764,7 @@ int zkr_key_adopt_arena(void *dev_ptr, size_t len, int device, zkr_key **out) {
   if (len < ARENA_HEADER_BYTES) { set_error("arena too small"); return ZKR_ERR_BAD_KEY; }
   ZKR_HIP_CHECK(hipMemcpy(&h, dev_ptr, sizeof(h), hipMemcpyDeviceToHost));
   if (const char *fault = arena_header_fault(h, len)) { set_error("arena header: %s", fault); return ZKR_ERR_BAD_KEY; }
-  if (int rc = arena_rows_check((const unsigned char *)dev_ptr, h)) return rc;
+  if (int rc = key_arena_check(device, (const unsigned char *)dev_ptr, h, 0, nullptr)) return rc;
   zkr_key *k = new zkr_key();
   k->device = device;
   k->arena = (unsigned char *)dev_ptr;
@@ -909,6 +900,8 @@ int zkr_key_adopt_base_arena(const void *dev_ptr, size_t len, int device, zkr_ke
     if (e == hipSuccess) e = cp(h.off_rank[t], b.off_rank[t], (size_t)rank_entries(h, t) * 4);
   }
   if (e != hipSuccess) { hipFree(arena); set_error("unpacking the compact arena failed: %s", hipGetErrorString(e)); return ZKR_ERR_HIP; }
+  // the unpacked rows and rank maps before anything is built from them (the window levels and twiddles are rebuilt below)
+  if (int crc = key_arena_check(device, arena, h, 0, nullptr)) { hipFree(arena); return crc; }
   for (int t = 0; t < N_TABLES; t++) {
     int rc = msm_precompute(device, t == T_B2, arena + h.off_pts[t], h.npts[t], plan[t]);
     if (rc) { hipFree(arena); return rc; }
@@ -982,7 +975,7 @@ int zkr_key_load_file(const char *path, int device, zkr_key **out) {
   }
   fclose(f);
   if (stage) hipHostFree(stage);
-  if (!rc) rc = arena_rows_check(arena, h);
+  if (!rc) rc = key_arena_check(device, arena, h, 0, nullptr);
   if (rc) { hipFree(arena); return rc; }
   zkr_key *k = new zkr_key();
   k->device = device;

@@ -25,6 +25,10 @@ export interface Bn128 {
   setupR1cs(r1csBin: Uint8Array, opts?: { toxic?: Array<bigint | string> }): any;
   saveKey(path: string): void;
   loadKeyFile(path: string): void;
+  /** What the held key's arena contains (zkr_key_check): every index the kernels follow stays inside its section; with
+   *  { deep: true } also the values (points on their curves at every window level, twiddles, coefficients, shared rank maps,
+   *  header constants).  Returns the clean report (all zero); throws the library's message naming the first faulty section. */
+  checkKey(opts?: { deep?: boolean }): { bad: number; section: number; part: number; first: number };
   /** Proof with the key currently held on the device. */
   prove(witnessBin: ArrayBuffer | Uint8Array, opts?: ProveOptions): Promise<Groth16Proof>;
   keyInfo(): { nVars: number; nPublic: number; domainSize: number; nnzA: number; nnzB: number } | null;

@@ -271,6 +271,13 @@ class Bn128 {
   }
   saveKey(path) { if (!this._key) throw new Error("no key loaded"); native().keySave(this._key, path); }
   loadKeyFile(path) { this._key = native().keyLoadFile(path, this.device); this._fp = "file:" + path; }
+  // what the held key's arena contains (zkr_key_check): the structure, and with { deep: true } the values as well (every point of
+  // every window level, twiddles, coefficients, shared rank maps, header constants); throws the library's message when damaged
+  checkKey(opts) {
+    if (!this._key) throw new Error("no key loaded");
+    const v = native().keyCheck(this._key, opts && opts.deep ? 1 : 0);
+    return { bad: v[0], section: v[1], part: v[2], first: v[3] };
+  }
   // proof with the key currently held (after setup / loadKeyFile / a groth16GenProof call)
   async prove(witnessBin, opts) {
     if (!this._key) throw new Error("no key loaded");

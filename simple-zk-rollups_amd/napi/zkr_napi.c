@@ -33,6 +33,7 @@ static struct {
   int (*setup_r1cs)(const void *, size_t, const uint8_t *, int, zkr_key **, void **, size_t *);
   int (*key_save)(const zkr_key *, const char *);
   int (*key_load_file)(const char *, int, zkr_key **);
+  int (*key_check)(const zkr_key *, int, uint64_t *);
   void (*free_)(void *);
   int (*multihash)(const uint8_t *, size_t, uint8_t *);
   int (*pubkey)(const uint8_t *, uint8_t *);
@@ -88,7 +89,7 @@ static napi_value js_load(napi_env env, napi_callback_info info) {
   if (!Z.field) return throw_msg(env, "libzkr_hip.so lacks symbol " name);
     SYM(last_error, "zkr_last_error") SYM(version, "zkr_version") SYM(device_count, "zkr_device_count")
     SYM(key_load_websnark, "zkr_key_load_websnark") SYM(key_free, "zkr_key_free") SYM(key_info, "zkr_key_info") SYM(prove, "zkr_prove") SYM(prove_batch, "zkr_prove_batch") SYM(prove_batch_multi, "zkr_prove_batch_multi") SYM(key_replicate, "zkr_key_replicate") SYM(key_shard, "zkr_key_shard") SYM(prove_sharded, "zkr_prove_sharded") SYM(key_device, "zkr_key_device") SYM(verify, "zkr_verify") SYM(verify_batch, "zkr_verify_batch")
-    SYM(setup_r1cs, "zkr_setup_r1cs") SYM(key_save, "zkr_key_save") SYM(key_load_file, "zkr_key_load_file") SYM(free_, "zkr_free")
+    SYM(setup_r1cs, "zkr_setup_r1cs") SYM(key_save, "zkr_key_save") SYM(key_load_file, "zkr_key_load_file") SYM(key_check, "zkr_key_check") SYM(free_, "zkr_free")
     SYM(multihash, "zkr_mimcsponge_multihash") SYM(pubkey, "zkr_babyjub_pubkey") SYM(eddsa_sign, "zkr_eddsa_sign") SYM(eddsa_verify, "zkr_eddsa_verify")
     SYM(multihash_batch, "zkr_mimcsponge_multihash_batch") SYM(tree_build, "zkr_balance_tree_build")
     SYM(format_privkey, "zkr_babyjub_format_privkey") SYM(withdraw_r1cs, "zkr_withdraw_r1cs") SYM(withdraw_witness, "zkr_withdraw_witness")
@@ -254,6 +255,28 @@ static napi_value js_key_load_file(napi_env env, napi_callback_info info) {
   napi_value ext;
   NAPI_OK(napi_create_external(env, key, key_finalize, NULL, &ext));
   return ext;
+}
+
+/* keyCheck(key, level): what the key's arena contains (zkr_key_check) -> [bad, section, part, first] (all 0 for a clean key);
+ * a damaged key throws the library's message */
+static napi_value js_key_check(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  zkr_key *key;
+  int32_t level = 0;
+  NAPI_OK(napi_get_value_external(env, argv[0], (void **)&key));
+  if (argc > 1) napi_get_value_int32(env, argv[1], &level);
+  uint64_t v[4];
+  if (Z.key_check(key, level, v)) return throw_msg(env, Z.last_error());
+  napi_value arr;
+  NAPI_OK(napi_create_array_with_length(env, 4, &arr));
+  for (uint32_t i = 0; i < 4; i++) {
+    napi_value x;
+    NAPI_OK(napi_create_double(env, (double)v[i], &x));
+    NAPI_OK(napi_set_element(env, arr, i, x));
+  }
+  return arr;
 }
 
 static napi_value js_key_info(napi_env env, napi_callback_info info) {
@@ -743,6 +766,7 @@ static napi_value init(napi_env env, napi_value exports) {
       {"keyReplicate", NULL, js_key_replicate, NULL, NULL, NULL, napi_default, NULL}, {"keyDevice", NULL, js_key_device, NULL, NULL, NULL, napi_default, NULL},
       {"setupR1cs", NULL, js_setup_r1cs, NULL, NULL, NULL, napi_default, NULL}, {"keySave", NULL, js_key_save, NULL, NULL, NULL, napi_default, NULL},
       {"keyLoadFile", NULL, js_key_load_file, NULL, NULL, NULL, napi_default, NULL},
+      {"keyCheck", NULL, js_key_check, NULL, NULL, NULL, napi_default, NULL},
       {"rollupCrypto", NULL, js_rollup_crypto, NULL, NULL, NULL, napi_default, NULL}, {"rollupCircuit", NULL, js_rollup_circuit, NULL, NULL, NULL, napi_default, NULL},
       {"withdrawCircuit", NULL, js_withdraw_circuit, NULL, NULL, NULL, napi_default, NULL},
       {"rollupGpuHash", NULL, js_rollup_gpu_hash, NULL, NULL, NULL, napi_default, NULL},

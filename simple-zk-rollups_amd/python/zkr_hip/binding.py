@@ -7,6 +7,7 @@ LIB_PATH = os.environ.get("ZKR_HIP_LIB") or os.path.normpath(os.path.join(_HERE,
 PROOF_BYTES = 256
 PARTIAL_BYTES = 640   # zkr.h ZKR_PARTIAL_BYTES
 REPLICATE_MODES = {"auto": 0, "full": 1, "base": 2}   # zkr.h ZKR_REPLICATE_*
+KEY_SECTIONS = ("none", "rowptr", "col", "wide", "rank", "header", "points", "twiddles", "coef", "shared rank", "consts")   # zkr.h ZKR_KEYSEC_*
 STAGES = ("ingest", "spmv", "ntt", "msm_sort", "msm_accum_g1", "msm_accum_g2", "msm_big", "msm_reduce", "total",
           "spmv_a", "ntt_pass", "combine_h")   # the last three: single streaming kernels (bench.py roofline.streaming)
 _lib = None
@@ -47,6 +48,7 @@ def lib():
     L.zkr_key_adopt_arena.argtypes = [vp, sz, i, c.POINTER(vp)]
     L.zkr_key_base_arena.argtypes = [vp, c.POINTER(vp), c.POINTER(sz)]
     L.zkr_key_adopt_base_arena.argtypes = [vp, sz, i, c.POINTER(vp)]
+    L.zkr_key_check.argtypes = [vp, i, c.POINTER(c.c_uint64)]
     L.zkr_key_replicate.argtypes = [vp, i, i, c.POINTER(vp)]
     L.zkr_key_device.argtypes = [vp]
     L.zkr_key_replication.argtypes = [vp, c.POINTER(i), c.POINTER(i)]
@@ -190,6 +192,15 @@ class ProvingKey:
         h = ctypes.c_void_p()
         _check(lib().zkr_key_load_file(os.fsencode(path), device, ctypes.byref(h)))
         return cls(h, device)
+
+    def check(self, level=0):
+        """What the key's arena contains (zkr_key_check): level 0 the structure (every index a kernel follows stays inside its
+        section), level 1 also the values (points on their curves at every window level, twiddles, coefficients below r, shared
+        rank maps, header constants).  A clean key returns the report {"bad": 0, "section": "none", "part": 0, "first": 0};
+        a damaged one raises ZkrError (code -2) naming the first faulty section."""
+        rep = (ctypes.c_uint64 * 4)()
+        _check(lib().zkr_key_check(self._h, level, rep))
+        return {"bad": int(rep[0]), "section": KEY_SECTIONS[rep[1]], "part": int(rep[2]), "first": int(rep[3])}
 
     def save(self, path):
         _check(lib().zkr_key_save(self._h, os.fsencode(path)))
