@@ -120,6 +120,17 @@ struct MsmPlan {
 // two tables whose bucket sets ONE reduction launch set can walk end to end (msm_reduce*_kernel take `batch` sets of one geometry)
 inline bool same_reduce_geometry(const MsmPlan &a, const MsmPlan &b) { return a.c == b.c && a.K == b.K && a.nbw == b.nbw && a.nb == b.nb && a.glog == b.glog && a.S == b.S; }
 
+// How the five tables of a key's proofs share digit sorts, bucket sets and reduction chains.  It depends on the key alone: worked
+// out once from the header and the plans (zkr_key.hip proof_layout) and read by every proof (zkr_prove.hip).
+struct ProofLayout {
+  bool share_b = false, share_ac = false;  // B2 accumulates over B1's sort (same signals), C over A's (one support)
+  int sort_src[N_TABLES] = {T_A, T_B1, T_B2, T_C, T_H};  // the table whose sort each table's accumulation reads
+  bool joint_ab = false;  // A is accumulated behind B1's bucket sets and reduced with them in one chain: B1's workspace holds both
+                          // results, B1's first
+  bool merge_ch = false;  // H is accumulated onto C's bucket set and reduced with it: C's workspace holds C + H
+  size_t sets[N_TABLES] = {1, 1, 1, 1, 1};  // bucket sets (with their reduction buffers) per proof in each table's workspace
+};
+
 }  // namespace zkr
 
 namespace zkr {
@@ -143,16 +154,13 @@ struct ProofSlot {
   DigitLists dig_w, dig_h;  // digit records of w (shared by A, B1, B2, C) and of h
   MsmWorkspace ws[N_TABLES];
   hipEvent_t ev_w = nullptr, ev_h = nullptr;
-  hipEvent_t ev_red[N_TABLES] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // end of the proof's work on each reduction stream
+  hipEvent_t ev_end[3] = {nullptr, nullptr, nullptr};  // end of the proof's work on the G2-chain, G1-chain and auxiliary streams
   hipEvent_t ev_done[N_TABLES] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   hipEvent_t ev_sorted[N_TABLES] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   hipEvent_t ev_res[N_TABLES] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // the table's result point has landed in its pinned host buffer
   bool res_pending[N_TABLES] = {false, false, false, false, false};
   int cap = 1;    // proofs one submit can fuse into shared launches (small circuits; every buffer above is cap times one proof's)
   int nbat = 0;   // proofs of the group in flight
-  bool merged_ch = false;  // this group's H was accumulated onto C's bucket set: C's workspace holds C + H
-  bool joint_ab = false;   // this group's A was accumulated behind B1's bucket sets and reduced with them in one chain: B1's workspace holds
-                           // the results of both, B1's first (zkr_prove.hip prove_submit_enqueue)
   std::vector<uint8_t> rb, sb;  // blinding scalars of the proofs in flight, cap x 32 B each
   bool busy = false, collecting = false;
   std::vector<ProfSpan> spans;
@@ -169,18 +177,16 @@ struct zkr_key {
   unsigned char *base_arena = nullptr;  // compact form for replication (zkr_key_base_arena), built on first request
   size_t base_arena_len = 0;
   zkr::ArenaHeader h;
-  hipStream_t stream = nullptr;
+  hipStream_t stream = nullptr;                    // the bucket accumulations
   zkr::WitnessStage stage[zkr::STAGE_BUFS];
   std::mutex stage_mu;
   std::condition_variable stage_freed;
   hipStream_t prep_stream = nullptr;               // digit records, digit sorts, calcH
-  hipStream_t red_stream[zkr::N_TABLES] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // reduction chains: [0] the G2 table, the G1 tables
-                                                                                           // round-robin over [1..n_red)
-  void *streams_owner = nullptr;                   // the DeviceStreams set (zkr_key.hip) the stream handles below come from
+  hipStream_t g2_stream = nullptr;                 // oversized buckets and reduction chain of the G2 table
+  hipStream_t g1_stream = nullptr;                 // those of the G1 tables, one after the other
+  hipStream_t aux_stream = nullptr;                // C's oversized-bucket partial sums in a lone proof of a small circuit, a shard's witness-side sorts
+  void *streams_owner = nullptr;                   // the DeviceStreams set (zkr_key.hip) the stream handles above come from
   std::mutex *enqueue_mu = nullptr;                // the device's enqueue lock (shared streams: one proof's launches are enqueued without interleaving)
-  hipStream_t aux_stream = nullptr;                // = red_stream[n_all - 1]: C's oversized-bucket partial sums when C shares H's bucket set (zkr_prove.hip c_big)
-  int n_red = 1;                                   // streams the reduction chains rotate over
-  int n_all = 1;                                   // streams in red_stream[] (n_red + the auxiliary one)
   zkr::ProofSlot slot[zkr::PROOF_SLOTS];
   int next_slot = 0;
   std::mutex mu;  // slot hand-out, the enqueue phase of a proof (so two host threads do not interleave launches), stage totals
@@ -193,6 +199,7 @@ struct zkr_key {
   bool replica_direct = false;  // ... and whether the two devices could address each other
   std::condition_variable slot_freed;
   zkr::MsmPlan plan[zkr::N_TABLES];
+  zkr::ProofLayout layout;
   // proof assembly on the host: 4-bit window tables of delta_1 / delta_2 (built on first use)
   zkr::Tw29 *tw29 = nullptr, *twl29 = nullptr;  // butterfly twiddles, derived from the arena's tables when the key is set up (not part of the arena)
   std::once_flag delta_once;
@@ -204,6 +211,10 @@ struct zkr_key {
 };
 
 namespace zkr {
+// every stream a proof of this key runs on idle (the streams are the device's: other keys' work on them is waited for too)
+inline void key_streams_sync(zkr_key *k) {
+  for (hipStream_t s : {k->stream, k->prep_stream, k->g2_stream, k->g1_stream, k->aux_stream}) (void)hipStreamSynchronize(s);
+}
 // zkr_key.hip
 int key_build(int device, uint32_t n, uint32_t p, uint32_t m, const std::vector<uint32_t> rowptr[2], const std::vector<uint32_t> col[2],
               const std::vector<uint8_t> coef[2], const void *const tbl_src[N_TABLES], const bool tbl_src_on_device[N_TABLES],
@@ -237,6 +248,7 @@ extern thread_local bool shard_turn_held;  // the caller of this thread's zkr_pr
 int fused_capacity(const ArenaHeader &h, const MsmPlan plan[N_TABLES]);
 void arena_layout(ArenaHeader &h);  // section offsets and total_len from the sizes in the header (n, p, m, nnz, n_wide, npts, win_c, sc_n): THE layout, whoever builds an arena
 const char *arena_header_fault(const ArenaHeader &h, size_t len);  // null when a full arena's header is consistent with its sizes
+const char *window_fault(const ArenaHeader &h);  // null when the header's windows are ones the proof path can run with
 void base_layout(const ArenaHeader &full, ArenaHeader &b);  // the same for the compact form (zkr_key_base_arena)
 // zkr_key_check.hip: what an arena whose header passed arena_header_fault CONTAINS (zkr_key_check; level 0 structure, 1 values)
 int key_arena_check(int device, const unsigned char *arena, const ArenaHeader &h, int level, uint64_t report[4]);

@@ -135,6 +135,17 @@ void arena_layout(ArenaHeader &h) {
   h.total_len = off;
 }
 
+// Window bits of every table in 2..26, and ONE window for the four tables over the witness: its digit records are made once, with
+// A's plan, and read by the sorts of B1, B2 and C with their own plans (zkr_prove.hip prove_submit_enqueue).  Keys built here always
+// have it (msm_plan picks c from the scalar count, which the four share); a header that breaks it can still have a valid layout.
+const char *window_fault(const ArenaHeader &h) {
+  for (int t = 0; t < N_TABLES; t++)
+    if (h.win_c[t] < 2 || h.win_c[t] > 26) return "bad window size";
+  for (int t : {T_B1, T_B2, T_C})
+    if (h.win_c[t] != h.win_c[T_A]) return "the tables A, B1, B2 and C share the witness's digit records but have different windows";
+  return nullptr;
+}
+
 // A full arena's header against the layout its own sizes imply (arena_layout is the only producer): null when consistent, else
 // what is wrong.  The sections' CONTENTS -- every index a kernel follows (row pointers, columns, wide rows, rank maps) -- are
 // checked next, on the device, by key_arena_check (zkr_key_check.hip) before a loaded or adopted arena becomes a key: a damaged
@@ -148,10 +159,9 @@ const char *arena_header_fault(const ArenaHeader &h, size_t len) {
   if (h.shard_parts == 1 && (h.sc_lo[0] || h.sc_lo[1] || h.sc_n[0] != h.n || h.sc_n[1] != h.m)) return "a whole key whose scalar ranges are not the whole vectors";
   for (int s = 0; s < 2; s++)
     if (h.n_wide[s] > h.m) return "more wide rows than rows";
-  for (int t = 0; t < N_TABLES; t++) {
-    if (h.win_c[t] < 2 || h.win_c[t] > 26) return "bad window size";
+  if (const char *fault = window_fault(h)) return fault;
+  for (int t = 0; t < N_TABLES; t++)
     if (h.npts[t] > rank_entries(h, t)) return "more points than scalars in a table";
-  }
   ArenaHeader want = h;
   arena_layout(want);
   bool same = want.total_len == h.total_len && want.off_tw == h.off_tw && want.off_twl == h.off_twl;
@@ -162,8 +172,6 @@ const char *arena_header_fault(const ArenaHeader &h, size_t len) {
 }
 
 // cap: proofs a fused batch can hold (cap bucket sets end to end; kernels_msm.hpp msm_digits_count_kernel)
-// sets: bucket sets (with their reduction buffers) the workspace holds per proof -- 2 for B1, whose chain also reduces A's buckets
-// (prove_submit_enqueue joint_ab)
 // sets: bucket sets (and reduction buffers) per proof -- 2 in B1's workspace when A is accumulated behind B1's sets and reduced with
 // them in one chain, 0 in A's own workspace then: it keeps only what its sort and its oversized buckets need
 static int alloc_msm_ws(MsmWorkspace &ws, size_t n, const MsmPlan &pl, size_t xyzz_bytes, size_t cap = 1, size_t sets = 1) {
@@ -176,7 +184,7 @@ static int alloc_msm_ws(MsmWorkspace &ws, size_t n, const MsmPlan &pl, size_t xy
   ZKR_HIP_CHECK(hipMalloc(&ws.entries, (n * pl.K * cap + 1) * 4));
   ZKR_HIP_CHECK(hipMalloc(&ws.big_list, BIG_CAP * 4));
   ZKR_HIP_CHECK(hipMalloc(&ws.big_count, 16));  // [0] oversized buckets, [1] total entries, [2] tile ticket (kernels_msm.hpp SortScratch)
-  ZKR_HIP_CHECK(hipMalloc(&ws.block_sums, (nb / SCAN_BLOCK + 2) * 8));  // one 64-bit look-back word per scan tile (msm_scan_fused_kernel)
+  ZKR_HIP_CHECK(hipMalloc(&ws.block_sums, (nb / SCAN_BLOCK + 2) * 8));  // the scan tiles' sums (msm_scan_sums_kernel, msm_scan_top_kernel)
   ZKR_HIP_CHECK(hipMalloc(&ws.big_partials, (size_t)BIG_CAP * BIG_SPLIT * xyzz_bytes));
   if (sets) {
     ZKR_HIP_CHECK(hipMalloc(&ws.buckets, nb * sets * xyzz_bytes));
@@ -236,27 +244,49 @@ void msm_ws_free(MsmWorkspace &ws) {
 // and the shared streams cannot wait for each other in a circle.
 namespace {
 struct DeviceStreams {
-  hipStream_t accum = nullptr, prep = nullptr, aux = nullptr, red[N_TABLES] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  hipStream_t accum = nullptr, prep = nullptr, g2 = nullptr, g1 = nullptr, aux = nullptr;  // zkr_internal.hpp zkr_key: the roles
   std::mutex enqueue_mu;
 };
 std::mutex g_streams_mu;
 std::map<int, DeviceStreams *> g_streams;  // never freed: the streams live as long as the process
 }  // namespace
 
-static int make_streams(DeviceStreams &ds, int n_red) {
+static int make_streams(DeviceStreams &ds) {
   // The accumulation stream is the bulk; preparation and reduction chains are short dependent launches whose
   // delay stalls it (the next sort, the proof's completion), so their workgroups are dispatched first.
   int prio_lo = 0, prio_hi = 0;
   ZKR_HIP_CHECK(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));  // numerically lower = higher priority
   if (!ds.accum) ZKR_HIP_CHECK(hipStreamCreateWithPriority(&ds.accum, hipStreamNonBlocking, prio_lo));
   if (!ds.prep) ZKR_HIP_CHECK(hipStreamCreateWithPriority(&ds.prep, hipStreamNonBlocking, prio_hi));
-  for (int j = 0; j < n_red; j++)
-    if (!ds.red[j]) ZKR_HIP_CHECK(hipStreamCreateWithPriority(&ds.red[j], hipStreamNonBlocking, prio_hi));
+  if (!ds.g2) ZKR_HIP_CHECK(hipStreamCreateWithPriority(&ds.g2, hipStreamNonBlocking, prio_hi));
+  if (!ds.g1) ZKR_HIP_CHECK(hipStreamCreateWithPriority(&ds.g1, hipStreamNonBlocking, prio_hi));
   // one more for C's oversized-bucket sums in a lone proof of a small circuit, and for a shard's witness-side sorts.  At the MIDDLE priority: a fifth
   // high-priority stream made the next one created -- the witness builder's (rollup_gpu.hip) -- share a hardware queue with the
   // preparation stream: its 28 ms kernel then stalled every proof behind it (facade pipeline 623 against 840 batches/s, tools/ab_hw_queues2.sh)
   if (!ds.aux) ZKR_HIP_CHECK(hipStreamCreateWithPriority(&ds.aux, hipStreamNonBlocking, (prio_lo + prio_hi) / 2));
   return 0;
+}
+
+static ProofLayout proof_layout(const ArenaHeader &h, const MsmPlan plan[N_TABLES]) {
+  ProofLayout L;
+  L.share_b = h.share_b != 0 && h.npts[T_B1] == h.npts[T_B2];
+  L.share_ac = h.share_ac != 0 && h.npts[T_A] == h.npts[T_C];  // A and C laid out over one support
+  L.sort_src[T_B2] = L.share_b ? T_B1 : T_B2;
+  L.sort_src[T_C] = L.share_ac ? T_A : T_C;
+  // A and B1 in ONE reduction chain (round 5): the G1 chains share one stream, and in a single proof of a small circuit that stream
+  // is the critical path from B1's accumulation to the end (three chains of ~0.4 ms back to back: H's chain starts 0.19 ms after H's
+  // accumulation has ended, profiles/r4_05_timeline_one_tx_proof.txt).  A is accumulated into the bucket sets BEHIND B1's (B1's
+  // workspace holds two sets per proof when the two tables' geometry agrees, A's none) and one launch set reduces both: a chain of
+  // latency-bound launches less per proof.
+  L.joint_ab = h.npts[T_A] && h.npts[T_B1] && same_reduce_geometry(plan[T_A], plan[T_B1]);
+  if (L.joint_ab) { L.sets[T_A] = 0; L.sets[T_B1] = 2; }
+  // C and H are only ever needed as C + H (App. B step 4: pi_c): when their bucket geometry agrees, H is accumulated ONTO
+  // C's bucket set and one reduction chain serves both -- a bucket reduction (2 x 2^19 full additions, ~1.6 % of a proof's
+  // instructions) and one latency chain less.  Oversized buckets of either table are ADDED to the shared set after H's
+  // accumulation (C's accumulation clears their slots), so no accumulation waits for a reduction stream.
+  const MsmPlan &pc = plan[T_C], &ph = plan[T_H];
+  L.merge_ch = h.npts[T_C] && h.npts[T_H] && pc.c == ph.c && pc.nbw == ph.nbw && pc.glog == ph.glog && pc.S == ph.S;
+  return L;
 }
 
 int key_alloc_workspace(zkr_key *k) {
@@ -266,14 +296,14 @@ int key_alloc_workspace(zkr_key *k) {
   // reduction streams: the chains of one proof add up to ~6 ms of serialised launches, so on a single in-order
   // stream they, not the accumulations, set the pace with two proofs in flight (94 vs 106 proofs/s with two)
   for (int t = 0; t < N_TABLES; t++) k->plan[t] = msm_plan(rank_entries(h, t), h.npts[t], (int)h.win_c[t]);
-  // Two reduction streams: the G2 chain on [0], the G1 chains one after the other on [1].  Round 2 ran circuits that fill the
+  k->layout = proof_layout(h, k->plan);
+  // Two reduction streams: the G2 chain on one, the G1 chains one after the other on the other.  Round 2 ran circuits that fill the
   // chip alone with three (136.3 against 132.1 proofs/s at 2^20); since C and H share one chain and the G2 reductions take a
   // whole SIMD's registers, the third stream only adds contention for the accumulations: 152.5-153.5 against 145.9-146.6
   // proofs/s at 2^20 (three same-box rounds), 38.5 against 37.4 at 2^22, a synchronous 2^20 proof 7.75 against 8.0 ms; one
   // stream: 122 (tools/sweep_knobs2.sh).  Keys whose proofs are fused into shared launches always ran with two (fewer, fatter
   // chains: 2^16 1745 against 1680, 2^17 943 against 910, 2^18 514 against 492, 2^19 237 against 231, the tx circuit 988
   // against 957 proofs/s).
-  k->n_red = 2;
   {
     DeviceStreams *ds = nullptr;
     {
@@ -285,16 +315,15 @@ int key_alloc_workspace(zkr_key *k) {
     int src = 0;
     {
       std::lock_guard<std::mutex> lk(g_streams_mu);  // creation of missing streams of a shared set, one key at a time
-      src = make_streams(*ds, k->n_red);
+      src = make_streams(*ds);
     }
     if (src) return src;
     k->streams_owner = ds;
     k->enqueue_mu = &ds->enqueue_mu;
     k->stream = ds->accum;
     k->prep_stream = ds->prep;
-    for (int j = 0; j < k->n_red; j++) k->red_stream[j] = ds->red[j];
-    k->red_stream[k->n_red] = ds->aux;  // an entry of red_stream behind the chains' streams
-    k->n_all = k->n_red + 1;
+    k->g2_stream = ds->g2;
+    k->g1_stream = ds->g1;
     k->aux_stream = ds->aux;
   }
   {
@@ -313,14 +342,12 @@ int key_alloc_workspace(zkr_key *k) {
     }
     ZKR_HIP_CHECK(hipEventCreateWithFlags(&sl.ev_w, hipEventDisableTiming));
     ZKR_HIP_CHECK(hipEventCreateWithFlags(&sl.ev_h, hipEventDisableTiming));
-    for (int j = 0; j < k->n_all; j++) ZKR_HIP_CHECK(hipEventCreateWithFlags(&sl.ev_red[j], hipEventDisableTiming));
+    for (hipEvent_t &e : sl.ev_end) ZKR_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     ZKR_HIP_CHECK(hipMalloc(&sl.d_w, (size_t)h.n * 32 * cap));
     Fr **vecs[5] = {&sl.va, &sl.vb, &sl.ca, &sl.cb, &sl.d_h};
     for (auto v : vecs) ZKR_HIP_CHECK(hipMalloc(v, (size_t)h.m * 32 * cap));
     for (int t = 0; t < N_TABLES; t++) {
-      const bool joint_ab = h.npts[T_A] && h.npts[T_B1] && same_reduce_geometry(k->plan[T_A], k->plan[T_B1]);  // A reduced with B1 (zkr_prove.hip)
-      const size_t sets = joint_ab ? (t == T_B1 ? 2 : t == T_A ? 0 : 1) : 1;
-      int rc = alloc_msm_ws(sl.ws[t], h.npts[t], k->plan[t], t == T_B2 ? sizeof(G2XYZZ) : sizeof(G1XYZZ), cap, sets);
+      int rc = alloc_msm_ws(sl.ws[t], h.npts[t], k->plan[t], t == T_B2 ? sizeof(G2XYZZ) : sizeof(G1XYZZ), cap, k->layout.sets[t]);
       if (rc) return rc;
     }
     int rc = digit_lists_alloc(sl.dig_w, (size_t)h.sc_n[0] * cap, k->plan[T_A]);
@@ -700,7 +727,7 @@ void zkr_key_free(zkr_key *k) {
   // the streams are the device's (one set per device, shared by its keys): wait for THIS key's work only -- the last events of its
   // proof slots and staged uploads (an event that was never recorded is complete) -- not for the proofs other keys have in flight
   for (ProofSlot &sl : k->slot) {
-    for (auto e : sl.ev_red)
+    for (auto e : sl.ev_end)
       if (e) hipEventSynchronize(e);
     for (int t = 0; t < N_TABLES; t++)
       if (sl.ev_res[t]) hipEventSynchronize(sl.ev_res[t]);
@@ -716,7 +743,7 @@ void zkr_key_free(zkr_key *k) {
     }
     if (sl.ev_w) hipEventDestroy(sl.ev_w);
     if (sl.ev_h) hipEventDestroy(sl.ev_h);
-    for (auto e : sl.ev_red)
+    for (auto e : sl.ev_end)
       if (e) hipEventDestroy(e);
     digit_lists_free(sl.dig_w); digit_lists_free(sl.dig_h);
     hipFree(sl.d_w); hipFree(sl.va); hipFree(sl.vb); hipFree(sl.ca); hipFree(sl.cb); hipFree(sl.d_h);
@@ -858,11 +885,9 @@ int zkr_key_adopt_base_arena(const void *dev_ptr, size_t len, int device, zkr_ke
   // the full layout, exactly as key_build lays it out
   ArenaHeader h = b;
   h.magic = ARENA_MAGIC;
+  if (const char *fault = window_fault(h)) { set_error("compact arena: %s", fault); return ZKR_ERR_BAD_KEY; }
   MsmPlan plan[N_TABLES];
-  for (int t = 0; t < N_TABLES; t++) {
-    if (h.win_c[t] < 2 || h.win_c[t] > 26) { set_error("compact arena: bad window size"); return ZKR_ERR_BAD_KEY; }
-    plan[t] = msm_plan(rank_entries(h, t), h.npts[t], (int)h.win_c[t]);
-  }
+  for (int t = 0; t < N_TABLES; t++) plan[t] = msm_plan(rank_entries(h, t), h.npts[t], (int)h.win_c[t]);
   if (h.sc_n[0] > h.n || h.sc_lo[0] > h.n - h.sc_n[0] || h.sc_n[1] > h.m || h.sc_lo[1] > h.m - h.sc_n[1]) { set_error("compact arena: scalar ranges outside the vectors"); return ZKR_ERR_BAD_KEY; }
   arena_layout(h);
   const size_t off = h.total_len;

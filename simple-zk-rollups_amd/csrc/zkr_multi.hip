@@ -315,10 +315,7 @@ void set_form(int form, const char *fmt, ...) {
 void drain_shards(zkr_key *const *shards, size_t parts) {
   for (size_t i = 0; i < parts; i++) {
     zkr_key *k = shards[i];
-    if (hipSetDevice(k->device) != hipSuccess) continue;
-    (void)hipStreamSynchronize(k->stream);
-    (void)hipStreamSynchronize(k->prep_stream);
-    for (int j = 0; j < k->n_all; j++) (void)hipStreamSynchronize(k->red_stream[j]);
+    if (hipSetDevice(k->device) == hipSuccess) key_streams_sync(k);
   }
   (void)hipGetLastError();
 }

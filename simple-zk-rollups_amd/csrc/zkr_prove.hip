@@ -185,30 +185,47 @@ static Fr fr_from_u64(uint64_t x) {
   return r;
 }
 
-// d_w (std, reduced) -> d_h (std, bit-reversed order).  See DESIGN.md "calcH on the GPU".
-int calc_h_device(zkr_key *k, ProofSlot &sl, hipStream_t s, int nbat) {
+// QAP rows [lo, hi) of nbat witnesses end to end (sl.d_w -> sl.va, sl.vb): both sides in one launch (blockIdx.z; one launch fewer in
+// the chain, twice the workgroups), then the rows wider than SPMV_WIDE terms
+static void spmv_enqueue(zkr_key *k, ProofSlot &sl, hipStream_t s, uint32_t lo, uint32_t hi, int nbat) {
   const Prof pf{k, &sl};
   const ArenaHeader &h = k->h;
   const unsigned char *ar = k->arena;
-  const Fr *tw = (const Fr *)(ar + h.off_tw);
-  int L = (int)h.logm, tlog = (int)h.tlog;
-  const NttTables tb{tw, k->tw29, k->twl29, tlog};
-  uint32_t m = h.m;
-  int sp = prof_begin(pf, s, "spmv");
+  const int sp = prof_begin(pf, s, "spmv");
   SpmvSide side[2];
   Fr *evals[2] = {sl.va, sl.vb};
   for (int i = 0; i < 2; i++)
     side[i] = SpmvSide{(const uint32_t *)(ar + h.off_rowptr[i]), (const uint32_t *)(ar + h.off_col[i]), (const Fr *)(ar + h.off_coef[i]), evals[i],
                        (const uint32_t *)(ar + h.off_wide[i]), h.n_wide[i]};
-  {  // both sides of the QAP in one launch (blockIdx.z): one launch fewer in the chain, twice the workgroups
-    const int sa = prof_begin(pf, s, "spmv_a");
-    spmv_kernel<<<dim3((m + 255) / 256, nbat, 2), 256, 0, s>>>(side[0], side[1], sl.d_w, m, h.n, 0, m);
-    prof_end(pf, s, sa);
-    const uint32_t nw = h.n_wide[0] > h.n_wide[1] ? h.n_wide[0] : h.n_wide[1];
-    if (nw) spmv_wide_kernel<<<dim3(nw, nbat, 2), 64, 0, s>>>(side[0], side[1], sl.d_w, m, h.n, 0, m);
-  }
+  const int sa = prof_begin(pf, s, "spmv_a");
+  spmv_kernel<<<dim3((hi - lo + 255) / 256, nbat, 2), 256, 0, s>>>(side[0], side[1], sl.d_w, h.m, h.n, lo, hi);
+  prof_end(pf, s, sa);
+  const uint32_t nw = h.n_wide[0] > h.n_wide[1] ? h.n_wide[0] : h.n_wide[1];
+  if (nw) spmv_wide_kernel<<<dim3(nw, nbat, 2), 64, 0, s>>>(side[0], side[1], sl.d_w, h.m, h.n, lo, hi);
   prof_end(pf, s, sp);
-  sp = prof_begin(pf, s, "ntt");
+}
+
+// constants of the combination: S' = m S / R, D' = m^3 D g^i / R  ->  h = S'*R^2/(2m) (*1/R)  -  D' g^-i * R^2/(2 m^3) (*1/R)
+static void combine_h_consts(uint32_t m, Fr &c1v, Fr &c2v) {
+  Fr r2 = Fr::r2();
+  Fr minv = inv(to_mont(fr_from_u64(m)));        // Montgomery(1/m)
+  Fr half = inv(to_mont(fr_from_u64(2)));        // Montgomery(1/2)
+  c1v = mul(mul(r2, half), minv);                // value R^2/(2m) ... as plain integer: from_mont of Montgomery product chain
+  // r2 is the integer R^2 mod r = Montgomery(R).  mul(r2, half) = Montgomery(R/2); times minv = Montgomery(R/(2m)).
+  // We need the plain integer R^2/(2m) = Montgomery(R/(2m)) exactly, so c1v is already the constant to pass.
+  c2v = mul(mul(c1v, minv), minv);               // Montgomery(R/(2m^3)) = integer R^2/(2m^3)
+}
+
+// d_w (std, reduced) -> d_h (std, bit-reversed order).  See DESIGN.md "calcH on the GPU".
+int calc_h_device(zkr_key *k, ProofSlot &sl, hipStream_t s, int nbat) {
+  const Prof pf{k, &sl};
+  const ArenaHeader &h = k->h;
+  const Fr *tw = (const Fr *)(k->arena + h.off_tw);
+  int L = (int)h.logm, tlog = (int)h.tlog;
+  const NttTables tb{tw, k->tw29, k->twl29, tlog};
+  uint32_t m = h.m;
+  spmv_enqueue(k, sl, s, 0, m, nbat);
+  const int sp = prof_begin(pf, s, "ntt");
   int rc;
   // The six transforms come in three pairs of the same shape, each pair in ONE set of launches (gridDim.z = 2):
   // coefficients of a and b (x m, bit-reversed), then their evaluations on the coset g*w^c (x m, natural),
@@ -221,14 +238,8 @@ int calc_h_device(zkr_key *k, ProofSlot &sl, hipStream_t s, int nbat) {
   if ((rc = run_ntt(s, sl.ca, nullptr, sl.ca, tb, L, false, false, PRE_COSET, nbat, pf, sl.cb, nullptr, sl.cb))) return rc;
   // then D' = iNTT(A(gw^c).B(gw^c)) and S' = iNTT(a.b), both unscaled and bit-reversed
   if ((rc = run_ntt(s, sl.ca, sl.cb, sl.ca, tb, L, true, true, PRE_MUL, nbat, pf, sl.va, sl.vb, sl.va, h_lo, h_n))) return rc;
-  // constants: S' = m S / R, D' = m^3 D g^i / R  ->  h = S'*R^2/(2m) (*1/R)  -  D' g^-i * R^2/(2 m^3) (*1/R)
-  Fr r2 = Fr::r2();
-  Fr minv = inv(to_mont(fr_from_u64(m)));        // Montgomery(1/m)
-  Fr half = inv(to_mont(fr_from_u64(2)));        // Montgomery(1/2)
-  Fr c1v = mul(mul(r2, half), minv);             // value R^2/(2m) ... as plain integer: from_mont of Montgomery product chain
-  // r2 is the integer R^2 mod r = Montgomery(R).  mul(r2, half) = Montgomery(R/2); times minv = Montgomery(R/(2m)).
-  // We need the plain integer R^2/(2m) = Montgomery(R/(2m)) exactly, so c1v is already the constant to pass.
-  Fr c2v = mul(mul(c1v, minv), minv);            // Montgomery(R/(2m^3)) = integer R^2/(2m^3)
+  Fr c1v, c2v;
+  combine_h_consts(m, c1v, c2v);
   const int csp = prof_begin(pf, s, "combine_h");
   const uint32_t pos0 = ranged ? h_lo : 0, pos1 = ranged ? h_lo + h_n : m;
   combine_h_kernel<<<dim3((pos1 - pos0 + 255) / 256, nbat), 256, 0, s>>>(sl.va, sl.ca, sl.d_h, tw, tlog, L, c1v, c2v, sl.dig_h.rng, DIGIT_CLEAR_WORDS, pos0, pos1);  // + the counters of h's digit records
@@ -294,8 +305,7 @@ static int calc_h_split(zkr_key *k, ProofSlot &sl, hipStream_t s, ShardGroup &g,
 static int calc_h_split_phases(zkr_key *k, ProofSlot &sl, hipStream_t s, ShardGroup &g, unsigned part, std::unique_lock<std::mutex> &lock) {
   const Prof pf{k, &sl};
   const ArenaHeader &h = k->h;
-  const unsigned char *ar = k->arena;
-  const Fr *tw = (const Fr *)(ar + h.off_tw);
+  const Fr *tw = (const Fr *)(k->arena + h.off_tw);
   const int L = (int)h.logm, tlog = (int)h.tlog, klog = g.klog, Lb = L - klog;
   const NttTables tb{tw, k->tw29, k->twl29, tlog};
   const uint32_t m = h.m, P = g.parts, Bk = m >> klog, cols = Bk >> klog, col_lo = part * cols, blk = part * Bk;
@@ -325,20 +335,7 @@ static int calc_h_split_phases(zkr_key *k, ProofSlot &sl, hipStream_t s, ShardGr
     for (unsigned b = 0; b < P; b++) g.vecs[b] = g.vecs[part];
   // 1: QAP rows of the block
   phase_begin();
-  {
-    const int sp = prof_begin(pf, s, "spmv");
-    SpmvSide side[2];
-    Fr *evals[2] = {sl.va, sl.vb};
-    for (int i = 0; i < 2; i++)
-      side[i] = SpmvSide{(const uint32_t *)(ar + h.off_rowptr[i]), (const uint32_t *)(ar + h.off_col[i]), (const Fr *)(ar + h.off_coef[i]), evals[i],
-                         (const uint32_t *)(ar + h.off_wide[i]), h.n_wide[i]};
-    const int sa = prof_begin(pf, s, "spmv_a");
-    spmv_kernel<<<dim3((Bk + 255) / 256, 1, 2), 256, 0, s>>>(side[0], side[1], sl.d_w, m, h.n, blk, blk + Bk);
-    prof_end(pf, s, sa);
-    const uint32_t nw = h.n_wide[0] > h.n_wide[1] ? h.n_wide[0] : h.n_wide[1];
-    if (nw) spmv_wide_kernel<<<dim3(nw, 1, 2), 64, 0, s>>>(side[0], side[1], sl.d_w, m, h.n, blk, blk + Bk);
-    prof_end(pf, s, sp);
-  }
+  spmv_enqueue(k, sl, s, blk, blk + Bk, 1);
   if ((rc = phase_end())) return rc;
   const Fr *r_va[8], *r_vb[8], *r_ca[8], *r_cb[8], *r_ga[8], *r_gb[8];
   Fr *w_ca[8], *w_cb[8], *w_dh[8], *w_ga[8], *w_gb[8];
@@ -377,11 +374,8 @@ static int calc_h_split_phases(zkr_key *k, ProofSlot &sl, hipStream_t s, ShardGr
   // 5: D' on the block, then h
   phase_begin();
   if ((rc = run_ntt(s, sl.ca + blk, nullptr, sl.ca + blk, tb, Lb, true, true, PRE_NONE, 1, pf))) return rc;
-  Fr r2 = Fr::r2();
-  Fr minv = inv(to_mont(fr_from_u64(m)));
-  Fr half = inv(to_mont(fr_from_u64(2)));
-  Fr c1v = mul(mul(r2, half), minv);
-  Fr c2v = mul(mul(c1v, minv), minv);
+  Fr c1v, c2v;
+  combine_h_consts(m, c1v, c2v);
   const int csp = prof_begin(pf, s, "combine_h");
   combine_h_kernel<<<dim3((Bk + 255) / 256, 1), 256, 0, s>>>(sl.d_h, sl.ca, sl.d_h, tw, tlog, L, c1v, c2v, sl.dig_h.rng, DIGIT_CLEAR_WORDS, blk, blk + Bk);
   prof_end(pf, s, csp);
@@ -599,6 +593,20 @@ static int draw_blinding(uint8_t out[32]) {
   fclose(f);
   return 0;
 }
+// r and s of one proof: the caller's, checked (both or neither), or drawn
+static int take_blinding(const uint8_t *r32, const uint8_t *s32, uint8_t rb[32], uint8_t sb[32]) {
+  if ((r32 == nullptr) != (s32 == nullptr)) { set_error("pass both r and s or neither"); return ZKR_ERR_ARG; }
+  if (!r32) {
+    int rc;
+    if ((rc = draw_blinding(rb)) || (rc = draw_blinding(sb))) return rc;
+    return 0;
+  }
+  memcpy(rb, r32, 32); memcpy(sb, s32, 32);
+  uint32_t rv[8], sv[8];
+  memcpy(rv, rb, 32); memcpy(sv, sb, 32);
+  if (!u256_lt(rv, FrParams::P) || !u256_lt(sv, FrParams::P)) { set_error("blinding scalar >= r"); return ZKR_ERR_ARG; }
+  return 0;
+}
 
 static int prove_submit_enqueue(zkr_key *k, ProofSlot &sl, const Fr *const *d_wsrcs, int nbat, const uint8_t *r32s, const uint8_t *s32s, hipStream_t caller, const hipEvent_t *readies);
 
@@ -611,39 +619,22 @@ static int prove_submit_enqueue(zkr_key *k, ProofSlot &sl, const Fr *const *d_ws
 static int prove_submit_group(zkr_key *k, ProofSlot &sl, const Fr *const *d_wsrcs, int nbat, const uint8_t *r32s, const uint8_t *s32s, hipStream_t caller, const hipEvent_t *readies = nullptr) {
   int rc = prove_submit_enqueue(k, sl, d_wsrcs, nbat, r32s, s32s, caller, readies);
   if (rc && rc != ZKR_ERR_ARG) {  // ZKR_ERR_ARG: refused before the first launch
-    hipStreamSynchronize(k->stream);
-    hipStreamSynchronize(k->prep_stream);
-    for (int j = 0; j < k->n_all; j++) hipStreamSynchronize(k->red_stream[j]);
+    key_streams_sync(k);
     sl.spans.clear();
     sl.event_next = 0;
   }
   return rc;
 }
-// one proof
-static int prove_submit(zkr_key *k, ProofSlot &sl, const Fr *d_wsrc, const uint8_t *r32, const uint8_t *s32, hipStream_t caller, hipEvent_t ready = nullptr) {
-  return prove_submit_group(k, sl, &d_wsrc, 1, r32, s32, caller, ready ? &ready : nullptr);
-}
 
 static int prove_submit_enqueue(zkr_key *k, ProofSlot &sl, const Fr *const *d_wsrcs, int nbat, const uint8_t *r32s, const uint8_t *s32s, hipStream_t caller, const hipEvent_t *readies) {
   ZKR_HIP_CHECK(hipSetDevice(k->device));
   const ArenaHeader &h = k->h;
+  const ProofLayout &lay = k->layout;
   const unsigned char *ar = k->arena;
   const Prof pf{k, &sl};
   if (nbat < 1 || nbat > sl.cap) { set_error("a proof slot of this key takes 1..%d proofs at once, got %d", sl.cap, nbat); return ZKR_ERR_ARG; }
-  if ((r32s == nullptr) != (s32s == nullptr)) { set_error("pass both r and s or neither"); return ZKR_ERR_ARG; }
-  for (int j = 0; j < nbat; j++) {
-    uint8_t *rb = &sl.rb[32 * j], *sb = &sl.sb[32 * j];
-    if (r32s) {
-      memcpy(rb, r32s + 32 * j, 32);
-      memcpy(sb, s32s + 32 * j, 32);
-      uint32_t rv[8], sv[8];
-      memcpy(rv, rb, 32); memcpy(sv, sb, 32);
-      if (!u256_lt(rv, FrParams::P) || !u256_lt(sv, FrParams::P)) { set_error("blinding scalar >= r"); return ZKR_ERR_ARG; }
-    } else {
-      int rc;
-      if ((rc = draw_blinding(rb)) || (rc = draw_blinding(sb))) return rc;
-    }
-  }
+  for (int j = 0; j < nbat; j++)
+    if (int rc = take_blinding(r32s ? r32s + 32 * j : nullptr, s32s ? s32s + 32 * j : nullptr, &sl.rb[32 * j], &sl.sb[32 * j])) return rc;
   sl.nbat = nbat;
   // The streams are the device's, shared by every key on it (zkr_key.hip DeviceStreams): the launches of one proof are enqueued
   // without another key's in between, so that every cross-stream wait below points at work enqueued before it
@@ -657,20 +648,20 @@ static int prove_submit_enqueue(zkr_key *k, ProofSlot &sl, const Fr *const *d_ws
   //   s  : the five bucket accumulations back to back, B2 first (its reduction chain is the longest), B1 on the
   //        same sort (h.share_b), then A, C, H, each waiting only for its table's sort.  Every accumulation
   //        saturates the VALUs on its own;
-  //   red[0] : oversized-bucket and reduction chain of the G2 table;  red[1] : those of the four G1 tables (more
+  //   g2 : oversized-bucket and reduction chain of the G2 table;  g1 : those of the four G1 tables (more
   //        streams measured slower, HISTORY.md 7b; one stream for all five chains is the bottleneck with two proofs in
   //        flight: ~6 ms of serialised launches per proof).  Few long-running wavefronts at raised wave priority
   //        that run under the following accumulations; the oversized buckets need only the sort and run beside
-  //        the accumulation.
+  //        the accumulation;
+  //   aux : C's oversized buckets in a lone proof of a small circuit (c_big below), a shard's witness-side sorts (par_sorts).
   // With two proofs in flight (zkr_prove_submit) the preparation of proof i+1 runs under the accumulations of
   // proof i, whose reduction tail and host assembly are covered by the accumulations of proof i+1.
-  static const bool serial = getenv("ZKR_SERIAL") != nullptr;  // profiling aid: one stream, isolated kernel durations
-  hipStream_t s = k->stream;
-  hipStream_t sp = serial ? s : k->prep_stream;
-  auto red_of = [&](int t) -> hipStream_t {  // G2 chain on [0], the G1 chains one after the other on [1] (zkr_key.hip key_alloc_workspace)
-    if (serial) return s;
-    return k->red_stream[t == T_B2 ? 0 : 1];
-  };
+  // ZKR_SERIAL=1 (a profiling aid: isolated kernel durations) puts every role on the accumulation stream and turns off what only
+  // concurrency is for: auxiliary-stream work, the split calcH, the latency-mode chain.  The same kernels then run in the same
+  // order; a wait for an event of the same stream orders nothing new.
+  static const bool serial = getenv("ZKR_SERIAL") != nullptr;
+  const hipStream_t s = k->stream;
+  const hipStream_t sp = serial ? s : k->prep_stream, s_g2 = serial ? s : k->g2_stream, s_g1 = serial ? s : k->g1_stream, aux = serial ? s : k->aux_stream;
   int rc;
   if (readies) {
     for (int j = 0; j < nbat; j++) ZKR_HIP_CHECK(hipStreamWaitEvent(sp, readies[j], 0));  // the staged uploads have landed
@@ -684,14 +675,12 @@ static int prove_submit_enqueue(zkr_key *k, ProofSlot &sl, const Fr *const *d_ws
     ingest_kernel<<<(h.n + 255) / 256, 256, 0, sp>>>(d_wsrcs[j], sl.d_w + (size_t)j * h.n, h.n, j == nbat - 1 ? sl.dig_w.rng : nullptr, j == nbat - 1 ? DIGIT_CLEAR_WORDS : 0u);
   prof_end(pf, sp, spn);
   const DigitLists *dig[N_TABLES] = {&sl.dig_w, &sl.dig_w, &sl.dig_w, &sl.dig_w, &sl.dig_h};
-  const bool share_b = h.share_b != 0 && h.npts[T_B1] == h.npts[T_B2];
-  const bool share_ac = h.share_ac != 0 && h.npts[T_A] == h.npts[T_C];  // A and C laid out over one support
-  int sort_src[N_TABLES] = {T_A, T_B1, share_b ? T_B1 : T_B2, share_ac ? T_A : T_C, T_H};
+  const int *sort_src = lay.sort_src;
   // A shard key's proof is as long as its replicated calcH plus what follows it (digits and sort of h, H's accumulation, the
   // last chain): the digit records and sorts of w -- an eighth of a whole key's, but in FRONT of calcH on the preparation stream --
   // go to the auxiliary stream instead and run beside it.
   const bool par_sorts = h.shard_parts > 1 && !serial;
-  hipStream_t sw = par_sorts ? k->aux_stream : sp;  // where w's digit records and the sorts of A, B1, B2, C are made
+  const hipStream_t sw = par_sorts ? aux : sp;  // where w's digit records and the sorts of A, B1, B2, C are made
   if (par_sorts) {
     ZKR_HIP_CHECK(hipEventRecord(sl.ev_w, sp));  // the ingested witness (and the cleared counters of its digit records)
     ZKR_HIP_CHECK(hipStreamWaitEvent(sw, sl.ev_w, 0));
@@ -701,23 +690,12 @@ static int prove_submit_enqueue(zkr_key *k, ProofSlot &sl, const Fr *const *d_ws
     hipStream_t st = t == T_H ? sp : sw;
     int rc = msm_sort_enqueue(pf, st, rank, *dig[t], rank_entries(h, t), h.npts[t], nbat, k->plan[t], sl.ws[t]);
     if (rc) return rc;
-    if (!serial) ZKR_HIP_CHECK(hipEventRecord(sl.ev_sorted[t], st));
+    ZKR_HIP_CHECK(hipEventRecord(sl.ev_sorted[t], st));
     return 0;
   };
-  // C and H are only ever needed as C + H (App. B step 4: pi_c): when their bucket geometry agrees, H is accumulated ONTO
-  // C's bucket set and one reduction chain serves both -- a bucket reduction (2 x 2^19 full additions, ~1.6 % of a proof's
-  // instructions) and one latency chain less.  Oversized buckets of either table are ADDED to the shared set after H's
-  // accumulation (C's accumulation clears their slots), so no accumulation waits for a reduction stream.
-  const MsmPlan &pc = k->plan[T_C], &ph = k->plan[T_H];
-  const bool merge_ch = h.npts[T_C] && h.npts[T_H] && pc.c == ph.c && pc.nbw == ph.nbw && pc.glog == ph.glog && pc.S == ph.S;
-  sl.merged_ch = merge_ch;
-  // A and B1 in ONE reduction chain (round 5): the G1 chains share one stream, and in a single proof of a small circuit that stream
-  // is the critical path from B1's accumulation to the end (three chains of ~0.4 ms back to back: H's chain starts 0.19 ms after H's
-  // accumulation has ended, profiles/r4_05_timeline_one_tx_proof.txt).  A is accumulated into the bucket sets BEHIND B1's (B1's
-  // workspace holds two sets per proof when the two tables' geometry agrees) and one launch set reduces both: a chain of latency-bound
-  // launches less per proof.
-  const bool joint_ab = h.npts[T_A] && h.npts[T_B1] && same_reduce_geometry(k->plan[T_A], k->plan[T_B1]) && sl.ws[T_B1].sets == 2;  // (the serial schedule too: A's workspace has no reduction buffers then)
-  sl.joint_ab = joint_ab;
+  // which bucket set each table's sums land in and which chain reduces them: H onto C's set (merge_ch), A behind B1's sets (joint_ab);
+  // the rules and their reasons: zkr_key.hip proof_layout
+  const bool merge_ch = lay.merge_ch, joint_ab = lay.joint_ab;
   for (int t = 0; t < N_TABLES; t++) sl.res_pending[t] = false;
   auto result_event = [&](int t, hipStream_t rs, int rc) -> int {  // after a table's reduction chain (its D2H copy is the last thing enqueued)
     if (rc) return rc;
@@ -745,20 +723,20 @@ static int prove_submit_enqueue(zkr_key *k, ProofSlot &sl, const Fr *const *d_ws
   // the bucket reduction, on the chain's stream again.
   auto accum_table = [&](int t) -> int {
     int rc;
-    hipStream_t rs = red_of(t);
+    const hipStream_t rs = t == T_B2 ? s_g2 : s_g1;
     last = rs;
     const MsmWorkspace &srt = sl.ws[sort_src[t]];
     const void *pts = ar + h.off_pts[t];
-    if (!serial) ZKR_HIP_CHECK(hipStreamWaitEvent(rs, sl.ev_sorted[sort_src[t]], 0));
+    ZKR_HIP_CHECK(hipStreamWaitEvent(rs, sl.ev_sorted[sort_src[t]], 0));
     // partial sums into the table's OWN partials buffer.  C's, when C shares H's bucket set, may have been enqueued in front of
     // every chain (c_big_first)
     if (!(t == T_C && c_big_first)) {
       if (t == T_B2) rc = msm_big_enqueue<Fq2>(pf, rs, (const G2Affine *)pts, h.npts[t], k->plan[t], srt, sl.ws[t]);
       else rc = msm_big_enqueue<Fq>(pf, rs, (const G1Affine *)pts, h.npts[t], k->plan[t], srt, sl.ws[t]);
       if (rc) return rc;
-      if (t == T_C && merge_ch && !serial) ZKR_HIP_CHECK(hipEventRecord(sl.ev_h, rs));  // C's partial sums are on their way: H's chain adds them in
+      if (t == T_C && merge_ch) ZKR_HIP_CHECK(hipEventRecord(sl.ev_h, rs));  // C's partial sums are on their way: H's chain adds them in
     }
-    if (!serial) ZKR_HIP_CHECK(hipStreamWaitEvent(s, sl.ev_sorted[sort_src[t]], 0));
+    ZKR_HIP_CHECK(hipStreamWaitEvent(s, sl.ev_sorted[sort_src[t]], 0));
     // whose bucket set the table lands in: H onto C's (merge_ch), A behind B1's sets (joint chain); its oversized-bucket sums stay its
     // own.  Shared set: C's accumulation clears the slots of ITS oversized buckets (their sums are added after H's accumulation, so
     // H's accumulation waits for nothing but C's, in front of it on the same stream)
@@ -768,16 +746,16 @@ static int prove_submit_enqueue(zkr_key *k, ProofSlot &sl, const Fr *const *d_ws
     if (t == T_B2) rc = msm_accum_enqueue<Fq2>(pf, s, (const G2Affine *)pts, h.npts[t], nbat, k->plan[t], srt, buckets);
     else rc = msm_accum_enqueue<Fq>(pf, s, (const G1Affine *)pts, h.npts[t], nbat, k->plan[t], srt, buckets, flags);
     if (rc) return rc;
-    if (!serial) ZKR_HIP_CHECK(hipEventRecord(sl.ev_done[t], s));
+    ZKR_HIP_CHECK(hipEventRecord(sl.ev_done[t], s));
     if (t == T_C && merge_ch) return 0;             // reduced with H
     if (joint_ab && t == T_B1) return 0;            // reduced with A, by A's turn on this stream (B1's oversized-bucket sums are on their way on it)
-    if (!serial) ZKR_HIP_CHECK(hipStreamWaitEvent(rs, sl.ev_done[t], 0));
+    ZKR_HIP_CHECK(hipStreamWaitEvent(rs, sl.ev_done[t], 0));
     if (t == T_B2) {
       if ((rc = msm_big_finish_enqueue<Fq2>(pf, rs, h.npts[t], srt, sl.ws[t]))) return rc;
       return result_event(t, rs, msm_reduce_enqueue<Fq2>(pf, rs, h.npts[t], nbat, 1, k->plan[t], srt, sl.ws[t]));
     }
     if (t == T_H && merge_ch) {  // both tables' oversized buckets are ADDED to what the shared set holds: C's partial sums (its own sort's list), then H's
-      if (!serial) ZKR_HIP_CHECK(hipStreamWaitEvent(rs, sl.ev_h, 0));
+      ZKR_HIP_CHECK(hipStreamWaitEvent(rs, sl.ev_h, 0));
       MsmWorkspace mixc = sl.ws[T_C];   // C's workspace: its partials, its buckets
       if ((rc = msm_big_finish_enqueue<Fq>(pf, rs, h.npts[T_C], sl.ws[sort_src[T_C]], mixc, true))) return rc;
       MsmWorkspace mix = sl.ws[T_C];
@@ -811,21 +789,20 @@ static int prove_submit_enqueue(zkr_key *k, ProofSlot &sl, const Fr *const *d_ws
   // (930-943 against 947-964 tx proofs/s, 150.5 against 151.0 at 2^20: tools/ab_c_big_tx.sh).
   auto c_big = [&]() -> int {
     if (!c_big_first) return 0;
-    hipStream_t bs = k->aux_stream;
-    ZKR_HIP_CHECK(hipStreamWaitEvent(bs, sl.ev_sorted[sort_src[T_C]], 0));
-    int rc = msm_big_enqueue<Fq>(pf, bs, (const G1Affine *)(ar + h.off_pts[T_C]), h.npts[T_C], k->plan[T_C], sl.ws[sort_src[T_C]], sl.ws[T_C]);
+    ZKR_HIP_CHECK(hipStreamWaitEvent(aux, sl.ev_sorted[sort_src[T_C]], 0));
+    int rc = msm_big_enqueue<Fq>(pf, aux, (const G1Affine *)(ar + h.off_pts[T_C]), h.npts[T_C], k->plan[T_C], sl.ws[sort_src[T_C]], sl.ws[T_C]);
     if (rc) return rc;
-    ZKR_HIP_CHECK(hipEventRecord(sl.ev_h, bs));
+    ZKR_HIP_CHECK(hipEventRecord(sl.ev_h, aux));
     return 0;
   };
   // preparation chain
   // a shard key (zkr_key_shard) multiplies only its sub-range of each scalar vector; a whole key: sc_lo = 0, sc_n = n / m
   if ((rc = msm_digits_enqueue(pf, sw, sl.d_w + h.sc_lo[0], h.sc_n[0], nbat, k->plan[T_A], sl.dig_w, true))) return rc;
   if ((rc = sort_table(T_B1))) return rc;
-  if (!share_b && (rc = sort_table(T_B2))) return rc;
+  if (!lay.share_b && (rc = sort_table(T_B2))) return rc;
   if (early && (rc = chains({T_B2, T_B1}))) return rc;
   if ((rc = sort_table(T_A))) return rc;
-  if (!share_ac && (rc = sort_table(T_C))) return rc;
+  if (!lay.share_ac && (rc = sort_table(T_C))) return rc;
   if (early && ((rc = c_big()) || (rc = chains({T_A, T_C})))) return rc;
   if (split_h) rc = calc_h_split(k, sl, sp, *group, shard_group_part, enqueue_lock);
   else rc = calc_h_device(k, sl, sp, nbat);
@@ -837,14 +814,11 @@ static int prove_submit_enqueue(zkr_key *k, ProofSlot &sl, const Fr *const *d_ws
   if (early) rc = chains({T_H});
   else { if ((rc = c_big())) return rc; rc = chains({T_B2, T_B1, T_A, T_C, T_H}); }
   if (rc) return rc;
-  // completion = every reduction stream done (prove_collect waits for the events on the host).  No stream is made
+  // completion = the chain and auxiliary streams done (prove_collect waits for the events on the host).  No stream is made
   // to wait for another, so nothing of the next proof queues behind this one's tail.
   prof_end(pf, last, tot);
-  if (!serial) {
-    for (int j = 0; j < k->n_all; j++) ZKR_HIP_CHECK(hipEventRecord(sl.ev_red[j], k->red_stream[j]));
-  } else {
-    ZKR_HIP_CHECK(hipEventRecord(sl.ev_red[0], s));
-  }
+  const hipStream_t ends[3] = {s_g2, s_g1, aux};  // sl.ev_end's order
+  for (int j = 0; j < 3; j++) ZKR_HIP_CHECK(hipEventRecord(sl.ev_end[j], ends[j]));
   sl.busy = true;
   return 0;
 }
@@ -911,7 +885,7 @@ static int prove_collect(zkr_key *k, ProofSlot &sl, uint8_t *proofs_out, Partial
   } release{k, sl};
   ZKR_HIP_CHECK(hipSetDevice(k->device));
   const ArenaHeader &h = k->h;
-  static const bool serial_mode = getenv("ZKR_SERIAL") != nullptr;
+  const ProofLayout &lay = k->layout;
   // Everything that needs A, B1, B2 only (assemble_ab: all the scalar multiplications) is done while the LAST chains (C, H: H's
   // sort only starts after calcH) still run on the GPU; when C + H lands, one addition and one inversion finish pi_c.
   // Single-proof latency: ~0.35 ms of host work off the critical path (with two proofs in flight it was hidden already).
@@ -925,7 +899,7 @@ static int prove_collect(zkr_key *k, ProofSlot &sl, uint8_t *proofs_out, Partial
   int status = 0;
   for (int j = 0; j < sl.nbat; j++) {
     // joint chain of A and B1 (prove_submit_enqueue): B1's workspace holds both results, B1's nbat first
-    G1XYZZ A = sl.joint_ab ? msm_finish<Fq>(h.npts[T_A], sl.ws[T_B1], sl.nbat + j) : msm_finish<Fq>(h.npts[T_A], sl.ws[T_A], j);
+    G1XYZZ A = lay.joint_ab ? msm_finish<Fq>(h.npts[T_A], sl.ws[T_B1], sl.nbat + j) : msm_finish<Fq>(h.npts[T_A], sl.ws[T_A], j);
     G1XYZZ B1 = msm_finish<Fq>(h.npts[T_B1], sl.ws[T_B1], j);
     G2XYZZ B2 = msm_finish<Fq2>(h.npts[T_B2], sl.ws[T_B2], j);
     if (partials_out) { partials_out[j].A = A; partials_out[j].B1 = B1; partials_out[j].B2 = B2; continue; }
@@ -933,12 +907,12 @@ static int prove_collect(zkr_key *k, ProofSlot &sl, uint8_t *proofs_out, Partial
     if (rc) status = rc;
   }
   if ((rcw = wait_table(T_C)) || (rcw = wait_table(T_H))) return rcw;
-  for (int j = 0; j < (serial_mode ? 1 : k->n_all); j++) ZKR_HIP_CHECK(hipEventSynchronize(sl.ev_red[j]));  // every stream of the slot is idle (all of it precedes the table events)
+  for (hipEvent_t e : sl.ev_end) ZKR_HIP_CHECK(hipEventSynchronize(e));  // every stream of the slot is idle (all of it precedes the table events)
   if (k->prof_on) { std::lock_guard<std::mutex> lk(k->mu); prof_collect(k, sl); }
   for (int j = 0; j < sl.nbat && !status; j++) {
     // merged bucket sets (prove_submit_enqueue): the one reduction result, C + H, sits in C's workspace
     G1XYZZ C = msm_finish<Fq>(h.npts[T_C], sl.ws[T_C], j);
-    G1XYZZ H = sl.merged_ch ? G1XYZZ::inf() : msm_finish<Fq>(h.npts[T_H], sl.ws[T_H], j);
+    G1XYZZ H = lay.merge_ch ? G1XYZZ::inf() : msm_finish<Fq>(h.npts[T_H], sl.ws[T_H], j);
     if (partials_out) { partials_out[j].CH = add_full(C, H); continue; }
     status = assemble_c(add_full(C, H), pic_part[j], proofs_out + 256 * j);
   }
@@ -1048,13 +1022,101 @@ static int refuse_shard(const zkr_key *key) {
   set_error("this key is shard %u of %u of a proving key: use zkr_prove_partial / zkr_prove_sharded", key->h.shard_part, key->h.shard_parts);
   return ZKR_ERR_ARG;
 }
+static int check_witness_len(const zkr_key *key, size_t witness_len) {
+  if (witness_len == (size_t)key->h.n * 32) return 0;
+  set_error("witness is %zu bytes, key expects nVars*32 = %zu", witness_len, (size_t)key->h.n * 32);
+  return ZKR_ERR_BAD_WITNESS;
+}
+
+// Where the witnesses of a proving call are: host buffers of `len` bytes each -- a host buffer is complete when the call is made;
+// it is staged (own staging buffer, uploaded outside the key's lock: concurrent callers copy in parallel and a third caller uploads
+// while two proofs are in flight) -- or device memory, read after whatever is enqueued on `stream` when its proof is submitted.
+struct Witnesses {
+  const void *const *w;
+  bool host;
+  size_t len;
+  hipStream_t stream;
+};
+
+// Every proving call but submit / collect: a pipeline of one host thread over groups of proofs (group_count; one proof per group
+// for circuits that fill the chip alone).  The host witnesses of the next group are staged BEFORE the oldest group in flight is
+// collected, i.e. while both proof slots compute; then the freed slot takes the group at once.  A single proof is a call of one:
+// with nothing in flight it waits for a staging buffer and for a slot.  Out: count x 256 B of proofs, or -- partial, count = 1 --
+// the MSM sums of a shard's proof, not assembled.
+static int prove_pipeline(zkr_key *key, const Witnesses &src, size_t count, const uint8_t *r32s, const uint8_t *s32s, uint8_t *proofs_out,
+                          PartialSums *partial = nullptr) {
+  size_t groups_left = group_count(key, count);
+  int tickets[PROOF_SLOTS], stages[PROOF_SLOTS];
+  size_t first[PROOF_SLOTS];
+  int in_flight = 0, rc = 0;
+  auto collect_oldest = [&]() {
+    int r = prove_collect(key, key->slot[tickets[0]], partial ? nullptr : proofs_out + 256 * first[0], partial);
+    if (stages[0] >= 0) stage_release(key, stages[0]);
+    for (int j = 1; j < in_flight; j++) { tickets[j - 1] = tickets[j]; first[j - 1] = first[j]; stages[j - 1] = stages[j]; }
+    in_flight--;
+    return r;
+  };
+  for (size_t i = 0; i < count && !rc;) {
+    const int nb = next_group(count - i, groups_left--);
+    int st = -1;
+    if (src.host) {
+      while (!rc && st < 0) {  // a staging buffer: without waiting while groups of this call hold slots and stages
+        if ((rc = stage_acquire(key, &st, in_flight == 0)) || st >= 0) break;
+        rc = collect_oldest();
+      }
+      if (rc) { if (st >= 0) stage_release(key, st); break; }
+      for (int j = 0; j < nb && !rc; j++) rc = stage_upload(key, st, j, src.w[i + j], src.len, j == nb - 1);
+    }
+    if (!rc && in_flight == PROOF_SLOTS) rc = collect_oldest();
+    int t = -1;
+    if (!rc) rc = take_slot(key, in_flight, &t, [&](ProofSlot &sl) -> int {
+      const Fr *w[MAX_FUSE];
+      hipEvent_t ready[MAX_FUSE];
+      for (int j = 0; j < nb; j++) {
+        w[j] = st >= 0 ? key->stage[st].d_w + (size_t)j * key->h.n : (const Fr *)src.w[i + j];
+        ready[j] = st >= 0 ? key->stage[st].ev_up : nullptr;
+      }
+      return prove_submit_group(key, sl, w, nb, r32s ? r32s + 32 * i : nullptr, s32s ? s32s + 32 * i : nullptr, st >= 0 ? key->prep_stream : src.stream,
+                                st >= 0 ? ready : nullptr);
+    }, collect_oldest);
+    if (rc) {
+      if (st >= 0) { hipStreamSynchronize(key->prep_stream); stage_release(key, st); }
+      break;
+    }
+    tickets[in_flight] = t; first[in_flight] = i; stages[in_flight] = st; in_flight++;
+    i += (size_t)nb;
+  }
+  while (in_flight > 0) {  // drain, also after an error: a submitted group must be collected to free its slot
+    int r = collect_oldest();
+    if (!rc) rc = r;
+  }
+  return rc;
+}
+
+// A shard proving on its own takes its shard's turn: a split group that failed on this shard set drains its stragglers (whose
+// cross passes write THIS shard's vectors) before it gives the turns back (zkr_multi.hip run_shards_once).  SHARED: standalone
+// partial proofs from several host threads still pipeline through the shard's two proof slots; only a split group is exclusive
+static std::shared_lock<std::shared_mutex> own_turn(zkr_key *key) {
+  if (key->h.shard_parts > 1 && !shard_turn_held) return std::shared_lock<std::shared_mutex>(key->split_mu);
+  return std::shared_lock<std::shared_mutex>();
+}
+// blinding plays no part before the assembly: a shard's slot gets zeros
+static const uint8_t ZERO32[32] = {0};
+static int prove_partial(zkr_key *key, const Witnesses &src, uint8_t partial_out[ZKR_PARTIAL_BYTES]) {
+  auto turn = own_turn(key);
+  PartialSums ps;
+  int rc = prove_pipeline(key, src, 1, ZERO32, ZERO32, nullptr, &ps);
+  if (!rc) memcpy(partial_out, &ps, sizeof(ps));
+  return rc;
+}
 
 extern "C" {
 
 int zkr_prove_submit(zkr_key *key, const void *d_witness_std, const uint8_t *r32, const uint8_t *s32, void *stream, int *ticket) {
   if (!key || !d_witness_std || !ticket) { set_error("null argument"); return ZKR_ERR_ARG; }
   if (int rs = refuse_shard(key)) return rs;
-  return with_free_slot(key, false, ticket, [&](ProofSlot &sl) { return prove_submit(key, sl, (const Fr *)d_witness_std, r32, s32, (hipStream_t)stream); });
+  const Fr *w = (const Fr *)d_witness_std;
+  return with_free_slot(key, false, ticket, [&](ProofSlot &sl) { return prove_submit_group(key, sl, &w, 1, r32, s32, (hipStream_t)stream); });
 }
 
 int zkr_prove_collect(zkr_key *key, int ticket, uint8_t proof_out[256]) {
@@ -1066,49 +1128,10 @@ int zkr_prove_batch(zkr_key *key, const void *const *witnesses_std, size_t witne
                     uint8_t *proofs_out) {
   if (!key || (!witnesses_std && count) || !proofs_out) { set_error("null argument"); return ZKR_ERR_ARG; }
   if (int rs = refuse_shard(key)) return rs;
-  if (witness_len != (size_t)key->h.n * 32) { set_error("witness is %zu bytes, key expects nVars*32 = %zu", witness_len, (size_t)key->h.n * 32); return ZKR_ERR_BAD_WITNESS; }
+  if (int rw = check_witness_len(key, witness_len)) return rw;
   for (size_t i = 0; i < count; i++)
     if (!witnesses_std[i]) { set_error("witness %zu is null", i); return ZKR_ERR_ARG; }
-  // Pipeline of one host thread over groups of `g` proofs (g = 1 for circuits that fill the chip alone): the witnesses of
-  // the next group are staged (copy into pinned memory + DMA) BEFORE the oldest group in flight is collected, i.e. while
-  // both proof slots compute; then the freed slot takes the group at once.
-  size_t groups_left = group_count(key, count);
-  int tickets[PROOF_SLOTS], stages[PROOF_SLOTS];
-  size_t first[PROOF_SLOTS];
-  int in_flight = 0, rc = 0;
-  auto collect_oldest = [&]() {
-    int r = prove_collect(key, key->slot[tickets[0]], proofs_out + 256 * first[0]);
-    stage_release(key, stages[0]);
-    for (int j = 1; j < in_flight; j++) { tickets[j - 1] = tickets[j]; first[j - 1] = first[j]; stages[j - 1] = stages[j]; }
-    in_flight--;
-    return r;
-  };
-  for (size_t i = 0; i < count && !rc;) {
-    const int nb = next_group(count - i, groups_left--);
-    int st = -1;
-    while (!rc && st < 0) {  // a staging buffer: without waiting while groups of this call hold slots and stages
-      if ((rc = stage_acquire(key, &st, in_flight == 0)) || st >= 0) break;
-      rc = collect_oldest();
-    }
-    if (rc) { if (st >= 0) stage_release(key, st); break; }
-    for (int j = 0; j < nb && !rc; j++) rc = stage_upload(key, st, j, witnesses_std[i + j], witness_len, j == nb - 1);
-    if (!rc && in_flight == PROOF_SLOTS) rc = collect_oldest();
-    int t = -1;
-    if (!rc) rc = take_slot(key, in_flight, &t, [&](ProofSlot &sl) -> int {
-      const Fr *src[MAX_FUSE];
-      hipEvent_t ready[MAX_FUSE];
-      for (int j = 0; j < nb; j++) { src[j] = key->stage[st].d_w + (size_t)j * key->h.n; ready[j] = key->stage[st].ev_up; }
-      return prove_submit_group(key, sl, src, nb, r32s ? r32s + 32 * i : nullptr, s32s ? s32s + 32 * i : nullptr, key->prep_stream, ready);
-    }, collect_oldest);
-    if (rc) { hipStreamSynchronize(key->prep_stream); stage_release(key, st); break; }
-    tickets[in_flight] = t; first[in_flight] = i; stages[in_flight] = st; in_flight++;
-    i += (size_t)nb;
-  }
-  while (in_flight > 0) {  // drain, also after an error: a submitted group must be collected to free its slot
-    int r = collect_oldest();
-    if (!rc) rc = r;
-  }
-  return rc;
+  return prove_pipeline(key, Witnesses{witnesses_std, true, witness_len, nullptr}, count, r32s, s32s, proofs_out);
 }
 
 int zkr_prove_batch_device(zkr_key *key, const void *const *d_witnesses_std, size_t count, const uint8_t *r32s, const uint8_t *s32s, void *stream,
@@ -1117,101 +1140,33 @@ int zkr_prove_batch_device(zkr_key *key, const void *const *d_witnesses_std, siz
   if (int rs = refuse_shard(key)) return rs;
   for (size_t i = 0; i < count; i++)
     if (!d_witnesses_std[i]) { set_error("witness %zu is null", i); return ZKR_ERR_ARG; }
-  size_t groups_left = group_count(key, count);
-  int tickets[PROOF_SLOTS];
-  size_t first[PROOF_SLOTS];
-  int in_flight = 0, rc = 0;
-  auto collect_oldest = [&]() {
-    int r = prove_collect(key, key->slot[tickets[0]], proofs_out + 256 * first[0]);
-    for (int j = 1; j < in_flight; j++) { tickets[j - 1] = tickets[j]; first[j - 1] = first[j]; }
-    in_flight--;
-    return r;
-  };
-  for (size_t i = 0; i < count && !rc;) {
-    const int nb = next_group(count - i, groups_left--);
-    if (in_flight == PROOF_SLOTS) rc = collect_oldest();
-    if (rc) break;
-    int t = -1;
-    rc = take_slot(key, in_flight, &t, [&](ProofSlot &sl) -> int {
-      return prove_submit_group(key, sl, (const Fr *const *)(d_witnesses_std + i), nb, r32s ? r32s + 32 * i : nullptr, s32s ? s32s + 32 * i : nullptr, (hipStream_t)stream);
-    }, collect_oldest);
-    if (!rc) { tickets[in_flight] = t; first[in_flight] = i; in_flight++; i += (size_t)nb; }
-  }
-  while (in_flight > 0) {
-    int r = collect_oldest();
-    if (!rc) rc = r;
-  }
-  return rc;
+  return prove_pipeline(key, Witnesses{d_witnesses_std, false, 0, (hipStream_t)stream}, count, r32s, s32s, proofs_out);
 }
 
 int zkr_prove_device(zkr_key *key, const void *d_witness_std, const uint8_t *r32, const uint8_t *s32, uint8_t proof_out[256], void *stream) {
   if (!key || !d_witness_std || !proof_out) { set_error("null argument"); return ZKR_ERR_ARG; }
   if (int rs = refuse_shard(key)) return rs;
-  int t = -1;
-  int rc = with_free_slot(key, true, &t, [&](ProofSlot &sl) { return prove_submit(key, sl, (const Fr *)d_witness_std, r32, s32, (hipStream_t)stream); });
-  if (rc) return rc;
-  return prove_collect(key, key->slot[t], proof_out);
+  return prove_pipeline(key, Witnesses{&d_witness_std, false, 0, (hipStream_t)stream}, 1, r32, s32, proof_out);
 }
 
 int zkr_prove(zkr_key *key, const void *witness_std, size_t witness_len, const uint8_t *r32, const uint8_t *s32, uint8_t proof_out[256], void *stream) {
   if (!key || !witness_std || !proof_out) { set_error("null argument"); return ZKR_ERR_ARG; }
   if (int rs = refuse_shard(key)) return rs;
-  if (witness_len != (size_t)key->h.n * 32) { set_error("witness is %zu bytes, key expects nVars*32 = %zu", witness_len, (size_t)key->h.n * 32); return ZKR_ERR_BAD_WITNESS; }
+  if (int rw = check_witness_len(key, witness_len)) return rw;
   (void)stream;  // a host buffer is complete when the call is made: nothing on the caller's stream to wait for
-  // Upload first (own staging buffer, outside the key's lock: concurrent callers copy in parallel and a third caller
-  // uploads while two proofs are in flight), then take a proof slot as soon as one frees.
-  int st = -1;
-  int rc = stage_acquire(key, &st);
-  if (rc) return rc;
-  rc = stage_upload(key, st, 0, witness_std, witness_len, true);
-  int t = -1;
-  if (!rc) rc = with_free_slot(key, true, &t, [&](ProofSlot &sl) -> int {
-    return prove_submit(key, sl, key->stage[st].d_w, r32, s32, key->prep_stream, key->stage[st].ev_up);
-  });
-  if (rc) { hipStreamSynchronize(key->prep_stream); stage_release(key, st); return rc; }
-  rc = prove_collect(key, key->slot[t], proof_out);
-  stage_release(key, st);
-  return rc;
+  return prove_pipeline(key, Witnesses{&witness_std, true, witness_len, nullptr}, 1, r32, s32, proof_out);
 }
 
 // ---- intra-proof sharding: a shard key's share of ONE proof, and the assembly from all shares
-static const uint8_t ZERO32[32] = {0};
 int zkr_prove_partial_device(zkr_key *key, const void *d_witness_std, void *stream, uint8_t partial_out[ZKR_PARTIAL_BYTES]) {
   if (!key || !d_witness_std || !partial_out) { set_error("null argument"); return ZKR_ERR_ARG; }
-  // a shard proving on its own takes its shard's turn: a split group that failed on this shard set drains its stragglers (whose
-  // cross passes write THIS shard's vectors) before it gives the turns back (zkr_multi.hip run_shards_once).  SHARED: standalone
-  // partial proofs from several host threads still pipeline through the shard's two proof slots; only a split group is exclusive
-  std::shared_lock<std::shared_mutex> own_turn;
-  if (key->h.shard_parts > 1 && !shard_turn_held) own_turn = std::shared_lock<std::shared_mutex>(key->split_mu);
-  int t = -1;
-  // blinding plays no part before the assembly: the slot gets zeros
-  int rc = with_free_slot(key, true, &t, [&](ProofSlot &sl) { return prove_submit(key, sl, (const Fr *)d_witness_std, ZERO32, ZERO32, (hipStream_t)stream); });
-  if (rc) return rc;
-  PartialSums ps;
-  rc = prove_collect(key, key->slot[t], nullptr, &ps);
-  if (!rc) memcpy(partial_out, &ps, sizeof(ps));
-  return rc;
+  return prove_partial(key, Witnesses{&d_witness_std, false, 0, (hipStream_t)stream}, partial_out);
 }
 
 int zkr_prove_partial(zkr_key *key, const void *witness_std, size_t witness_len, uint8_t partial_out[ZKR_PARTIAL_BYTES]) {
   if (!key || !witness_std || !partial_out) { set_error("null argument"); return ZKR_ERR_ARG; }
-  if (witness_len != (size_t)key->h.n * 32) { set_error("witness is %zu bytes, key expects nVars*32 = %zu", witness_len, (size_t)key->h.n * 32); return ZKR_ERR_BAD_WITNESS; }
-  std::shared_lock<std::shared_mutex> own_turn;  // as in zkr_prove_partial_device
-  if (key->h.shard_parts > 1 && !shard_turn_held) own_turn = std::shared_lock<std::shared_mutex>(key->split_mu);
-  int st = -1;
-  int rc = stage_acquire(key, &st);
-  if (rc) return rc;
-  rc = stage_upload(key, st, 0, witness_std, witness_len, true);
-  int t = -1;
-  if (!rc) rc = with_free_slot(key, true, &t, [&](ProofSlot &sl) -> int {
-    return prove_submit(key, sl, key->stage[st].d_w, ZERO32, ZERO32, key->prep_stream, key->stage[st].ev_up);
-  });
-  if (rc) { hipStreamSynchronize(key->prep_stream); stage_release(key, st); return rc; }
-  PartialSums ps;
-  rc = prove_collect(key, key->slot[t], nullptr, &ps);
-  stage_release(key, st);
-  if (!rc) memcpy(partial_out, &ps, sizeof(ps));
-  return rc;
+  if (int rw = check_witness_len(key, witness_len)) return rw;
+  return prove_partial(key, Witnesses{&witness_std, true, witness_len, nullptr}, partial_out);
 }
 
 int zkr_bench_shard_split_solo(zkr_key *shard, const void *d_witness_std, double *ms_out) {
@@ -1243,17 +1198,8 @@ int zkr_bench_shard_split_solo(zkr_key *shard, const void *d_witness_std, double
 
 int zkr_prove_combine(zkr_key *key, const uint8_t *partials, size_t parts, const uint8_t *r32, const uint8_t *s32, uint8_t proof_out[256]) {
   if (!key || !partials || !proof_out || parts == 0) { set_error("null argument"); return ZKR_ERR_ARG; }
-  if ((r32 == nullptr) != (s32 == nullptr)) { set_error("pass both r and s or neither"); return ZKR_ERR_ARG; }
   uint8_t rb[32], sb[32];
-  if (r32) {
-    memcpy(rb, r32, 32); memcpy(sb, s32, 32);
-    uint32_t rv[8], sv[8];
-    memcpy(rv, rb, 32); memcpy(sv, sb, 32);
-    if (!u256_lt(rv, FrParams::P) || !u256_lt(sv, FrParams::P)) { set_error("blinding scalar >= r"); return ZKR_ERR_ARG; }
-  } else {
-    int rc;
-    if ((rc = draw_blinding(rb)) || (rc = draw_blinding(sb))) return rc;
-  }
+  if (int rc = take_blinding(r32, s32, rb, sb)) return rc;
   PartialSums sum;
   memcpy(&sum, partials, sizeof(sum));
   for (size_t i = 1; i < parts; i++) {  // the one exchange step of the sharded proof: four additions per share

@@ -1,6 +1,7 @@
 """zkr_key_check on the MI355X: every kind of key the library builds passes both levels; an arena whose header is intact but
 whose row pointers, columns, wide-row list or rank maps are damaged is refused by zkr_key_load_file, zkr_key_adopt_arena and
-zkr_key_adopt_base_arena before any kernel reads through it; value damage passes level 0 and is named by level 1.
+zkr_key_adopt_base_arena before any kernel reads through it; a header whose witness tables disagree on the window is refused at
+load; value damage passes level 0 and is named by level 1.
 
 Safety: no test proves with, or runs any kernel but the check on, a damaged key.  A damaged load that succeeds is closed at once
 and fails the test."""
@@ -27,6 +28,7 @@ FR_MODULUS = 2188824287183927522224640574525727508854836440041603434369820418657
 # csrc/zkr_internal.hpp ArenaHeader, field by field (no padding: off_tw lands at byte 64, npts at 40, nnzA at 32)
 HDR = struct.Struct("<QQ4I2I5II" "QQ2Q2Q2Q2Q2I5Q5Q" "64s64s64s128s128s" "I5II5I2I2III")
 assert HDR.size == 752
+WIN_C = struct.calcsize("<QQ4I2I5II" "QQ2Q2Q2Q2Q2I5Q5Q" "64s64s64s128s128s" "I")   # byte offset of win_c[5]
 
 
 def _header(buf):
@@ -247,6 +249,26 @@ def test_structural_damage_refused_by_adopt_base_arena(case, tx_key):
     _patch_tensor(mem, damage(host, _header(host)))
     e = _refused(lambda: zkr_hip.ProvingKey.adopt_base_arena(mem.data_ptr(), n, 0))
     assert e.code == -2 and "key check: " + names + ":" in str(e), str(e)
+
+
+def test_unequal_witness_windows_refused_by_load_file(tmp_path, monkeypatch):
+    """A, B1, B2 and C read one set of digit records of w, made with A's window.  c = 17 and c = 18 both give K = 15 window
+    levels, so a key file whose B1 window is flipped from 17 to 18 keeps every section offset valid: only that rule refuses it."""
+    import zkr_hip
+    monkeypatch.setenv("ZKR_MSM_C", "17")   # window bits of keys built in this process
+    key, _, _ = zkr_hip.ProvingKey.synth(10, want_aux=False)
+    path = str(tmp_path / "c17.zkrkey")
+    try:
+        key.save(path)
+    finally:
+        key.close()
+    blob = open(path, "rb").read()
+    assert _header(blob)["win_c"] == [17] * 5
+    bad = str(tmp_path / "bad.zkrkey")
+    with open(bad, "wb") as f:
+        f.write(_apply(blob, [_put(WIN_C + 4 * T_B1, 18)]))
+    e = _refused(lambda: zkr_hip.ProvingKey.load_file(bad))
+    assert e.code == -2 and "different windows" in str(e), str(e)
 
 
 # ---- 4. value damage: level 0 accepts it, level 1 names it

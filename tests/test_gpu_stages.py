@@ -551,7 +551,7 @@ print("PARITY", ok)
 @pytest.mark.parametrize("env", [{"ZKR_SERIAL": "1"}, {"ZKR_MSM_C": "11"}])
 def test_schedule_and_window_knobs_give_the_same_proofs(tmp_path, env):
     """The two proving-path knobs the library keeps are read once per process: the serial schedule (one stream, the profiling
-    aid: no joint A / B1 chain, every launch in order) and another window size each run in their own process and must reproduce
+    aid: every launch in order on one stream; the joint A / B1 chain stays) and another window size each run in their own process and must reproduce
     the closed form -- single proofs and fused batches, 2^9 to 2^17."""
     import subprocess
     import sys
