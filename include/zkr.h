@@ -295,6 +295,45 @@ int zkr_setup_r1cs(const void *r1cs_bin, size_t r1cs_len, const uint8_t *toxic16
 int zkr_setup_r1cs_websnark(const void *r1cs_bin, size_t r1cs_len, const uint8_t *toxic160, int device, void **pk_out, size_t *pk_len, void **vk_out,
                             size_t *vk_len);
 
+/* ---- a further party's contribution to a key's delta (what makes a key somebody else can trust) ------
+ * zkr_setup_r1cs is a ONE-party setup: whoever ran it saw (or chose) delta, and delta forges proofs.  A contributor
+ * re-randomises delta with a secret d of its own and none of the toxic values:
+ *   delta1' = d delta1, delta2' = d delta2, C'[s] = d^-1 C[s] (s > nPublic), hExps'[i] = d^-1 hExps[i]; vk_delta_2' = d vk_delta_2
+ * -- exactly the key a setup with delta d would have produced (byte for byte), sound while ONE contributor forgot its secret.
+ * The record (ZKR_CONTRIBUTION_BYTES; every coordinate 32 B LE standard form, as in vk_bin):
+ *   delta1_before (64) | delta1_after (64) | delta2_after (128) | R (64) | z (32)
+ * R, z: a Schnorr proof that the contributor knows d with delta1_after = d delta1_before -- R = k delta1_before for a fresh k,
+ * c = zkr_mimcsponge_multihash(delta1_before.x, .y, delta1_after.x, .y, delta2_after.x.re, .x.im, .y.re, .y.im, R.x, R.y),
+ * z = k + c d mod r.  Records chain by delta1_before == the previous record's delta1_after. */
+#define ZKR_CONTRIBUTION_BYTES 352
+/* key: a whole key (a shard: ZKR_ERR_ARG).  d32: 32 B LE, 1 < d < r, for reproducible tests; NULL draws d from the OS CSPRNG
+ * inside the call.  Either way d, d^-1 and the Schnorr nonce are wiped from host and device memory before the call returns.
+ * *out: a new, independent key on the same device (own arena and workspaces; every window level of C and H rebuilt from the new
+ * base points, everything else carried over); `key` is left untouched and usable, so the caller can verify the pair.  Working
+ * memory: the two keys and one compact arena; an allocation that does not fit fails with ZKR_ERR_HIP. */
+int zkr_key_contribute(const zkr_key *key, const uint8_t *d32, zkr_key **out, uint8_t record_out[ZKR_CONTRIBUTION_BYTES]);
+/* Host only (no GPU).  *valid = 1 iff every point of the record is on its curve and in its subgroup, none at infinity,
+ * delta1_after != delta1_before, z < r, z delta1_before == R + c delta1_after, and e(delta1_after, g2) == e(g1, delta2_after);
+ * zkr_last_error says what failed.  An error status only for a null pointer. */
+int zkr_contribution_check(const uint8_t record[ZKR_CONTRIBUTION_BYTES], int *valid);
+/* What a party that did NOT make the contribution runs on the key it was handed (both keys on one device).  *valid = 1 iff
+ *   1. zkr_contribution_check(record);
+ *   2. the record's delta1_before is `before`'s delta1, its delta1_after / delta2_after are `after`'s, and
+ *      e(delta1_after, delta2_before) == e(delta1_before, delta2_after);
+ *   3. same geometry, and the QAP sections, twiddles, rank maps, the A, B1 and B2 tables, alfa1, beta1, beta2 byte-identical;
+ *   4. the window levels of `after`'s C and H tables are the multiples of its own base points (rebuilt from its compact arena
+ *      and compared byte for byte; zkr_key_check level 1 only says that every stored point is on its curve);
+ *   5. e(sum rho_s C'[s] + sum sigma_i H'[i], delta2_after) == e(sum rho_s C[s] + sum sigma_i H[i], delta2_before) for 128-bit
+ *      rho_s, sigma_i from the OS CSPRNG (a wrong entry slips through with probability 2^-128), the sums by the keys' MSM path.
+ * report (may be null): [0] = the first failed step (0: none), [1] = ZKR_KEYSEC_* of the first differing section (steps 3, 4).
+ * ZKR_OK with *valid = 0 and a zkr_last_error line naming the step for a bad contribution; an error status only for bad
+ * arguments (a shard, keys on different devices: ZKR_ERR_ARG) or a HIP failure. */
+int zkr_key_contribution_verify(const zkr_key *before, const zkr_key *after, const uint8_t record[ZKR_CONTRIBUTION_BYTES], int *valid, uint64_t report[2]);
+/* Host only.  The verifying key that goes with the contributed proving key: checks the record (zkr_contribution_check) and
+ * that it continues THIS key (e(delta1_before, g2) == e(g1, vk_delta_2)), and returns a malloc'ed copy of vk_bin (zkr_free)
+ * with vk_delta_2 (bytes 320..447) replaced by the record's delta2_after; ZKR_ERR_ARG otherwise. */
+int zkr_vk_contribute(const void *vk_bin, size_t vk_len, const uint8_t record[ZKR_CONTRIBUTION_BYTES], void **vk_out, size_t *vk_out_len);
+
 /* Circuit shape drawn by the zkr_synth_* calls of the CALLING THREAD (thread-local, default 0): 0 = rollup-shaped (default; 1-3 terms
  * per row, 3 % boolean and 2 % small signals, a third of the signals absent from B), 1 = dense random (BASELINE.json
  * configs[4]: every row is (4 random signals) x (4 random signals) = new signal; no infinity points in any query). */

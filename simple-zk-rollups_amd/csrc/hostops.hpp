@@ -22,6 +22,19 @@ static inline G2Affine load_g2(const uint8_t *p) {
   return G2Affine{Fq2{load_fp<FqParams>(p), load_fp<FqParams>(p + 32)}, Fq2{load_fp<FqParams>(p + 64), load_fp<FqParams>(p + 96)}};
 }
 
+// the generators (Montgomery affine): G1 (1, 2), TxVerifier.sol:24-26; G2 in snarkjs order [re, im] (TxVerifier.sol:30-35 lists [im, re])
+static inline G1Affine g1_generator() { return G1Affine{Fq::one(), add(Fq::one(), Fq::one())}; }
+static inline G2Affine g2_generator() {
+  static const uint32_t GX0[8] = {0xd992f6edu, 0x46debd5cu, 0xf75edaddu, 0x674322d4u, 0x5e5c4479u, 0x426a0066u, 0x121f1e76u, 0x1800deefu};
+  static const uint32_t GX1[8] = {0xaef312c2u, 0x97e485b7u, 0x35a9e712u, 0xf1aa4933u, 0x31fb5d25u, 0x7260bfb7u, 0x920d483au, 0x198e9393u};
+  static const uint32_t GY0[8] = {0x66fa7daau, 0x4ce6cc01u, 0x0c43d37bu, 0xe3d1e769u, 0x8dcb408fu, 0x4aab7180u, 0xdb8c6debu, 0x12c85ea5u};
+  static const uint32_t GY1[8] = {0xd122975bu, 0x55acdadcu, 0x70b38ef3u, 0xbc4b3133u, 0x690c3395u, 0xec9e99adu, 0x585ff075u, 0x090689d0u};
+  G2Affine g;
+  memcpy(g.x.a.v, GX0, 32); memcpy(g.x.b.v, GX1, 32); memcpy(g.y.a.v, GY0, 32); memcpy(g.y.b.v, GY1, 32);
+  g.x.a = to_mont(g.x.a); g.x.b = to_mont(g.x.b); g.y.a = to_mont(g.y.a); g.y.b = to_mont(g.y.b);
+  return g;
+}
+
 // k * P, k a 256-bit standard-form integer (left-to-right double-and-add)
 template <class F>
 static inline XYZZ<F> scalar_mul(const XYZZ<F> &p, const U256 &k) {

@@ -1,0 +1,492 @@
+// zkr_contribute.hip -- a further party's delta contribution to a device key, with a record anybody can check.
+//
+// zkr_setup_r1cs is a one-party setup (as `snarkjs setup` in the reference's workflow, prover/package.json:34,37):
+// whoever ran it could know delta, and delta forges proofs.  A contributor draws d and re-randomises delta without any of the
+// toxic values:
+//     delta1' = d delta1    delta2' = d delta2    C'[s] = d^-1 C[s]  (s > nPublic)    hExps'[i] = d^-1 hExps[i]
+// which is exactly the key a setup with delta d would have produced; it is sound as long as ONE contributor forgot its secret.
+//
+// The hot part is n - p - 1 + m VARIABLE-base multiplications by ONE scalar (scale_points_kernel below); everything else is
+// what the library already does: the compact base arena (zkr_key_base_arena) holds the base points, the receiver path of a
+// replica (arena_from_base / zkr_key_adopt_base_arena) rebuilds the window levels, the keys' MSM path multiplies their C and H
+// tables by random coefficients for the check, pairing.hpp evaluates the few pairings on the host.
+#include <stddef.h>
+#include <stdio.h>
+#include <string.h>
+#include <vector>
+#include "kernels_msm.hpp"
+#include "hostops.hpp"
+#include "pairing.hpp"
+#include "zkr_internal.hpp"
+
+namespace zkr {
+
+// ---------------------------------------------------------------- the scaling kernel
+// pts[i] <- e * pts[i] for ONE scalar e, in place, affine in the key's boundary radix (x 2^256) in and out; infinity (the
+// placeholders of a table laid out over a shared support) stays infinity.  Every lane runs the same signed-binary (NAF)
+// double-and-add schedule, so the digits are wave-uniform: read through the scalar unit, branched on uniformly, no per-lane digit
+// storage and no table of multiples (a run-time indexed per-thread table would live in scratch).  The group law is the hot path's
+// (curve29.hpp: XYZZ accumulator, dbl_xyzz29, add_mixed29 with its neg_q flag for the -1 digits).  A thread takes `npt` points
+// (stride = the launch's threads, so a wavefront's loads stay contiguous), leaves each product unnormalised -- X, Y in the
+// point's own slot, ZZ, ZZZ in `ztmp` ([2][n] coordinates) -- and makes them affine with ONE inversion of the product of their
+// ZZZ (x = X ZZ^2 / ZZZ^2, y = Y / ZZZ, since ZZ^3 = ZZZ^2), as msm_precompute_kernel does over its levels.
+// `naf`: 16 words in device memory, [0..7] bit b set = digit b is non-zero, [8..15] bit b set = it is -1; `top` = index of the
+// leading digit (always +1).  The buffer is the only device copy of the secret scalar: the caller wipes it.
+constexpr int SCALE_THREADS = 256;
+constexpr int SCALE_MAX_PTS = 8;
+// Fq products of the schedule, for the accounting beside the measured times (tools/contribution_time.py):
+// dbl_xyzz29 = 9 (4 squares + 3 products + the two-product Y form), add_mixed29 = 11 (2 squares + 7 products + the two-product Y
+// form).  Per point: `top` doublings, one addition per non-zero digit below the leading one, 2 products for the radix change in,
+// ~9 + npt / 2 for the way back out, and 1 / npt of an inversion (253 squares + one product per set bit of p - 2).
+
+static __global__ __launch_bounds__(SCALE_THREADS) void scale_points_kernel(G1Affine *pts, uint32_t n, int npt, const uint32_t *naf, int top, Fq *ztmp) {
+  using C = G1C;
+  const uint32_t stride = gridDim.x * SCALE_THREADS, t0 = blockIdx.x * SCALE_THREADS + threadIdx.x;
+  auto prod = C::one().template to<4>();  // product of this thread's ZZZ
+#pragma unroll 1
+  for (int j = 0; j < npt; j++) {
+    const uint32_t i = t0 + (uint32_t)j * stride;
+    if (i >= n) break;
+    const G1Affine p = load_pod(pts + i);
+    XYZZ29<C> acc = XYZZ29<C>::inf();
+    if (!p.is_inf()) {
+      const Affine29<C> q{canonical_small(mul(C::template unpack<10>(p.x), C::to261())), canonical_small(mul(C::template unpack<10>(p.y), C::to261()))};
+      acc = make_xyzz<C>(q.x, q.y, C::one(), C::one());  // the leading digit
+#pragma unroll 1
+      for (int b = top - 1; b >= 0; b--) {
+        acc = dbl_xyzz29<C>(acc);
+        const uint32_t nz = __builtin_amdgcn_readfirstlane(naf[b >> 5]), sg = __builtin_amdgcn_readfirstlane(naf[8 + (b >> 5)]);
+        if ((nz >> (b & 31)) & 1u) acc = add_mixed29<C>(acc, q, ((sg >> (b & 31)) & 1u) != 0);
+      }
+    }
+    if (acc.is_inf()) {  // a placeholder, or (a point off the curve only) a multiple that came out as infinity: stored as infinity, a factor of one
+      if (!p.is_inf()) store_pod(pts + i, G1Affine{Fq::zero(), Fq::zero()});
+      store_pod(ztmp + i, Fq::zero());
+      store_pod(ztmp + (size_t)n + i, C::template pack<2>(C::one()));
+      continue;
+    }
+    store_pod(pts + i, G1Affine{C::template pack<3>(weak(acc.x)), C::template pack<HY>(acc.y)});
+    store_pod(ztmp + i, C::template pack<HY>(acc.zz));
+    store_pod(ztmp + (size_t)n + i, C::template pack<HY>(acc.zzz));
+    prod = mul(prod, acc.zzz).template to<4>();
+  }
+  auto inv = inv29(prod);  // 1 / (ZZZ_0 ... ZZZ_{npt-1})
+#pragma unroll 1
+  for (int j = npt - 1; j >= 0; j--) {
+    const uint32_t i = t0 + (uint32_t)j * stride;
+    if (i >= n) continue;
+    auto pre = C::one().template to<4>();  // ZZZ_0 ... ZZZ_{j-1}
+#pragma unroll 1
+    for (int l = 0; l < j; l++) pre = mul(pre, C::template unpack<HY>(load_pod(ztmp + (size_t)n + t0 + (uint32_t)l * stride))).template to<4>();
+    const auto zzz = C::template unpack<HY>(load_pod(ztmp + (size_t)n + i));
+    const auto izzz = mul(inv, pre);  // 1 / ZZZ_j
+    inv = mul(inv, zzz).template to<4>();
+    const auto zz = C::template unpack<HY>(load_pod(ztmp + i));
+    if (zz.all_zero()) continue;  // infinity
+    const auto izz = mul(sqr(zz), sqr(izzz));
+    const G1Affine a = load_pod(pts + i);
+    const auto x = mul(C::template unpack<3>(a.x), izz), y = mul(C::template unpack<HY>(a.y), izzz);
+    store_pod(pts + i, G1Affine{C::template pack<2>(canonical_small(mul(x, C::to256()))), C::template pack<2>(canonical_small(mul(y, C::to256())))});
+  }
+}
+
+// ---------------------------------------------------------------- the compare kernel
+// Byte ranges of two arenas that must agree, 16 bytes per thread and step; blockIdx.y = range.  *first = smallest index of a
+// range with a difference (the ranges come in the order faults are reported).
+struct CmpRange {
+  uint64_t off_a, off_b, units;  // units of 16 bytes (sections start 256-aligned and their slack is zeroed: arena_layout, key_build)
+  uint32_t section, table;       // ZKR_KEYSEC_* and QAP side / table, for the report
+};
+static __global__ __launch_bounds__(256) void compare_ranges_kernel(const unsigned char *a, const unsigned char *b, const CmpRange *ranges, uint32_t *first) {
+  const CmpRange r = ranges[blockIdx.y];
+  const uint4 *pa = reinterpret_cast<const uint4 *>(a + r.off_a), *pb = reinterpret_cast<const uint4 *>(b + r.off_b);
+  bool differ = false;
+  for (uint64_t u = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; u < r.units; u += (uint64_t)gridDim.x * blockDim.x) {
+    const uint4 x = pa[u], y = pb[u];
+    differ = differ || x.x != y.x || x.y != y.y || x.z != y.z || x.w != y.w;
+  }
+  if (differ) atomicMin(first, blockIdx.y);
+}
+
+namespace {
+
+const char *section_name(uint32_t s) {
+  static const char *const names[] = {"none", "row pointers", "columns", "wide rows", "rank map", "header", "points", "twiddles", "coefficients", "shared rank", "constants"};
+  return s < sizeof(names) / sizeof(names[0]) ? names[s] : "?";
+}
+
+// *first_out = index of the first differing range, 0xffffffff when the arenas agree on all of them
+int compare_ranges(int device, const unsigned char *a, const unsigned char *b, const std::vector<CmpRange> &ranges, uint32_t *first_out) {
+  ZKR_HIP_CHECK(hipSetDevice(device));
+  DevBuf dr, df;
+  int rc;
+  if ((rc = dr.alloc(ranges.size() * sizeof(CmpRange))) || (rc = df.alloc(4))) return rc;
+  const uint32_t none = 0xffffffffu;
+  ZKR_HIP_CHECK(hipMemcpy(dr.p, ranges.data(), ranges.size() * sizeof(CmpRange), hipMemcpyHostToDevice));
+  ZKR_HIP_CHECK(hipMemcpy(df.p, &none, 4, hipMemcpyHostToDevice));
+  compare_ranges_kernel<<<dim3(1024, (unsigned)ranges.size()), 256>>>(a, b, dr.as<CmpRange>(), df.as<uint32_t>());
+  ZKR_HIP_CHECK(hipGetLastError());
+  ZKR_HIP_CHECK(hipMemcpy(first_out, df.p, 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+CmpRange range_of(uint64_t off_a, uint64_t off_b, uint64_t bytes, uint32_t section, uint32_t table) { return CmpRange{off_a, off_b, (bytes + 15) / 16, section, table}; }
+
+// ---- host arithmetic on the record's members
+bool lt_words(const uint8_t *p, const uint32_t (&m)[8]) {
+  uint32_t v[8];
+  memcpy(v, p, 32);
+  for (int i = 7; i >= 0; i--)
+    if (v[i] != m[i]) return v[i] < m[i];
+  return false;
+}
+// standard-form bytes -> Montgomery affine; false for a coordinate >= q, the point at infinity or a point off its curve (G2: or
+// outside the order-r subgroup, as the verifier reads G2 members)
+bool read_g1_std(const uint8_t *p, G1Affine &out) {
+  if (!lt_words(p, FqParams::P) || !lt_words(p + 32, FqParams::P)) return false;
+  out = G1Affine{to_mont(load_fp<FqParams>(p)), to_mont(load_fp<FqParams>(p + 32))};
+  return !out.is_inf() && pairing::g1_on_curve(out);
+}
+bool read_g2_std(const uint8_t *p, G2Affine &out) {
+  for (int i = 0; i < 4; i++)
+    if (!lt_words(p + 32 * i, FqParams::P)) return false;
+  out = G2Affine{Fq2{to_mont(load_fp<FqParams>(p)), to_mont(load_fp<FqParams>(p + 32))}, Fq2{to_mont(load_fp<FqParams>(p + 64)), to_mont(load_fp<FqParams>(p + 96))}};
+  return !out.is_inf() && pairing::g2_on_curve(out) && pairing::g2_in_subgroup(out);
+}
+bool same_point(const G1XYZZ &a, const G1XYZZ &b) {
+  if (a.is_inf() || b.is_inf()) return a.is_inf() && b.is_inf();
+  const G1Affine x = to_affine(a), y = to_affine(b);
+  return x.x == y.x && x.y == y.y;
+}
+// e(a, b) == e(c, d)
+bool pairings_equal(const G1Affine &a, const G2Affine &b, const G1Affine &c, const G2Affine &d) {
+  const G1Affine ps[2] = {a, G1Affine{c.x, neg(c.y)}};
+  const G2Affine qs[2] = {b, d};
+  return pairing::pairing_product_is_one(ps, qs, 2);
+}
+
+// record layout (ZKR_CONTRIBUTION_BYTES): delta1_before | delta1_after | delta2_after | R | z
+constexpr size_t REC_D1B = 0, REC_D1A = 64, REC_D2A = 128, REC_R = 256, REC_Z = 320;
+// the Schnorr challenge: the library's host MiMC sponge over the ten coordinates the proof binds
+int challenge(const uint8_t *d1b, const uint8_t *d1a, const uint8_t *d2a, const uint8_t *r, uint8_t c_out[32]) {
+  uint8_t in[320];
+  memcpy(in, d1b, 64); memcpy(in + 64, d1a, 64); memcpy(in + 128, d2a, 128); memcpy(in + 256, r, 64);
+  return zkr_mimcsponge_multihash(in, 10, c_out);
+}
+
+struct Parsed {
+  G1Affine d1b, d1a, r;
+  G2Affine d2a;
+};
+// everything zkr_contribution_check states; `why` names what failed
+bool record_valid(const uint8_t *rec, Parsed &p, const char **why) {
+  if (!read_g1_std(rec + REC_D1B, p.d1b) || !read_g1_std(rec + REC_D1A, p.d1a) || !read_g1_std(rec + REC_R, p.r)) { *why = "a G1 member is at infinity, out of range or off the curve"; return false; }
+  if (!read_g2_std(rec + REC_D2A, p.d2a)) { *why = "delta2_after is not a member of G2"; return false; }
+  if (memcmp(rec + REC_D1B, rec + REC_D1A, 64) == 0) { *why = "delta did not move"; return false; }
+  if (!lt_words(rec + REC_Z, FrParams::P)) { *why = "z is not below r"; return false; }
+  uint8_t c[32];
+  if (challenge(rec + REC_D1B, rec + REC_D1A, rec + REC_D2A, rec + REC_R, c)) { *why = "challenge hash failed"; return false; }
+  // z delta1_before == R + c delta1_after
+  const G1XYZZ lhs = scalar_mul(to_xyzz(p.d1b), load_u256(rec + REC_Z));
+  const G1XYZZ rhs = add_full(to_xyzz(p.r), scalar_mul(to_xyzz(p.d1a), load_u256(c)));
+  if (!same_point(lhs, rhs)) { *why = "the proof of knowledge of d does not verify"; return false; }
+  if (!pairings_equal(p.d1a, g2_generator(), g1_generator(), p.d2a)) { *why = "delta1_after and delta2_after are not the same multiple of the generators"; return false; }
+  return true;
+}
+
+void store_g1_mont(uint8_t *out, const G1Affine &a) { store_fp(out, a.x); store_fp(out + 32, a.y); }
+void store_g2_mont(uint8_t *out, const G2Affine &a) { store_fp(out, a.x.a); store_fp(out + 32, a.x.b); store_fp(out + 64, a.y.a); store_fp(out + 96, a.y.b); }
+
+// draws 1 < v < r from the OS CSPRNG (rejection sampling over 254 bits)
+int draw_secret(U256 &v) {
+  FILE *f = fopen("/dev/urandom", "rb");
+  if (!f) { set_error("cannot open /dev/urandom"); return ZKR_ERR_ARG; }
+  uint8_t b[32];
+  int rc = 0;
+  for (;;) {
+    if (fread(b, 1, 32, f) != 32) { set_error("short read from /dev/urandom"); rc = ZKR_ERR_ARG; break; }
+    b[31] &= 0x3f;
+    bool small = b[0] <= 1;
+    for (int i = 1; i < 32 && small; i++) small = b[i] == 0;
+    if (lt_words(b, FrParams::P) && !small) break;
+  }
+  fclose(f);
+  if (!rc) memcpy(v.v, b, 32);
+  explicit_bzero(b, sizeof(b));
+  return rc;
+}
+
+// signed binary (non-adjacent) form of e: nz bit b = digit b non-zero, sg bit b = digit b is -1; returns the leading digit's index
+int naf_of(const U256 &e, uint32_t nz[8], uint32_t sg[8]) {
+  uint32_t k[9];
+  memcpy(k, e.v, 32);
+  k[8] = 0;
+  memset(nz, 0, 32); memset(sg, 0, 32);
+  int top = 0;
+  for (int b = 0; b < 256; b++) {
+    if (k[0] & 1u) {
+      nz[b >> 5] |= 1u << (b & 31);
+      top = b;
+      if ((k[0] & 3u) == 3u) {  // digit -1: k += 1
+        sg[b >> 5] |= 1u << (b & 31);
+        for (int i = 0; i < 9 && ++k[i] == 0; i++) {}
+      } else k[0] -= 1u;
+    }
+    for (int i = 0; i < 8; i++) k[i] = (k[i] >> 1) | (k[i + 1] << 31);
+    k[8] >>= 1;
+  }
+  explicit_bzero(k, sizeof(k));
+  return top;
+}
+
+// everything that reveals d: wiped however zkr_key_contribute is left
+struct Secrets {
+  U256 d, dinv, nonce, z;
+  Fr dm, tmp;
+  uint32_t naf[16];
+  DevBuf d_naf;
+  ~Secrets() {
+    if (d_naf.p) { (void)hipMemset(d_naf.p, 0, sizeof(naf)); (void)hipDeviceSynchronize(); }
+    explicit_bzero(&d, sizeof(d)); explicit_bzero(&dinv, sizeof(dinv)); explicit_bzero(&nonce, sizeof(nonce)); explicit_bzero(&z, sizeof(z));
+    explicit_bzero(&dm, sizeof(dm)); explicit_bzero(&tmp, sizeof(tmp)); explicit_bzero(naf, sizeof(naf));
+  }
+};
+
+int refuse_shard(const zkr_key *key, const char *what) {
+  if (key->h.shard_parts <= 1) return 0;
+  set_error("%s: this key is shard %u of %u of a proving key; it takes a whole key", what, key->h.shard_part, key->h.shard_parts);
+  return ZKR_ERR_ARG;
+}
+
+int scale_table(int device, G1Affine *pts, uint32_t n, const uint32_t *d_naf, int top, Fq *ztmp) {
+  if (!n) return 0;
+  // points per thread: one while that leaves the chip short of wavefronts (4 per SIMD on 1024 SIMDs), up to SCALE_MAX_PTS
+  int npt = (int)(n / (1024u * 64u * 4u));
+  npt = npt < 1 ? 1 : npt > SCALE_MAX_PTS ? SCALE_MAX_PTS : npt;
+  const uint32_t threads = (n + (uint32_t)npt - 1) / (uint32_t)npt;
+  scale_points_kernel<<<(threads + SCALE_THREADS - 1) / SCALE_THREADS, SCALE_THREADS>>>(pts, n, npt, d_naf, top, ztmp);
+  ZKR_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+}  // namespace
+}  // namespace zkr
+
+using namespace zkr;
+
+extern "C" {
+
+int zkr_contribution_check(const uint8_t record[ZKR_CONTRIBUTION_BYTES], int *valid) {
+  if (!record || !valid) { set_error("null argument"); return ZKR_ERR_ARG; }
+  Parsed p;
+  const char *why = "";
+  *valid = record_valid(record, p, &why) ? 1 : 0;
+  if (!*valid) set_error("contribution record: %s", why);
+  return 0;
+}
+
+int zkr_vk_contribute(const void *vk_bin, size_t vk_len, const uint8_t record[ZKR_CONTRIBUTION_BYTES], void **vk_out, size_t *vk_out_len) {
+  if (!vk_bin || !record || !vk_out || !vk_out_len) { set_error("null argument"); return ZKR_ERR_ARG; }
+  const uint8_t *vk = (const uint8_t *)vk_bin;
+  const size_t fixed = 64 + 3 * 128 + 4;
+  uint32_t n_ic = 0;
+  if (vk_len >= fixed) memcpy(&n_ic, vk + 64 + 3 * 128, 4);
+  if (vk_len < fixed || vk_len != fixed + 64ull * n_ic) { set_error("verifying key length %zu does not match its IC count", vk_len); return ZKR_ERR_ARG; }
+  Parsed p;
+  const char *why = "";
+  if (!record_valid(record, p, &why)) { set_error("contribution record: %s", why); return ZKR_ERR_ARG; }
+  G2Affine vk_delta2;
+  if (!read_g2_std(vk + 320, vk_delta2)) { set_error("vk_delta_2 is not a member of G2"); return ZKR_ERR_ARG; }
+  if (!pairings_equal(p.d1b, g2_generator(), g1_generator(), vk_delta2)) { set_error("the record does not continue this verifying key (its delta1_before is not this key's delta)"); return ZKR_ERR_ARG; }
+  uint8_t *out = (uint8_t *)malloc(vk_len);
+  if (!out) { set_error("out of memory"); return ZKR_ERR_ARG; }
+  memcpy(out, vk, vk_len);
+  memcpy(out + 320, record + REC_D2A, 128);
+  *vk_out = out;
+  *vk_out_len = vk_len;
+  return 0;
+}
+
+int zkr_key_contribute(const zkr_key *key, const uint8_t *d32, zkr_key **out, uint8_t record_out[ZKR_CONTRIBUTION_BYTES]) {
+  if (!key || !out || !record_out) { set_error("null argument"); return ZKR_ERR_ARG; }
+  if (int rs = refuse_shard(key, "zkr_key_contribute")) return rs;
+  Secrets s;
+  int rc;
+  if (d32) {
+    bool small = d32[0] <= 1;
+    for (int i = 1; i < 32 && small; i++) small = d32[i] == 0;
+    if (small || !lt_words(d32, FrParams::P)) { set_error("zkr_key_contribute: d must satisfy 1 < d < r"); return ZKR_ERR_ARG; }
+    memcpy(s.d.v, d32, 32);
+  } else if ((rc = draw_secret(s.d))) return rc;
+  if ((rc = draw_secret(s.nonce))) return rc;
+  memcpy(s.dm.v, s.d.v, 32);
+  s.dm = to_mont(s.dm);
+  s.tmp = from_mont(inv(s.dm));
+  memcpy(s.dinv.v, s.tmp.v, 32);
+  const int top = naf_of(s.dinv, s.naf, s.naf + 8);
+
+  // the new delta and the record (host; a few hundred group operations)
+  const ArenaHeader &h = key->h;
+  const G1Affine d1b = load_g1(h.delta1);
+  const G2Affine d2b = load_g2(h.delta2);
+  const G1XYZZ d1a_x = scalar_mul(to_xyzz(d1b), s.d);
+  const G2XYZZ d2a_x = scalar_mul(to_xyzz(d2b), s.d);
+  const G1XYZZ r_x = scalar_mul(to_xyzz(d1b), s.nonce);
+  if (d1b.is_inf() || d1a_x.is_inf() || d2a_x.is_inf() || r_x.is_inf()) { set_error("zkr_key_contribute: the key's delta is not a point of order r"); return ZKR_ERR_BAD_KEY; }
+  const G1Affine d1a = to_affine(d1a_x), r_pt = to_affine(r_x);
+  const G2Affine d2a = to_affine(d2a_x);
+  uint8_t rec[ZKR_CONTRIBUTION_BYTES];
+  store_g1_std(rec + REC_D1B, d1b); store_g1_std(rec + REC_D1A, d1a); store_g2_std(rec + REC_D2A, d2a); store_g1_std(rec + REC_R, r_pt);
+  uint8_t c[32];
+  if ((rc = challenge(rec + REC_D1B, rec + REC_D1A, rec + REC_D2A, rec + REC_R, c))) return rc;
+  {  // z = k + c d mod r
+    Fr cm = to_mont(load_fp<FrParams>(c)), km;
+    memcpy(km.v, s.nonce.v, 32);
+    s.tmp = from_mont(add(to_mont(km), mul(cm, s.dm)));
+    explicit_bzero(&km, sizeof(km));
+    memcpy(s.z.v, s.tmp.v, 32);
+    memcpy(rec + REC_Z, s.z.v, 32);  // z itself is public
+  }
+
+  // a device copy of the compact arena (the key's own is cached on it and stays as it is): scale C and H there, patch delta
+  void *base = nullptr;
+  size_t base_len = 0;
+  if ((rc = zkr_key_base_arena(const_cast<zkr_key *>(key), &base, &base_len))) return rc;
+  ZKR_HIP_CHECK(hipSetDevice(key->device));
+  ArenaHeader b;
+  base_layout(h, b);
+  DevBuf copy, ztmp;
+  const uint32_t n_max = h.npts[T_C] > h.npts[T_H] ? h.npts[T_C] : h.npts[T_H];
+  if ((rc = copy.alloc(base_len)) || (rc = ztmp.alloc((size_t)n_max * 2 * sizeof(Fq))) || (rc = s.d_naf.alloc(sizeof(s.naf)))) return rc;
+  ZKR_HIP_CHECK(hipMemcpy(copy.p, base, base_len, hipMemcpyDeviceToDevice));
+  ZKR_HIP_CHECK(hipMemcpy(s.d_naf.p, s.naf, sizeof(s.naf), hipMemcpyHostToDevice));
+  unsigned char *cb = copy.as<unsigned char>();
+  for (int t : {T_C, T_H})
+    if ((rc = scale_table(key->device, (G1Affine *)(cb + b.off_pts[t]), h.npts[t], s.d_naf.as<uint32_t>(), top, ztmp.as<Fq>()))) return rc;
+  uint8_t consts[192];
+  store_g1_mont(consts, d1a);
+  store_g2_mont(consts + 64, d2a);
+  ZKR_HIP_CHECK(hipMemcpy(cb + offsetof(ArenaHeader, delta1), consts, 64, hipMemcpyHostToDevice));
+  ZKR_HIP_CHECK(hipMemcpy(cb + offsetof(ArenaHeader, delta2), consts + 64, 128, hipMemcpyHostToDevice));
+  {
+    hipError_t e = hipDeviceSynchronize();
+    if (e != hipSuccess) { set_error("scaling the C and H points failed: %s", hipGetErrorString(e)); return ZKR_ERR_HIP; }
+  }
+  // the receiver path of a replica: THE layout, window levels, twiddles, level-0 check, workspaces
+  if ((rc = zkr_key_adopt_base_arena(copy.p, base_len, key->device, out))) return rc;
+  memcpy(record_out, rec, ZKR_CONTRIBUTION_BYTES);
+  return 0;
+}
+
+int zkr_key_contribution_verify(const zkr_key *before, const zkr_key *after, const uint8_t record[ZKR_CONTRIBUTION_BYTES], int *valid, uint64_t report[2]) {
+  if (!before || !after || !record || !valid) { set_error("null argument"); return ZKR_ERR_ARG; }
+  *valid = 0;
+  uint64_t rep_local[2];
+  uint64_t *rep = report ? report : rep_local;
+  rep[0] = rep[1] = 0;
+  if (int rs = refuse_shard(before, "zkr_key_contribution_verify")) return rs;
+  if (int rs = refuse_shard(after, "zkr_key_contribution_verify")) return rs;
+  if (before->device != after->device) { set_error("zkr_key_contribution_verify: the keys live on devices %d and %d; replicate one to the other's", before->device, after->device); return ZKR_ERR_ARG; }
+  const int device = before->device;
+  const ArenaHeader &hb = before->h, &ha = after->h;
+  auto fail = [&](uint64_t step, uint64_t section, const char *what) {
+    rep[0] = step; rep[1] = section;
+    set_error("contribution verify: step %llu failed: %s", (unsigned long long)step, what);
+    return 0;
+  };
+  // 1. the record by itself
+  Parsed p;
+  const char *why = "";
+  if (!record_valid(record, p, &why)) return fail(1, 0, why);
+  // 2. the record is about THESE keys, and delta moved by the same factor in both groups
+  uint8_t m1[64], m2[128];
+  store_g1_mont(m1, p.d1b);
+  if (memcmp(m1, hb.delta1, 64) != 0) return fail(2, 0, "the record's delta1_before is not the first key's delta1");
+  store_g1_mont(m1, p.d1a);
+  store_g2_mont(m2, p.d2a);
+  if (memcmp(m1, ha.delta1, 64) != 0 || memcmp(m2, ha.delta2, 128) != 0) return fail(2, 0, "the record's delta1_after / delta2_after are not the second key's");
+  const G2Affine d2b = load_g2(hb.delta2);
+  if (d2b.is_inf() || !pairing::g2_on_curve(d2b) || !pairing::g2_in_subgroup(d2b)) return fail(2, 0, "the first key's delta2 is not a member of G2");
+  if (!pairings_equal(p.d1a, d2b, p.d1b, p.d2a)) return fail(2, 0, "delta1 and delta2 moved by different factors");
+  // 3. same geometry, and everything a contribution must not touch byte-identical
+  {
+    bool geo = ha.total_len == hb.total_len && ha.n == hb.n && ha.p == hb.p && ha.m == hb.m && ha.logm == hb.logm && ha.nnzA == hb.nnzA && ha.nnzB == hb.nnzB && ha.tlog == hb.tlog &&
+               ha.share_b == hb.share_b && ha.share_ac == hb.share_ac && ha.off_tw == hb.off_tw && ha.off_twl == hb.off_twl;
+    for (int s = 0; s < 2; s++)
+      geo = geo && ha.n_wide[s] == hb.n_wide[s] && ha.off_rowptr[s] == hb.off_rowptr[s] && ha.off_col[s] == hb.off_col[s] && ha.off_coef[s] == hb.off_coef[s] && ha.off_wide[s] == hb.off_wide[s];
+    for (int t = 0; t < N_TABLES; t++)
+      geo = geo && ha.npts[t] == hb.npts[t] && ha.win_c[t] == hb.win_c[t] && ha.rank_identity[t] == hb.rank_identity[t] && ha.off_pts[t] == hb.off_pts[t] && ha.off_rank[t] == hb.off_rank[t];
+    if (!geo) return fail(3, ZKR_KEYSEC_HEADER, "the keys differ in geometry (sizes, point counts, windows)");
+    if (memcmp(ha.alfa1, hb.alfa1, 64) != 0 || memcmp(ha.beta1, hb.beta1, 64) != 0 || memcmp(ha.beta2, hb.beta2, 128) != 0) return fail(3, ZKR_KEYSEC_CONSTS, "alfa1, beta1 or beta2 changed");
+  }
+  auto levels = [&](int t) { return (uint64_t)((255 + ha.win_c[t] - 1) / ha.win_c[t]); };
+  {
+    std::vector<CmpRange> rg;
+    for (int s = 0; s < 2; s++) {
+      const uint64_t nnz = s == 0 ? ha.nnzA : ha.nnzB;
+      rg.push_back(range_of(ha.off_rowptr[s], hb.off_rowptr[s], ((uint64_t)ha.m + 1) * 4, ZKR_KEYSEC_ROWPTR, (uint32_t)s));
+      rg.push_back(range_of(ha.off_col[s], hb.off_col[s], nnz * 4, ZKR_KEYSEC_COL, (uint32_t)s));
+      rg.push_back(range_of(ha.off_wide[s], hb.off_wide[s], (uint64_t)ha.n_wide[s] * 4, ZKR_KEYSEC_WIDE, (uint32_t)s));
+    }
+    for (int t = 0; t < N_TABLES; t++) rg.push_back(range_of(ha.off_rank[t], hb.off_rank[t], (uint64_t)rank_entries(ha, t) * 4, ZKR_KEYSEC_RANK, (uint32_t)t));
+    for (int t : {T_A, T_B1, T_B2}) rg.push_back(range_of(ha.off_pts[t], hb.off_pts[t], (uint64_t)ha.npts[t] * levels(t) * (t == T_B2 ? 128 : 64), ZKR_KEYSEC_POINTS, (uint32_t)t));
+    rg.push_back(range_of(ha.off_tw, hb.off_tw, (uint64_t)ha.m * 32, ZKR_KEYSEC_TWIDDLES, 0));
+    rg.push_back(range_of(ha.off_twl, hb.off_twl, ha.off_rowptr[0] - ha.off_twl, ZKR_KEYSEC_TWIDDLES, 1));  // the local table, up to the next section
+    for (int s = 0; s < 2; s++) rg.push_back(range_of(ha.off_coef[s], hb.off_coef[s], (uint64_t)(s == 0 ? ha.nnzA : ha.nnzB) * 32, ZKR_KEYSEC_COEF, (uint32_t)s));
+    uint32_t first = 0;
+    if (int rc = compare_ranges(device, after->arena, before->arena, rg, &first)) return rc;
+    if (first != 0xffffffffu) {
+      char msg[96];
+      snprintf(msg, sizeof(msg), "the %s (side / table %u) differ between the keys", section_name(rg[first].section), rg[first].table);
+      return fail(3, rg[first].section, msg);
+    }
+  }
+  // 4. the window levels of `after`'s C and H tables are what its own base points give: rebuilt, compared, freed
+  {
+    void *base = nullptr;
+    size_t base_len = 0;
+    if (int rc = zkr_key_base_arena(const_cast<zkr_key *>(after), &base, &base_len)) return rc;
+    unsigned char *tmp = nullptr;
+    ArenaHeader ht;
+    if (int rc = arena_from_base(base, base_len, device, &tmp, &ht)) return rc;
+    DevBuf tmp_owner;
+    tmp_owner.p = tmp;
+    std::vector<CmpRange> rg;
+    for (int t : {T_C, T_H}) rg.push_back(range_of(ha.off_pts[t], ht.off_pts[t], (uint64_t)ha.npts[t] * levels(t) * 64, ZKR_KEYSEC_POINTS, (uint32_t)t));
+    uint32_t first = 0;
+    if (ht.total_len != ha.total_len || ht.off_pts[T_C] != ha.off_pts[T_C] || ht.off_pts[T_H] != ha.off_pts[T_H]) return fail(4, ZKR_KEYSEC_HEADER, "the rebuilt arena has another layout");
+    if (int rc = compare_ranges(device, after->arena, tmp, rg, &first)) return rc;
+    if (first != 0xffffffffu) return fail(4, ZKR_KEYSEC_POINTS, first == 0 ? "the window levels of the C table are not the multiples of its base points" : "the window levels of the H table are not the multiples of its base points");
+  }
+  // 5. every C and H point moved by the inverse factor: random 128-bit combinations of both keys' tables (2^-128 per wrong entry)
+  {
+    const size_t nw = rank_entries(ha, T_C), nh = rank_entries(ha, T_H);
+    std::vector<uint8_t> sc((nw + nh) * 32, 0);
+    {
+      FILE *f = fopen("/dev/urandom", "rb");
+      if (!f) { set_error("cannot open /dev/urandom"); return ZKR_ERR_ARG; }
+      std::vector<uint8_t> rnd((nw + nh) * 16);
+      const bool bad = fread(rnd.data(), 1, rnd.size(), f) != rnd.size();
+      fclose(f);
+      if (bad) { set_error("short read from /dev/urandom"); return ZKR_ERR_ARG; }
+      for (size_t i = 0; i < nw + nh; i++) memcpy(&sc[32 * i], &rnd[16 * i], 16);
+    }
+    ZKR_HIP_CHECK(hipSetDevice(device));
+    DevBuf dsc;
+    if (int rc = dsc.alloc(sc.size())) return rc;
+    ZKR_HIP_CHECK(hipMemcpy(dsc.p, sc.data(), sc.size(), hipMemcpyHostToDevice));
+    G1XYZZ sum[2];  // after, before
+    const zkr_key *keys[2] = {after, before};
+    for (int j = 0; j < 2; j++) {
+      G1XYZZ c_sum, h_sum;
+      if (int rc = key_table_msm(keys[j], T_C, dsc.as<Fr>(), &c_sum)) return rc;
+      if (int rc = key_table_msm(keys[j], T_H, dsc.as<Fr>() + nw, &h_sum)) return rc;
+      sum[j] = add_full(c_sum, h_sum);
+    }
+    if (sum[0].is_inf() != sum[1].is_inf()) return fail(5, 0, "the C and H points did not move by the inverse of delta's factor");
+    if (!sum[0].is_inf() && !pairings_equal(to_affine(sum[0]), p.d2a, to_affine(sum[1]), d2b)) return fail(5, 0, "the C and H points did not move by the inverse of delta's factor");
+  }
+  *valid = 1;
+  return 0;
+}
+
+}  // extern "C"

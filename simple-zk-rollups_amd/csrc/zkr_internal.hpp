@@ -250,6 +250,10 @@ void arena_layout(ArenaHeader &h);  // section offsets and total_len from the si
 const char *arena_header_fault(const ArenaHeader &h, size_t len);  // null when a full arena's header is consistent with its sizes
 const char *window_fault(const ArenaHeader &h);  // null when the header's windows are ones the proof path can run with
 void base_layout(const ArenaHeader &full, ArenaHeader &b);  // the same for the compact form (zkr_key_base_arena)
+int arena_from_base(const void *dev_ptr, size_t len, int device, unsigned char **arena_out, ArenaHeader *h_out);  // the full arena a compact one stands for, rebuilt (caller hipFree's)
+// zkr_prove.hip: sum_s scalars[s] * (table t of the key)[rank[s]] by the key's MSM path on a workspace of its own (zkr_key_contribution_verify);
+// d_scalars: the table's whole scalar vector on the key's device, standard form below r; *out as the proof assembly reads MSM results
+int key_table_msm(const zkr_key *k, int t, const Fr *d_scalars, XYZZ<Fq> *out);
 // zkr_key_check.hip: what an arena whose header passed arena_header_fault CONTAINS (zkr_key_check; level 0 structure, 1 values)
 int key_arena_check(int device, const unsigned char *arena, const ArenaHeader &h, int level, uint64_t report[4]);
 MsmPlan msm_plan(size_t n_scalars, size_t n_points, int c_fixed = 0);

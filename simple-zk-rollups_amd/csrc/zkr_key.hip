@@ -606,14 +606,7 @@ int fixed_base_points(int device, bool g2, const uint8_t *scalars_std, size_t n,
     G1Affine g{Fq::one(), add(Fq::one(), Fq::one())};  // (1, 2), TxVerifier.sol:24-26
     return fixed_base_impl<Fq>(device, g, scalars_std, n, d_out, wipe_scalars);
   }
-  // G2 generator, snarkjs order [re, im] (TxVerifier.sol:30-35 lists [im, re])
-  static const uint32_t GX0[8] = {0xd992f6edu, 0x46debd5cu, 0xf75edaddu, 0x674322d4u, 0x5e5c4479u, 0x426a0066u, 0x121f1e76u, 0x1800deefu};
-  static const uint32_t GX1[8] = {0xaef312c2u, 0x97e485b7u, 0x35a9e712u, 0xf1aa4933u, 0x31fb5d25u, 0x7260bfb7u, 0x920d483au, 0x198e9393u};
-  static const uint32_t GY0[8] = {0x66fa7daau, 0x4ce6cc01u, 0x0c43d37bu, 0xe3d1e769u, 0x8dcb408fu, 0x4aab7180u, 0xdb8c6debu, 0x12c85ea5u};
-  static const uint32_t GY1[8] = {0xd122975bu, 0x55acdadcu, 0x70b38ef3u, 0xbc4b3133u, 0x690c3395u, 0xec9e99adu, 0x585ff075u, 0x090689d0u};
-  G2Affine g;
-  memcpy(g.x.a.v, GX0, 32); memcpy(g.x.b.v, GX1, 32); memcpy(g.y.a.v, GY0, 32); memcpy(g.y.b.v, GY1, 32);
-  g.x.a = to_mont(g.x.a); g.x.b = to_mont(g.x.b); g.y.a = to_mont(g.y.a); g.y.b = to_mont(g.y.b);
+  const G2Affine g = g2_generator();
   return fixed_base_impl<Fq2>(device, g, scalars_std, n, d_out, wipe_scalars);
 }
 
@@ -874,9 +867,12 @@ int zkr_key_base_arena(zkr_key *k, void **dev_ptr, size_t *len) {
   return 0;
 }
 
-int zkr_key_adopt_base_arena(const void *dev_ptr, size_t len, int device, zkr_key **out) {
-  if (!dev_ptr || !out) { set_error("null argument"); return ZKR_ERR_ARG; }
-  if (zkr_device_count() <= device || device < 0) { set_error("no HIP device %d", device); return ZKR_ERR_NO_DEVICE; }
+}  // extern "C"
+namespace zkr {
+// The full arena a compact one stands for, rebuilt on `device` (the caller hipFree's *arena_out): sections copied to their
+// places in THE layout, window levels and twiddles recomputed.  The receiver of a replica makes a key of it
+// (zkr_key_adopt_base_arena); zkr_key_contribution_verify compares it with the arena it was handed.
+int arena_from_base(const void *dev_ptr, size_t len, int device, unsigned char **arena_out, ArenaHeader *h_out) {
   ZKR_HIP_CHECK(hipSetDevice(device));
   if (len < ARENA_HEADER_BYTES) { set_error("compact arena too small"); return ZKR_ERR_BAD_KEY; }
   ArenaHeader b;
@@ -936,10 +932,23 @@ int zkr_key_adopt_base_arena(const void *dev_ptr, size_t len, int device, zkr_ke
   e = hipGetLastError();
   if (e == hipSuccess) e = hipDeviceSynchronize();
   if (e != hipSuccess) { hipFree(arena); set_error("rebuilding the window tables failed: %s", hipGetErrorString(e)); return ZKR_ERR_HIP; }
+  *arena_out = arena;
+  *h_out = h;
+  return 0;
+}
+}  // namespace zkr
+extern "C" {
+
+int zkr_key_adopt_base_arena(const void *dev_ptr, size_t len, int device, zkr_key **out) {
+  if (!dev_ptr || !out) { set_error("null argument"); return ZKR_ERR_ARG; }
+  if (zkr_device_count() <= device || device < 0) { set_error("no HIP device %d", device); return ZKR_ERR_NO_DEVICE; }
+  unsigned char *arena = nullptr;
+  ArenaHeader h;
+  if (int brc = arena_from_base(dev_ptr, len, device, &arena, &h)) return brc;
   zkr_key *k = new zkr_key();
   k->device = device;
   k->arena = arena;
-  k->arena_len = off;
+  k->arena_len = h.total_len;
   k->owns_arena = true;
   k->h = h;
   int rc = key_alloc_workspace(k);

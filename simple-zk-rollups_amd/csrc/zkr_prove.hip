@@ -1324,6 +1324,29 @@ static int msm_hook(const void *points_mont, const void *scalars_std, size_t n, 
   return 0;
 }
 
+namespace zkr {
+int key_table_msm(const zkr_key *k, int t, const Fr *d_scalars, G1XYZZ *out) {
+  if (t == T_B2) { set_error("key_table_msm: G1 tables only"); return ZKR_ERR_ARG; }
+  ZKR_HIP_CHECK(hipSetDevice(k->device));
+  const ArenaHeader &h = k->h;
+  *out = G1XYZZ::inf();
+  if (!h.npts[t]) return 0;
+  struct WsGuard {
+    MsmWorkspace ws;
+    ~WsGuard() { msm_ws_free(ws); }
+  } g;
+  int rc = msm_ws_alloc(g.ws, h.npts[t], k->plan[t], sizeof(G1XYZZ));
+  if (rc) return rc;
+  rc = msm_enqueue<Fq>(Prof{nullptr, nullptr}, nullptr, (const G1Affine *)(k->arena + h.off_pts[t]), (const uint32_t *)(k->arena + h.off_rank[t]), d_scalars,
+                       rank_entries(h, t), h.npts[t], k->plan[t], g.ws);
+  hipError_t e = hipDeviceSynchronize();  // also after a failed enqueue: the workspace goes with this scope
+  if (!rc && e != hipSuccess) { set_error("msm over a key table failed: %s", hipGetErrorString(e)); rc = ZKR_ERR_HIP; }
+  if (rc) return rc;
+  *out = msm_finish<Fq>(h.npts[t], g.ws);
+  return 0;
+}
+}  // namespace zkr
+
 extern "C" {
 
 int zkr_msm_g1(const void *points_mont, const void *scalars_std, size_t n, uint8_t out[64], int *is_inf, int device) {

@@ -23,6 +23,9 @@ export interface Bn128 {
   setup(circuitDef: any, opts?: { toxic?: Array<bigint | string> }): any;
   /** The same for a constraint system in the r1cs_bin layout (RollupCircuit.r1cs()). */
   setupR1cs(r1csBin: Uint8Array, opts?: { toxic?: Array<bigint | string> }): any;
+  /** A further party's contribution to the held key's delta (zkr_key_contribute): the object's key becomes the contributed one;
+   *  returns the 352-byte record.  opts.d: the secret (1 < d < r) for reproducible tests; by default drawn inside the library. */
+  contribute(opts?: { d?: bigint | string }): { record: Uint8Array };
   saveKey(path: string): void;
   loadKeyFile(path: string): void;
   /** What the held key's arena contains (zkr_key_check): every index the kernels follow stays inside its section; with
@@ -41,6 +44,10 @@ export function binarifyProvingKey(provingKey: any): ArrayBuffer;
 export function solidityProof(proof: Groth16Proof, publicSignals: Array<bigint | string>): { a: string[]; b: string[][]; c: string[]; inputs: string[] };
 /** snarkjs groth.isValid(vk, proof, publicSignals) on the native host verifier (no GPU needed). */
 export function isValid(verifyingKey: any, proof: Groth16Proof, publicSignals: Array<bigint | string>): boolean;
+/** The record of a delta contribution by itself: points on their curves, the Schnorr proof, the pairing check (host only). */
+export function contributionCheck(record: Uint8Array): boolean;
+/** vkBin with vk_delta_2 replaced by the record's delta2_after; throws for a bad record or one that does not continue this key. */
+export function vkContribute(vkBin: Uint8Array, record: Uint8Array): Uint8Array;
 /** All proofs of a batch under one key with one merged pairing product (random linear combination). */
 export function isValidBatch(verifyingKey: any, proofs: Groth16Proof[], publicSignalsList: Array<Array<bigint | string>>): boolean;
 export function binarifyVerifyingKey(verifyingKey: any): Uint8Array;

@@ -269,6 +269,17 @@ class Bn128 {
     this._key = key; this._fp = "setup";
     return verifyingKeyFromBytes(vkBin);
   }
+  // A further party's contribution to the held key's delta (zkr_key_contribute): the object's key becomes the contributed one.
+  // opts.d: the secret (1 < d < r) for reproducible tests; by default it is drawn from the OS CSPRNG inside the library and wiped
+  // there.  Returns the 352-byte record anybody can check (contributionCheck) and apply to the verifying key (vkContribute;
+  // solidityVerifyingKeySource of the result regenerates the contract's constants).
+  contribute(opts) {
+    if (!this._key) throw new Error("no key loaded");
+    const d = opts && opts.d !== undefined ? bigintToLe32(BigInt(opts.d)) : null;
+    const [key, record] = native().keyContribute(this._key, d);
+    this._key = key; this._fp = "contributed"; this._replicas = null;
+    return { record: new Uint8Array(record) };
+  }
   saveKey(path) { if (!this._key) throw new Error("no key loaded"); native().keySave(this._key, path); }
   loadKeyFile(path) { this._key = native().keyLoadFile(path, this.device); this._fp = "file:" + path; }
   // what the held key's arena contains (zkr_key_check): the structure, and with { deep: true } the values as well (every point of
@@ -418,6 +429,11 @@ function isValid(vk, proof, publicSignals) {
   return native().verify(binarifyVerifyingKey(vk), pb, pub);
 }
 
+// the record of a delta contribution by itself (zkr_contribution_check), and the verifying key that goes with the contributed
+// proving key: vkBin with vk_delta_2 replaced (zkr_vk_contribute; throws for a bad record or one that does not continue this key)
+function contributionCheck(record) { return native().contributionCheck(record); }
+function vkContribute(vkBin, record) { return native().vkContribute(vkBin, record); }  // a Buffer, like binarifyVerifyingKey's
+
 // every proof of a batch under one key, merged into one pairing product (zkr_verify_batch): true iff all verify
 function isValidBatch(vk, proofs, publicSignalsList) {
   if (proofs.length === 0) return true;
@@ -518,6 +534,7 @@ class WithdrawCircuit {
 
 module.exports = {
   buildBn128, genProof, binarifyWitness, binarifyProvingKey, solidityProof, proofFromBytes, isValid, isValidBatch, binarifyVerifyingKey,
+  contributionCheck, vkContribute,
   binarifyR1cs, verifyingKeyFromBytes, solidityVerifyingKey, solidityVerifyingKeySource,
   // which form the last sharded proof took and why ({form: "split" | "replicated" | "none", reason}); how a key handle came to its device
   shardedLastForm: () => native().shardedLastForm(), keyReplication: (key) => native().keyReplication(key),

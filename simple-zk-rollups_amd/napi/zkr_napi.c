@@ -49,6 +49,9 @@ static struct {
   int (*rollup_witness)(uint32_t, uint32_t, const uint8_t *, size_t, void **, size_t *);
   int (*sharded_last_form)(int *, char *, size_t);
   int (*key_replication)(const zkr_key *, int *, int *);
+  int (*key_contribute)(const zkr_key *, const uint8_t *, zkr_key **, uint8_t *);
+  int (*contribution_check)(const uint8_t *, int *);
+  int (*vk_contribute)(const void *, size_t, const uint8_t *, void **, size_t *);
 } Z;
 /* which form the last sharded proof took (zkr_prove_sharded_last_form, read on the worker thread that ran it, published on the JS
  * thread when its promise settles) */
@@ -95,6 +98,7 @@ static napi_value js_load(napi_env env, napi_callback_info info) {
     SYM(format_privkey, "zkr_babyjub_format_privkey") SYM(withdraw_r1cs, "zkr_withdraw_r1cs") SYM(withdraw_witness, "zkr_withdraw_witness")
     SYM(rollup_info, "zkr_rollup_info") SYM(rollup_r1cs, "zkr_rollup_r1cs") SYM(rollup_witness, "zkr_rollup_witness")
     SYM(sharded_last_form, "zkr_prove_sharded_last_form") SYM(key_replication, "zkr_key_replication")
+    SYM(key_contribute, "zkr_key_contribute") SYM(contribution_check, "zkr_contribution_check") SYM(vk_contribute, "zkr_vk_contribute")
     Z.handle = h;
   }
   napi_value out;
@@ -225,6 +229,69 @@ static napi_value js_setup_r1cs(napi_env env, napi_callback_info info) {
   NAPI_OK(napi_set_element(env, arr, 0, ext));
   NAPI_OK(napi_set_element(env, arr, 1, vkb));
   return arr;
+}
+
+/* A further party's delta contribution (include/zkr.h, ZKR_CONTRIBUTION_BYTES = 352).
+ * keyContribute(key, d32|null) -> [handle of the contributed key, record Buffer] (zkr_key_contribute; synchronous, once per ceremony step);
+ * contributionCheck(record) -> boolean (zkr_contribution_check, host only);
+ * vkContribute(vkBin, record) -> vkBin Buffer with vk_delta_2 replaced (zkr_vk_contribute, host only). */
+#define CONTRIBUTION_BYTES 352
+static napi_value js_key_contribute(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (!Z.handle) return throw_msg(env, "libzkr_hip.so not loaded");
+  zkr_key *src = NULL, *key = NULL;
+  const uint8_t *d = NULL;
+  size_t d_len = 0;
+  if (argc < 1 || napi_get_value_external(env, argv[0], (void **)&src) != napi_ok) return throw_msg(env, "keyContribute(key, d32|null)");
+  napi_valuetype t = napi_null;
+  if (argc > 1) napi_typeof(env, argv[1], &t);
+  if (t != napi_null && t != napi_undefined) {
+    if (!get_bytes(env, argv[1], &d, &d_len) || d_len != 32) return throw_msg(env, "d must be 32 bytes (little endian) or null");
+  }
+  uint8_t rec[CONTRIBUTION_BYTES];
+  if (Z.key_contribute(src, d, &key, rec)) return throw_msg(env, Z.last_error());
+  napi_value ext, recb, arr;
+  void *copy;
+  NAPI_OK(napi_create_external(env, key, key_finalize, NULL, &ext));
+  NAPI_OK(napi_create_buffer_copy(env, CONTRIBUTION_BYTES, rec, &copy, &recb));
+  NAPI_OK(napi_create_array_with_length(env, 2, &arr));
+  NAPI_OK(napi_set_element(env, arr, 0, ext));
+  NAPI_OK(napi_set_element(env, arr, 1, recb));
+  return arr;
+}
+static napi_value js_contribution_check(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (!Z.handle) return throw_msg(env, "libzkr_hip.so not loaded");
+  const uint8_t *rec;
+  size_t len;
+  if (argc < 1 || !get_bytes(env, argv[0], &rec, &len) || len != CONTRIBUTION_BYTES) return throw_msg(env, "a contribution record is 352 bytes");
+  int valid = 0;
+  if (Z.contribution_check(rec, &valid)) return throw_msg(env, Z.last_error());
+  napi_value out;
+  NAPI_OK(napi_get_boolean(env, valid != 0, &out));
+  return out;
+}
+static napi_value js_vk_contribute(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (!Z.handle) return throw_msg(env, "libzkr_hip.so not loaded");
+  const uint8_t *vk, *rec;
+  size_t vk_len, len;
+  if (argc < 2 || !get_bytes(env, argv[0], &vk, &vk_len)) return throw_msg(env, "vkBin must be an ArrayBuffer / Buffer / TypedArray");
+  if (!get_bytes(env, argv[1], &rec, &len) || len != CONTRIBUTION_BYTES) return throw_msg(env, "a contribution record is 352 bytes");
+  void *out_vk = NULL;
+  size_t out_len = 0;
+  if (Z.vk_contribute(vk, vk_len, rec, &out_vk, &out_len)) return throw_msg(env, Z.last_error());
+  napi_value out;
+  void *copy;
+  NAPI_OK(napi_create_buffer_copy(env, out_len, out_vk, &copy, &out));
+  Z.free_(out_vk);
+  return out;
 }
 
 /* keySave(key, path) / keyLoadFile(path, device): the packed device-layout key file (zkr_key_save / zkr_key_load_file) */
@@ -773,6 +840,9 @@ static napi_value init(napi_env env, napi_value exports) {
       {"verifyBatch", NULL, js_verify_batch, NULL, NULL, NULL, napi_default, NULL},
       {"shardedLastForm", NULL, js_sharded_last_form, NULL, NULL, NULL, napi_default, NULL},
       {"keyReplication", NULL, js_key_replication, NULL, NULL, NULL, napi_default, NULL},
+      {"keyContribute", NULL, js_key_contribute, NULL, NULL, NULL, napi_default, NULL},
+      {"contributionCheck", NULL, js_contribution_check, NULL, NULL, NULL, napi_default, NULL},
+      {"vkContribute", NULL, js_vk_contribute, NULL, NULL, NULL, napi_default, NULL},
   };
   napi_define_properties(env, exports, sizeof(props) / sizeof(props[0]), props);
   return exports;

@@ -6,6 +6,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ZKR_HIP_LIB") or os.path.normpath(os.path.join(_HERE, "..", "..", "csrc", "libzkr_hip.so"))  # same override as index.js
 PROOF_BYTES = 256
 PARTIAL_BYTES = 640   # zkr.h ZKR_PARTIAL_BYTES
+CONTRIBUTION_BYTES = 352   # zkr.h ZKR_CONTRIBUTION_BYTES
 REPLICATE_MODES = {"auto": 0, "full": 1, "base": 2}   # zkr.h ZKR_REPLICATE_*
 KEY_SECTIONS = ("none", "rowptr", "col", "wide", "rank", "header", "points", "twiddles", "coef", "shared rank", "consts")   # zkr.h ZKR_KEYSEC_*
 STAGES = ("ingest", "spmv", "ntt", "msm_sort", "msm_accum_g1", "msm_accum_g2", "msm_big", "msm_reduce", "total",
@@ -50,6 +51,10 @@ def lib():
     L.zkr_key_adopt_base_arena.argtypes = [vp, sz, i, c.POINTER(vp)]
     L.zkr_key_check.argtypes = [vp, i, c.POINTER(c.c_uint64)]
     L.zkr_key_replicate.argtypes = [vp, i, i, c.POINTER(vp)]
+    L.zkr_key_contribute.argtypes = [vp, u8p, c.POINTER(vp), u8p]
+    L.zkr_contribution_check.argtypes = [u8p, c.POINTER(i)]
+    L.zkr_key_contribution_verify.argtypes = [vp, vp, u8p, c.POINTER(i), c.POINTER(c.c_uint64)]
+    L.zkr_vk_contribute.argtypes = [u8p, sz, u8p, c.POINTER(vp), c.POINTER(sz)]
     L.zkr_key_device.argtypes = [vp]
     L.zkr_key_replication.argtypes = [vp, c.POINTER(i), c.POINTER(i)]
     L.zkr_prove_sharded_last_form.argtypes = [c.POINTER(i), c.c_char_p, sz]
@@ -212,6 +217,26 @@ class ProvingKey:
         h = ctypes.c_void_p()
         _check(lib().zkr_key_replicate(self._h, device, REPLICATE_MODES[mode], ctypes.byref(h)))
         return ProvingKey(h, device)
+
+    def contribute(self, d=None):
+        """A further party's delta contribution (zkr_key_contribute): -> (new ProvingKey on the same device, the 352-byte
+        record).  d: None (drawn from the OS CSPRNG inside the call and wiped there) or an int with 1 < d < r for reproducible
+        tests.  This key stays as it is, so the pair can be verified."""
+        db = None if d is None else int(d).to_bytes(32, "little")
+        h = ctypes.c_void_p()
+        rec = ctypes.create_string_buffer(CONTRIBUTION_BYTES)
+        _check(lib().zkr_key_contribute(self._h, db, ctypes.byref(h), ctypes.cast(rec, ctypes.c_char_p)))
+        return ProvingKey(h, self.device), rec.raw
+
+    def contribution_verify(self, after, record: bytes):
+        """What a party that did not make the contribution runs (zkr_key_contribution_verify): self = the key before, `after` the
+        key it was handed -> (valid, first failed step or 0, ZKR_KEYSEC_* number of the first differing section for steps 3 and 4:
+        KEY_SECTIONS names it)."""
+        assert len(record) == CONTRIBUTION_BYTES
+        ok = ctypes.c_int(0)
+        rep = (ctypes.c_uint64 * 2)()
+        _check(lib().zkr_key_contribution_verify(self._h, after._h, bytes(record), ctypes.byref(ok), rep))
+        return bool(ok.value), int(rep[0]), int(rep[1])
 
     def replication(self):
         """How this key came to its device (zkr_key_replication): {"mode": "none" | "full" | "base", "peer_direct": bool}."""
@@ -495,6 +520,23 @@ def verify(vk_bin: bytes, proof: bytes, public_signals) -> bool:
     ok = ctypes.c_int(0)
     _check(lib().zkr_verify(bytes(vk_bin), len(vk_bin), bytes(proof), pub, len(public_signals), ctypes.byref(ok)))
     return bool(ok.value)
+
+
+def contribution_check(record: bytes) -> bool:
+    """zkr_contribution_check: the record of a delta contribution by itself (host only)."""
+    assert len(record) == CONTRIBUTION_BYTES
+    ok = ctypes.c_int(0)
+    _check(lib().zkr_contribution_check(bytes(record), ctypes.byref(ok)))
+    return bool(ok.value)
+
+
+def vk_contribute(vk_bin: bytes, record: bytes) -> bytes:
+    """zkr_vk_contribute: the verifying key that goes with the contributed proving key (vk_delta_2 replaced); raises ZkrError
+    for a bad record or one that does not continue this key."""
+    assert len(record) == CONTRIBUTION_BYTES
+    out, n = ctypes.c_void_p(), ctypes.c_size_t()
+    _check(lib().zkr_vk_contribute(bytes(vk_bin), len(vk_bin), bytes(record), ctypes.byref(out), ctypes.byref(n)))
+    return _take(out, n.value)
 
 
 def verify_batch(vk_bin: bytes, proofs, public_signals) -> bool:
