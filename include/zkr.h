@@ -296,10 +296,13 @@ int zkr_setup_r1cs_websnark(const void *r1cs_bin, size_t r1cs_len, const uint8_t
                             size_t *vk_len);
 
 /* ---- a further party's contribution to a key's delta (what makes a key somebody else can trust) ------
- * zkr_setup_r1cs is a ONE-party setup: whoever ran it saw (or chose) delta, and delta forges proofs.  A contributor
+ * Whoever ran a setup saw (or chose) delta, and delta forges proofs (a key from a transcript has delta = 1).  A contributor
  * re-randomises delta with a secret d of its own and none of the toxic values:
  *   delta1' = d delta1, delta2' = d delta2, C'[s] = d^-1 C[s] (s > nPublic), hExps'[i] = d^-1 hExps[i]; vk_delta_2' = d vk_delta_2
- * -- exactly the key a setup with delta d would have produced (byte for byte), sound while ONE contributor forgot its secret.
+ * -- exactly the key a setup with delta d would have produced (byte for byte).  It protects against the earlier holders of
+ * DELTA only: a key from zkr_setup_r1cs stays forgeable by whoever knows t, alfa and beta (hExps[0] = Z(t)/delta G1 hands the
+ * runner of the setup (1/delta') G1 whatever d was).  A key from zkr_setup_r1cs_ptau followed by at least one zkr_key_contribute
+ * is sound if ONE phase-1 contributor of the transcript and ONE delta contributor forgot their secrets.
  * The record (ZKR_CONTRIBUTION_BYTES; every coordinate 32 B LE standard form, as in vk_bin):
  *   delta1_before (64) | delta1_after (64) | delta2_after (128) | R (64) | z (32)
  * R, z: a Schnorr proof that the contributor knows d with delta1_after = d delta1_before -- R = k delta1_before for a fresh k,
@@ -333,6 +336,75 @@ int zkr_key_contribution_verify(const zkr_key *before, const zkr_key *after, con
  * that it continues THIS key (e(delta1_before, g2) == e(g1, vk_delta_2)), and returns a malloc'ed copy of vk_bin (zkr_free)
  * with vk_delta_2 (bytes 320..447) replaced by the record's delta2_after; ZKR_ERR_ARG otherwise. */
 int zkr_vk_contribute(const void *vk_bin, size_t vk_len, const uint8_t record[ZKR_CONTRIBUTION_BYTES], void **vk_out, size_t *vk_out_len);
+
+/* ---- a powers-of-tau transcript: the start of a key in which NO party knows t, alfa, beta -----------------------
+ * A key from zkr_setup_r1cs is forgeable by whoever ran the setup: it knows t, alfa and beta, and a later delta contribution
+ * does not take that away (the key publishes hExps[0] = Z(t)/delta G1 and the runner knows Z(t)).  The phase-1 transcript of
+ * Bowe-Gabizon-Miers holds the powers a setup needs as GROUP ELEMENTS whose discrete logs are products of every contributor's
+ * secrets, so they are unknown while ONE contributor forgot its share:
+ *   ZKRPTAU1, power K (1..24), M = 2^K -- every coordinate 32 B LE standard form, G2 as x.re, x.im, y.re, y.im (as in vk_bin):
+ *   32 B header: "ZKRPTAU1" | u32 K | u32 0 | u64 total length | 8 B zero
+ *   tauG1 [2M] x 64 B (tau^i G1) | tauG2 [M] x 128 B (tau^i G2) | alfaTauG1 [M] x 64 B | betaTauG1 [M] x 64 B | betaG2 128 B
+ * = 160 + 384 M bytes, in host memory; no point is ever infinity.  A transcript of power K serves every domain m <= M.
+ * The record of a contribution (ZKR_PTAU_RECORD_BYTES), with tau1 = tauG1[1], alfa1 = alfaTauG1[0], beta1 = betaTauG1[0],
+ * tau2 = tauG2[1], beta2 = betaG2:
+ *   tau1_before | tau1_after | alfa1_before | alfa1_after | beta1_before | beta1_after (6 x 64) | tau2_after | beta2_after (2 x 128)
+ *   | R_tau | R_alfa | R_beta (3 x 64) | z_tau | z_alfa | z_beta (3 x 32)
+ * Three Schnorr proofs in the form of the delta record's: R = k before, z = k + c s mod r, accepted iff z before == R + c after,
+ * with c = zkr_mimcsponge_multihash over a domain tag and the coordinates the proof binds (each point as x, y; G2 as 4 words):
+ *   c_tau = H(1, tau1_before, tau1_after, tau2_after, R_tau), c_alfa = H(2, alfa1_before, alfa1_after, R_alfa),
+ *   c_beta = H(3, beta1_before, beta1_after, beta2_after, R_beta). */
+#define ZKR_PTAU_RECORD_BYTES 928
+/* Host only: the transcript with tau = alfa = beta = 1 (every entry the generator of its group); malloc'ed, free with zkr_free. */
+int zkr_ptau_new(unsigned power, void **ptau_out, size_t *ptau_len);
+/* Multiplies tauG1[i], tauG2[i] by tau^i, alfaTauG1[i] by alfa tau^i, betaTauG1[i] by beta tau^i and betaG2 by beta, on the GPU
+ * (one variable-base multiplication per point, each by a scalar of its own).  secrets96 = tau | alfa | beta, each 32 B LE with
+ * 1 < s < r, for reproducible tests; NULL draws them from the OS CSPRNG inside the call.  Either way every copy of the secrets
+ * the library holds in memory of its own -- the device table of powers, the device buffer of the ladders' unnormalised results,
+ * the host staging, the Schnorr nonces and what z is formed from -- is wiped before the call returns.  Not within its reach: tau,
+ * alfa and beta are handed to two small kernels by value, so they pass through the HIP runtime's kernel-argument buffers.  The input is checked
+ * first (header and length; every coordinate canonical, every point finite and on its curve: ZKR_ERR_ARG otherwise).
+ * *ptau_out: a new malloc'ed transcript (zkr_free); the input is left untouched.  No CPU fallback (ZKR_ERR_NO_DEVICE). */
+int zkr_ptau_contribute(const void *ptau, size_t len, const uint8_t *secrets96, int device, void **ptau_out, size_t *out_len, uint8_t record_out[ZKR_PTAU_RECORD_BYTES]);
+/* Host only.  records: n_records x ZKR_PTAU_RECORD_BYTES in the order the contributions were made.  *valid = 1 iff, for every
+ * record, every point is on its curve and in its subgroup and none is infinity, each `after` differs from its `before`, each
+ * z < r, the three Schnorr equations hold, e(tau1_after, g2) == e(g1, tau2_after) and the same for beta; and the records chain:
+ * record 0's three `before` points are the G1 generator, record j + 1's `before` = record j's `after`.  zkr_last_error names the
+ * record and the check that failed.  An error status only for a null pointer. */
+int zkr_ptau_record_check(const uint8_t *records, size_t n_records, int *valid);
+/* *valid = 1 iff every step holds; report (may be null): [0] = the first failed step (0: none), [1] = the vector it was found in
+ * (0..4 in the layout's order):
+ *   1. header and length are consistent (a failure here is ZKR_ERR_ARG: there is no transcript to speak of);
+ *   2. every coordinate is canonical, every point finite and on its curve -- on the device, before any group arithmetic reads them;
+ *   3. every G2 point has order r, [r] Q == O point by point (the twist's cofactor has small factors: a random combination
+ *      would let a low-order component through with noticeable probability);
+ *   4. tauG1[0] == G1 and tauG2[0] == G2;
+ *   5. with 128-bit rho_i, sigma_i from the OS CSPRNG and the sums by the library's MSM path:
+ *      e(sum rho_i tauG1[i+1], G2) == e(sum rho_i tauG1[i], tauG2[1]), i < 2M - 1;
+ *      e(tauG1[1], S0) == e(G1, S1), S0 = sum_{i < M-1} sigma_i tauG2[i], S1 = sum_{i < M-1} sigma_i tauG2[i+1];
+ *      e(sum_{i < M} sigma_i alfaTauG1[i], G2) == e(alfaTauG1[0], sum_{i < M} sigma_i tauG2[i]), the same for betaTauG1;
+ *      e(betaTauG1[0], G2) == e(G1, betaG2);
+ *   6. zkr_ptau_record_check(records), and the last record's `after` values are this transcript's tauG1[1], alfaTauG1[0],
+ *      betaTauG1[0], tauG2[1], betaG2; n_records == 0 is accepted only for the all-generators transcript.
+ * A bad transcript is ZKR_OK with *valid = 0 and a zkr_last_error line naming the step; a status below zero only for bad
+ * arguments (step 1 included) or a HIP failure. */
+int zkr_ptau_verify(const void *ptau, size_t len, const uint8_t *records, size_t n_records, int device, int *valid, uint64_t report[2]);
+/* zkr_setup_r1cs with the transcript in the place of the toxic scalars: the key is, byte for byte, the key
+ * zkr_setup_r1cs(r1cs, toxic = (tau, alfa, beta, 1, 1)) returns for the transcript's discrete logs -- which nobody knows -- and
+ * vk_bin has vk_gamma_2 = vk_delta_2 = G2.  delta = 1 is public: the key is NOT sound before at least one zkr_key_contribute.
+ * The domain m follows zkr_setup_r1cs's rule; m > 2^K is ZKR_ERR_ARG.  Steps 1-5 of zkr_ptau_verify run on the input first (a
+ * failure of 2-5 is ZKR_ERR_BAD_KEY); the records are the caller's matter.  Derivation, all on the GPU: the Lagrange-basis points
+ * of the first m entries of tauG1, tauG2, alfaTauG1, betaTauG1 by the inverse NTT over points; A[s], B1[s], B2[s] and
+ * K[s] = sum polsA LagBeta + sum polsB LagAlfa + sum polsC Lag1 (C[s] above nPublic, IC[s] up to it) as sparse combinations of
+ * them; hExps[i] = tauG1[i+m] - tauG1[i].  A table entry is dropped exactly when its point is infinity. */
+int zkr_setup_r1cs_ptau(const void *r1cs_bin, size_t r1cs_len, const void *ptau, size_t ptau_len, int device, zkr_key **key_out, void **vk_out, size_t *vk_len);
+/* Stage hooks, as zkr_ntt / zkr_msm_g1 are: n points in host memory, Montgomery affine as zkr_msm_g1 / g2 take them (64 B G1 /
+ * 128 B G2 when g2 != 0; x == 0 encodes infinity), transformed in place.
+ * zkr_points_scale_each: points[i] <- scalars[i] points[i], scalars 32 B LE standard form below r (ZKR_ERR_ARG otherwise).
+ * zkr_group_ntt: the NTT of zkr_ntt with points for coefficients, n = 2^logn (logn 1..25), natural order in and out; the inverse
+ * includes the factor 1 / n, so the inverse transform of tau^i G is the Lagrange-basis points L_j(tau) G of the domain. */
+int zkr_points_scale_each(void *points_mont, const void *scalars_std, size_t n, int g2, int device);
+int zkr_group_ntt(void *points_mont, unsigned logn, int inverse, int g2, int device);
 
 /* Circuit shape drawn by the zkr_synth_* calls of the CALLING THREAD (thread-local, default 0): 0 = rollup-shaped (default; 1-3 terms
  * per row, 3 % boolean and 2 % small signals, a third of the signals absent from B), 1 = dense random (BASELINE.json

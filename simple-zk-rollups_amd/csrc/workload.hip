@@ -292,9 +292,14 @@ static uint32_t bitrev32(uint32_t x, unsigned bits) {
   return r;
 }
 
-// CSR rows of the QAP (A gets the nPublic+1 input-consistency rows), the kept points of every table, then the arena
-static int build_key_from_generated(const Generated &g, int device, zkr_key **key_out) {
-  const Circuit &c = g.circ;
+// Which points of the tables a key keeps: a signal whose polynomial vanishes at t has the point at infinity and is dropped.
+struct KeptPoints {
+  std::vector<uint8_t> a, b, c, h;  // per signal (A; B1 and B2), per private signal s - nPublic - 1 (C), per power i (H)
+};
+// CSR rows of the QAP (A gets the nPublic+1 input-consistency rows), the kept points of every table, then the arena.
+// d_tbl: device tables; the C point of private signal s is entry s - nPublic - 1 + c_src_base of d_tbl[T_C].
+static int build_key_from_tables(const Circuit &c, const KeptPoints &keep, void *const d_tbl[N_TABLES], uint32_t c_src_base, const uint8_t *consts448, int device,
+                                 zkr_key **key_out) {
   uint32_t n = c.n, p = c.p, m = c.m;
   // QAP rows in CSR (A gets the nPublic+1 input-consistency rows)
   std::vector<uint32_t> rowptr[2], col[2];
@@ -325,26 +330,35 @@ static int build_key_from_generated(const Generated &g, int device, zkr_key **ke
   }
   std::vector<uint32_t> srcidx[N_TABLES], sidx[N_TABLES];
   for (uint32_t s = 0; s < n; s++) {
-    if (!g.sc.a[s].is_zero()) { srcidx[T_A].push_back(s); sidx[T_A].push_back(s); }
-    if (!g.sc.b[s].is_zero()) { srcidx[T_B1].push_back(s); sidx[T_B1].push_back(s); srcidx[T_B2].push_back(s); sidx[T_B2].push_back(s); }
+    if (keep.a[s]) { srcidx[T_A].push_back(s); sidx[T_A].push_back(s); }
+    if (keep.b[s]) { srcidx[T_B1].push_back(s); sidx[T_B1].push_back(s); srcidx[T_B2].push_back(s); sidx[T_B2].push_back(s); }
   }
   for (uint32_t i = 0; i < n - p - 1; i++)
-    if (!g.sc.cpriv[i].is_zero()) { srcidx[T_C].push_back(i); sidx[T_C].push_back(i + p + 1); }
+    if (keep.c[i]) { srcidx[T_C].push_back(i + c_src_base); sidx[T_C].push_back(i + p + 1); }
   unsigned logm = 0;
   while ((1u << logm) < m) logm++;
   for (uint32_t j = 0; j < m; j++) {
     uint32_t i = bitrev32(j, logm);
-    if (!g.sc.hx[i].is_zero()) { srcidx[T_H].push_back(i); sidx[T_H].push_back(j); }
+    if (keep.h[i]) { srcidx[T_H].push_back(i); sidx[T_H].push_back(j); }
   }
   const void *src[N_TABLES];
   bool on_dev[N_TABLES];
-  for (int t = 0; t < N_TABLES; t++) { src[t] = g.d_tbl[t]; on_dev[t] = true; }
-  return key_build(device, n, p, m, rowptr, col, coef, src, on_dev, srcidx, sidx, g.consts, key_out);
+  for (int t = 0; t < N_TABLES; t++) { src[t] = d_tbl[t]; on_dev[t] = true; }
+  return key_build(device, n, p, m, rowptr, col, coef, src, on_dev, srcidx, sidx, consts448, key_out);
+}
+static int build_key_from_generated(const Generated &g, int device, zkr_key **key_out) {
+  KeptPoints keep;
+  auto nonzero = [](const std::vector<Fr> &v, std::vector<uint8_t> &k) {
+    k.resize(v.size());
+    for (size_t i = 0; i < v.size(); i++) k[i] = !v[i].is_zero();
+  };
+  nonzero(g.sc.a, keep.a); nonzero(g.sc.b, keep.b); nonzero(g.sc.cpriv, keep.c); nonzero(g.sc.hx, keep.h);
+  return build_key_from_tables(g.circ, keep, g.d_tbl, 0, g.consts, device, key_out);
 }
 
 // vk_bin (zkr_verify layout) from the setup's own data
 static void vk_from_generated(const Generated &g, std::vector<uint8_t> &vk) {
-  const size_t nic = g.sc.ic.size();
+  const size_t nic = g.ic_std.size() / 64;
   vk.resize(64 + 3 * 128 + 4 + 64 * nic);
   store_g1_std(vk.data(), load_g1(g.consts));
   store_g2_std(vk.data() + 64, load_g2(g.consts + 192));
@@ -378,11 +392,10 @@ static int draw_fr(FILE *f, Fr &out) {
   }
 }
 
-// r1cs_bin (include/zkr.h) -> g.circ; toxic waste injected or drawn; QAP at t and every group element on the GPU
-static int setup_parse_and_run(const void *r1cs_bin, size_t r1cs_len, const uint8_t *toxic160, int device, Generated &g) {
+// r1cs_bin (include/zkr.h) -> the circuit, with its domain
+static int parse_r1cs(const void *r1cs_bin, size_t r1cs_len, Circuit &c) {
   const uint8_t *b = (const uint8_t *)r1cs_bin, *end = b + r1cs_len;
   if (r1cs_len < 12) { set_error("R1CS shorter than its header"); return ZKR_ERR_ARG; }
-  Circuit &c = g.circ;
   memcpy(&c.n, b, 4); memcpy(&c.p, b + 4, 4); memcpy(&c.nC, b + 8, 4);
   b += 12;
   if (c.n < 1 || (uint64_t)c.p + 1 > c.n || c.nC < 1 || (uint64_t)c.nC + c.p + 1 > (1ull << 26)) { set_error("bad R1CS geometry nVars=%u nPublic=%u nConstraints=%u", c.n, c.p, c.nC); return ZKR_ERR_ARG; }
@@ -410,6 +423,12 @@ static int setup_parse_and_run(const void *r1cs_bin, size_t r1cs_len, const uint
     }
   }
   if (b != end) { set_error("R1CS has %zu trailing bytes", (size_t)(end - b)); return ZKR_ERR_ARG; }
+  return 0;
+}
+
+// r1cs_bin -> g.circ; toxic waste injected or drawn; QAP at t and every group element on the GPU
+static int setup_parse_and_run(const void *r1cs_bin, size_t r1cs_len, const uint8_t *toxic160, int device, Generated &g) {
+  if (int rc = parse_r1cs(r1cs_bin, r1cs_len, g.circ)) return rc;
   Fr *tox[5] = {&g.tox.t, &g.tox.alfa, &g.tox.beta, &g.tox.gamma, &g.tox.delta};
   if (toxic160) {
     for (int i = 0; i < 5; i++) {
@@ -444,6 +463,63 @@ int zkr_setup_r1cs(const void *r1cs_bin, size_t r1cs_len, const uint8_t *toxic16
   int rc = setup_parse_and_run(r1cs_bin, r1cs_len, toxic160, device, g);
   if (!rc) rc = build_key_from_generated(g, device, key_out);
   if (rc) return rc;
+  vk_to_malloc(g, vk_out, vk_len);
+  return 0;
+}
+
+// The same key from a powers-of-tau transcript instead of toxic scalars (zkr_ptau.hip): nobody knows t, alfa, beta; delta = gamma = 1
+int zkr_setup_r1cs_ptau(const void *r1cs_bin, size_t r1cs_len, const void *ptau, size_t ptau_len, int device, zkr_key **key_out, void **vk_out, size_t *vk_len) {
+  if (!r1cs_bin || !ptau || !key_out || !vk_out || !vk_len) { set_error("null argument"); return ZKR_ERR_ARG; }
+  Generated g;
+  Circuit &c = g.circ;
+  int rc = parse_r1cs(r1cs_bin, r1cs_len, c);
+  if (rc) return rc;
+  const uint32_t n = c.n, p = c.p, m = c.m;
+  // the QAP by signal, constraint index ascending (A with its input-consistency rows), coefficients in standard form
+  QapColumns cols[3];
+  const std::vector<uint32_t> *rp[3] = {&c.rowA, &c.rowB, &c.rowC};
+  const std::vector<Term> *tt[3] = {&c.tA, &c.tB, &c.tC};
+  for (int k = 0; k < 3; k++) {
+    QapColumns &q = cols[k];
+    q.colptr.assign(n + 1, 0);
+    for (const Term &t : *tt[k]) q.colptr[t.sig + 1]++;
+    if (k == 0) for (uint32_t i = 0; i <= p; i++) q.colptr[i + 1]++;
+    for (uint32_t s = 0; s < n; s++) q.colptr[s + 1] += q.colptr[s];
+    q.row.resize(q.colptr[n]);
+    q.coef.resize((size_t)q.colptr[n] * 32);
+    std::vector<uint32_t> fill(q.colptr.begin(), q.colptr.end() - 1);
+    auto put = [&](uint32_t sig, uint32_t row, const Fr &coef_mont) {
+      const uint32_t e = fill[sig]++;
+      const Fr std_form = from_mont(coef_mont);
+      q.row[e] = row;
+      memcpy(&q.coef[(size_t)e * 32], std_form.v, 32);
+    };
+    for (uint32_t r = 0; r < c.nC; r++)
+      for (uint32_t e = (*rp[k])[r]; e < (*rp[k])[r + 1]; e++) put((*tt[k])[e].sig, r, (*tt[k])[e].coef);
+    if (k == 0) for (uint32_t i = 0; i <= p; i++) put(i, c.nC + i, Fr::one());
+  }
+  if ((rc = ptau_key_tables(ptau, ptau_len, device, m, n, cols, g.d_tbl, g.consts))) return rc;
+  // a table entry is dropped exactly when its point is infinity; the IC points for the verifying key
+  KeptPoints keep;
+  std::vector<uint8_t> host;
+  auto finite = [&](int t, size_t count, size_t first, std::vector<uint8_t> &k) -> int {
+    host.resize(count * 64);
+    if (count) ZKR_HIP_CHECK(hipMemcpy(host.data(), (const uint8_t *)g.d_tbl[t] + first * 64, host.size(), hipMemcpyDeviceToHost));
+    k.resize(count);
+    for (size_t i = 0; i < count; i++) k[i] = !load_g1(&host[i * 64]).is_inf();
+    return 0;
+  };
+  if ((rc = finite(T_H, m, 0, keep.h)) || (rc = finite(T_A, n, 0, keep.a)) || (rc = finite(T_B1, n, 0, keep.b)) || (rc = finite(T_C, n - p - 1, p + 1, keep.c))) return rc;
+  host.resize((size_t)(p + 1) * 64);
+  ZKR_HIP_CHECK(hipMemcpy(host.data(), g.d_tbl[T_C], host.size(), hipMemcpyDeviceToHost));
+  g.ic_std.assign(host.size(), 0);
+  for (uint32_t i = 0; i <= p; i++) {
+    const G1Affine ic = load_g1(&host[(size_t)i * 64]);
+    if (!ic.is_inf()) store_g1_std(&g.ic_std[(size_t)i * 64], ic);
+  }
+  g.gamma2_std.resize(128);
+  store_g2_std(g.gamma2_std.data(), g2_generator());
+  if ((rc = build_key_from_tables(c, keep, g.d_tbl, p + 1, g.consts, device, key_out))) return rc;
   vk_to_malloc(g, vk_out, vk_len);
   return 0;
 }

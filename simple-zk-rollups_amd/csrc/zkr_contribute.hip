@@ -4,7 +4,9 @@
 // whoever ran it could know delta, and delta forges proofs.  A contributor draws d and re-randomises delta without any of the
 // toxic values:
 //     delta1' = d delta1    delta2' = d delta2    C'[s] = d^-1 C[s]  (s > nPublic)    hExps'[i] = d^-1 hExps[i]
-// which is exactly the key a setup with delta d would have produced; it is sound as long as ONE contributor forgot its secret.
+// which is exactly the key a setup with delta d would have produced.  This protects against the earlier DELTA holders only: the
+// runner of a one-party setup also knows t, alfa and beta, which forge on their own -- a key that can guard deposits starts from
+// a powers-of-tau transcript (zkr_ptau.hip, zkr_setup_r1cs_ptau) and takes its delta contributions after that.
 //
 // The hot part is n - p - 1 + m VARIABLE-base multiplications by ONE scalar (scale_points_kernel below); everything else is
 // what the library already does: the compact base arena (zkr_key_base_arena) holds the base points, the receiver path of a
@@ -17,6 +19,7 @@
 #include "kernels_msm.hpp"
 #include "hostops.hpp"
 #include "pairing.hpp"
+#include "record_util.hpp"
 #include "zkr_internal.hpp"
 
 namespace zkr {
@@ -131,38 +134,6 @@ int compare_ranges(int device, const unsigned char *a, const unsigned char *b, c
 }
 CmpRange range_of(uint64_t off_a, uint64_t off_b, uint64_t bytes, uint32_t section, uint32_t table) { return CmpRange{off_a, off_b, (bytes + 15) / 16, section, table}; }
 
-// ---- host arithmetic on the record's members
-bool lt_words(const uint8_t *p, const uint32_t (&m)[8]) {
-  uint32_t v[8];
-  memcpy(v, p, 32);
-  for (int i = 7; i >= 0; i--)
-    if (v[i] != m[i]) return v[i] < m[i];
-  return false;
-}
-// standard-form bytes -> Montgomery affine; false for a coordinate >= q, the point at infinity or a point off its curve (G2: or
-// outside the order-r subgroup, as the verifier reads G2 members)
-bool read_g1_std(const uint8_t *p, G1Affine &out) {
-  if (!lt_words(p, FqParams::P) || !lt_words(p + 32, FqParams::P)) return false;
-  out = G1Affine{to_mont(load_fp<FqParams>(p)), to_mont(load_fp<FqParams>(p + 32))};
-  return !out.is_inf() && pairing::g1_on_curve(out);
-}
-bool read_g2_std(const uint8_t *p, G2Affine &out) {
-  for (int i = 0; i < 4; i++)
-    if (!lt_words(p + 32 * i, FqParams::P)) return false;
-  out = G2Affine{Fq2{to_mont(load_fp<FqParams>(p)), to_mont(load_fp<FqParams>(p + 32))}, Fq2{to_mont(load_fp<FqParams>(p + 64)), to_mont(load_fp<FqParams>(p + 96))}};
-  return !out.is_inf() && pairing::g2_on_curve(out) && pairing::g2_in_subgroup(out);
-}
-bool same_point(const G1XYZZ &a, const G1XYZZ &b) {
-  if (a.is_inf() || b.is_inf()) return a.is_inf() && b.is_inf();
-  const G1Affine x = to_affine(a), y = to_affine(b);
-  return x.x == y.x && x.y == y.y;
-}
-// e(a, b) == e(c, d)
-bool pairings_equal(const G1Affine &a, const G2Affine &b, const G1Affine &c, const G2Affine &d) {
-  const G1Affine ps[2] = {a, G1Affine{c.x, neg(c.y)}};
-  const G2Affine qs[2] = {b, d};
-  return pairing::pairing_product_is_one(ps, qs, 2);
-}
 
 // record layout (ZKR_CONTRIBUTION_BYTES): delta1_before | delta1_after | delta2_after | R | z
 constexpr size_t REC_D1B = 0, REC_D1A = 64, REC_D2A = 128, REC_R = 256, REC_Z = 320;
@@ -193,50 +164,6 @@ bool record_valid(const uint8_t *rec, Parsed &p, const char **why) {
   return true;
 }
 
-void store_g1_mont(uint8_t *out, const G1Affine &a) { store_fp(out, a.x); store_fp(out + 32, a.y); }
-void store_g2_mont(uint8_t *out, const G2Affine &a) { store_fp(out, a.x.a); store_fp(out + 32, a.x.b); store_fp(out + 64, a.y.a); store_fp(out + 96, a.y.b); }
-
-// draws 1 < v < r from the OS CSPRNG (rejection sampling over 254 bits)
-int draw_secret(U256 &v) {
-  FILE *f = fopen("/dev/urandom", "rb");
-  if (!f) { set_error("cannot open /dev/urandom"); return ZKR_ERR_ARG; }
-  uint8_t b[32];
-  int rc = 0;
-  for (;;) {
-    if (fread(b, 1, 32, f) != 32) { set_error("short read from /dev/urandom"); rc = ZKR_ERR_ARG; break; }
-    b[31] &= 0x3f;
-    bool small = b[0] <= 1;
-    for (int i = 1; i < 32 && small; i++) small = b[i] == 0;
-    if (lt_words(b, FrParams::P) && !small) break;
-  }
-  fclose(f);
-  if (!rc) memcpy(v.v, b, 32);
-  explicit_bzero(b, sizeof(b));
-  return rc;
-}
-
-// signed binary (non-adjacent) form of e: nz bit b = digit b non-zero, sg bit b = digit b is -1; returns the leading digit's index
-int naf_of(const U256 &e, uint32_t nz[8], uint32_t sg[8]) {
-  uint32_t k[9];
-  memcpy(k, e.v, 32);
-  k[8] = 0;
-  memset(nz, 0, 32); memset(sg, 0, 32);
-  int top = 0;
-  for (int b = 0; b < 256; b++) {
-    if (k[0] & 1u) {
-      nz[b >> 5] |= 1u << (b & 31);
-      top = b;
-      if ((k[0] & 3u) == 3u) {  // digit -1: k += 1
-        sg[b >> 5] |= 1u << (b & 31);
-        for (int i = 0; i < 9 && ++k[i] == 0; i++) {}
-      } else k[0] -= 1u;
-    }
-    for (int i = 0; i < 8; i++) k[i] = (k[i] >> 1) | (k[i + 1] << 31);
-    k[8] >>= 1;
-  }
-  explicit_bzero(k, sizeof(k));
-  return top;
-}
 
 // everything that reveals d: wiped however zkr_key_contribute is left
 struct Secrets {

@@ -256,6 +256,16 @@ int arena_from_base(const void *dev_ptr, size_t len, int device, unsigned char *
 int key_table_msm(const zkr_key *k, int t, const Fr *d_scalars, XYZZ<Fq> *out);
 // zkr_key_check.hip: what an arena whose header passed arena_header_fault CONTAINS (zkr_key_check; level 0 structure, 1 values)
 int key_arena_check(int device, const unsigned char *arena, const ArenaHeader &h, int level, uint64_t report[4]);
+// zkr_ptau.hip: the group elements of a key from a powers-of-tau transcript (zkr_setup_r1cs_ptau; delta = gamma = 1).
+// One QAP matrix by signal: column s = the terms [colptr[s], colptr[s + 1]), term e = coef[32 e ..] (standard form) x L_row[e]
+struct QapColumns {
+  std::vector<uint32_t> colptr, row;
+  std::vector<uint8_t> coef;
+};
+// cols: A (with the input-consistency rows), B, C over the domain m.  Steps 1-5 of zkr_ptau_verify run on the transcript first
+// (ZKR_ERR_BAD_KEY).  d_tbl (device, Montgomery affine, infinity where a signal's polynomial vanishes; the caller hipFree's them):
+// [T_A], [T_B1], [T_B2]: n points; [T_C]: the n points K[s] = beta A_s + alfa B_s + C_s (IC for s <= nPublic, C above); [T_H]: m
+int ptau_key_tables(const void *ptau, size_t len, int device, uint32_t m, uint32_t n, const QapColumns cols[3], void *d_tbl[N_TABLES], uint8_t consts448[448]);
 MsmPlan msm_plan(size_t n_scalars, size_t n_points, int c_fixed = 0);
 uint32_t big_threshold(size_t n_points, int K, uint32_t nbw, int nbat);  // occupancy above which a bucket goes to msm_big_kernel (zkr_key.hip)
 int digit_lists_alloc(DigitLists &dl, size_t n_scalars, const MsmPlan &pl);

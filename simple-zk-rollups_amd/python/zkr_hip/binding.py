@@ -7,6 +7,7 @@ LIB_PATH = os.environ.get("ZKR_HIP_LIB") or os.path.normpath(os.path.join(_HERE,
 PROOF_BYTES = 256
 PARTIAL_BYTES = 640   # zkr.h ZKR_PARTIAL_BYTES
 CONTRIBUTION_BYTES = 352   # zkr.h ZKR_CONTRIBUTION_BYTES
+PTAU_RECORD_BYTES = 928   # zkr.h ZKR_PTAU_RECORD_BYTES
 REPLICATE_MODES = {"auto": 0, "full": 1, "base": 2}   # zkr.h ZKR_REPLICATE_*
 KEY_SECTIONS = ("none", "rowptr", "col", "wide", "rank", "header", "points", "twiddles", "coef", "shared rank", "consts")   # zkr.h ZKR_KEYSEC_*
 STAGES = ("ingest", "spmv", "ntt", "msm_sort", "msm_accum_g1", "msm_accum_g2", "msm_big", "msm_reduce", "total",
@@ -55,6 +56,13 @@ def lib():
     L.zkr_contribution_check.argtypes = [u8p, c.POINTER(i)]
     L.zkr_key_contribution_verify.argtypes = [vp, vp, u8p, c.POINTER(i), c.POINTER(c.c_uint64)]
     L.zkr_vk_contribute.argtypes = [u8p, sz, u8p, c.POINTER(vp), c.POINTER(sz)]
+    L.zkr_ptau_new.argtypes = [c.c_uint, c.POINTER(vp), c.POINTER(sz)]
+    L.zkr_ptau_contribute.argtypes = [u8p, sz, u8p, i, c.POINTER(vp), c.POINTER(sz), u8p]
+    L.zkr_ptau_record_check.argtypes = [u8p, sz, c.POINTER(i)]
+    L.zkr_ptau_verify.argtypes = [u8p, sz, u8p, sz, i, c.POINTER(i), c.POINTER(c.c_uint64)]
+    L.zkr_setup_r1cs_ptau.argtypes = [u8p, sz, u8p, sz, i, c.POINTER(vp), c.POINTER(vp), c.POINTER(sz)]
+    L.zkr_points_scale_each.argtypes = [u8p, u8p, sz, i, i]
+    L.zkr_group_ntt.argtypes = [u8p, c.c_uint, i, i, i]
     L.zkr_key_device.argtypes = [vp]
     L.zkr_key_replication.argtypes = [vp, c.POINTER(i), c.POINTER(i)]
     L.zkr_prove_sharded_last_form.argtypes = [c.POINTER(i), c.c_char_p, sz]
@@ -186,6 +194,17 @@ class ProvingKey:
         tb = None if toxic is None else b"".join(int(x).to_bytes(32, "little") for x in toxic)
         h, vk, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_size_t()
         _check(lib().zkr_setup_r1cs(bytes(r1cs_bin), len(r1cs_bin), tb, device, ctypes.byref(h), ctypes.byref(vk), ctypes.byref(n)))
+        try:
+            return cls(h, device), ctypes.string_at(vk, n.value)
+        finally:
+            lib().zkr_free(vk)
+
+    @classmethod
+    def setup_r1cs_ptau(cls, r1cs_bin: bytes, ptau: bytes, device=0):
+        """Groth16 setup of an R1CS from a powers-of-tau transcript (zkr_setup_r1cs_ptau): nobody knows t, alfa, beta; delta =
+        gamma = 1, so at least one contribute() must follow before the key guards anything.  Returns (key, vk_bin)."""
+        h, vk, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_size_t()
+        _check(lib().zkr_setup_r1cs_ptau(bytes(r1cs_bin), len(r1cs_bin), bytes(ptau), len(ptau), device, ctypes.byref(h), ctypes.byref(vk), ctypes.byref(n)))
         try:
             return cls(h, device), ctypes.string_at(vk, n.value)
         finally:
@@ -537,6 +556,67 @@ def vk_contribute(vk_bin: bytes, record: bytes) -> bytes:
     out, n = ctypes.c_void_p(), ctypes.c_size_t()
     _check(lib().zkr_vk_contribute(bytes(vk_bin), len(vk_bin), bytes(record), ctypes.byref(out), ctypes.byref(n)))
     return _take(out, n.value)
+
+
+def ptau_new(power: int) -> bytes:
+    """zkr_ptau_new: the powers-of-tau transcript of power `power` with tau = alfa = beta = 1 (host only)."""
+    out, n = ctypes.c_void_p(), ctypes.c_size_t()
+    _check(lib().zkr_ptau_new(power, ctypes.byref(out), ctypes.byref(n)))
+    return _take(out, n.value)
+
+
+def ptau_contribute(ptau: bytes, secrets=None, device=0):
+    """zkr_ptau_contribute: -> (the new transcript, the 928-byte record).  secrets: (tau, alfa, beta) as ints with 1 < s < r for
+    reproducible tests; None draws them inside the library, where they are wiped before the call returns."""
+    sb = None if secrets is None else b"".join(int(x).to_bytes(32, "little") for x in secrets)
+    assert sb is None or len(sb) == 96
+    out, n = ctypes.c_void_p(), ctypes.c_size_t()
+    rec = ctypes.create_string_buffer(PTAU_RECORD_BYTES)
+    _check(lib().zkr_ptau_contribute(bytes(ptau), len(ptau), sb, device, ctypes.byref(out), ctypes.byref(n), ctypes.cast(rec, ctypes.c_char_p)))
+    return _take(out, n.value), rec.raw
+
+
+def ptau_record_check(records) -> bool:
+    """zkr_ptau_record_check: a chain of contribution records (a list of 928-byte records, or their concatenation), host only."""
+    rb = bytes(records) if isinstance(records, (bytes, bytearray)) else b"".join(bytes(r) for r in records)
+    assert len(rb) % PTAU_RECORD_BYTES == 0
+    ok = ctypes.c_int(0)
+    _check(lib().zkr_ptau_record_check(rb, len(rb) // PTAU_RECORD_BYTES, ctypes.byref(ok)))
+    return bool(ok.value)
+
+
+def ptau_verify(ptau: bytes, records=(), device=0):
+    """zkr_ptau_verify: -> (valid, step, vector); step = the first failed step (0: none), vector = where it was found (0..4:
+    tauG1, tauG2, alfaTauG1, betaTauG1, betaG2).  zkr_hip.lib().zkr_last_error() names what failed."""
+    rb = bytes(records) if isinstance(records, (bytes, bytearray)) else b"".join(bytes(r) for r in records)
+    assert len(rb) % PTAU_RECORD_BYTES == 0
+    ok = ctypes.c_int(0)
+    rep = (ctypes.c_uint64 * 2)()
+    _check(lib().zkr_ptau_verify(bytes(ptau), len(ptau), rb if rb else None, len(rb) // PTAU_RECORD_BYTES, device, ctypes.byref(ok), rep))
+    return bool(ok.value), int(rep[0]), int(rep[1])
+
+
+def points_scale_each(points: bytes, scalars: bytes, g2=False, device=0) -> bytes:
+    """zkr_points_scale_each: points[i] <- scalars[i] * points[i] (Montgomery affine points, standard-form scalars below r)."""
+    pb = 128 if g2 else 64
+    n = len(scalars) // 32
+    if len(points) != n * pb or len(scalars) != n * 32:
+        raise ValueError("points/scalars length mismatch")
+    buf = ctypes.create_string_buffer(bytes(points), len(points))
+    _check(lib().zkr_points_scale_each(ctypes.cast(buf, ctypes.c_char_p), bytes(scalars), n, 1 if g2 else 0, device))
+    return buf.raw
+
+
+def group_ntt(points: bytes, inverse=False, g2=False, device=0) -> bytes:
+    """zkr_group_ntt: the NTT of `ntt` with points for coefficients (Montgomery affine, natural order in and out)."""
+    pb = 128 if g2 else 64
+    n = len(points) // pb
+    logn = n.bit_length() - 1
+    if n < 2 or (1 << logn) != n or len(points) != n * pb:
+        raise ValueError("length must be a power of two >= 2 points")
+    buf = ctypes.create_string_buffer(bytes(points), len(points))
+    _check(lib().zkr_group_ntt(ctypes.cast(buf, ctypes.c_char_p), logn, 1 if inverse else 0, 1 if g2 else 0, device))
+    return buf.raw
 
 
 def verify_batch(vk_bin: bytes, proofs, public_signals) -> bool:
