@@ -41,6 +41,14 @@ struct FrParams {
                                      0x53bb8085u, 0x8c49833du, 0x7f4e44a5u, 0x0216d0b1u};
 };
 
+// a < b as 256-bit integers, least significant word first: THE range check of a coordinate (b = q) or a scalar (b = r)
+ZKR_HD bool words_below(const uint32_t (&a)[8], const uint32_t (&b)[8]) {
+#pragma unroll
+  for (int i = 7; i >= 0; i--)
+    if (a[i] != b[i]) return a[i] < b[i];
+  return false;
+}
+
 template <class PM>
 struct Fp {
   uint32_t v[8];

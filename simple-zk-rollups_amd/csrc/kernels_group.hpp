@@ -1,12 +1,13 @@
 // kernels_group.hpp -- arithmetic on VECTORS OF GROUP ELEMENTS, which the proving path never needs (its points are fixed, its
 // scalars vary) and a powers-of-tau transcript is made of: every point multiplied by a scalar of its own, and the radix-2 NTT
-// whose coefficients are points (the Lagrange-basis form of tau^i G).  Templated over the coordinate families of curve29.hpp
+// whose coefficients are points (the Lagrange-basis form of tau^i G).  The delta contribution's kernel (every point times ONE
+// scalar, zkr_contribute.hip) and the curve-equation check of the key loader are here too: one home for them all.  Templated over the coordinate families of curve29.hpp
 // (G1C over Fq, G2C over Fq2); the group law is the hot path's (XYZZ accumulator, dbl_xyzz29, add_mixed29).
 //
 // Points are affine in the key's boundary radix (x 2^256; x == 0 = infinity) in memory, in and out, as zkr_msm_g1 / g2 take them.
 // A kernel leaves its results unnormalised -- X, Y in the point's own slot, ZZ, ZZZ in `ztmp` ([2][n] coordinates) -- and each
-// thread makes its own results affine with ONE inversion of the product of their ZZZ, as scale_points_kernel (zkr_contribute.hip)
-// does: x = X ZZ^2 / ZZZ^2, y = Y / ZZZ.
+// thread makes its own results affine with ONE inversion of the product of their ZZZ (x = X ZZ^2 / ZZZ^2, y = Y / ZZZ, since
+// ZZ^3 = ZZZ^2), as msm_precompute_kernel does over its levels.
 //
 // Per-lane scalars: the 64 lanes of a wavefront hold 64 different scalars, so "add where the bit is set" runs for the wave in
 // practically every step whatever form the digits take (a signed form saves nothing: some lane always has a non-zero digit).  The
@@ -17,12 +18,27 @@
 #pragma once
 #include "kernels_msm.hpp"  // load_pod / store_pod, curve29.hpp
 #include "kernels_ntt.hpp"  // load_fr / store_fr, twiddle_table_kernel
+#include "pairing.hpp"      // the curve constants
 
 namespace zkr {
 
 constexpr int GROUP_THREADS = 256;
-constexpr int GROUP_MAX_PTS = 8;   // points one thread of group_scale_each_kernel multiplies and normalises together
+constexpr int GROUP_MAX_PTS = 8;   // points one thread of a scaling kernel multiplies and normalises together
 constexpr int GROUP_SCALAR_BITS = 254;  // scalars are below r < 2^254
+// Blocks of a scaling launch over n points, and the points a thread takes: one while that leaves the chip short of wavefronts
+// (4 per SIMD on 1024 SIMDs), up to GROUP_MAX_PTS.
+inline unsigned group_scale_grid(size_t n, int *npt) {
+  const size_t per = n / (1024u * 64u * 4u);
+  *npt = per < 1 ? 1 : per > (size_t)GROUP_MAX_PTS ? GROUP_MAX_PTS : (int)per;
+  const size_t threads = (n + (size_t)*npt - 1) / (size_t)*npt;
+  return (unsigned)((threads + GROUP_THREADS - 1) / GROUP_THREADS);
+}
+
+// a checking kernel's tally: bad[0] = entries that fail, bad[1] = the smallest index among them (host side: FaultCounter)
+__device__ __forceinline__ void group_note_bad(uint32_t *bad, uint32_t i) {
+  atomicAdd(&bad[0], 1u);
+  atomicMin(&bad[1], i);
+}
 
 // packed affine x 2^256 -> registers x 2^261 (canonical); the caller has filtered infinity
 template <class C>
@@ -38,6 +54,21 @@ __device__ __forceinline__ XYZZ29<C> group_lane_mul(const Affine29<C> &q, const 
   for (int b = bits - 1; b >= 0; b--) {
     acc = dbl_xyzz29<C>(acc);
     if ((k[b >> 5] >> (b & 31)) & 1u) acc = add_mixed29<C>(acc, q, false);
+  }
+  return acc;
+}
+
+// e q for ONE e common to all lanes, in signed-binary (NAF) form: `naf` = 16 words in device memory, [0..7] bit b set = digit b is
+// non-zero, [8..15] bit b set = it is -1; `top` = index of the leading digit (always +1).  The digits are wave-uniform: read
+// through the scalar unit and branched on uniformly, the -1 digits by add_mixed29's neg_q flag.
+template <class C>
+__device__ __forceinline__ XYZZ29<C> group_uniform_mul(const Affine29<C> &q, const uint32_t *naf, int top) {
+  XYZZ29<C> acc = make_xyzz<C>(q.x, q.y, C::one(), C::one());  // the leading digit
+#pragma unroll 1
+  for (int b = top - 1; b >= 0; b--) {
+    acc = dbl_xyzz29<C>(acc);
+    const uint32_t nz = __builtin_amdgcn_readfirstlane(naf[b >> 5]), sg = __builtin_amdgcn_readfirstlane(naf[8 + (b >> 5)]);
+    if ((nz >> (b & 31)) & 1u) acc = add_mixed29<C>(acc, q, ((sg >> (b & 31)) & 1u) != 0);
   }
   return acc;
 }
@@ -90,26 +121,45 @@ __device__ __forceinline__ void group_normalise_own(Affine<typename C::W> *pts, 
   }
 }
 
-// pts[i] <- s[i] pts[i], in place.  scalars: 8 words each, standard form below r; scalar i is at scalars + 8 i sc_stride
-// (sc_stride = 0: ONE scalar for all points -- every branch of the ladder is then uniform across the wavefront).  A thread takes
-// `npt` points at stride = the launch's threads, so a wavefront's loads stay contiguous.
-template <class C>
-static __global__ __launch_bounds__(GROUP_THREADS) void group_scale_each_kernel(Affine<typename C::W> *pts, uint32_t n, int npt, const uint32_t *scalars, uint32_t sc_stride,
-                                                                                 typename C::W *ztmp) {
+// The frame of the two scaling kernels: pts[i] <- mul(q_i, i) in place, infinity staying infinity.  A thread takes up to `npt`
+// points at stride = the launch's threads, so a wavefront's loads stay contiguous, and normalises them with one inversion.
+// Its count is worked out BEFORE the loop: updated inside it, the uniform kernel needs 169-170 VGPRs, and 168 is the last
+// allocation that lets three wavefronts share a SIMD.
+// The store writes zeros over an infinity slot; the placeholders of a shared-support table (key_build) are all-zero already,
+// so a key's bytes come out as if the slot had been left alone.
+template <class C, class Mul>
+__device__ __forceinline__ void group_scale_frame(Affine<typename C::W> *pts, uint32_t n, int npt, typename C::W *ztmp, Mul mul_point) {
   const uint32_t stride = gridDim.x * GROUP_THREADS, t0 = blockIdx.x * GROUP_THREADS + threadIdx.x;
+  const int cnt = t0 < n ? (int)min((uint32_t)npt, (n - 1 - t0) / stride + 1) : 0;
   auto prod = C::one().template to<4>();
-  int cnt = 0;
 #pragma unroll 1
-  for (int j = 0; j < npt; j++) {
-    const uint64_t i = (uint64_t)t0 + (uint64_t)j * stride;
-    if (i >= n) break;
-    cnt = j + 1;
+  for (int j = 0; j < cnt; j++) {
+    const uint32_t i = t0 + (uint32_t)j * stride;
     const Affine<typename C::W> p = load_pod(pts + i);
     XYZZ29<C> acc = XYZZ29<C>::inf();
-    if (!p.is_inf()) acc = group_lane_mul<C>(group_affine_in<C>(p), scalars + 8 * i * sc_stride);
+    if (!p.is_inf()) acc = mul_point(group_affine_in<C>(p), i);
     group_store_unnormalised<C>(pts, ztmp, n, i, acc, prod);
   }
   group_normalise_own<C>(pts, ztmp, n, t0, stride, cnt, prod);
+}
+
+// pts[i] <- s[i] pts[i].  scalars: 8 words each, standard form below r; scalar i is at scalars + 8 i sc_stride (sc_stride = 0:
+// one scalar for all points, every branch of the ladder then uniform across the wavefront).
+template <class C>
+static __global__ __launch_bounds__(GROUP_THREADS) void group_scale_each_kernel(Affine<typename C::W> *pts, uint32_t n, int npt, const uint32_t *scalars, uint32_t sc_stride,
+                                                                                 typename C::W *ztmp) {
+  group_scale_frame<C>(pts, n, npt, ztmp, [=](const Affine29<C> &q, uint32_t i) { return group_lane_mul<C>(q, scalars + 8 * (uint64_t)i * sc_stride); });
+}
+
+// pts[i] <- e pts[i] for ONE scalar e in the form group_uniform_mul reads: no per-lane digit storage and no table of multiples.
+// A delta contribution's C and H tables; `naf` is then the only device copy of the secret scalar, and the caller wipes it.
+// Fq products, for the accounting beside the measured times (tools/contribution_time.py): dbl_xyzz29 = 9 (4
+// squares + 3 products + the two-product Y form), add_mixed29 = 11 (2 squares + 7 products + the two-product Y form).  Per
+// point: `top` doublings, one addition per non-zero digit below the leading one, 2 products for the radix change in, ~9 + npt / 2
+// for the way back out, and 1 / npt of an inversion (253 squares + one product per set bit of p - 2).
+template <class C>
+static __global__ __launch_bounds__(GROUP_THREADS) void group_scale_uniform_kernel(Affine<typename C::W> *pts, uint32_t n, int npt, const uint32_t *naf, int top, typename C::W *ztmp) {
+  group_scale_frame<C>(pts, n, npt, ztmp, [=](const Affine29<C> &q, uint32_t) { return group_uniform_mul<C>(q, naf, top); });
 }
 
 // One radix-2 stage of the NTT over points, decimation in time on bit-reversed input, in place: thread t owns the butterfly
@@ -154,26 +204,31 @@ static __global__ void group_bitrev_kernel(const Affine<W> *in, Affine<W> *out, 
 
 // [e] P == O for every point, e the same for all of them: the order-r test of a vector of G2 points (e = r; the twist's cofactor
 // has small factors, so a random combination would let a low-order component through with noticeable probability).  e is public
-// and common, so the digits are wave-uniform: the signed-binary schedule of scale_points_kernel (zkr_contribute.hip) -- `naf`
-// [0..7] bit b set = digit b is non-zero, [8..15] = it is -1, `top` = the leading digit (+1) -- read through the scalar unit.
-// bad[0] = points that fail, bad[1] = the smallest index among them.  Infinity entries pass (the caller refuses them earlier).
+// and common: `naf`, `top` as group_uniform_mul reads them.  Infinity entries pass (the caller refuses them earlier).
 template <class C>
 static __global__ __launch_bounds__(GROUP_THREADS) void group_order_check_kernel(const Affine<typename C::W> *pts, uint32_t n, const uint32_t *naf, int top, uint32_t *bad) {
   const uint32_t i = blockIdx.x * GROUP_THREADS + threadIdx.x;
   if (i >= n) return;
   const Affine<typename C::W> p = load_pod(pts + i);
   if (p.is_inf()) return;
-  const Affine29<C> q = group_affine_in<C>(p);
-  XYZZ29<C> acc = make_xyzz<C>(q.x, q.y, C::one(), C::one());  // the leading digit
-#pragma unroll 1
-  for (int b = top - 1; b >= 0; b--) {
-    acc = dbl_xyzz29<C>(acc);
-    const uint32_t nz = __builtin_amdgcn_readfirstlane(naf[b >> 5]), sg = __builtin_amdgcn_readfirstlane(naf[8 + (b >> 5)]);
-    if ((nz >> (b & 31)) & 1u) acc = add_mixed29<C>(acc, q, ((sg >> (b & 31)) & 1u) != 0);
-  }
-  if (acc.is_inf()) return;
-  atomicAdd(&bad[0], 1u);
-  atomicMin(&bad[1], i);
+  if (!group_uniform_mul<C>(group_affine_in<C>(p), naf, top).is_inf()) group_note_bad(bad, i);
+}
+
+// Every point satisfies its curve's equation y^2 = x^3 + b (Montgomery coordinates x 2^256, the key's wire form); infinity
+// passes or fails as the caller says.
+template <class F>
+static __global__ void group_on_curve_kernel(const Affine<F> *pts, uint32_t n, F b, bool infinity_passes, uint32_t *bad) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const Affine<F> p = load_pod(pts + i);
+  if (p.is_inf() ? infinity_passes : sqr(p.y) == add(mul(sqr(p.x), p.x), b)) return;
+  group_note_bad(bad, i);
+}
+inline Fq group_curve_b(const Fq *) { return pairing::fq_small(3); }
+inline Fq2 group_curve_b(const Fq2 *) { return Fq2{pairing::fq_from_limbs(pairing::TWIST_B0), pairing::fq_from_limbs(pairing::TWIST_B1)}; }
+template <class F>
+void group_on_curve_launch(const void *pts, uint32_t n, bool infinity_passes, uint32_t *bad) {
+  group_on_curve_kernel<F><<<(n + 255) / 256, 256>>>((const Affine<F> *)pts, n, group_curve_b((const F *)nullptr), infinity_passes, bad);
 }
 
 // Sparse linear combinations of points: task t sums the terms [tb[t], tb[t + 1]) -- term e = coefficient x pts[row[e]] -- into

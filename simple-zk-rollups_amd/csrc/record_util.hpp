@@ -1,8 +1,8 @@
 // record_util.hpp -- host-side reading and writing of the members of a ceremony record (zkr_contribute.hip: the delta contribution;
-// zkr_ptau.hip: the powers-of-tau transcript), and the draw of a secret scalar from the OS CSPRNG.
+// zkr_ptau.hip: the powers-of-tau transcript), the Schnorr proof both records carry, and the draws from the OS CSPRNG.
 #pragma once
-#include <stdio.h>
 #include <string.h>
+#include <vector>
 #include "hostops.hpp"
 #include "pairing.hpp"
 #include "zkr_internal.hpp"
@@ -13,9 +13,7 @@ namespace zkr {
 static inline bool lt_words(const uint8_t *p, const uint32_t (&m)[8]) {
   uint32_t v[8];
   memcpy(v, p, 32);
-  for (int i = 7; i >= 0; i--)
-    if (v[i] != m[i]) return v[i] < m[i];
-  return false;
+  return words_below(v, m);
 }
 // standard-form bytes -> Montgomery affine; false for a coordinate >= q, the point at infinity or a point off its curve (G2: or
 // outside the order-r subgroup, as the verifier reads G2 members)
@@ -45,23 +43,53 @@ static inline bool pairings_equal(const G1Affine &a, const G2Affine &b, const G1
 static inline void store_g1_mont(uint8_t *out, const G1Affine &a) { store_fp(out, a.x); store_fp(out + 32, a.y); }
 static inline void store_g2_mont(uint8_t *out, const G2Affine &a) { store_fp(out, a.x.a); store_fp(out + 32, a.x.b); store_fp(out + 64, a.y.a); store_fp(out + 96, a.y.b); }
 
+// ---- the proof of knowledge of s with after = s before: R = k before, c = the record's challenge hash, z = k + c s mod r
+// z before == R + c after (z, c: 32 bytes, standard form)
+static inline bool schnorr_verify(const G1Affine &before, const G1Affine &after, const G1Affine &r, const uint8_t *z, const uint8_t *c) {
+  const G1XYZZ lhs = scalar_mul(to_xyzz(before), load_u256(z));
+  const G1XYZZ rhs = add_full(to_xyzz(r), scalar_mul(to_xyzz(after), load_u256(c)));
+  return same_point(lhs, rhs);
+}
+// what a response passes through on its way to z: lives in the caller's secrets and goes with them
+struct ResponseScratch {
+  Fr km, prod, z;  // the nonce in Montgomery form, c s, and their sum
+  ~ResponseScratch() { explicit_bzero(this, sizeof(*this)); }
+};
+// z_out = k + c s mod r (z itself is public); sm = s in Montgomery form
+static inline void schnorr_response(const U256 &k, const uint8_t c[32], const Fr &sm, ResponseScratch &w, uint8_t z_out[32]) {
+  const Fr cm = to_mont(load_fp<FrParams>(c));  // public
+  memcpy(w.km.v, k.v, 32);
+  w.km = to_mont(w.km);
+  w.prod = mul(cm, sm);
+  w.z = from_mont(add(w.km, w.prod));
+  memcpy(z_out, w.z.v, 32);
+}
+
+// ---- secrets and random coefficients
+static inline bool valid_secret(const uint8_t *s) {  // 1 < s < r
+  bool small = s[0] <= 1;
+  for (int i = 1; i < 32 && small; i++) small = s[i] == 0;
+  return !small && lt_words(s, FrParams::P);
+}
 // draws 1 < v < r from the OS CSPRNG (rejection sampling over 254 bits)
 static inline int draw_secret(U256 &v) {
-  FILE *f = fopen("/dev/urandom", "rb");
-  if (!f) { set_error("cannot open /dev/urandom"); return ZKR_ERR_ARG; }
   uint8_t b[32];
-  int rc = 0;
-  for (;;) {
-    if (fread(b, 1, 32, f) != 32) { set_error("short read from /dev/urandom"); rc = ZKR_ERR_ARG; break; }
+  int rc;
+  do {
+    rc = os_random(b, 32);
     b[31] &= 0x3f;
-    bool small = b[0] <= 1;
-    for (int i = 1; i < 32 && small; i++) small = b[i] == 0;
-    if (lt_words(b, FrParams::P) && !small) break;
-  }
-  fclose(f);
+  } while (!rc && !valid_secret(b));
   if (!rc) memcpy(v.v, b, 32);
   explicit_bzero(b, sizeof(b));
   return rc;
+}
+// n scalars of 32 bytes, 128 random bits each: the coefficients of a random combination (2^-128 per wrong entry)
+static inline int random_128(std::vector<uint8_t> &sc, size_t n) {
+  sc.assign(n * 32, 0);
+  std::vector<uint8_t> rnd(n * 16);
+  if (int rc = os_random(rnd.data(), rnd.size())) return rc;
+  for (size_t i = 0; i < n; i++) memcpy(&sc[32 * i], &rnd[16 * i], 16);
+  return 0;
 }
 
 // signed binary (non-adjacent) form of e: nz bit b = digit b non-zero, sg bit b = digit b is -1; returns the leading digit's index

@@ -29,10 +29,7 @@ struct SplitMix64 {
       Fr v;
       v.v[0] = (uint32_t)a; v.v[1] = (uint32_t)(a >> 32); v.v[2] = (uint32_t)b; v.v[3] = (uint32_t)(b >> 32);
       v.v[4] = (uint32_t)c; v.v[5] = (uint32_t)(c >> 32); v.v[6] = (uint32_t)d; v.v[7] = (uint32_t)(d >> 32);
-      bool lt = false;
-      for (int i = 7; i >= 0; i--)
-        if (v.v[i] != FrParams::P[i]) { lt = v.v[i] < FrParams::P[i]; break; }
-      if (lt) return v;
+      if (words_below(v.v, FrParams::P)) return v;
     }
   }
   Fr fr() { return to_mont(fr_std()); }
@@ -232,7 +229,7 @@ struct Generated {
 
 // g.circ and g.tox are in place: QAP polynomials at t, then every group element of the key on the GPU
 static int setup_from_circuit(int device, Generated &g) {
-  if (zkr_device_count() <= device || device < 0) { set_error("no HIP device %d; key points are computed on the GPU (no CPU fallback)", device); return ZKR_ERR_NO_DEVICE; }
+  if (int rc = need_device(device)) return rc;
   setup_scalars(g.circ, g.tox, g.sc, g.secret);
   struct Staging {  // standard-form copies of the scalars on their way to the device: wiped with the rest
     std::vector<uint8_t> v;
@@ -279,7 +276,7 @@ static int setup_from_circuit(int device, Generated &g) {
 
 static int generate(unsigned log_m, unsigned n_public, uint64_t circuit_seed, uint64_t toxic_seed, int device, Generated &g) {
   if (log_m < 2 || log_m > 26 || n_public + 2 > (1u << log_m)) { set_error("bad synthetic geometry log_m=%u nPublic=%u", log_m, n_public); return ZKR_ERR_ARG; }
-  if (zkr_device_count() <= device || device < 0) { set_error("no HIP device %d; key points are computed on the GPU (no CPU fallback)", device); return ZKR_ERR_NO_DEVICE; }
+  if (int rc = need_device(device)) return rc;
   synth_circuit(g.circ, 1u << log_m, n_public, circuit_seed, circuit_seed);
   SplitMix64 rng(toxic_seed);
   g.tox.t = rng.fr(); g.tox.alfa = rng.fr(); g.tox.beta = rng.fr(); g.tox.gamma = rng.fr(); g.tox.delta = rng.fr();
@@ -379,14 +376,12 @@ extern "C" {
 // (/root/reference/prover/package.json:34,37; SURVEY App. B "Setup") with the key's group elements computed on the GPU
 static bool read_fr_std(const uint8_t *p, Fr &out) {
   memcpy(out.v, p, 32);
-  for (int i = 7; i >= 0; i--)
-    if (out.v[i] != FrParams::P[i]) return out.v[i] < FrParams::P[i];
-  return false;
+  return words_below(out.v, FrParams::P);
 }
-static int draw_fr(FILE *f, Fr &out) {
+static int draw_fr(Fr &out) {
   for (;;) {
     uint8_t b[32];
-    if (fread(b, 1, 32, f) != 32) return 1;
+    if (int rc = os_random(b, 32)) return rc;
     b[31] &= 0x3f;
     if (read_fr_std(b, out) && !out.is_zero()) return 0;
   }
@@ -439,12 +434,11 @@ static int setup_parse_and_run(const void *r1cs_bin, size_t r1cs_len, const uint
   } else {  // fresh toxic waste from the OS CSPRNG; it never leaves this call (Generated::~Generated wipes it and
             // everything derived from it, host and device copies)
     g.secret = true;
-    FILE *f = fopen("/dev/urandom", "rb");
-    if (!f) { set_error("cannot open /dev/urandom"); return ZKR_ERR_ARG; }
-    int bad = 0;
-    for (int i = 0; i < 5 && !bad; i++) { Fr v; bad = draw_fr(f, v); *tox[i] = to_mont(v); }
-    fclose(f);
-    if (bad) { set_error("short read from /dev/urandom"); return ZKR_ERR_ARG; }
+    for (int i = 0; i < 5; i++) {
+      Fr v;
+      if (int rc = draw_fr(v)) return rc;
+      *tox[i] = to_mont(v);
+    }
   }
   return setup_from_circuit(device, g);
 }

@@ -8,7 +8,7 @@
 // runner of a one-party setup also knows t, alfa and beta, which forge on their own -- a key that can guard deposits starts from
 // a powers-of-tau transcript (zkr_ptau.hip, zkr_setup_r1cs_ptau) and takes its delta contributions after that.
 //
-// The hot part is n - p - 1 + m VARIABLE-base multiplications by ONE scalar (scale_points_kernel below); everything else is
+// The hot part is n - p - 1 + m VARIABLE-base multiplications by ONE scalar (group_scale_uniform_kernel, kernels_group.hpp); everything else is
 // what the library already does: the compact base arena (zkr_key_base_arena) holds the base points, the receiver path of a
 // replica (arena_from_base / zkr_key_adopt_base_arena) rebuilds the window levels, the keys' MSM path multiplies their C and H
 // tables by random coefficients for the check, pairing.hpp evaluates the few pairings on the host.
@@ -16,82 +16,13 @@
 #include <stdio.h>
 #include <string.h>
 #include <vector>
-#include "kernels_msm.hpp"
+#include "kernels_group.hpp"
 #include "hostops.hpp"
 #include "pairing.hpp"
 #include "record_util.hpp"
 #include "zkr_internal.hpp"
 
 namespace zkr {
-
-// ---------------------------------------------------------------- the scaling kernel
-// pts[i] <- e * pts[i] for ONE scalar e, in place, affine in the key's boundary radix (x 2^256) in and out; infinity (the
-// placeholders of a table laid out over a shared support) stays infinity.  Every lane runs the same signed-binary (NAF)
-// double-and-add schedule, so the digits are wave-uniform: read through the scalar unit, branched on uniformly, no per-lane digit
-// storage and no table of multiples (a run-time indexed per-thread table would live in scratch).  The group law is the hot path's
-// (curve29.hpp: XYZZ accumulator, dbl_xyzz29, add_mixed29 with its neg_q flag for the -1 digits).  A thread takes `npt` points
-// (stride = the launch's threads, so a wavefront's loads stay contiguous), leaves each product unnormalised -- X, Y in the
-// point's own slot, ZZ, ZZZ in `ztmp` ([2][n] coordinates) -- and makes them affine with ONE inversion of the product of their
-// ZZZ (x = X ZZ^2 / ZZZ^2, y = Y / ZZZ, since ZZ^3 = ZZZ^2), as msm_precompute_kernel does over its levels.
-// `naf`: 16 words in device memory, [0..7] bit b set = digit b is non-zero, [8..15] bit b set = it is -1; `top` = index of the
-// leading digit (always +1).  The buffer is the only device copy of the secret scalar: the caller wipes it.
-constexpr int SCALE_THREADS = 256;
-constexpr int SCALE_MAX_PTS = 8;
-// Fq products of the schedule, for the accounting beside the measured times (tools/contribution_time.py):
-// dbl_xyzz29 = 9 (4 squares + 3 products + the two-product Y form), add_mixed29 = 11 (2 squares + 7 products + the two-product Y
-// form).  Per point: `top` doublings, one addition per non-zero digit below the leading one, 2 products for the radix change in,
-// ~9 + npt / 2 for the way back out, and 1 / npt of an inversion (253 squares + one product per set bit of p - 2).
-
-static __global__ __launch_bounds__(SCALE_THREADS) void scale_points_kernel(G1Affine *pts, uint32_t n, int npt, const uint32_t *naf, int top, Fq *ztmp) {
-  using C = G1C;
-  const uint32_t stride = gridDim.x * SCALE_THREADS, t0 = blockIdx.x * SCALE_THREADS + threadIdx.x;
-  auto prod = C::one().template to<4>();  // product of this thread's ZZZ
-#pragma unroll 1
-  for (int j = 0; j < npt; j++) {
-    const uint32_t i = t0 + (uint32_t)j * stride;
-    if (i >= n) break;
-    const G1Affine p = load_pod(pts + i);
-    XYZZ29<C> acc = XYZZ29<C>::inf();
-    if (!p.is_inf()) {
-      const Affine29<C> q{canonical_small(mul(C::template unpack<10>(p.x), C::to261())), canonical_small(mul(C::template unpack<10>(p.y), C::to261()))};
-      acc = make_xyzz<C>(q.x, q.y, C::one(), C::one());  // the leading digit
-#pragma unroll 1
-      for (int b = top - 1; b >= 0; b--) {
-        acc = dbl_xyzz29<C>(acc);
-        const uint32_t nz = __builtin_amdgcn_readfirstlane(naf[b >> 5]), sg = __builtin_amdgcn_readfirstlane(naf[8 + (b >> 5)]);
-        if ((nz >> (b & 31)) & 1u) acc = add_mixed29<C>(acc, q, ((sg >> (b & 31)) & 1u) != 0);
-      }
-    }
-    if (acc.is_inf()) {  // a placeholder, or (a point off the curve only) a multiple that came out as infinity: stored as infinity, a factor of one
-      if (!p.is_inf()) store_pod(pts + i, G1Affine{Fq::zero(), Fq::zero()});
-      store_pod(ztmp + i, Fq::zero());
-      store_pod(ztmp + (size_t)n + i, C::template pack<2>(C::one()));
-      continue;
-    }
-    store_pod(pts + i, G1Affine{C::template pack<3>(weak(acc.x)), C::template pack<HY>(acc.y)});
-    store_pod(ztmp + i, C::template pack<HY>(acc.zz));
-    store_pod(ztmp + (size_t)n + i, C::template pack<HY>(acc.zzz));
-    prod = mul(prod, acc.zzz).template to<4>();
-  }
-  auto inv = inv29(prod);  // 1 / (ZZZ_0 ... ZZZ_{npt-1})
-#pragma unroll 1
-  for (int j = npt - 1; j >= 0; j--) {
-    const uint32_t i = t0 + (uint32_t)j * stride;
-    if (i >= n) continue;
-    auto pre = C::one().template to<4>();  // ZZZ_0 ... ZZZ_{j-1}
-#pragma unroll 1
-    for (int l = 0; l < j; l++) pre = mul(pre, C::template unpack<HY>(load_pod(ztmp + (size_t)n + t0 + (uint32_t)l * stride))).template to<4>();
-    const auto zzz = C::template unpack<HY>(load_pod(ztmp + (size_t)n + i));
-    const auto izzz = mul(inv, pre);  // 1 / ZZZ_j
-    inv = mul(inv, zzz).template to<4>();
-    const auto zz = C::template unpack<HY>(load_pod(ztmp + i));
-    if (zz.all_zero()) continue;  // infinity
-    const auto izz = mul(sqr(zz), sqr(izzz));
-    const G1Affine a = load_pod(pts + i);
-    const auto x = mul(C::template unpack<3>(a.x), izz), y = mul(C::template unpack<HY>(a.y), izzz);
-    store_pod(pts + i, G1Affine{C::template pack<2>(canonical_small(mul(x, C::to256()))), C::template pack<2>(canonical_small(mul(y, C::to256())))});
-  }
-}
 
 // ---------------------------------------------------------------- the compare kernel
 // Byte ranges of two arenas that must agree, 16 bytes per thread and step; blockIdx.y = range.  *first = smallest index of a
@@ -156,10 +87,7 @@ bool record_valid(const uint8_t *rec, Parsed &p, const char **why) {
   if (!lt_words(rec + REC_Z, FrParams::P)) { *why = "z is not below r"; return false; }
   uint8_t c[32];
   if (challenge(rec + REC_D1B, rec + REC_D1A, rec + REC_D2A, rec + REC_R, c)) { *why = "challenge hash failed"; return false; }
-  // z delta1_before == R + c delta1_after
-  const G1XYZZ lhs = scalar_mul(to_xyzz(p.d1b), load_u256(rec + REC_Z));
-  const G1XYZZ rhs = add_full(to_xyzz(p.r), scalar_mul(to_xyzz(p.d1a), load_u256(c)));
-  if (!same_point(lhs, rhs)) { *why = "the proof of knowledge of d does not verify"; return false; }
+  if (!schnorr_verify(p.d1b, p.d1a, p.r, rec + REC_Z, c)) { *why = "the proof of knowledge of d does not verify"; return false; }
   if (!pairings_equal(p.d1a, g2_generator(), g1_generator(), p.d2a)) { *why = "delta1_after and delta2_after are not the same multiple of the generators"; return false; }
   return true;
 }
@@ -167,13 +95,14 @@ bool record_valid(const uint8_t *rec, Parsed &p, const char **why) {
 
 // everything that reveals d: wiped however zkr_key_contribute is left
 struct Secrets {
-  U256 d, dinv, nonce, z;
+  U256 d, dinv, nonce;
   Fr dm, tmp;
+  ResponseScratch resp;  // wipes itself
   uint32_t naf[16];
   DevBuf d_naf;
   ~Secrets() {
     if (d_naf.p) { (void)hipMemset(d_naf.p, 0, sizeof(naf)); (void)hipDeviceSynchronize(); }
-    explicit_bzero(&d, sizeof(d)); explicit_bzero(&dinv, sizeof(dinv)); explicit_bzero(&nonce, sizeof(nonce)); explicit_bzero(&z, sizeof(z));
+    explicit_bzero(&d, sizeof(d)); explicit_bzero(&dinv, sizeof(dinv)); explicit_bzero(&nonce, sizeof(nonce));
     explicit_bzero(&dm, sizeof(dm)); explicit_bzero(&tmp, sizeof(tmp)); explicit_bzero(naf, sizeof(naf));
   }
 };
@@ -184,13 +113,11 @@ int refuse_shard(const zkr_key *key, const char *what) {
   return ZKR_ERR_ARG;
 }
 
-int scale_table(int device, G1Affine *pts, uint32_t n, const uint32_t *d_naf, int top, Fq *ztmp) {
+int scale_table(G1Affine *pts, uint32_t n, const uint32_t *d_naf, int top, Fq *ztmp) {
   if (!n) return 0;
-  // points per thread: one while that leaves the chip short of wavefronts (4 per SIMD on 1024 SIMDs), up to SCALE_MAX_PTS
-  int npt = (int)(n / (1024u * 64u * 4u));
-  npt = npt < 1 ? 1 : npt > SCALE_MAX_PTS ? SCALE_MAX_PTS : npt;
-  const uint32_t threads = (n + (uint32_t)npt - 1) / (uint32_t)npt;
-  scale_points_kernel<<<(threads + SCALE_THREADS - 1) / SCALE_THREADS, SCALE_THREADS>>>(pts, n, npt, d_naf, top, ztmp);
+  int npt;
+  const unsigned grid = group_scale_grid(n, &npt);
+  group_scale_uniform_kernel<G1C><<<grid, GROUP_THREADS>>>(pts, n, npt, d_naf, top, ztmp);
   ZKR_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -239,9 +166,7 @@ int zkr_key_contribute(const zkr_key *key, const uint8_t *d32, zkr_key **out, ui
   Secrets s;
   int rc;
   if (d32) {
-    bool small = d32[0] <= 1;
-    for (int i = 1; i < 32 && small; i++) small = d32[i] == 0;
-    if (small || !lt_words(d32, FrParams::P)) { set_error("zkr_key_contribute: d must satisfy 1 < d < r"); return ZKR_ERR_ARG; }
+    if (!valid_secret(d32)) { set_error("zkr_key_contribute: d must satisfy 1 < d < r"); return ZKR_ERR_ARG; }
     memcpy(s.d.v, d32, 32);
   } else if ((rc = draw_secret(s.d))) return rc;
   if ((rc = draw_secret(s.nonce))) return rc;
@@ -265,14 +190,7 @@ int zkr_key_contribute(const zkr_key *key, const uint8_t *d32, zkr_key **out, ui
   store_g1_std(rec + REC_D1B, d1b); store_g1_std(rec + REC_D1A, d1a); store_g2_std(rec + REC_D2A, d2a); store_g1_std(rec + REC_R, r_pt);
   uint8_t c[32];
   if ((rc = challenge(rec + REC_D1B, rec + REC_D1A, rec + REC_D2A, rec + REC_R, c))) return rc;
-  {  // z = k + c d mod r
-    Fr cm = to_mont(load_fp<FrParams>(c)), km;
-    memcpy(km.v, s.nonce.v, 32);
-    s.tmp = from_mont(add(to_mont(km), mul(cm, s.dm)));
-    explicit_bzero(&km, sizeof(km));
-    memcpy(s.z.v, s.tmp.v, 32);
-    memcpy(rec + REC_Z, s.z.v, 32);  // z itself is public
-  }
+  schnorr_response(s.nonce, c, s.dm, s.resp, rec + REC_Z);
 
   // a device copy of the compact arena (the key's own is cached on it and stays as it is): scale C and H there, patch delta
   void *base = nullptr;
@@ -288,7 +206,7 @@ int zkr_key_contribute(const zkr_key *key, const uint8_t *d32, zkr_key **out, ui
   ZKR_HIP_CHECK(hipMemcpy(s.d_naf.p, s.naf, sizeof(s.naf), hipMemcpyHostToDevice));
   unsigned char *cb = copy.as<unsigned char>();
   for (int t : {T_C, T_H})
-    if ((rc = scale_table(key->device, (G1Affine *)(cb + b.off_pts[t]), h.npts[t], s.d_naf.as<uint32_t>(), top, ztmp.as<Fq>()))) return rc;
+    if ((rc = scale_table((G1Affine *)(cb + b.off_pts[t]), h.npts[t], s.d_naf.as<uint32_t>(), top, ztmp.as<Fq>()))) return rc;
   uint8_t consts[192];
   store_g1_mont(consts, d1a);
   store_g2_mont(consts + 64, d2a);
@@ -387,16 +305,8 @@ int zkr_key_contribution_verify(const zkr_key *before, const zkr_key *after, con
   // 5. every C and H point moved by the inverse factor: random 128-bit combinations of both keys' tables (2^-128 per wrong entry)
   {
     const size_t nw = rank_entries(ha, T_C), nh = rank_entries(ha, T_H);
-    std::vector<uint8_t> sc((nw + nh) * 32, 0);
-    {
-      FILE *f = fopen("/dev/urandom", "rb");
-      if (!f) { set_error("cannot open /dev/urandom"); return ZKR_ERR_ARG; }
-      std::vector<uint8_t> rnd((nw + nh) * 16);
-      const bool bad = fread(rnd.data(), 1, rnd.size(), f) != rnd.size();
-      fclose(f);
-      if (bad) { set_error("short read from /dev/urandom"); return ZKR_ERR_ARG; }
-      for (size_t i = 0; i < nw + nh; i++) memcpy(&sc[32 * i], &rnd[16 * i], 16);
-    }
+    std::vector<uint8_t> sc;
+    if (int rc = random_128(sc, nw + nh)) return rc;
     ZKR_HIP_CHECK(hipSetDevice(device));
     DevBuf dsc;
     if (int rc = dsc.alloc(sc.size())) return rc;

@@ -17,6 +17,13 @@ namespace zkr {
 
 struct Tw29;  // kernels_ntt.hpp: a butterfly twiddle as nine 29-bit limbs
 void set_error(const char *fmt, ...);
+int os_random(void *out, size_t bytes);  // `bytes` from the OS CSPRNG (zkr_key.hip, beside set_error); ZKR_ERR_ARG with a message when it cannot be read
+// every entry point that needs a GPU refuses the same way when there is none
+inline int need_device(int device) {
+  const int found = zkr_device_count();
+  if (found <= device || device < 0) { set_error("no HIP device %d (found %d); libzkr_hip has no CPU fallback", device, found); return ZKR_ERR_NO_DEVICE; }
+  return 0;
+}
 #define ZKR_HIP_CHECK(expr)                                                                 \
   do {                                                                                      \
     hipError_t _e = (expr);                                                                 \
@@ -37,6 +44,26 @@ struct DevBuf {
   int alloc(size_t bytes) { ZKR_HIP_CHECK(hipMalloc(&p, bytes ? bytes : 1)); return 0; }
   template <class T> T *as() const { return static_cast<T *>(p); }
   void *release() { void *q = p; p = nullptr; return q; }
+};
+// "How many are bad, and which comes first": the two words a checking kernel updates with group_note_bad (kernels_group.hpp).
+struct FaultCounter {
+  DevBuf buf;
+  uint32_t count = 0, first = 0xffffffffu;  // as of the last read()
+  uint32_t *dev() const { return buf.as<uint32_t>(); }
+  int reset() {  // before every launch
+    if (!buf.p)
+      if (int rc = buf.alloc(8)) return rc;
+    const uint32_t none[2] = {0u, 0xffffffffu};
+    ZKR_HIP_CHECK(hipMemcpy(buf.p, none, 8, hipMemcpyHostToDevice));
+    return 0;
+  }
+  int read() {  // after the launch: its launch error, if any, or its tally
+    uint32_t res[2];
+    ZKR_HIP_CHECK(hipGetLastError());
+    ZKR_HIP_CHECK(hipMemcpy(res, buf.p, 8, hipMemcpyDeviceToHost));
+    count = res[0]; first = res[1];
+    return 0;
+  }
 };
 struct ScopedEvent {
   hipEvent_t e = nullptr;

@@ -8,8 +8,8 @@
 #include <string.h>
 #include "kernels_msm.hpp"
 #include "kernels_ntt.hpp"
+#include "kernels_group.hpp"  // group_on_curve_launch for ZKR_CHECK_POINTS
 #include "hostops.hpp"
-#include "pairing.hpp"  // the curve equations (g1_on_curve / g2_on_curve constants) for ZKR_CHECK_POINTS
 #include <map>
 #include "zkr_internal.hpp"
 
@@ -21,6 +21,15 @@ void set_error(const char *fmt, ...) {
   va_start(ap, fmt);
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
   va_end(ap);
+}
+int os_random(void *out, size_t bytes) {
+  static const char source[] = "/dev/urandom";
+  FILE *f = fopen(source, "rb");
+  if (!f) { set_error("cannot open %s", source); return ZKR_ERR_ARG; }
+  const bool bad = fread(out, 1, bytes, f) != bytes;
+  fclose(f);
+  if (bad) { set_error("short read from %s", source); return ZKR_ERR_ARG; }
+  return 0;
 }
 
 static inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
@@ -379,30 +388,15 @@ int radix_convert(int device, bool g2, void *d_points, size_t count, bool to261)
 // ZKR_CHECK_POINTS=1: every base point of a table (wire form, x 2^256) satisfies its curve's equation y^2 = x^3 + b before
 // anything is derived from it.  Off by default, as in the reference (websnark multiplies whatever the key holds): a point off
 // the curve makes the window-table build produce garbage multiples silently (its doubling chain may hit Y = 0).
-template <class F>
-static __global__ void on_curve_kernel(const Affine<F> *pts, uint32_t n, F b, uint32_t *bad) {  // bad[0] = count, bad[1] = smallest index
-  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  Affine<F> p = load_pod(pts + i);
-  if (p.is_inf()) return;  // placeholder of a shared-support table
-  if (sqr(p.y) == add(mul(sqr(p.x), p.x), b)) return;
-  atomicAdd(&bad[0], 1u);
-  atomicMin(&bad[1], i);
-}
 static int check_points_on_curve(bool g2, const void *d_table, uint32_t n) {
-  DevBuf buf;
-  int rc = buf.alloc(8);
-  if (rc) return rc;
-  const uint32_t init[2] = {0u, 0xffffffffu};
-  ZKR_HIP_CHECK(hipMemcpy(buf.p, init, 8, hipMemcpyHostToDevice));
-  const unsigned grid = (n + 255) / 256;
-  if (g2) on_curve_kernel<Fq2><<<grid, 256>>>((const G2Affine *)d_table, n, Fq2{pairing::fq_from_limbs(pairing::TWIST_B0), pairing::fq_from_limbs(pairing::TWIST_B1)}, buf.as<uint32_t>());
-  else on_curve_kernel<Fq><<<grid, 256>>>((const G1Affine *)d_table, n, pairing::fq_small(3), buf.as<uint32_t>());
-  ZKR_HIP_CHECK(hipGetLastError());
-  uint32_t bad[2];
-  ZKR_HIP_CHECK(hipMemcpy(bad, buf.p, 8, hipMemcpyDeviceToHost));
-  if (bad[0]) {
-    set_error("%u point(s) of a %s table are not on the curve (first: kept point %u); ZKR_CHECK_POINTS=1", bad[0], g2 ? "G2" : "G1", bad[1]);
+  FaultCounter bad;
+  int rc;
+  if ((rc = bad.reset())) return rc;
+  if (g2) group_on_curve_launch<Fq2>(d_table, n, true, bad.dev());  // infinity passes: the placeholder of a shared-support table
+  else group_on_curve_launch<Fq>(d_table, n, true, bad.dev());
+  if ((rc = bad.read())) return rc;
+  if (bad.count) {
+    set_error("%u point(s) of a %s table are not on the curve (first: kept point %u); ZKR_CHECK_POINTS=1", bad.count, g2 ? "G2" : "G1", bad.first);
     return ZKR_ERR_BAD_KEY;
   }
   return 0;
@@ -637,7 +631,7 @@ static bool all_zero(const uint8_t *p, size_t n) { for (size_t i = 0; i < n; i++
 
 int zkr_key_load_websnark(const void *pk_bin, size_t pk_len, int device, zkr_key **out) {
   if (!pk_bin || !out) { set_error("null argument"); return ZKR_ERR_ARG; }
-  if (zkr_device_count() <= device || device < 0) { set_error("no HIP device %d (found %d); libzkr_hip has no CPU fallback", device, zkr_device_count()); return ZKR_ERR_NO_DEVICE; }
+  if (int rc = need_device(device)) return rc;
   const uint8_t *pk = (const uint8_t *)pk_bin;
   if (pk_len < 488) { set_error("proving key shorter than its fixed header (488 bytes)"); return ZKR_ERR_BAD_KEY; }
   uint32_t n = rd32(pk), p = rd32(pk + 4), m = rd32(pk + 8);
@@ -980,7 +974,7 @@ int zkr_key_save(const zkr_key *k, const char *path) {
 
 int zkr_key_load_file(const char *path, int device, zkr_key **out) {
   if (!path || !out) { set_error("null argument"); return ZKR_ERR_ARG; }
-  if (zkr_device_count() <= device || device < 0) { set_error("no HIP device %d (found %d); libzkr_hip has no CPU fallback", device, zkr_device_count()); return ZKR_ERR_NO_DEVICE; }
+  if (int rc = need_device(device)) return rc;
   ZKR_HIP_CHECK(hipSetDevice(device));
   FILE *f = fopen(path, "rb");
   if (!f) { set_error("cannot open %s", path); return ZKR_ERR_BAD_KEY; }

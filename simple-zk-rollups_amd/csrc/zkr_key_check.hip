@@ -146,13 +146,8 @@ static __global__ __launch_bounds__(CHECK_THREADS) void rank_check_kernel(RankAr
 }
 
 // ---- level 1: values
-__device__ bool below(const uint32_t (&w)[8], const uint32_t (&p)[8]) {  // w < p as 256-bit integers
-  for (int i = 7; i >= 0; i--)
-    if (w[i] != p[i]) return w[i] < p[i];
-  return false;
-}
-__device__ bool canonical_words(const Fq &x) { return below(x.v, FqParams::P); }
-__device__ bool canonical_words(const Fq2 &x) { return below(x.a.v, FqParams::P) && below(x.b.v, FqParams::P); }
+__device__ bool canonical_words(const Fq &x) { return words_below(x.v, FqParams::P); }
+__device__ bool canonical_words(const Fq2 &x) { return words_below(x.a.v, FqParams::P) && words_below(x.b.v, FqParams::P); }
 __device__ bool zero_words(const Fq &x) {
   uint32_t o = 0;
   for (int i = 0; i < 8; i++) o |= x.v[i];
@@ -200,7 +195,7 @@ static __global__ __launch_bounds__(CHECK_THREADS) void coef_check_kernel(CoefAr
   Tally tl;
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.nnz[s]; i += (uint64_t)gridDim.x * blockDim.x) {
     const Fr c = load_fr(a.coef[s] + i);
-    tl.note(!below(c.v, FrParams::P), i);
+    tl.note(!words_below(c.v, FrParams::P), i);
   }
   flush(tl, &a.rec->count[ZKR_KEYSEC_COEF][s], &a.rec->first[ZKR_KEYSEC_COEF][s]);
 }
@@ -232,11 +227,7 @@ Fq to261(const Fq &x) {
 }
 Fq2 to261(const Fq2 &x) { return Fq2{to261(x.a), to261(x.b)}; }
 
-bool canonical_fq(const Fq &x) {
-  for (int i = 7; i >= 0; i--)
-    if (x.v[i] != FqParams::P[i]) return x.v[i] < FqParams::P[i];
-  return false;
-}
+bool canonical_fq(const Fq &x) { return words_below(x.v, FqParams::P); }
 
 // One result record (device) and its pinned host copy per device, made on first use and kept for the process (like the device's
 // stream set, zkr_key.hip): a check frees nothing, and a free would wait for the whole device.  Checks on one device take turns.

@@ -574,23 +574,13 @@ static XYZZ<F> msm_finish(uint32_t n, const MsmWorkspace &ws, int j = 0) {  // j
   return ((const XYZZ<F> *)ws.h_result)[j];
 }
 
-static bool u256_lt(const uint32_t *a, const uint32_t *b) {
-  for (int i = 7; i >= 0; i--)
-    if (a[i] != b[i]) return a[i] < b[i];
-  return false;
-}
-
 static int draw_blinding(uint8_t out[32]) {
-  FILE *f = fopen("/dev/urandom", "rb");
-  if (!f) { set_error("cannot open /dev/urandom"); return ZKR_ERR_ARG; }
-  for (;;) {
-    if (fread(out, 1, 32, f) != 32) { fclose(f); set_error("short read from /dev/urandom"); return ZKR_ERR_ARG; }
+  uint32_t v[8];
+  do {
+    if (int rc = os_random(out, 32)) return rc;
     out[31] &= 0x3f;
-    uint32_t v[8];
     memcpy(v, out, 32);
-    if (u256_lt(v, FrParams::P)) break;
-  }
-  fclose(f);
+  } while (!words_below(v, FrParams::P));
   return 0;
 }
 // r and s of one proof: the caller's, checked (both or neither), or drawn
@@ -604,7 +594,7 @@ static int take_blinding(const uint8_t *r32, const uint8_t *s32, uint8_t rb[32],
   memcpy(rb, r32, 32); memcpy(sb, s32, 32);
   uint32_t rv[8], sv[8];
   memcpy(rv, rb, 32); memcpy(sv, sb, 32);
-  if (!u256_lt(rv, FrParams::P) || !u256_lt(sv, FrParams::P)) { set_error("blinding scalar >= r"); return ZKR_ERR_ARG; }
+  if (!words_below(rv, FrParams::P) || !words_below(sv, FrParams::P)) { set_error("blinding scalar >= r"); return ZKR_ERR_ARG; }
   return 0;
 }
 
@@ -1244,7 +1234,7 @@ int zkr_calc_h(zkr_key *key, const void *witness_std, size_t witness_len, void *
 
 int zkr_ntt(void *data_std, unsigned logn, int inverse, int device) {
   if (!data_std || logn < 1 || logn > 27) { set_error("bad argument"); return ZKR_ERR_ARG; }
-  if (zkr_device_count() <= device || device < 0) { set_error("no HIP device %d; libzkr_hip has no CPU fallback", device); return ZKR_ERR_NO_DEVICE; }
+  if (int rc = need_device(device)) return rc;
   ZKR_HIP_CHECK(hipSetDevice(device));
   if (int lrc = ntt_lds_check(device)) return lrc;
   size_t n = (size_t)1 << logn;
@@ -1274,7 +1264,7 @@ int zkr_ntt(void *data_std, unsigned logn, int inverse, int device) {
 template <class F>
 static int msm_hook(const void *points_mont, const void *scalars_std, size_t n, uint8_t *out, int *is_inf, int device) {
   if (!points_mont || !scalars_std || !out || !is_inf) { set_error("null argument"); return ZKR_ERR_ARG; }
-  if (zkr_device_count() <= device || device < 0) { set_error("no HIP device %d; libzkr_hip has no CPU fallback", device); return ZKR_ERR_NO_DEVICE; }
+  if (int rc = need_device(device)) return rc;
   ZKR_HIP_CHECK(hipSetDevice(device));
   const size_t pb = sizeof(Affine<F>);
   const uint8_t *pts = (const uint8_t *)points_mont;

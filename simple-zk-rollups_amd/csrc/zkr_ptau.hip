@@ -36,28 +36,14 @@ Fr host_root_of_unity(unsigned k);  // zkr_key.hip
 static __global__ void ptau_coords_in_kernel(Fq *c, size_t n, uint32_t *bad) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  Fq x = load_pod(c + i);
-  bool lt = false;
-#pragma unroll
-  for (int w = 7; w >= 0; w--)
-    if (x.v[w] != FqParams::P[w]) { lt = x.v[w] < FqParams::P[w]; break; }
-  if (!lt) { atomicAdd(&bad[0], 1u); atomicMin(&bad[1], (uint32_t)i); return; }
+  const Fq x = load_pod(c + i);
+  if (!words_below(x.v, FqParams::P)) { group_note_bad(bad, (uint32_t)i); return; }
   store_pod(c + i, to_mont(x));
 }
 static __global__ void ptau_coords_out_kernel(Fq *c, size_t n) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   store_pod(c + i, from_mont(load_pod(c + i)));
-}
-// every point is finite and on its curve: bad[0] = count, bad[1] = smallest index (the model: on_curve_kernel, zkr_key.hip)
-template <class F>
-static __global__ void ptau_on_curve_kernel(const Affine<F> *pts, uint32_t n, F b, uint32_t *bad) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const Affine<F> p = load_pod(pts + i);
-  if (!p.is_inf() && sqr(p.y) == add(mul(sqr(p.x), p.x), b)) return;
-  atomicAdd(&bad[0], 1u);
-  atomicMin(&bad[1], i);
 }
 
 namespace {
@@ -108,26 +94,15 @@ const char *ptau_header_fault(const void *ptau, size_t len, PtauLayout &l) {
   return nullptr;
 }
 
-bool valid_secret(const uint8_t *s) {  // 1 < s < r
-  bool small = s[0] <= 1;
-  for (int i = 1; i < 32 && small; i++) small = s[i] == 0;
-  return !small && lt_words(s, FrParams::P);
-}
-
 // ---------------------------------------------------------------- launches
-int points_per_thread(size_t n) {  // one while that leaves the chip short of wavefronts (4 per SIMD on 1024 SIMDs), up to GROUP_MAX_PTS
-  const size_t npt = n / (1024u * 64u * 4u);
-  return npt < 1 ? 1 : npt > (size_t)GROUP_MAX_PTS ? GROUP_MAX_PTS : (int)npt;
-}
 // pts[i] <- s[i] pts[i] on the current device; d_scalars: standard form, one per point (sc_stride 1) or one for all (0);
 // ztmp: 2 n coordinates
 template <class C>
 int scale_each_launch(Affine<typename C::W> *pts, size_t n, const Fr *d_scalars, uint32_t sc_stride, void *ztmp) {
   if (!n) return 0;
-  const int npt = points_per_thread(n);
-  const size_t threads = (n + (size_t)npt - 1) / (size_t)npt;
-  group_scale_each_kernel<C><<<(unsigned)((threads + GROUP_THREADS - 1) / GROUP_THREADS), GROUP_THREADS>>>(pts, (uint32_t)n, npt, (const uint32_t *)d_scalars, sc_stride,
-                                                                                                     (typename C::W *)ztmp);
+  int npt;
+  const unsigned grid = group_scale_grid(n, &npt);
+  group_scale_each_kernel<C><<<grid, GROUP_THREADS>>>(pts, (uint32_t)n, npt, (const uint32_t *)d_scalars, sc_stride, (typename C::W *)ztmp);
   ZKR_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -167,10 +142,6 @@ int group_ntt_launch(Affine<typename C::W> *pts, Affine<typename C::W> *tmp, uns
   return 0;
 }
 
-int need_device(int device) {
-  if (zkr_device_count() <= device || device < 0) { set_error("no HIP device %d; libzkr_hip has no CPU fallback", device); return ZKR_ERR_NO_DEVICE; }
-  return 0;
-}
 int sync_or_fail(const char *what) {
   const hipError_t e = hipDeviceSynchronize();
   if (e != hipSuccess) { set_error("%s failed: %s", what, hipGetErrorString(e)); return ZKR_ERR_HIP; }
@@ -215,36 +186,28 @@ int ptau_upload(const void *ptau, const PtauLayout &l, DevicePtau &d, int *fault
   d.l = l;
   *fault_vector = -1;
   const size_t body = l.total - PTAU_HEADER, n_coords = body / 32;
-  DevBuf bad;
+  FaultCounter bad;
   int rc;
-  if ((rc = d.body.alloc(body)) || (rc = bad.alloc(8))) return rc;
+  if ((rc = d.body.alloc(body)) || (rc = bad.reset())) return rc;
   ZKR_HIP_CHECK(hipMemcpy(d.body.p, (const uint8_t *)ptau + PTAU_HEADER, body, hipMemcpyHostToDevice));
-  const uint32_t none[2] = {0u, 0xffffffffu};
-  ZKR_HIP_CHECK(hipMemcpy(bad.p, none, 8, hipMemcpyHostToDevice));
-  ptau_coords_in_kernel<<<(unsigned)((n_coords + 255) / 256), 256>>>(d.body.as<Fq>(), n_coords, bad.as<uint32_t>());
-  ZKR_HIP_CHECK(hipGetLastError());
-  uint32_t res[2];
-  ZKR_HIP_CHECK(hipMemcpy(res, bad.p, 8, hipMemcpyDeviceToHost));
-  if (res[0]) {
-    const size_t at = PTAU_HEADER + 32 * (size_t)res[1];  // the first of them, which names the vector
+  ptau_coords_in_kernel<<<(unsigned)((n_coords + 255) / 256), 256>>>(d.body.as<Fq>(), n_coords, bad.dev());
+  if ((rc = bad.read())) return rc;
+  if (bad.count) {
+    const size_t at = PTAU_HEADER + 32 * (size_t)bad.first;  // the first of them, which names the vector
     int v = 0;
     while (v + 1 < N_VECTORS && at >= l.off[v + 1]) v++;
     *fault_vector = v;
-    snprintf(why, why_len, "%u coordinate(s) are not below q (first: in entry %zu of %s)", res[0], (at - l.off[v]) / (vector_is_g2(v) ? 128 : 64), VECTOR_NAME[v]);
+    snprintf(why, why_len, "%u coordinate(s) are not below q (first: in entry %zu of %s)", bad.count, (at - l.off[v]) / (vector_is_g2(v) ? 128 : 64), VECTOR_NAME[v]);
     return 0;
   }
-  const Fq2 b2{pairing::fq_from_limbs(pairing::TWIST_B0), pairing::fq_from_limbs(pairing::TWIST_B1)};
   for (int v = 0; v < N_VECTORS; v++) {
-    const uint32_t init[2] = {0u, 0xffffffffu};
-    ZKR_HIP_CHECK(hipMemcpy(bad.p, init, 8, hipMemcpyHostToDevice));
-    const uint32_t n = (uint32_t)l.count[v];
-    if (vector_is_g2(v)) ptau_on_curve_kernel<Fq2><<<(n + 255) / 256, 256>>>(d.vec<G2Affine>(v), n, b2, bad.as<uint32_t>());
-    else ptau_on_curve_kernel<Fq><<<(n + 255) / 256, 256>>>(d.vec<G1Affine>(v), n, pairing::fq_small(3), bad.as<uint32_t>());
-    ZKR_HIP_CHECK(hipGetLastError());
-    ZKR_HIP_CHECK(hipMemcpy(res, bad.p, 8, hipMemcpyDeviceToHost));
-    if (res[0]) {
+    if ((rc = bad.reset())) return rc;
+    if (vector_is_g2(v)) group_on_curve_launch<Fq2>(d.vec<void>(v), (uint32_t)l.count[v], false, bad.dev());
+    else group_on_curve_launch<Fq>(d.vec<void>(v), (uint32_t)l.count[v], false, bad.dev());
+    if ((rc = bad.read())) return rc;
+    if (bad.count) {
       *fault_vector = v;
-      snprintf(why, why_len, "%u point(s) of %s are at infinity or off the curve (first: entry %u)", res[0], VECTOR_NAME[v], res[1]);
+      snprintf(why, why_len, "%u point(s) of %s are at infinity or off the curve (first: entry %u)", bad.count, VECTOR_NAME[v], bad.first);
       return 0;
     }
   }
@@ -302,10 +265,7 @@ bool ptau_record_valid(const uint8_t *rec, ParsedPtauRecord &p, char *why, size_
     if (!lt_words(rec + PREC_Z[k], FrParams::P)) { snprintf(why, why_len, "z_%s is not below r", nm); return false; }
     uint8_t c[32];
     if (ptau_challenge(rec, k, c)) { snprintf(why, why_len, "challenge hash failed"); return false; }
-    // z before == R + c after
-    const G1XYZZ lhs = scalar_mul(to_xyzz(p.before[k]), load_u256(rec + PREC_Z[k]));
-    const G1XYZZ rhs = add_full(to_xyzz(p.r[k]), scalar_mul(to_xyzz(p.after[k]), load_u256(c)));
-    if (!same_point(lhs, rhs)) { snprintf(why, why_len, "the proof of knowledge of %s does not verify", nm); return false; }
+    if (!schnorr_verify(p.before[k], p.after[k], p.r[k], rec + PREC_Z[k], c)) { snprintf(why, why_len, "the proof of knowledge of %s does not verify", nm); return false; }
     if (k != 1 && !pairings_equal(p.after[k], g2_generator(), g1_generator(), p.g2[k])) {
       snprintf(why, why_len, "%s1_after and %s2_after are not the same multiple of the generators", nm, nm);
       return false;
@@ -339,17 +299,6 @@ struct PtauVerdict {
   uint64_t step = 0, vector = 0;  // the first failed step (0: none) and the vector it was found in
   char why[240] = "";
 };
-int random_128(std::vector<uint8_t> &sc, size_t n) {  // n scalars of 32 bytes, 128 random bits each
-  sc.assign(n * 32, 0);
-  std::vector<uint8_t> rnd(n * 16);
-  FILE *f = fopen("/dev/urandom", "rb");
-  if (!f) { set_error("cannot open /dev/urandom"); return ZKR_ERR_ARG; }
-  const bool bad = fread(rnd.data(), 1, rnd.size(), f) != rnd.size();
-  fclose(f);
-  if (bad) { set_error("short read from /dev/urandom"); return ZKR_ERR_ARG; }
-  for (size_t i = 0; i < n; i++) memcpy(&sc[32 * i], &rnd[16 * i], 16);
-  return 0;
-}
 // sum_i sc[i] pts[i] by the library's MSM path (host buffers, Montgomery affine points); *inf: the sum is the point at infinity
 int msm_g1_host(const uint8_t *pts, const uint8_t *sc, size_t n, int device, G1Affine &out, bool &inf) {
   uint8_t o[64];
@@ -388,18 +337,17 @@ int ptau_check(const void *ptau, const PtauLayout &l, int device, DevicePtau &d,
     U256 r;
     memcpy(r.v, FrParams::P, 32);
     const int top = naf_of(r, naf, naf + 8);
-    DevBuf dn, bad;
-    if ((rc = dn.alloc(sizeof(naf))) || (rc = bad.alloc(8))) return rc;
+    DevBuf dn;
+    FaultCounter bad;
+    if ((rc = dn.alloc(sizeof(naf)))) return rc;
     ZKR_HIP_CHECK(hipMemcpy(dn.p, naf, sizeof(naf), hipMemcpyHostToDevice));
     for (int vec : {V_TAU2, V_BETA2}) {
-      const uint32_t init[2] = {0u, 0xffffffffu}, n = (uint32_t)l.count[vec];
-      uint32_t res[2];
-      ZKR_HIP_CHECK(hipMemcpy(bad.p, init, 8, hipMemcpyHostToDevice));
-      group_order_check_kernel<G2C><<<(n + GROUP_THREADS - 1) / GROUP_THREADS, GROUP_THREADS>>>(d.vec<G2Affine>(vec), n, dn.as<uint32_t>(), top, bad.as<uint32_t>());
-      ZKR_HIP_CHECK(hipGetLastError());
-      ZKR_HIP_CHECK(hipMemcpy(res, bad.p, 8, hipMemcpyDeviceToHost));
-      if (res[0]) {
-        snprintf(why, sizeof(why), "%u point(s) are on the twist but outside the order-r subgroup G2 (first: entry %u)", res[0], res[1]);
+      const uint32_t n = (uint32_t)l.count[vec];
+      if ((rc = bad.reset())) return rc;
+      group_order_check_kernel<G2C><<<(n + GROUP_THREADS - 1) / GROUP_THREADS, GROUP_THREADS>>>(d.vec<G2Affine>(vec), n, dn.as<uint32_t>(), top, bad.dev());
+      if ((rc = bad.read())) return rc;
+      if (bad.count) {
+        snprintf(why, sizeof(why), "%u point(s) are on the twist but outside the order-r subgroup G2 (first: entry %u)", bad.count, bad.first);
         return fail(3, (uint64_t)vec, why);
       }
     }
@@ -600,8 +548,8 @@ int combine_run(const DeviceCombinePlan &dp, const Affine<typename C::W> *pts, v
 // everything that reveals tau, alfa or beta: wiped however zkr_ptau_contribute is left
 struct PtauSecrets {
   U256 s[3], nonce[3];
-  Fr sm[3], tmp;
-  Fr km, prod;    // the nonce in Montgomery form and c s, on their way into z
+  Fr sm[3];
+  ResponseScratch resp;  // wipes itself
   DevBuf powers;  // tau^i (2 M) | alfa tau^i (M) | beta tau^i (M): Montgomery while they are built, then standard form
   DevBuf ztmp;    // the ZZ, ZZZ of the ladders' unnormalised results: functions of the secret scalars
   size_t powers_bytes = 0, ztmp_bytes = 0;
@@ -609,8 +557,7 @@ struct PtauSecrets {
     if (powers.p) (void)hipMemset(powers.p, 0, powers_bytes);
     if (ztmp.p) (void)hipMemset(ztmp.p, 0, ztmp_bytes);
     if (powers.p || ztmp.p) (void)hipDeviceSynchronize();
-    explicit_bzero(s, sizeof(s)); explicit_bzero(nonce, sizeof(nonce)); explicit_bzero(sm, sizeof(sm)); explicit_bzero(&tmp, sizeof(tmp));
-    explicit_bzero(&km, sizeof(km)); explicit_bzero(&prod, sizeof(prod));
+    explicit_bzero(s, sizeof(s)); explicit_bzero(nonce, sizeof(nonce)); explicit_bzero(sm, sizeof(sm));
   }
 };
 
@@ -856,13 +803,7 @@ int zkr_ptau_contribute(const void *ptau, size_t len, const uint8_t *secrets96, 
     store_g1_std(rec + PREC_R[k], to_affine(r_x));
     uint8_t c[32];
     if ((rc = ptau_challenge(rec, k, c))) return rc;
-    // z = k + c s mod r
-    const Fr cm = to_mont(load_fp<FrParams>(c));  // public
-    memcpy(s.km.v, s.nonce[k].v, 32);
-    s.km = to_mont(s.km);
-    s.prod = mul(cm, s.sm[k]);
-    s.tmp = from_mont(add(s.km, s.prod));
-    memcpy(rec + PREC_Z[k], s.tmp.v, 32);  // z itself is public
+    schnorr_response(s.nonce[k], c, s.sm[k], s.resp, rec + PREC_Z[k]);
   }
   memcpy(record_out, rec, ZKR_PTAU_RECORD_BYTES);
   *ptau_out = out;

@@ -21,16 +21,12 @@ using namespace zkr;
 static bool fq_lt_q(const uint8_t *p) {
   uint32_t v[8];
   memcpy(v, p, 32);
-  for (int i = 7; i >= 0; i--)
-    if (v[i] != FqParams::P[i]) return v[i] < FqParams::P[i];
-  return false;
+  return words_below(v, FqParams::P);
 }
 static bool fr_lt_r(const uint8_t *p) {
   uint32_t v[8];
   memcpy(v, p, 32);
-  for (int i = 7; i >= 0; i--)
-    if (v[i] != FrParams::P[i]) return v[i] < FrParams::P[i];
-  return false;
+  return words_below(v, FrParams::P);
 }
 // standard-form bytes -> Montgomery affine; false when a coordinate is >= q or the point is off the curve
 static bool read_g1(const uint8_t *p, G1Affine &out) {
@@ -260,12 +256,9 @@ extern "C" int zkr_verify_batch(const void *vk_bin, size_t vk_len, const uint8_t
   const uint8_t *pub = (const uint8_t *)publics_std;
   std::vector<uint8_t> z(32 * n_proofs, 0);
   {
-    FILE *f = fopen("/dev/urandom", "rb");
-    if (!f) { set_error("cannot open /dev/urandom"); return ZKR_ERR_ARG; }
-    bool bad = false;
-    for (size_t i = 1; i < n_proofs && !bad; i++) bad = fread(&z[32 * i], 1, 16, f) != 16;
-    fclose(f);
-    if (bad) { set_error("short read from /dev/urandom"); return ZKR_ERR_ARG; }
+    std::vector<uint8_t> rnd(16 * (n_proofs - 1));
+    if ((rc = os_random(rnd.data(), rnd.size()))) return rc;
+    for (size_t i = 1; i < n_proofs; i++) memcpy(&z[32 * i], &rnd[16 * (i - 1)], 16);
     z[0] = 1;
   }
   std::vector<G1Affine> ps;

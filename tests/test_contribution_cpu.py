@@ -131,7 +131,8 @@ def test_vk_contribute_replaces_vk_delta_2_only_and_refuses_a_foreign_record():
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 def test_contribution_kernels_use_no_scratch(tmp_path):
     """The compiler's own metadata, read as tests/test_kernel_resources.py reads it: no kernel of zkr_contribute.hip spills or keeps a
-    stack frame, and the scaling kernel leaves room for at least two wavefronts per SIMD (512 VGPRs)."""
+    stack frame, and the scaling kernel (group_scale_uniform_kernel of kernels_group.hpp, instantiated here for G1 alone) leaves
+    room for three wavefronts per SIMD: 168 VGPRs is the last allocation of 512 that does."""
     out = tmp_path / "zkr_contribute.s"
     subprocess.check_call([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-Wno-unused-function", "-Wno-unused-result", "-Wno-unused-value",
                            "--cuda-device-only", "-S", os.path.join(ROOT, "simple-zk-rollups_amd", "csrc", "zkr_contribute.hip"), "-o", str(out)], stderr=subprocess.DEVNULL)
@@ -139,10 +140,11 @@ def test_contribution_kernels_use_no_scratch(tmp_path):
     for m in re.finditer(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", out.read_text(), re.S):
         g = lambda key: int(re.search(r"\.amdhsa_" + key + r"\s+(\d+)", m.group(2)).group(1))
         rows[m.group(1)] = (g("private_segment_fixed_size"), g("next_free_vgpr"))
-    scale = [v for k, v in rows.items() if "scale_points_kernel" in k]
+    scale = [v for k, v in rows.items() if "group_scale_uniform_kernel" in k and "G1C" in k]
+    assert len([k for k in rows if "group_scale_uniform_kernel" in k]) == 1
     assert len(scale) == 1 and any("compare_ranges_kernel" in k for k in rows)
     assert {k: v for k, v in rows.items() if v[0]} == {}
-    assert scale[0][1] <= 256
+    assert scale[0][1] <= 168
 
 
 NODE = shutil.which("node")

@@ -188,7 +188,7 @@ def test_ptau_kernels_use_no_scratch(tmp_path):
     rows = {}
     for m in re.finditer(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", out.read_text(), re.S):
         rows[m.group(1)] = int(re.search(r"\.amdhsa_private_segment_fixed_size\s+(\d+)", m.group(2)).group(1))
-    for kernel in ("group_scale_each_kernel", "group_butterfly_kernel", "group_bitrev_kernel", "ptau_on_curve_kernel"):
+    for kernel in ("group_scale_each_kernel", "group_butterfly_kernel", "group_bitrev_kernel", "group_on_curve_kernel"):
         inst = [k for k in rows if kernel in k]
         assert len(inst) == 2 and any("G2C" in k or "Fq2" in k for k in inst), (kernel, inst)   # G1 and G2
     for kernel in ("group_combine_kernel",):

@@ -4,9 +4,9 @@ device synchronise), median of REPS after one warm-up, all in one process so tha
   python tools/contribution_time.py            the tx circuit (2^17, zkr_setup_r1cs) and a synthetic key at 2^20 (zkr_synth_key)
   python tools/contribution_time.py once 20    ONE contribution of a 2^20 key and nothing else: the run to put under
                                                `rocprofv3 --kernel-trace --stats -- python tools/contribution_time.py once 20`
-                                               for the scaling kernel's own time (scale_points_kernel, two launches: C and H)
--> one JSON line per size.  fq_products: what the kernel's schedule multiplies for THIS d (csrc/zkr_contribute.hip,
-scale_points_kernel): per point `top` doublings of 9 products and one addition of 11 per non-zero NAF digit below the leading
+                                               for the scaling kernel's own time (group_scale_uniform_kernel, two launches: C and H)
+-> one JSON line per size.  fq_products: what the kernel's schedule multiplies for THIS d (csrc/kernels_group.hpp,
+group_scale_uniform_kernel): per point `top` doublings of 9 products and one addition of 11 per non-zero NAF digit below the leading
 one, 2 + 9 for the radix changes and the affine form, npt / 2 for the prefix products, and 1 / npt of an inversion."""
 import json, os, sys, time
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "simple-zk-rollups_amd", "python"))
@@ -35,7 +35,7 @@ def naf(e):
 def products_per_point(d, n_points):
     digits = naf(pow(d, -1, R))
     top, adds = len(digits) - 1, sum(1 for z in digits[:-1] if z)
-    npt = min(8, max(1, n_points // (1024 * 64 * 4)))          # scale_table's points per thread
+    npt = min(8, max(1, n_points // (1024 * 64 * 4)))          # group_scale_grid's points per thread
     inversion = 253 + bin(Q - 2).count("1")
     return top * DBL_PRODUCTS + adds * ADD_PRODUCTS + 2 + 9 + npt / 2 + inversion / npt, top, adds, npt
 
