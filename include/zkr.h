@@ -295,6 +295,53 @@ int zkr_setup_r1cs(const void *r1cs_bin, size_t r1cs_len, const uint8_t *toxic16
 int zkr_setup_r1cs_websnark(const void *r1cs_bin, size_t r1cs_len, const uint8_t *toxic160, int device, void **pk_out, size_t *pk_len, void **vk_out,
                             size_t *vk_len);
 
+/* ---- does a witness satisfy its constraint system? (`snarkjs wtns check`, on the GPU) ----------------------------
+ * zkr_prove proves whatever witness it is given: the key holds the A and B sides of the QAP and no C side, the quotient divides
+ * exactly for every witness, and a witness that violates the circuit gives ZKR_OK and 256 bytes no verifier accepts.  The
+ * reference stands two things beside its prover: `Circuit.calculateWitness` (operator/src/snarks/common.ts:15-17), which throws
+ * on inputs that violate the circuit it was compiled from, and `groth.isValid` after every proof (common.ts:30-38), which answers
+ * "invalid" and never where.  The witness builders of this library (zkr_rollup_witness*) stand in for the first for this build's
+ * own two circuits only; zkr_r1cs_check stands in for it for ANY system and witness producer, before the proof, on the device
+ * where batch witnesses already live (zkr_rollup_witness_batch_device -> zkr_r1cs_check_device -> zkr_prove_batch_device), and
+ * names the first violated constraint.
+ * zkr_r1cs_load: r1cs_bin in the layout of zkr_setup_r1cs, parsed by the same parser (same bounds, same messages) BEFORE any
+ * device call -- a malformed buffer is ZKR_ERR_ARG on a machine without a GPU too, a well-formed one without a device
+ * ZKR_ERR_NO_DEVICE (no CPU fallback).  The system stays on `device`: three CSR sides with Montgomery coefficients, the list of
+ * wide constraints, a small result buffer.  Nothing is normalised: a signal that appears twice in one side adds up, an empty
+ * side is zero.  zkr_r1cs_info: out[0..5] = nVars, nPublic, nConstraints, terms of A, of B, of C.
+ * One zkr_r1cs serves ONE call at a time (it owns one stream and one result buffer, as a key owns its proof workspaces): calls on
+ * the same system from several host threads must be serialised by the caller; different systems are independent. */
+typedef struct zkr_r1cs zkr_r1cs;
+int zkr_r1cs_load(const void *r1cs_bin, size_t r1cs_len, int device, zkr_r1cs **out);
+void zkr_r1cs_free(zkr_r1cs *cs);
+int zkr_r1cs_info(const zkr_r1cs *cs, uint64_t out[6]);
+/* The check.  Witnesses: nVars x 32 B standard form, exactly what zkr_prove(_device) takes; _device: `count` pointers into HBM
+ * on the system's device, `stream` as for zkr_prove_device (the check starts after the work already queued there -- the witness
+ * producer -- and runs on the system's own stream); the call returns once the reports are on the host.  The host form uploads the
+ * witnesses (witness_len != nVars * 32: ZKR_ERR_BAD_WITNESS) and calls the device form.
+ * reports (may be NULL): count x 3 words per witness:
+ *   [0] constraints violated   [1] the smallest violated constraint (UINT64_MAX: none)   [2] 1 when signal 0 is not 1
+ * *all_satisfied = 1 iff every witness has [0] == 0 and [2] == 0.
+ * What is judged is the witness the prover would use: every word is reduced below r first (a word w + r gets the verdict of w).
+ * Signal 0 must be 1: the verifier's IC_0 assumes it, and a consistent witness with w[0] = 2 satisfies every constraint and still
+ * proves nothing.  A violated witness is NOT an error status (as with zkr_verify): ZKR_OK, *all_satisfied = 0 and a
+ * zkr_last_error line for the first failing witness, "witness 2: 3 constraints violated, first 492" or "witness 0: signal 0 is
+ * not 1".  A status below zero only for bad arguments (count == 0 and null pointers: ZKR_ERR_ARG) or a HIP failure. */
+int zkr_r1cs_check_device(zkr_r1cs *cs, const void *const *d_witnesses_std, size_t count, void *stream, uint64_t *reports, int *all_satisfied);
+int zkr_r1cs_check(zkr_r1cs *cs, const void *const *witnesses_std, size_t witness_len, size_t count, uint64_t *reports, int *all_satisfied);
+/* Which key a system belongs to -- nothing else stops a caller from checking witnesses against the wrong or a stale circuit file.
+ * *same = 1 iff nVars and nPublic agree, the key's domain is the one zkr_setup_r1cs's rule gives the system, and for ONE random
+ * vector v of nVars field elements (OS CSPRNG) the key's QAP sides, evaluated by the prover's own row kernels over the key's
+ * arena, agree word for word with the system: A v on the rows below nConstraints, v[s] on row nConstraints + s for s <= nPublic
+ * (the rows snarkjs's setup appends), zero above; B v on the rows below nConstraints, zero above.  Two different matrices agree
+ * on a random v with probability 1/r; term order inside a row does not matter.
+ * WHAT THIS BINDS: the A and B sides only.  A key has no C side to compare -- C reaches a key only through the C-query points of
+ * its setup -- so a system that differs from the key's in C alone is reported as the same.  The call catches the wrong or stale
+ * circuit file; it is no statement about the key's C query.
+ * A shard key is accepted (it holds the whole QAP).  Key and system on different devices: ZKR_ERR_ARG.  A mismatch is ZKR_OK with
+ * *same = 0 and a zkr_last_error line naming the geometry, or the side and the first differing row. */
+int zkr_r1cs_matches_key(zkr_r1cs *cs, const zkr_key *key, int *same);
+
 /* ---- a further party's contribution to a key's delta (what makes a key somebody else can trust) ------
  * Whoever ran a setup saw (or chose) delta, and delta forges proofs (a key from a transcript has delta = 1).  A contributor
  * re-randomises delta with a secret d of its own and none of the toxic values:

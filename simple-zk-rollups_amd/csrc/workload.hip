@@ -42,14 +42,6 @@ static Fr fr_u64(uint64_t x) {
   return to_mont(r);
 }
 
-struct Term { uint32_t sig; Fr coef; };  // coef Montgomery
-struct Circuit {
-  uint32_t n = 0, p = 0, nC = 0, m = 0;
-  std::vector<uint32_t> rowA, rowB, rowC;  // CSR row pointers (nC+1)
-  std::vector<Term> tA, tB, tC;
-  std::vector<Fr> w;  // Montgomery
-};
-
 static Fr dot(const std::vector<Term> &t, size_t b, size_t e, const std::vector<Fr> &w) {
   Fr acc = Fr::zero();
   for (size_t i = b; i < e; i++) acc = add(acc, mul(t[i].coef, w[t[i].sig]));
@@ -366,29 +358,13 @@ static void vk_from_generated(const Generated &g, std::vector<uint8_t> &vk) {
   memcpy(vk.data() + 452, g.ic_std.data(), 64 * nic);
 }
 
-}  // namespace zkr
-
-using namespace zkr;
-
-extern "C" {
-
-// ---- Groth16 setup for an arbitrary R1CS (SURVEY 8(f-2)): restates `snarkjs setup --protocol groth`
-// (/root/reference/prover/package.json:34,37; SURVEY App. B "Setup") with the key's group elements computed on the GPU
 static bool read_fr_std(const uint8_t *p, Fr &out) {
   memcpy(out.v, p, 32);
   return words_below(out.v, FrParams::P);
 }
-static int draw_fr(Fr &out) {
-  for (;;) {
-    uint8_t b[32];
-    if (int rc = os_random(b, 32)) return rc;
-    b[31] &= 0x3f;
-    if (read_fr_std(b, out) && !out.is_zero()) return 0;
-  }
-}
 
 // r1cs_bin (include/zkr.h) -> the circuit, with its domain
-static int parse_r1cs(const void *r1cs_bin, size_t r1cs_len, Circuit &c) {
+int parse_r1cs(const void *r1cs_bin, size_t r1cs_len, Circuit &c) {
   const uint8_t *b = (const uint8_t *)r1cs_bin, *end = b + r1cs_len;
   if (r1cs_len < 12) { set_error("R1CS shorter than its header"); return ZKR_ERR_ARG; }
   memcpy(&c.n, b, 4); memcpy(&c.p, b + 4, 4); memcpy(&c.nC, b + 8, 4);
@@ -419,6 +395,23 @@ static int parse_r1cs(const void *r1cs_bin, size_t r1cs_len, Circuit &c) {
   }
   if (b != end) { set_error("R1CS has %zu trailing bytes", (size_t)(end - b)); return ZKR_ERR_ARG; }
   return 0;
+}
+
+}  // namespace zkr
+
+using namespace zkr;
+
+extern "C" {
+
+// ---- Groth16 setup for an arbitrary R1CS (SURVEY 8(f-2)): restates `snarkjs setup --protocol groth`
+// (/root/reference/prover/package.json:34,37; SURVEY App. B "Setup") with the key's group elements computed on the GPU
+static int draw_fr(Fr &out) {
+  for (;;) {
+    uint8_t b[32];
+    if (int rc = os_random(b, 32)) return rc;
+    b[31] &= 0x3f;
+    if (read_fr_std(b, out) && !out.is_zero()) return 0;
+  }
 }
 
 // r1cs_bin -> g.circ; toxic waste injected or drawn; QAP at t and every group element on the GPU

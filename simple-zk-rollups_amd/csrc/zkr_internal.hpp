@@ -293,6 +293,15 @@ struct QapColumns {
 // (ZKR_ERR_BAD_KEY).  d_tbl (device, Montgomery affine, infinity where a signal's polynomial vanishes; the caller hipFree's them):
 // [T_A], [T_B1], [T_B2]: n points; [T_C]: the n points K[s] = beta A_s + alfa B_s + C_s (IC for s <= nPublic, C above); [T_H]: m
 int ptau_key_tables(const void *ptau, size_t len, int device, uint32_t m, uint32_t n, const QapColumns cols[3], void *d_tbl[N_TABLES], uint8_t consts448[448]);
+// workload.hip: a rank-1 constraint system as the setups and zkr_r1cs.hip take it, rows in CSR
+struct Term { uint32_t sig; Fr coef; };  // coef Montgomery
+struct Circuit {
+  uint32_t n = 0, p = 0, nC = 0, m = 0;
+  std::vector<uint32_t> rowA, rowB, rowC;  // CSR row pointers (nC+1)
+  std::vector<Term> tA, tB, tC;
+  std::vector<Fr> w;  // Montgomery
+};
+int parse_r1cs(const void *r1cs_bin, size_t r1cs_len, Circuit &c);  // r1cs_bin (include/zkr.h) -> the circuit, with its domain; host only; ZKR_ERR_ARG with a message
 MsmPlan msm_plan(size_t n_scalars, size_t n_points, int c_fixed = 0);
 uint32_t big_threshold(size_t n_points, int K, uint32_t nbw, int nbat);  // occupancy above which a bucket goes to msm_big_kernel (zkr_key.hip)
 int digit_lists_alloc(DigitLists &dl, size_t n_scalars, const MsmPlan &pl);

@@ -51,6 +51,13 @@ def lib():
     L.zkr_key_base_arena.argtypes = [vp, c.POINTER(vp), c.POINTER(sz)]
     L.zkr_key_adopt_base_arena.argtypes = [vp, sz, i, c.POINTER(vp)]
     L.zkr_key_check.argtypes = [vp, i, c.POINTER(c.c_uint64)]
+    L.zkr_r1cs_load.argtypes = [u8p, sz, i, c.POINTER(vp)]
+    L.zkr_r1cs_free.argtypes = [vp]
+    L.zkr_r1cs_free.restype = None
+    L.zkr_r1cs_info.argtypes = [vp, c.POINTER(c.c_uint64)]
+    L.zkr_r1cs_check_device.argtypes = [vp, c.POINTER(vp), sz, vp, c.POINTER(c.c_uint64), c.POINTER(i)]
+    L.zkr_r1cs_check.argtypes = [vp, c.POINTER(c.c_char_p), sz, sz, c.POINTER(c.c_uint64), c.POINTER(i)]
+    L.zkr_r1cs_matches_key.argtypes = [vp, vp, c.POINTER(i)]
     L.zkr_key_replicate.argtypes = [vp, i, i, c.POINTER(vp)]
     L.zkr_key_contribute.argtypes = [vp, u8p, c.POINTER(vp), u8p]
     L.zkr_contribution_check.argtypes = [u8p, c.POINTER(i)]
@@ -437,6 +444,77 @@ class ProvingKey:
             _check(lib().zkr_prof_get(self._h, st.encode(), ctypes.byref(ms), ctypes.byref(n)))
             out[st] = (ms.value, n.value)
         return out
+
+
+class ConstraintSystem:
+    """A rank-1 constraint system resident on the device (zkr_r1cs*): does a witness satisfy it, and if not, which constraint
+    fails first -- before the proof, where ProvingKey.prove* would return a proof no verifier accepts.  One ConstraintSystem
+    serves one call at a time."""
+
+    def __init__(self, handle, device):
+        self._h = handle
+        self.device = device
+
+    @classmethod
+    def load(cls, r1cs_bin: bytes, device=0):
+        """r1cs_bin as ProvingKey.setup_r1cs takes it (binarify_r1cs, RollupCircuit.r1cs)."""
+        h = ctypes.c_void_p()
+        _check(lib().zkr_r1cs_load(bytes(r1cs_bin), len(r1cs_bin), device, ctypes.byref(h)))
+        return cls(h, device)
+
+    def info(self):
+        out = (ctypes.c_uint64 * 6)()
+        _check(lib().zkr_r1cs_info(self._h, out))
+        return dict(zip(("nVars", "nPublic", "nConstraints", "nnzA", "nnzB", "nnzC"), [int(x) for x in out]))
+
+    @staticmethod
+    def _reports(rep, n):
+        none = (1 << 64) - 1
+        return [{"violated": int(rep[3 * j]), "first": None if rep[3 * j + 1] == none else int(rep[3 * j + 1]), "one_ok": rep[3 * j + 2] == 0} for j in range(n)]
+
+    def check(self, witnesses):
+        """zkr_r1cs_check: host witnesses (bytes of equal length, nVars x 32 B standard form) -> (all satisfied, one report per
+        witness: {"violated": count, "first": smallest violated constraint or None, "one_ok": signal 0 is 1}).  A violated witness
+        raises nothing; zkr_hip.lib().zkr_last_error() names the first one."""
+        n = len(witnesses)
+        if n == 0:
+            raise ValueError("no witness to check")
+        wlen = _equal_length(witnesses)
+        arr = (ctypes.c_char_p * n)(*[bytes(w) for w in witnesses])
+        rep = (ctypes.c_uint64 * (3 * n))()
+        ok = ctypes.c_int(0)
+        _check(lib().zkr_r1cs_check(self._h, arr, wlen, n, rep, ctypes.byref(ok)))
+        return bool(ok.value), self._reports(rep, n)
+
+    def check_device(self, d_witness_ptrs, stream=None):
+        """zkr_r1cs_check_device: the same for witnesses resident in HBM on the system's device (device pointers, e.g.
+        t[i].data_ptr() of RollupCircuit.calculate_witness_batch_device); stream as for ProvingKey.prove_device."""
+        n = len(d_witness_ptrs)
+        if n == 0:
+            raise ValueError("no witness to check")
+        arr = (ctypes.c_void_p * n)(*[ctypes.c_void_p(p) for p in d_witness_ptrs])
+        rep = (ctypes.c_uint64 * (3 * n))()
+        ok = ctypes.c_int(0)
+        _check(lib().zkr_r1cs_check_device(self._h, arr, n, ctypes.c_void_p(stream or 0), rep, ctypes.byref(ok)))
+        return bool(ok.value), self._reports(rep, n)
+
+    def matches_key(self, key) -> bool:
+        """zkr_r1cs_matches_key: is `key` (a ProvingKey on the same device) a key of this system?  Binds the A and B sides only:
+        a key has no C side, so a system that differs in C alone still matches."""
+        same = ctypes.c_int(0)
+        _check(lib().zkr_r1cs_matches_key(self._h, key._h, ctypes.byref(same)))
+        return bool(same.value)
+
+    def close(self):
+        if self._h:
+            lib().zkr_r1cs_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def _blinding_bytes(rs, ss, n=None):
