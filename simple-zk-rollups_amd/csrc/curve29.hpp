@@ -120,7 +120,10 @@ ZKR_HD XYZZ29<C> dbl_xyzz29(const XYZZ29<C> &p) {
 #endif
 // acc + q (q affine, not infinity: callers filter); neg_q adds -q.  The sign goes into the product Y2 ZZZ1 as a factor
 // without its carry sweep (field29.hpp U29), as do Q - X3 and -Y1 in the Y coordinate: three sweeps and a select less per
-// addition; the negated y itself is only formed on the rare paths that store it.
+// addition; the negated y itself is only formed on the rare paths that store it.  6 products + 2 squares + the two-product Y
+// form (1 467 multiply-adds over Fq).  Onto an empty accumulator it costs nothing -- (x, +-y, 1, 1) -- but the NEXT addition
+// then multiplies by that one four times: the accumulation kernels start a chain of two entries or more with
+// add_affine_affine29 below instead (kernels_msm.hpp chain_head).
 template <class C>
 ZKR_HD XYZZ29<C> add_mixed29(const XYZZ29<C> &acc, const Affine29<C> &q, bool neg_q) {
   if (acc.is_inf()) {
@@ -155,6 +158,34 @@ ZKR_HD XYZZ29<C> add_mixed29(const XYZZ29<C> &acc, const Affine29<C> &q, bool ne
   auto x3 = sub_sub_dbl(sqr(r), ppp, qq);  // R^2 - P^3 - 2 Q, one carry sweep
   auto y3 = mul_sub(r, sub_factor(qq, x3), acc.y, ppp);
   return make_xyzz<C>(x3, y3, zz3, zzz3);
+}
+
+// (+-a) + (+-b), both affine and not infinity: the head of a bucket chain.  add_mixed29 turns the first entry into (x, +-y, 1, 1)
+// for free, but then runs the second entry through its whole form with ZZ = ZZZ = 1: the products X2 ZZ1, Y2 ZZZ1, ZZ1 P^2 and
+// ZZZ1 P^3 multiply by one.  Straight from the two affine points: P = x2 - x1, R = +-y2 -+ y1, ZZ3 = P^2, ZZZ3 = P^3 -- 2
+// products + 2 squares + the two-product Y form (819 multiply-adds over Fq) where the mixed addition has 6 + 2 + the Y form
+// (1 467).  The signs are applied to the y coordinates themselves (one negation with its sweep each, once per chain: the first
+// entry paid it before as well).  Same bounds out as add_mixed29 (R <= 4 where it has <= 8), same special cases.
+template <class C>
+ZKR_HD XYZZ29<C> add_affine_affine29(const Affine29<C> &a, bool neg_a, const Affine29<C> &b, bool neg_b) {
+  auto ay = a.y, by = b.y;
+  if (neg_a) ay = neg(a.y).template to<2>();  // p - y (<= p)
+  if (neg_b) by = neg(b.y).template to<2>();
+  auto p = sub(b.x, a.x);
+  auto r = sub(by, ay);
+  auto pp = sqr(p);
+  if (maybe_zero_mod_p(pp) && is_zero_mod_p(pp)) {  // same x: the same point (double it) or its negative (infinity)
+    if (is_zero_mod_p(sqr(r))) return dbl_affine29<C>(a.x, ay);
+    return XYZZ29<C>::inf();
+  }
+  ZKR_PIN_ORDER();
+  auto ppp = mul(p, pp);
+  ZKR_PIN_ORDER();
+  auto qq = mul(a.x, pp);
+  ZKR_PIN_ORDER();
+  auto x3 = sub_sub_dbl(sqr(r), ppp, qq);  // R^2 - P^3 - 2 Q, one carry sweep
+  auto y3 = mul_sub(r, sub_factor(qq, x3), ay, ppp);
+  return make_xyzz<C>(x3, y3, pp, ppp);
 }
 
 // a + b, both XYZZ.  `again()` yields b once more (from the memory it came from): the one case that needs a whole operand after

@@ -73,6 +73,34 @@ template <class F> static int chain29(const uint8_t *pts, const uint8_t *signs, 
   else store_g2_std(out, *reinterpret_cast<G2Affine *>(&a));
   return 0;
 }
+// sum_i (+-) P_i as the accumulation kernels walk a fresh chain (kernels_msm.hpp chain_head, msm_accum_kernel): the first two
+// entries through add_affine_affine29 -- an infinity placeholder among them leaves at most one point, which starts the chain --
+// and the rest through add_mixed29.  Points, signs and result as chain29.
+template <class F> static int chain29_from_head(const uint8_t *pts, const uint8_t *signs, size_t n, uint8_t *out) {
+  using C = typename CoordOf<F>::C;
+  const size_t pb = sizeof(Affine<F>);
+  std::vector<Affine<F>> q(n);
+  for (size_t i = 0; i < n; i++) {
+    memcpy(&q[i], pts + i * pb, pb);
+    if (!q[i].is_inf()) q[i] = Affine<F>{radix_to_261(q[i].x), radix_to_261(q[i].y)};
+  }
+  XYZZ29<C> acc = XYZZ29<C>::inf();
+  size_t j = 0;
+  if (n >= 2) {
+    if (!q[0].is_inf() && !q[1].is_inf()) acc = add_affine_affine29<C>(unpack_affine(q[0]), signs[0] != 0, unpack_affine(q[1]), signs[1] != 0);
+    else if (!q[0].is_inf()) acc = add_mixed29<C>(acc, unpack_affine(q[0]), signs[0] != 0);
+    else if (!q[1].is_inf()) acc = add_mixed29<C>(acc, unpack_affine(q[1]), signs[1] != 0);
+    j = 2;
+  }
+  for (; j < n; j++)
+    if (!q[j].is_inf()) acc = add_mixed29<C>(acc, unpack_affine(q[j]), signs[j] != 0);
+  XYZZ<F> res = xyzz_to_256(pack_xyzz<F>(acc));   // through the packed form, as the kernels store buckets
+  if (res.is_inf()) return 1;
+  Affine<F> a = to_affine(res);
+  if constexpr (sizeof(F) == 32) store_g1_std(out, *reinterpret_cast<G1Affine *>(&a));
+  else store_g2_std(out, *reinterpret_cast<G2Affine *>(&a));
+  return 0;
+}
 // 2^(c l) P for l = 1..levels as msm_precompute_kernel computes them: Jacobian doubling chain on the 29-bit limbs, ONE
 // inversion of the product of the denominators, affine results.  p: wire form (x 2^256); out: levels x standard-form affine
 template <class F> static void jac_levels29(const uint8_t *pt, int c, int levels, uint8_t *out) {
@@ -100,6 +128,33 @@ template <class F> static void jac_levels29(const uint8_t *pt, int c, int levels
     if constexpr (sizeof(F) == 32) store_g1_std(out + (size_t)l * 64, *reinterpret_cast<G1Affine *>(&a));
     else store_g2_std(out + (size_t)l * 128, *reinterpret_cast<G2Affine *>(&a));
   }
+}
+
+// ---- the chain-head and running-sum forms of curve29.hpp on coordinates given as integers (standard form, 32 B per Fq word; an Fq2
+// coordinate is re, im).  The forms are arithmetic identities, so the tests feed them coordinates at the edges of their bounds as
+// well as points of the curve.
+template <class C> struct CoordIO;
+template <> struct CoordIO<G1C> {
+  static constexpr size_t bytes = 32;
+  static L29<Fq29, 2> in(const uint8_t *p) { return canonical(to_m261<Fq29>(p)); }
+  template <int H> static void out(const L29<Fq29, H> &x, uint8_t *p) { from_m261(x, p); }
+};
+template <> struct CoordIO<G2C> {
+  static constexpr size_t bytes = 64;
+  static Q29<2> in(const uint8_t *p) { return Q29<2>{canonical(to_m261<Fq29>(p)), canonical(to_m261<Fq29>(p + 32))}; }
+  template <int H> static void out(const Q29<H> &x, uint8_t *p) { from_m261(x.a, p); from_m261(x.b, p + 32); }
+};
+template <class C> static int xyzz_out(const XYZZ29<C> &r, uint8_t *out) {  // X, Y, ZZ, ZZZ; 1 for infinity
+  using IO = CoordIO<C>;
+  if (r.is_inf()) return 1;
+  IO::out(weak(r.x), out); IO::out(r.y, out + IO::bytes); IO::out(r.zz, out + 2 * IO::bytes); IO::out(r.zzz, out + 3 * IO::bytes);
+  return 0;
+}
+// (+-a) + (+-b) of two affine points (x, y each) through add_affine_affine29
+template <class C> static int affine_affine29(const uint8_t *a, int neg_a, const uint8_t *b, int neg_b, uint8_t *out) {
+  using IO = CoordIO<C>;
+  Affine29<C> pa{IO::in(a), IO::in(a + IO::bytes)}, pb{IO::in(b), IO::in(b + IO::bytes)};
+  return xyzz_out<C>(add_affine_affine29<C>(pa, neg_a != 0, pb, neg_b != 0), out);
 }
 
 #include <atomic>
@@ -189,6 +244,12 @@ void zkt29_loose(int field, const uint32_t *a9, const uint32_t *b9, uint32_t *nl
 }
 void zkt29_g1_levels(const uint8_t *pt, int c, int levels, uint8_t *out) { jac_levels29<Fq>(pt, c, levels, out); }
 void zkt29_g2_levels(const uint8_t *pt, int c, int levels, uint8_t *out) { jac_levels29<Fq2>(pt, c, levels, out); }
+int zkt29_affine_affine(int g2, const uint8_t *a, int neg_a, const uint8_t *b, int neg_b, uint8_t *out) {
+  return g2 ? affine_affine29<G2C>(a, neg_a, b, neg_b, out) : affine_affine29<G1C>(a, neg_a, b, neg_b, out);
+}
+int zkt29_chain_from_head(int g2, const uint8_t *pts, const uint8_t *signs, size_t n, uint8_t *out) {
+  return g2 ? chain29_from_head<Fq2>(pts, signs, n, out) : chain29_from_head<Fq>(pts, signs, n, out);
+}
 int zkt29_g1_chain(const uint8_t *pts, const uint8_t *signs, size_t n, int twice, uint8_t *out) { return chain29<Fq>(pts, signs, n, twice, out); }
 int zkt29_g2_chain(const uint8_t *pts, const uint8_t *signs, size_t n, int twice, uint8_t *out) { return chain29<Fq2>(pts, signs, n, twice, out); }
 

@@ -546,6 +546,20 @@ static __global__ __launch_bounds__(SCAN_THREADS) void msm_order_kernel(const ui
     if (base + k < nb) order[s_hist[bin[k]] + rank[k]] = base + k;
 }
 
+// The first two entries of a chain that starts from nothing -> its first partial sum.  Two points: their affine sum
+// (curve29.hpp add_affine_affine29: 4 products fewer than the mixed addition onto (x, y, 1, 1)).  An infinity placeholder of a
+// shared-support table among them: what is left is at most one point, which add_mixed29 takes onto the empty sum for nothing --
+// from a second fetch: both points kept in registers for this rare path cost msm_accum_kernel<Fq2> 12 VGPRs (253 against 241).
+template <class F>
+__device__ __forceinline__ XYZZ29<typename CoordOf<F>::C> chain_head(const Affine<F> *points, const Affine<F> &a, uint32_t ea, const Affine<F> &b, uint32_t eb) {
+  using C = typename CoordOf<F>::C;
+  const bool ia = a.is_inf(), ib = b.is_inf();
+  if (!ia && !ib) return add_affine_affine29<C>(unpack_affine(a), (ea & 1) != 0, unpack_affine(b), (eb & 1) != 0);
+  if (ia && ib) return XYZZ29<C>::inf();
+  const uint32_t e = ia ? eb : ea;
+  return add_mixed29<C>(XYZZ29<C>::inf(), unpack_affine(load_pod(points + (e >> 1))), (e & 1) != 0);
+}
+
 // bucket accumulation: thread per bucket, buckets taken in `order` (fullest first): the 64 lanes of a
 // wavefront get buckets of (almost) equal occupancy, so no lane idles while another finishes, and the long
 // buckets start first.
@@ -553,6 +567,9 @@ static __global__ __launch_bounds__(SCAN_THREADS) void msm_order_kernel(const ui
 // so a gather's address has been in a register for a whole addition when the gather is issued; for the 128-byte G2 points a
 // second point in registers would spill, there only the index runs ahead.  Loads past the end of a chain re-read its last
 // entry / point (no branch around a load, nothing out of bounds).
+// A fresh chain of two entries or more starts with chain_head on its first two points (all three points of the start -- the
+// third is the loop's first -- are fetched together) and the loop takes the rest: two trips fewer, never more than before;
+// chains onto a loaded bucket (ACC_ONTO) keep the plain loop.
 // Round 6 measured around this loop: B1 + A + C in ONE launch (the launch tails it removes are where the other
 // streams' kernels found room: -3 %), two points ahead, the next point through the LDS DMA path, aligned non-temporal loads, the
 // G2 launch on a stream of its own -- all within +-1 % of this form; with every gather redirected into 1 MB of its table
@@ -578,19 +595,28 @@ static __global__ __launch_bounds__(ACC_THREADS) __attribute__((amdgpu_waves_per
   XYZZ29<C> acc = (onto & ACC_ONTO) ? unpack_xyzz(load_pod(buckets + b)) : XYZZ29<C>::inf();
   if (o0 < o1) {
     const uint32_t last = o1 - 1;
-    uint32_t e = entries[o0], e1 = entries[min(o0 + 1, last)];
+    uint32_t j = o0, e = entries[o0], e1 = entries[min(o0 + 1, last)];
+    Affine<F> p;
+    const bool head = !(onto & ACC_ONTO) && o0 < last;  // a fresh chain of two entries or more starts from their affine sum (chain_head)
+    Affine<F> ha, hb;
+    const uint32_t ea = e, eb = e1;
+    if (head) {
+      j = o0 + 2; e = entries[min(j, last)]; e1 = entries[min(j + 1, last)];  // the loop goes on at the third entry, its index two ahead as ever
+      ha = load_pod(points + (ea >> 1)); hb = load_pod(points + (eb >> 1));
+    }
+    if (AHEAD) p = load_pod(points + (e >> 1));
+    if (head) acc = chain_head<F>(points, ha, ea, hb, eb);
     if (AHEAD) {
-      Affine<F> p = load_pod(points + (e >> 1));
-      for (uint32_t j = o0; j < o1; j++) {
+      for (; j < o1; j++) {
         const uint32_t e2 = entries[min(j + 2, last)];
         const Affine<F> pn = load_pod(points + (e1 >> 1));
         if (!p.is_inf()) acc = add_mixed29<C>(acc, unpack_affine(p), (e & 1) != 0);  // infinity: placeholder of a shared-support table
         e = e1; e1 = e2; p = pn;
       }
     } else {
-      for (uint32_t j = o0; j < o1; j++) {
+      for (; j < o1; j++) {
         const uint32_t e2 = entries[min(j + 2, last)];
-        const Affine<F> p = load_pod(points + (e >> 1));
+        p = load_pod(points + (e >> 1));
         if (!p.is_inf()) acc = add_mixed29<C>(acc, unpack_affine(p), (e & 1) != 0);
         e = e1; e1 = e2;
       }
@@ -626,8 +652,17 @@ static __global__ __launch_bounds__(ACC_THREADS) __attribute__((amdgpu_waves_per
   using C = typename CoordOf<F>::C;
   const uint32_t o0 = offsets[b], o1 = offsets[b + 1];
   XYZZ29<C> acc = (onto & ACC_ONTO) && sub == 0 ? unpack_xyzz(load_pod(buckets + b)) : XYZZ29<C>::inf();  // see msm_accum_kernel
-  uint32_t e = o0 + sub < o1 ? entries[o0 + sub] : 0u;
-  for (uint32_t j = o0 + sub; j < o1; j += SPLIT) {
+  uint32_t j = o0 + sub;
+  uint32_t e = j < o1 ? entries[j] : 0u;
+  if (!(onto & ACC_ONTO) && j + SPLIT < o1) {  // this lane's first two entries: see chain_head (with ACC_ONTO every lane keeps the plain loop: equal trips)
+    const uint32_t eb = entries[j + SPLIT];
+    const Affine<F> ha = load_pod(points + (e >> 1)), hb = load_pod(points + (eb >> 1));
+    j += 2 * SPLIT;
+    const uint32_t en = j < o1 ? entries[j] : 0u;
+    acc = chain_head<F>(points, ha, e, hb, eb);
+    e = en;
+  }
+  for (; j < o1; j += SPLIT) {
     uint32_t en = j + SPLIT < o1 ? entries[j + SPLIT] : 0u;
     Affine<F> p = load_pod(points + (e >> 1));
     if (!p.is_inf()) acc = add_mixed29<C>(acc, unpack_affine(p), (e & 1) != 0);
@@ -668,7 +703,13 @@ __device__ __forceinline__ void msm_big_body(const Affine<F> *points, const uint
     uint32_t b = big_list[w];
     uint32_t o0 = offsets[b], o1 = offsets[b + 1];
     XYZZ29<C> acc = XYZZ29<C>::inf();
-    for (uint32_t j = o0 + sub * MSM_THREADS + threadIdx.x; j < o1; j += MSM_THREADS * BIG_SPLIT) {
+    uint32_t j = o0 + sub * MSM_THREADS + threadIdx.x;
+    if (j + MSM_THREADS * BIG_SPLIT < o1) {  // this lane's first two entries: see chain_head
+      const uint32_t ea = entries[j], eb = entries[j + MSM_THREADS * BIG_SPLIT];
+      acc = chain_head<F>(points, load_pod(points + (ea >> 1)), ea, load_pod(points + (eb >> 1)), eb);
+      j += 2 * MSM_THREADS * BIG_SPLIT;
+    }
+    for (; j < o1; j += MSM_THREADS * BIG_SPLIT) {
       uint32_t e = entries[j];
       Affine<F> p = load_pod(points + (e >> 1));
       if (!p.is_inf()) acc = add_mixed29<C>(acc, unpack_affine(p), (e & 1) != 0);
