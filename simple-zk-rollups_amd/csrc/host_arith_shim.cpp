@@ -4,6 +4,7 @@
 #include "hostops.hpp"
 #include "pairing.hpp"
 #include "curve29.hpp"
+#include "msm_plan.hpp"
 using namespace zkr;
 
 // ---- the 29-bit-limb hot-path arithmetic (field29.hpp, curve29.hpp) compiled for the host
@@ -190,6 +191,27 @@ static int shard_group_selftest(unsigned parts, unsigned rounds, unsigned fail_p
 }
 
 extern "C" {
+// msm_plan(n_scalars, n_points, c_fixed) as ten words: c, K, glog, nbw, nb, big_thresh, nR, nbl, J, S
+void zkt_msm_plan(size_t n_scalars, size_t n_points, int c_fixed, uint32_t out[10]) {
+  const MsmPlan p = msm_plan(n_scalars, n_points, c_fixed);
+  const uint32_t w[10] = {(uint32_t)p.c, (uint32_t)p.K, (uint32_t)p.glog, p.nbw, p.nb, p.big_thresh, p.nR, p.nbl, p.J, p.S};
+  memcpy(out, w, sizeof w);
+}
+uint32_t zkt_big_threshold(size_t n_points, int K, uint32_t nbw, int nbat) { return big_threshold(n_points, K, nbw, nbat); }
+// proof_layout of a key with n witness scalars, m scalars of h, npts[t] points and window win_c[t] (0: the plan's own) per table, as a
+// key plans its tables (zkr_key.hip key_alloc_workspace).  out, 63 ints: share_b, share_ac, n_chains, then per table (5 x)
+// sort_src, chain, set, flags, own_result, then per chain (5 x, unused ones as the layout leaves them) n_members, members[2], sets,
+// geom, g2, latency.  Returns 1 when same_reduce_geometry(A, B1).
+int zkt_proof_layout(uint32_t n, uint32_t m, const uint32_t npts[5], const uint32_t win_c[5], int share_b, int share_ac, int out[63]) {
+  MsmPlan plan[N_TABLES];
+  for (int t = 0; t < N_TABLES; t++) plan[t] = msm_plan(t == T_H ? m : n, npts[t], (int)win_c[t]);
+  const ProofLayout L = proof_layout(npts, share_b != 0, share_ac != 0, plan);
+  int *o = out;
+  *o++ = L.share_b; *o++ = L.share_ac; *o++ = L.n_chains;
+  for (int t = 0; t < N_TABLES; t++) { *o++ = L.sort_src[t]; *o++ = L.chain[t]; *o++ = L.set[t]; *o++ = L.flags[t]; *o++ = L.own_result(t); }
+  for (const ChainLayout &c : L.chains) { *o++ = c.n_members; *o++ = c.members[0]; *o++ = c.members[1]; *o++ = c.sets; *o++ = c.geom; *o++ = c.g2; *o++ = c.latency; }
+  return same_reduce_geometry(plan[T_A], plan[T_B1]);
+}
 int zkr_host_shard_group_selftest(unsigned parts, unsigned rounds, unsigned fail_part, unsigned fail_round) {
   return shard_group_selftest(parts, rounds, fail_part, fail_round);
 }

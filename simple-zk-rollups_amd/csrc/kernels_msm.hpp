@@ -27,11 +27,11 @@
 #pragma once
 #include "curve.hpp"
 #include "curve29.hpp"  // the group law the accumulation / reduction kernels run: 9 x 29-bit limbs, radix 2^261 (field29.hpp)
+#include "msm_plan.hpp"  // MSM_THREADS, MAX_RANGES, SORT_RANGE_DEFAULT, SORT_CHUNK_RECORDS, ACC_*: shared with the host-side planning
 
 namespace zkr {
 
 #define ZKR_RED_PRIO 3  // wave priority of the oversized-bucket and reduction kernels (s_setprio takes a literal)
-constexpr int MSM_THREADS = 256;
 constexpr uint32_t BIG_CAP = 1024;  // oversized buckets tracked per MSM
 
 template <class F> struct PointBytes;
@@ -68,11 +68,9 @@ __device__ __forceinline__ void copy_pod(T *dst, const T *src) {
 }
 
 struct MsmGeom {
-  uint32_t n;        // points (base points of the table; the table holds K * n)
   int c;             // window bits
   int K;             // windows
   uint32_t nbw;      // buckets = 2^(c-1), one set shared by all windows
-  uint32_t big_thresh;
   int glog;          // reduce group = 2^glog buckets
   uint32_t S;        // reduce2: workgroups per task
   uint32_t batch;    // proofs fused into the launches (small circuits): `batch` bucket sets of nbw buckets laid end to end
@@ -165,7 +163,6 @@ __device__ __forceinline__ uint32_t lane_id() { return __lane_id(); }
 constexpr int ENT_WIN_SHIFT = 17;
 constexpr int ENT_TAG_SHIFT = 24;     // staged records carry their list's range in bits 24..31 until they are written out
 static_assert(MSM_THREADS == 256, "the digit kernels keep one range counter per thread");
-constexpr uint32_t MAX_RANGES = 256;  // x SORT_RANGE_MAX buckets = 2^21: window sizes up to c = 22 (2^24-point tables), or fused batches of small circuits
 constexpr uint32_t DIGIT_XCDS = 8;
 constexpr uint32_t DIGIT_STAGE = 2 * 256 * 13;  // records a workgroup groups in LDS (x 8 bytes = 53 KB)
 constexpr uint32_t DIGIT_CLEAR_WORDS = 2 * DIGIT_XCDS * MAX_RANGES;  // counts[range][XCD slot] | fill cursors[range][XCD slot]: zero before the count kernel
@@ -296,8 +293,6 @@ static __global__ __launch_bounds__(MSM_THREADS) void msm_digits_scatter_kernel(
 constexpr int SORT_THREADS = 256;
 constexpr uint32_t SORT_RANGE_MAX = 8192;  // bucket counters per workgroup (x 4 B of LDS): small footprint, so these
                                            // memory/LDS-bound workgroups find room on CUs busy with an accumulation
-constexpr uint32_t SORT_RANGE_DEFAULT = 2048;   // buckets per range and records per (range, chunk) workgroup that msm_plan aims
-constexpr uint32_t SORT_CHUNK_RECORDS = 3328;   // for (zkr_key.hip: the L2 footprint of the scatter decides)
 constexpr uint32_t RANK_NONE = 0xffffffffu;
 constexpr int SORT_UNROLL = 8;
 
@@ -574,7 +569,6 @@ __device__ __forceinline__ XYZZ29<typename CoordOf<F>::C> chain_head(const Affin
 // streams' kernels found room: -3 %), two points ahead, the next point through the LDS DMA path, aligned non-temporal loads, the
 // G2 launch on a stream of its own -- all within +-1 % of this form; with every gather redirected into 1 MB of its table
 // (garbage sums) the pipelined rate is 8.6 % higher: that is all the memory side costs (profiles/r6_07_fake_gather_bound.txt).
-constexpr int ACC_ONTO = 1, ACC_ZERO_BIG = 2;  // flags of the accumulation kernels' `onto` argument
 constexpr int ACC_THREADS = 256;
 template <class F, int MINW, bool AHEAD>
 static __global__ __launch_bounds__(ACC_THREADS) __attribute__((amdgpu_waves_per_eu(MINW, MINW))) void msm_accum_kernel(const Affine<F> *points, const uint32_t *offsets, const uint32_t *entries,

@@ -11,6 +11,7 @@
 #include <vector>
 #include "../../include/zkr.h"
 #include "hostops.hpp"
+#include "msm_plan.hpp"
 #include "shard_group.hpp"
 
 namespace zkr {
@@ -74,8 +75,6 @@ struct ScopedEvent {
   int create() { ZKR_HIP_CHECK(hipEventCreate(&e)); return 0; }
 };
 
-enum { T_A = 0, T_B1 = 1, T_B2 = 2, T_C = 3, T_H = 4, N_TABLES = 5 };
-
 // The device key is ONE position-independent arena: header + sections addressed by byte offsets,
 // so a replica on another GPU is a single broadcast of [arena, arena+len).
 struct ArenaHeader {
@@ -113,17 +112,34 @@ struct DigitLists {
   uint32_t *ent_s = nullptr, *ent_b = nullptr;
 };
 
-struct MsmWorkspace {
+// The digit sort of one point set: bucket occupancies, offsets and the sorted entry list, read by the accumulation of every table over
+// that point set (B2 over B1's, C over A's: ProofLayout::sort_src) and by their oversized-bucket kernels.
+struct MsmSort {
   uint32_t *counts = nullptr, *offsets = nullptr, *entries = nullptr;
   uint32_t *size_hist = nullptr, *order = nullptr;  // [2][SIZE_BINS] size-class histogram + hand-out counters; bucket ids fullest first
   uint32_t *chunk_cnt = nullptr;  // [K][J][nbw] per-chunk bucket occupancies, then per-bucket prefixes over chunks
-  DigitLists own_dig;             // digit records when the workspace is not attached to a key (stage hooks)
   uint32_t *big_list = nullptr, *big_count = nullptr, *block_sums = nullptr;
-  void *big_partials = nullptr;
-  void *buckets = nullptr, *group_out = nullptr, *task_out = nullptr, *result = nullptr;
-  void *h_result = nullptr;  // pinned host copy of the MSM result point (XYZZ)
   size_t max_nb = 0, max_entries = 0;
-  size_t sets = 1;  // bucket sets (and reduction buffers) per proof: 2 in B1's workspace when A is reduced with it (zkr_key.hip alloc_msm_ws)
+};
+// One reduction chain: `sets` bucket sets per proof end to end (the fused proofs of each set together) with the buffers of the
+// launch set that reduces them (ChainLayout).  result / h_result: one point per set and proof, set-major.
+struct MsmChain {
+  void *buckets = nullptr, *group_out = nullptr, *task_out = nullptr, *result = nullptr;
+  void *h_result = nullptr;  // pinned host copy of the result points (XYZZ)
+  size_t sets = 1;
+  bool g2 = false;
+};
+// One table multiplied on its own (the stage hooks zkr_msm_g1 / g2, key_table_msm): its digit records, sort, oversized-bucket
+// partial sums and chain, all of which go with the scope -- the hooks return early on every failed HIP call
+struct MsmScratch {
+  DigitLists dig;
+  MsmSort sort;
+  void *big_partials = nullptr;
+  MsmChain chain;
+  MsmScratch() = default;
+  MsmScratch(const MsmScratch &) = delete;
+  MsmScratch &operator=(const MsmScratch &) = delete;
+  ~MsmScratch();
 };
 
 struct ProfStage {
@@ -136,32 +152,10 @@ struct ProfSpan {
   hipEvent_t e0, e1;
 };
 
-constexpr int LAT_GLOG = 3;  // reduction groups of a chain nothing can hide (a synchronous proof's last one): 2^3 buckets, see msm_reduce_enqueue
-struct MsmPlan {
-  int c, K, glog;
-  uint32_t nbw, nb, big_thresh;  // nb = nbw = 2^(c-1) buckets, one set shared by the K windows
-  uint32_t nR, nbl;   // digit sort: nR bucket ranges of nbl buckets (LDS counters of one workgroup)
-  uint32_t J;         // digit sort: J chunks per bucket range
-  uint32_t S;         // reduction: workgroups per task in msm_reduce2_kernel
-};
-// two tables whose bucket sets ONE reduction launch set can walk end to end (msm_reduce*_kernel take `batch` sets of one geometry)
-inline bool same_reduce_geometry(const MsmPlan &a, const MsmPlan &b) { return a.c == b.c && a.K == b.K && a.nbw == b.nbw && a.nb == b.nb && a.glog == b.glog && a.S == b.S; }
-
-// How the five tables of a key's proofs share digit sorts, bucket sets and reduction chains.  It depends on the key alone: worked
-// out once from the header and the plans (zkr_key.hip proof_layout) and read by every proof (zkr_prove.hip).
-struct ProofLayout {
-  bool share_b = false, share_ac = false;  // B2 accumulates over B1's sort (same signals), C over A's (one support)
-  int sort_src[N_TABLES] = {T_A, T_B1, T_B2, T_C, T_H};  // the table whose sort each table's accumulation reads
-  bool joint_ab = false;  // A is accumulated behind B1's bucket sets and reduced with them in one chain: B1's workspace holds both
-                          // results, B1's first
-  bool merge_ch = false;  // H is accumulated onto C's bucket set and reduced with it: C's workspace holds C + H
-  size_t sets[N_TABLES] = {1, 1, 1, 1, 1};  // bucket sets (with their reduction buffers) per proof in each table's workspace
-};
-
 }  // namespace zkr
 
 namespace zkr {
-// Everything one proof in flight owns: witness + calcH vectors, digit codes, the five MSM workspaces, its
+// Everything one proof in flight owns: witness + calcH vectors, digit codes, the sorts, partial sums and chains of its MSMs, its
 // events and timing spans.  A key has PROOF_SLOTS of them so that the GPU work of the next proof is enqueued
 // (zkr_prove_submit) while the host still assembles the previous one (zkr_prove_collect).
 constexpr int PROOF_SLOTS = 2;  // three measured the same (134.1 against 134.1 / 134.3 proofs/s, HISTORY.md 7b)
@@ -179,12 +173,14 @@ struct WitnessStage {
 struct ProofSlot {
   Fr *d_w = nullptr, *va = nullptr, *vb = nullptr, *ca = nullptr, *cb = nullptr, *d_h = nullptr;
   DigitLists dig_w, dig_h;  // digit records of w (shared by A, B1, B2, C) and of h
-  MsmWorkspace ws[N_TABLES];
+  MsmSort sort[N_TABLES];          // of the tables that own their sort (layout.sort_src[t] == t) and have points
+  void *big_partials[N_TABLES] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // oversized-bucket partial sums of every table that has points
+  MsmChain chain[N_TABLES];        // the first layout.n_chains of them
   hipEvent_t ev_w = nullptr, ev_h = nullptr;
   hipEvent_t ev_end[3] = {nullptr, nullptr, nullptr};  // end of the proof's work on the G2-chain, G1-chain and auxiliary streams
   hipEvent_t ev_done[N_TABLES] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   hipEvent_t ev_sorted[N_TABLES] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  hipEvent_t ev_res[N_TABLES] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // the table's result point has landed in its pinned host buffer
+  hipEvent_t ev_res[N_TABLES] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // by chain: its result points have landed in its pinned host buffer
   bool res_pending[N_TABLES] = {false, false, false, false, false};
   int cap = 1;    // proofs one submit can fuse into shared launches (small circuits; every buffer above is cap times one proof's)
   int nbat = 0;   // proofs of the group in flight
@@ -302,10 +298,9 @@ struct Circuit {
   std::vector<Fr> w;  // Montgomery
 };
 int parse_r1cs(const void *r1cs_bin, size_t r1cs_len, Circuit &c);  // r1cs_bin (include/zkr.h) -> the circuit, with its domain; host only; ZKR_ERR_ARG with a message
-MsmPlan msm_plan(size_t n_scalars, size_t n_points, int c_fixed = 0);
-uint32_t big_threshold(size_t n_points, int K, uint32_t nbw, int nbat);  // occupancy above which a bucket goes to msm_big_kernel (zkr_key.hip)
 int digit_lists_alloc(DigitLists &dl, size_t n_scalars, const MsmPlan &pl);
 void digit_lists_free(DigitLists &dl);
+int msm_scratch_alloc(MsmScratch &m, size_t n_scalars, size_t n_points, const MsmPlan &pl, bool g2);  // for one proof of one table
 int msm_precompute(int device, bool g2, void *d_table, uint32_t n, const MsmPlan &pl);  // fills levels 1..K-1 of a table whose level 0 is in place, then converts the table to the hot path's radix
 int radix_convert(int device, bool g2, void *d_points, size_t count, bool to261);
 }  // namespace zkr

@@ -54,73 +54,6 @@ static Fr fr_root_of_unity(unsigned k) {
 }
 Fr host_root_of_unity(unsigned k) { return fr_root_of_unity(k); }
 
-// Oversized buckets (summed by msm_big_kernel's workgroups instead of one thread of the accumulation).  A bucket of E entries is
-// E dependent additions on one lane -- 7 us each for G1, 18 us for G2 -- so any bucket longer than the accumulation's bulk
-// time stretches the whole kernel: the bulk is the launch's additions (n K per proof, nbat proofs in a fused launch) at ~100 k
-// additions per chain step chip-wide, i.e. the threshold is n K nbat / 2^17, between twice and eight times the mean occupancy,
-// never below 64.  Round 3's rule (max(8 mean, 256)) left buckets of up to 256 entries to single lanes of SPARSE bucket sets: a
-// shard of a 2^22 key (mean 9) spent 4.9 ms in a G2 accumulation of 0.8 ms of work (profiles/r4_25_shard_big_threshold.txt).
-uint32_t big_threshold(size_t n, int K, uint32_t nbw, int nbat) {
-  const uint64_t mean = (uint64_t)n * K / nbw + 1;
-  const uint64_t by_bulk = ((uint64_t)n * K * (uint64_t)(nbat < 1 ? 1 : nbat)) >> 17;
-  uint64_t thr = by_bulk < mean * 8 ? by_bulk : mean * 8;
-  if (thr < 2 * mean) thr = 2 * mean;  // dense little bucket sets (tiny circuits): only real outliers leave the accumulation
-  return thr > 64 ? (uint32_t)thr : 64u;
-}
-
-// Window size from the length of the SCALAR vector (tables that share scalars share the digit codes,
-// kernels_msm.hpp msm_digits_kernel) unless the key fixes it (c_fixed: the window tables in the arena were built
-// for that c); chunking and the oversized-bucket threshold from the table itself.
-MsmPlan msm_plan(size_t n_scalars, size_t n, int c_fixed) {
-  MsmPlan pl;
-  int lg = 0;
-  while (((size_t)1 << lg) < n_scalars) lg++;
-  int c = lg;  // 2^(c-1) buckets for ~n * 255/c entries: a few dozen entries per bucket
-  if (c < 4) c = 4;
-  // c stays at 20 above 2^20 scalars.  The digit sort takes up to 2^21 buckets (MAX_RANGES x SORT_RANGE_MAX), and by
-  // multiplication counts c = 22 would pay at 2^24 points (12 instead of 13 additions per point for four times the
-  // buckets: 1961 vs 2078 M multiplications per G1 table), but measured on the 2^24 rollup-shaped key it loses: 8.19 /
-  // 7.50 proofs/s at c = 20 / 21, and at c = 22 the accumulation of a table takes 26.6 ms instead of 18 ms alone
-  // (2 M bucket threads with short chains gather worse) and 3.5 -> 0.37 proofs/s with two proofs in flight; at 2^22
-  // the counts already tie (530 / 544 / 532 M).  ZKR_MSM_C overrides (a documented knob: window bits of keys built in this process).
-  if (c > 20) c = 20;
-  if (const char *e = getenv("ZKR_MSM_C")) { int v = atoi(e); if (v >= 2 && v <= 22) c = v; }
-  if (c_fixed) c = c_fixed;
-  pl.c = c;
-  pl.K = (255 + c - 1) / c;
-  pl.nbw = 1u << (c - 1);
-  pl.nb = pl.nbw;
-  // bucket reduction in groups of 2^glog buckets (kernels_msm.hpp msm_reduce1_kernel: a chain of 2 * 2^glog - 2 additions
-  // per thread).  At 2^19 buckets groups of 32 measured best (108 / 110 / 113 / 105 proofs/s at 8 / 16 / 32 / 64); with
-  // fewer buckets the chip is not filled and the chain length is what counts: keep about 2^14 groups
-  // (tx circuit, 2^16 buckets: 233 / 320 / 349 / 351 / 322 proofs/s at 32 / 16 / 8 / 4 / 2)
-  int glog = c - 1 - 14 < 2 ? 2 : c - 1 - 14 > 5 ? 5 : c - 1 - 14;
-  pl.glog = c - 1 < glog ? c - 1 : glog;
-  pl.big_thresh = big_threshold(n, pl.K, pl.nbw, 1);
-  // digit sort: one workgroup per (bucket range, chunk).  Ranges of 2048 buckets, chunks of ~3300 records: what counts is the
-  // window of the entry array that the workgroups resident on one XCD scatter into together -- it has to stay in that XCD's
-  // 4 MB L2 until its lines are complete (kernels_msm.hpp sort_block_to_chunk).  At 2^20 points: 256 ranges x 16 chunks, a
-  // range's window is 212 KB, ~12 ranges in flight per XCD; with ranges of 8192 buckets (round 2) the same 16 chunks per range
-  // kept 6.8 MB in flight per XCD and every line left L2 in pieces (WRITE_SIZE 386 MB per launch for 54 MB of entries, against
-  // 98 MB now; kernel 159 -> 83 us; profiles/r3_ab_sort_ranges.md).
-  uint32_t range_max = SORT_RANGE_DEFAULT;
-  if (pl.nbw / range_max > MAX_RANGES) range_max = pl.nbw / MAX_RANGES;
-  pl.nbl = pl.nbw < range_max ? pl.nbw : range_max;
-  pl.nR = pl.nbw / pl.nbl;
-  uint64_t J64 = ((uint64_t)n * pl.K + (uint64_t)pl.nR * SORT_CHUNK_RECORDS - 1) / ((uint64_t)pl.nR * SORT_CHUNK_RECORDS);
-  uint32_t J = J64 > 64 ? 64u : (uint32_t)J64;
-  if (J < 1) J = 1;
-  pl.J = J;
-  // reduction: every task sums ng/2 .. ng group results; one workgroup per 2048 of them, all tasks together at
-  // most one workgroup per CU (msm_reduce3_kernel takes ntask * S <= MSM_THREADS partial sums)
-  uint32_t ng = pl.nbw >> pl.glog, ntask = (uint32_t)(c - 1 - pl.glog) + 2;
-  uint32_t S = (ng + 2047) / 2048;
-  if (S > 16) S = 16;
-  if (S > MSM_THREADS / ntask) S = MSM_THREADS / ntask;
-  pl.S = S < 1 ? 1 : S;
-  return pl;
-}
-
 // The arena's layout: header, twiddles, the two QAP sides (CSR), then per table its K window levels and its rank map.
 // Everything that builds an arena -- key_build, the receiver of a compact arena, zkr_key_shard -- takes the offsets from here,
 // so replicas and shards of one key agree byte for byte on where things are.
@@ -180,35 +113,48 @@ const char *arena_header_fault(const ArenaHeader &h, size_t len) {
   return same ? nullptr : "section offsets differ from the layout the sizes imply";
 }
 
-// cap: proofs a fused batch can hold (cap bucket sets end to end; kernels_msm.hpp msm_digits_count_kernel)
-// sets: bucket sets (and reduction buffers) per proof -- 2 in B1's workspace when A is accumulated behind B1's sets and reduced with
-// them in one chain, 0 in A's own workspace then: it keeps only what its sort and its oversized buckets need
-static int alloc_msm_ws(MsmWorkspace &ws, size_t n, const MsmPlan &pl, size_t xyzz_bytes, size_t cap = 1, size_t sets = 1) {
+// the sort buffers of a table of n points; cap: proofs a fused batch can hold (cap bucket sets end to end; kernels_msm.hpp
+// msm_digits_count_kernel)
+static int msm_sort_alloc(MsmSort &so, size_t n, const MsmPlan &pl, size_t cap) {
   size_t nb = pl.nb * cap;
-  ZKR_HIP_CHECK(hipMalloc(&ws.counts, (nb + 1) * 4));
-  ZKR_HIP_CHECK(hipMalloc(&ws.offsets, (nb + 1) * 4));
-  ZKR_HIP_CHECK(hipMalloc(&ws.size_hist, 2 * SIZE_BINS * 4));
-  ZKR_HIP_CHECK(hipMalloc(&ws.order, (nb + 1) * 4));
-  ZKR_HIP_CHECK(hipMalloc(&ws.chunk_cnt, (size_t)pl.J * nb * 4 + 4));
-  ZKR_HIP_CHECK(hipMalloc(&ws.entries, (n * pl.K * cap + 1) * 4));
-  ZKR_HIP_CHECK(hipMalloc(&ws.big_list, BIG_CAP * 4));
-  ZKR_HIP_CHECK(hipMalloc(&ws.big_count, 16));  // [0] oversized buckets, [1] total entries, [2] tile ticket (kernels_msm.hpp SortScratch)
-  ZKR_HIP_CHECK(hipMalloc(&ws.block_sums, (nb / SCAN_BLOCK + 2) * 8));  // the scan tiles' sums (msm_scan_sums_kernel, msm_scan_top_kernel)
-  ZKR_HIP_CHECK(hipMalloc(&ws.big_partials, (size_t)BIG_CAP * BIG_SPLIT * xyzz_bytes));
-  if (sets) {
-    ZKR_HIP_CHECK(hipMalloc(&ws.buckets, nb * sets * xyzz_bytes));
-    // sized for the plan's groups AND for the smaller groups of a latency-mode chain (zkr_prove.hip msm_reduce_enqueue: groups of
-    // 2^LAT_GLOG buckets when nothing else is in flight), whose task sums take up to 16 splits
-    const int g_min = pl.glog < LAT_GLOG ? pl.glog : LAT_GLOG;
-    ZKR_HIP_CHECK(hipMalloc(&ws.group_out, (size_t)(pl.nbw >> g_min) * cap * sets * 2 * xyzz_bytes));
-    ZKR_HIP_CHECK(hipMalloc(&ws.task_out, (size_t)(pl.c + 2) * (pl.S > 16 ? pl.S : 16) * cap * sets * xyzz_bytes));
-    ZKR_HIP_CHECK(hipMalloc(&ws.result, xyzz_bytes * cap * sets));
-    ZKR_HIP_CHECK(hipHostMalloc(&ws.h_result, xyzz_bytes * cap * sets, hipHostMallocDefault));
-  }
-  ws.max_nb = nb;
-  ws.max_entries = n * pl.K * cap;
-  ws.sets = sets;
+  ZKR_HIP_CHECK(hipMalloc(&so.counts, (nb + 1) * 4));
+  ZKR_HIP_CHECK(hipMalloc(&so.offsets, (nb + 1) * 4));
+  ZKR_HIP_CHECK(hipMalloc(&so.size_hist, 2 * SIZE_BINS * 4));
+  ZKR_HIP_CHECK(hipMalloc(&so.order, (nb + 1) * 4));
+  ZKR_HIP_CHECK(hipMalloc(&so.chunk_cnt, (size_t)pl.J * nb * 4 + 4));
+  ZKR_HIP_CHECK(hipMalloc(&so.entries, (n * pl.K * cap + 1) * 4));
+  ZKR_HIP_CHECK(hipMalloc(&so.big_list, BIG_CAP * 4));
+  ZKR_HIP_CHECK(hipMalloc(&so.big_count, 16));  // [0] oversized buckets, [1] total entries, [2] tile ticket (kernels_msm.hpp SortScratch)
+  ZKR_HIP_CHECK(hipMalloc(&so.block_sums, (nb / SCAN_BLOCK + 2) * 8));  // the scan tiles' sums (msm_scan_sums_kernel, msm_scan_top_kernel)
+  so.max_nb = nb;
+  so.max_entries = n * pl.K * cap;
   return 0;
+}
+static void msm_sort_free(MsmSort &so) {
+  hipFree(so.counts); hipFree(so.offsets); hipFree(so.chunk_cnt); hipFree(so.size_hist); hipFree(so.order); hipFree(so.entries); hipFree(so.big_list); hipFree(so.big_count); hipFree(so.block_sums);
+  so = MsmSort();
+}
+static size_t xyzz_bytes(bool g2) { return g2 ? sizeof(G2XYZZ) : sizeof(G1XYZZ); }
+static int big_partials_alloc(void **p, bool g2) { ZKR_HIP_CHECK(hipMalloc(p, (size_t)BIG_CAP * BIG_SPLIT * xyzz_bytes(g2))); return 0; }
+// `sets` bucket sets per proof (2 in the chain that reduces A behind B1) of the plan's geometry, with their reduction buffers
+static int msm_chain_alloc(MsmChain &ch, const MsmPlan &pl, bool g2, size_t cap, size_t sets) {
+  const size_t nb = pl.nb * cap, xb = xyzz_bytes(g2);
+  ch.sets = sets;
+  ch.g2 = g2;
+  ZKR_HIP_CHECK(hipMalloc(&ch.buckets, nb * sets * xb));
+  // sized for the plan's groups AND for the smaller groups of a latency-mode chain (zkr_prove.hip msm_reduce_enqueue: groups of
+  // 2^LAT_GLOG buckets when nothing else is in flight), whose task sums take up to 16 splits
+  const int g_min = pl.glog < LAT_GLOG ? pl.glog : LAT_GLOG;
+  ZKR_HIP_CHECK(hipMalloc(&ch.group_out, (size_t)(pl.nbw >> g_min) * cap * sets * 2 * xb));
+  ZKR_HIP_CHECK(hipMalloc(&ch.task_out, (size_t)(pl.c + 2) * (pl.S > 16 ? pl.S : 16) * cap * sets * xb));
+  ZKR_HIP_CHECK(hipMalloc(&ch.result, xb * cap * sets));
+  ZKR_HIP_CHECK(hipHostMalloc(&ch.h_result, xb * cap * sets, hipHostMallocDefault));
+  return 0;
+}
+static void msm_chain_free(MsmChain &ch) {
+  hipFree(ch.buckets); hipFree(ch.group_out); hipFree(ch.task_out); hipFree(ch.result);
+  if (ch.h_result) hipHostFree(ch.h_result);
+  ch = MsmChain();
 }
 int digit_lists_alloc(DigitLists &dl, size_t n_scalars, const MsmPlan &pl) {  // n_scalars: of the whole (fused) vector
   ZKR_HIP_CHECK(hipMalloc(&dl.rng, DIGIT_RNG_WORDS * 4));
@@ -235,12 +181,16 @@ void digit_lists_free(DigitLists &dl) {
   hipFree(dl.rng); hipFree(dl.ent_s); hipFree(dl.ent_b);
   dl = DigitLists();
 }
-int msm_ws_alloc(MsmWorkspace &ws, size_t n, const MsmPlan &pl, size_t xyzz_bytes) { return alloc_msm_ws(ws, n, pl, xyzz_bytes, 1); }
-void msm_ws_free(MsmWorkspace &ws) {
-  hipFree(ws.counts); hipFree(ws.offsets); hipFree(ws.chunk_cnt); hipFree(ws.size_hist); hipFree(ws.order); digit_lists_free(ws.own_dig); hipFree(ws.entries); hipFree(ws.big_list); hipFree(ws.big_count); hipFree(ws.block_sums); hipFree(ws.big_partials);
-  hipFree(ws.buckets); hipFree(ws.group_out); hipFree(ws.task_out); hipFree(ws.result);
-  if (ws.h_result) hipHostFree(ws.h_result);
-  ws = MsmWorkspace();
+int msm_scratch_alloc(MsmScratch &m, size_t n_scalars, size_t n, const MsmPlan &pl, bool g2) {
+  int rc;
+  if ((rc = digit_lists_alloc(m.dig, n_scalars, pl)) || (rc = msm_sort_alloc(m.sort, n, pl, 1)) || (rc = big_partials_alloc(&m.big_partials, g2))) return rc;
+  return msm_chain_alloc(m.chain, pl, g2, 1, 1);
+}
+MsmScratch::~MsmScratch() {
+  digit_lists_free(dig);
+  msm_sort_free(sort);
+  hipFree(big_partials);
+  msm_chain_free(chain);
 }
 
 // The streams of a device, made ONCE per process and shared by every key on that device.  The HIP runtime multiplexes the streams
@@ -276,28 +226,6 @@ static int make_streams(DeviceStreams &ds) {
   return 0;
 }
 
-static ProofLayout proof_layout(const ArenaHeader &h, const MsmPlan plan[N_TABLES]) {
-  ProofLayout L;
-  L.share_b = h.share_b != 0 && h.npts[T_B1] == h.npts[T_B2];
-  L.share_ac = h.share_ac != 0 && h.npts[T_A] == h.npts[T_C];  // A and C laid out over one support
-  L.sort_src[T_B2] = L.share_b ? T_B1 : T_B2;
-  L.sort_src[T_C] = L.share_ac ? T_A : T_C;
-  // A and B1 in ONE reduction chain (round 5): the G1 chains share one stream, and in a single proof of a small circuit that stream
-  // is the critical path from B1's accumulation to the end (three chains of ~0.4 ms back to back: H's chain starts 0.19 ms after H's
-  // accumulation has ended, profiles/r4_05_timeline_one_tx_proof.txt).  A is accumulated into the bucket sets BEHIND B1's (B1's
-  // workspace holds two sets per proof when the two tables' geometry agrees, A's none) and one launch set reduces both: a chain of
-  // latency-bound launches less per proof.
-  L.joint_ab = h.npts[T_A] && h.npts[T_B1] && same_reduce_geometry(plan[T_A], plan[T_B1]);
-  if (L.joint_ab) { L.sets[T_A] = 0; L.sets[T_B1] = 2; }
-  // C and H are only ever needed as C + H (App. B step 4: pi_c): when their bucket geometry agrees, H is accumulated ONTO
-  // C's bucket set and one reduction chain serves both -- a bucket reduction (2 x 2^19 full additions, ~1.6 % of a proof's
-  // instructions) and one latency chain less.  Oversized buckets of either table are ADDED to the shared set after H's
-  // accumulation (C's accumulation clears their slots), so no accumulation waits for a reduction stream.
-  const MsmPlan &pc = plan[T_C], &ph = plan[T_H];
-  L.merge_ch = h.npts[T_C] && h.npts[T_H] && pc.c == ph.c && pc.nbw == ph.nbw && pc.glog == ph.glog && pc.S == ph.S;
-  return L;
-}
-
 int key_alloc_workspace(zkr_key *k) {
   ZKR_HIP_CHECK(hipSetDevice(k->device));
   if (int lrc = ntt_lds_check(k->device)) return lrc;
@@ -305,7 +233,8 @@ int key_alloc_workspace(zkr_key *k) {
   // reduction streams: the chains of one proof add up to ~6 ms of serialised launches, so on a single in-order
   // stream they, not the accumulations, set the pace with two proofs in flight (94 vs 106 proofs/s with two)
   for (int t = 0; t < N_TABLES; t++) k->plan[t] = msm_plan(rank_entries(h, t), h.npts[t], (int)h.win_c[t]);
-  k->layout = proof_layout(h, k->plan);
+  k->layout = proof_layout(h.npts, h.share_b != 0, h.share_ac != 0, k->plan);
+  const ProofLayout &lay = k->layout;
   // Two reduction streams: the G2 chain on one, the G1 chains one after the other on the other.  Round 2 ran circuits that fill the
   // chip alone with three (136.3 against 132.1 proofs/s at 2^20); since C and H share one chain and the G2 reductions take a
   // whole SIMD's registers, the third stream only adds contention for the accumulations: 152.5-153.5 against 145.9-146.6
@@ -355,11 +284,14 @@ int key_alloc_workspace(zkr_key *k) {
     ZKR_HIP_CHECK(hipMalloc(&sl.d_w, (size_t)h.n * 32 * cap));
     Fr **vecs[5] = {&sl.va, &sl.vb, &sl.ca, &sl.cb, &sl.d_h};
     for (auto v : vecs) ZKR_HIP_CHECK(hipMalloc(v, (size_t)h.m * 32 * cap));
-    for (int t = 0; t < N_TABLES; t++) {
-      int rc = alloc_msm_ws(sl.ws[t], h.npts[t], k->plan[t], t == T_B2 ? sizeof(G2XYZZ) : sizeof(G1XYZZ), cap, k->layout.sets[t]);
-      if (rc) return rc;
+    int rc = 0;
+    for (int t = 0; t < N_TABLES && !rc; t++) {
+      if (!h.npts[t]) continue;  // an empty table is sorted, accumulated and reduced nowhere (it is in no chain of the layout)
+      if (lay.sort_src[t] == t) rc = msm_sort_alloc(sl.sort[t], h.npts[t], k->plan[t], cap);
+      if (!rc) rc = big_partials_alloc(&sl.big_partials[t], t == T_B2);
     }
-    int rc = digit_lists_alloc(sl.dig_w, (size_t)h.sc_n[0] * cap, k->plan[T_A]);
+    for (int c = 0; c < lay.n_chains && !rc; c++) rc = msm_chain_alloc(sl.chain[c], k->plan[lay.chains[c].geom], lay.chains[c].g2, cap, (size_t)lay.chains[c].sets);
+    if (!rc) rc = digit_lists_alloc(sl.dig_w, (size_t)h.sc_n[0] * cap, k->plan[T_A]);
     if (!rc) rc = digit_lists_alloc(sl.dig_h, (size_t)h.sc_n[1] * cap, k->plan[T_H]);
     if (rc) return rc;
   }
@@ -726,7 +658,9 @@ void zkr_key_free(zkr_key *k) {
       if (sl.ev_done[t]) hipEventDestroy(sl.ev_done[t]);
       if (sl.ev_sorted[t]) hipEventDestroy(sl.ev_sorted[t]);
       if (sl.ev_res[t]) hipEventDestroy(sl.ev_res[t]);
-      msm_ws_free(sl.ws[t]);
+      msm_sort_free(sl.sort[t]);
+      hipFree(sl.big_partials[t]);
+      msm_chain_free(sl.chain[t]);
     }
     if (sl.ev_w) hipEventDestroy(sl.ev_w);
     if (sl.ev_h) hipEventDestroy(sl.ev_h);

@@ -16,8 +16,6 @@
 #include "zkr_internal.hpp"
 
 namespace zkr {
-int msm_ws_alloc(MsmWorkspace &ws, size_t n, const MsmPlan &pl, size_t xyzz_bytes);
-void msm_ws_free(MsmWorkspace &ws);
 Fr host_root_of_unity(unsigned k);
 
 // ------------------------------------------------------------------ profiling (hipEvents on the launch stream)
@@ -421,8 +419,7 @@ static int msm_digits_enqueue(Prof pf, hipStream_t s, const Fr *scalars, uint32_
 
 // digit sort of one table: LDS histogram per (window, chunk) -> scans -> LDS-cursor scatter
 // n_scalars: scalars per proof (the records carry indices into the concatenated vectors of the batch); n: points of the table
-static int msm_sort_enqueue(Prof pf, hipStream_t s, const uint32_t *rank, const DigitLists &dl, uint32_t n_scalars, uint32_t n, int nbat, const MsmPlan &pl, MsmWorkspace &ws) {
-  if (n == 0) return 0;
+static int msm_sort_enqueue(Prof pf, hipStream_t s, const uint32_t *rank, const DigitLists &dl, uint32_t n_scalars, uint32_t n, int nbat, const MsmPlan &pl, const MsmSort &ws) {
   int sp = prof_begin(pf, s, "msm_sort");
   const uint32_t nb = pl.nb * (uint32_t)nbat;  // the bucket sets of the batch end to end
   const unsigned sort_grid = pl.nR * (unsigned)nbat * pl.J;
@@ -448,30 +445,36 @@ static int msm_sort_enqueue(Prof pf, hipStream_t s, const uint32_t *rank, const 
   return 0;
 }
 
+// The launch helpers below take the group as a bit (g2: the table's, or its chain's) and choose the kernels' field once, here.
 // bucket accumulation of one point table over a finished sort (`srt` may belong to another table with the same point set: B1 and
-// B2 share one); `buckets`: where the sums land (the table's own set, a set behind another table's, or -- ACC_ONTO -- a set that
-// already holds another table's sums)
+// B2 share one); `buckets`: where the sums land (the table's set of its chain: the chain's only one, a set behind another table's,
+// or -- ACC_ONTO -- a set that already holds another table's sums)
 template <class F>
-static int msm_accum_enqueue(Prof pf, hipStream_t s, const Affine<F> *pts, uint32_t n, int nbat, const MsmPlan &pl, const MsmWorkspace &srt, void *buckets, int onto = 0) {
-  if (n == 0) return 0;
-  const uint32_t nb = pl.nb * (uint32_t)nbat;
-  int sp = prof_begin(pf, s, MsmCfg<F>::ACC_STAGE);
+static void msm_accum_launch(hipStream_t s, const void *pts, uint32_t nb, const MsmSort &srt, void *buckets, int onto) {
   // small bucket sets: several lanes per bucket (kernels_msm.hpp msm_accum_split_kernel).
   // lanes per bucket by bucket count, from single-proof latencies: 2^11 / 2^13 / 2^15 buckets (circuits of 2^12 / 2^14 / 2^16):
   // 1.52 / 1.31 / 1.33, 1.83 / 1.64 / 1.68, 1.76 / 1.69 / 2.00 ms at 2 / 4 / 8 lanes; the tx circuit's 2^16 buckets: 2.30 / 2.02 /
   // 2.15 / 2.52 ms at 1 / 2 / 4 / 8 (and 631 against 614 unfused pipelined proofs/s at 2 / 4)
   const int split = nb <= (1u << 15) ? 4 : nb <= (1u << 17) ? 2 : 1;
+  const Affine<F> *p = (const Affine<F> *)pts;
+  XYZZ<F> *b = (XYZZ<F> *)buckets;
   if (split > 1) {
     const unsigned sgrid = (unsigned)(((size_t)nb * split + ACC_THREADS - 1) / ACC_THREADS);
     // (the Fq2 form is built for ONE wavefront per SIMD: its lane exchange holds two XYZZ points of 72 words, and the budget for
     // two spilled 170-200 B per lane; a tx proof measures the same either way, profiles/r4_11_tx_single_split_w_g2.txt)
-    if (split == 2) msm_accum_split_kernel<F, MsmCfg<F>::SPLIT_W, 2><<<sgrid, ACC_THREADS, 0, s>>>(pts, srt.offsets, srt.entries, nb, srt.counts, srt.order, (XYZZ<F> *)buckets, onto);
-    else msm_accum_split_kernel<F, MsmCfg<F>::SPLIT_W, 4><<<sgrid, ACC_THREADS, 0, s>>>(pts, srt.offsets, srt.entries, nb, srt.counts, srt.order, (XYZZ<F> *)buckets, onto);
+    if (split == 2) msm_accum_split_kernel<F, MsmCfg<F>::SPLIT_W, 2><<<sgrid, ACC_THREADS, 0, s>>>(p, srt.offsets, srt.entries, nb, srt.counts, srt.order, b, onto);
+    else msm_accum_split_kernel<F, MsmCfg<F>::SPLIT_W, 4><<<sgrid, ACC_THREADS, 0, s>>>(p, srt.offsets, srt.entries, nb, srt.counts, srt.order, b, onto);
   } else {
     // two wavefronts per SIMD for both G1 and G2 (amdgpu_waves_per_eu pins the register budget): with three G1 wavefronts the
     // other streams' kernels find no registers beside them, one loses the latency cover (HISTORY.md 7b)
-    msm_accum_kernel<F, MsmCfg<F>::ACC_W, MsmCfg<F>::ACC_AHEAD><<<(nb + ACC_THREADS - 1) / ACC_THREADS, ACC_THREADS, 0, s>>>(pts, srt.offsets, srt.entries, nb, srt.counts, srt.order, (XYZZ<F> *)buckets, onto);
+    msm_accum_kernel<F, MsmCfg<F>::ACC_W, MsmCfg<F>::ACC_AHEAD><<<(nb + ACC_THREADS - 1) / ACC_THREADS, ACC_THREADS, 0, s>>>(p, srt.offsets, srt.entries, nb, srt.counts, srt.order, b, onto);
   }
+}
+static int msm_accum_enqueue(Prof pf, hipStream_t s, bool g2, const void *pts, int nbat, const MsmPlan &pl, const MsmSort &srt, void *buckets, int onto = 0) {
+  const uint32_t nb = pl.nb * (uint32_t)nbat;
+  int sp = prof_begin(pf, s, g2 ? MsmCfg<Fq2>::ACC_STAGE : MsmCfg<Fq>::ACC_STAGE);
+  if (g2) msm_accum_launch<Fq2>(s, pts, nb, srt, buckets, onto);
+  else msm_accum_launch<Fq>(s, pts, nb, srt, buckets, onto);
   prof_end(pf, s, sp);
   ZKR_HIP_CHECK(hipGetLastError());
   return 0;
@@ -479,33 +482,39 @@ static int msm_accum_enqueue(Prof pf, hipStream_t s, const Affine<F> *pts, uint3
 
 // oversized buckets (digit +-1 of 0/1-heavy witnesses): needs only the sort, so it runs beside the table's accumulation
 template <class F>
-static int msm_big_enqueue(Prof pf, hipStream_t s, const Affine<F> *pts, uint32_t n, const MsmPlan &pl, const MsmWorkspace &srt, MsmWorkspace &ws) {
-  if (n == 0) return 0;
+static void msm_big_launch(hipStream_t s, const void *pts, const MsmSort &srt, void *partials) {
+  msm_big_kernel<F><<<BIG_SLOTS * BIG_SPLIT, MSM_THREADS, MSM_THREADS * sizeof(XYZZ<F>), s>>>((const Affine<F> *)pts, srt.offsets, srt.entries, srt.big_list, srt.big_count,
+                                                                                                             BIG_CAP, (XYZZ<F> *)partials);
+}
+static int msm_big_enqueue(Prof pf, hipStream_t s, bool g2, const void *pts, const MsmSort &srt, void *partials) {
   int sp = prof_begin(pf, s, "msm_big");
-  msm_big_kernel<F><<<BIG_SLOTS * BIG_SPLIT, MSM_THREADS, MSM_THREADS * sizeof(XYZZ<F>), s>>>(pts, srt.offsets, srt.entries, srt.big_list, srt.big_count,
-                                                                                                             BIG_CAP, (XYZZ<F> *)ws.big_partials);
+  if (g2) msm_big_launch<Fq2>(s, pts, srt, partials);
+  else msm_big_launch<Fq>(s, pts, srt, partials);
   prof_end(pf, s, sp);
   ZKR_HIP_CHECK(hipGetLastError());
   return 0;
 }
 
 // big-bucket partial sums -> buckets (onto: added to what the bucket holds, the other table of a shared bucket set)
-template <class F>
-static int msm_big_finish_enqueue(Prof pf, hipStream_t s, uint32_t n, const MsmWorkspace &srt, MsmWorkspace &ws, bool onto = false) {
-  if (n == 0) return 0;
+static int msm_big_finish_enqueue(Prof pf, hipStream_t s, bool g2, const MsmSort &srt, const void *partials, void *buckets, bool onto = false) {
   int sp = prof_begin(pf, s, "msm_big");
-  msm_big_finish_kernel<F><<<BIG_CAP / 64, 64, 0, s>>>((const XYZZ<F> *)ws.big_partials, srt.big_list, srt.big_count, BIG_CAP, (XYZZ<F> *)ws.buckets, onto ? 1 : 0);
+  if (g2) msm_big_finish_kernel<Fq2><<<BIG_CAP / 64, 64, 0, s>>>((const G2XYZZ *)partials, srt.big_list, srt.big_count, BIG_CAP, (G2XYZZ *)buckets, onto ? 1 : 0);
+  else msm_big_finish_kernel<Fq><<<BIG_CAP / 64, 64, 0, s>>>((const G1XYZZ *)partials, srt.big_list, srt.big_count, BIG_CAP, (G1XYZZ *)buckets, onto ? 1 : 0);
   prof_end(pf, s, sp);
   ZKR_HIP_CHECK(hipGetLastError());
   return 0;
 }
-// bucket reduction -> the MSM result in ws.h_result: short launches of few, long-running wavefronts (raised wave
-// priority), meant to run beside the next table's accumulation.  nbat: proofs fused into the launches; sets: bucket sets per
-// proof that ONE launch set walks end to end (2: A's sets behind B1's, the joint chain) -- the group-size rules below key on the
-// fused proofs only.
 template <class F>
-static int msm_reduce_enqueue(Prof pf, hipStream_t s, uint32_t n, int nbat, int sets, const MsmPlan &pl, const MsmWorkspace &srt, MsmWorkspace &ws, bool latency = false) {
-  if (n == 0) return 0;
+static void msm_reduce_launch(hipStream_t s, const MsmGeom &g, uint32_t ngroups, uint32_t ntask, const MsmChain &ch) {
+  msm_reduce1_kernel<F><<<(ngroups + MSM_THREADS - 1) / MSM_THREADS, MSM_THREADS, 0, s>>>((const XYZZ<F> *)ch.buckets, g, (XYZZ<F> *)ch.group_out);
+  msm_reduce2_kernel<F><<<dim3(ntask * g.S, g.batch), MSM_THREADS, MSM_THREADS * sizeof(XYZZ<F>), s>>>((const XYZZ<F> *)ch.group_out, g, (XYZZ<F> *)ch.task_out);
+  msm_reduce3_kernel<F><<<g.batch, MSM_THREADS, MSM_THREADS * sizeof(XYZZ<F>), s>>>((const XYZZ<F> *)ch.task_out, g, (XYZZ<F> *)ch.result);
+}
+// bucket reduction of a chain -> its result points in ch.h_result: short launches of few, long-running wavefronts (raised wave
+// priority), meant to run beside the next table's accumulation.  nbat: proofs fused into the launches; the chain's sets: bucket sets
+// per proof that ONE launch set walks end to end (2: A's sets behind B1's) -- the group-size rules below key on the fused proofs only.
+static int msm_reduce_enqueue(Prof pf, hipStream_t s, int nbat, const MsmPlan &pl, const MsmChain &ch, bool latency = false) {
+  const int sets = (int)ch.sets;
   // Group size of a FUSED launch: the plan's groups keep about 2^14 of them per proof, which is what a single proof of a small
   // circuit needs to fill the chip (msm_plan); nbat proofs in one launch bring nbat times the groups, so they take larger ones --
   // about 2^15 groups per launch -- and reduce2 / reduce3 have that much less to sum: the tx circuit in batches of eight 1 063 /
@@ -540,38 +549,28 @@ static int msm_reduce_enqueue(Prof pf, hipStream_t s, uint32_t n, int nbat, int 
   }
   const int nset = nbat * sets;  // bucket sets of the launch, end to end
   MsmGeom g;
-  g.n = n; g.c = pl.c; g.K = pl.K; g.nbw = pl.nbw; g.big_thresh = pl.big_thresh; g.glog = glog; g.S = S; g.batch = (uint32_t)nset;
+  g.c = pl.c; g.K = pl.K; g.nbw = pl.nbw; g.glog = glog; g.S = S; g.batch = (uint32_t)nset;
   int sp = prof_begin(pf, s, "msm_reduce");
   uint32_t ngroups = (pl.nbw >> glog) * (uint32_t)nset;
   uint32_t ntask = (uint32_t)(pl.c - 1 - glog) + 2;
-  msm_reduce1_kernel<F><<<(ngroups + MSM_THREADS - 1) / MSM_THREADS, MSM_THREADS, 0, s>>>((const XYZZ<F> *)ws.buckets, g, (XYZZ<F> *)ws.group_out);
-  msm_reduce2_kernel<F><<<dim3(ntask * S, nset), MSM_THREADS, MSM_THREADS * sizeof(XYZZ<F>), s>>>((const XYZZ<F> *)ws.group_out, g, (XYZZ<F> *)ws.task_out);
-  msm_reduce3_kernel<F><<<nset, MSM_THREADS, MSM_THREADS * sizeof(XYZZ<F>), s>>>((const XYZZ<F> *)ws.task_out, g, (XYZZ<F> *)ws.result);
+  if (ch.g2) msm_reduce_launch<Fq2>(s, g, ngroups, ntask, ch);
+  else msm_reduce_launch<Fq>(s, g, ngroups, ntask, ch);
   prof_end(pf, s, sp);
-  ZKR_HIP_CHECK(hipMemcpyAsync(ws.h_result, ws.result, sizeof(XYZZ<F>) * nset, hipMemcpyDeviceToHost, s));
+  ZKR_HIP_CHECK(hipMemcpyAsync(ch.h_result, ch.result, (ch.g2 ? sizeof(G2XYZZ) : sizeof(G1XYZZ)) * nset, hipMemcpyDeviceToHost, s));
   ZKR_HIP_CHECK(hipGetLastError());
   return 0;
 }
 
-// stage-hook path: one table with its own scalars (n_scalars of them; rank maps scalars to kept points)
-template <class F>
-static int msm_enqueue(Prof pf, hipStream_t s, const Affine<F> *pts, const uint32_t *rank, const Fr *scalars, uint32_t n_scalars, uint32_t n,
-                       const MsmPlan &pl, MsmWorkspace &ws) {
+// stage-hook path: one table with its own scalars (n_scalars of them; rank maps scalars to kept points) on a scratch of its own
+static int msm_enqueue(Prof pf, hipStream_t s, bool g2, const void *pts, const uint32_t *rank, const Fr *scalars, uint32_t n_scalars, uint32_t n,
+                       const MsmPlan &pl, const MsmScratch &m) {
   int rc;
-  if (!ws.own_dig.rng && (rc = digit_lists_alloc(ws.own_dig, n_scalars, pl))) return rc;
-  if ((rc = msm_digits_enqueue(pf, s, scalars, n_scalars, 1, pl, ws.own_dig))) return rc;
-  if ((rc = msm_sort_enqueue(pf, s, rank, ws.own_dig, n_scalars, n, 1, pl, ws))) return rc;
-  if ((rc = msm_big_enqueue<F>(pf, s, pts, n, pl, ws, ws))) return rc;
-  if ((rc = msm_accum_enqueue<F>(pf, s, pts, n, 1, pl, ws, ws.buckets))) return rc;
-  if ((rc = msm_big_finish_enqueue<F>(pf, s, n, ws, ws))) return rc;
-  return msm_reduce_enqueue<F>(pf, s, n, 1, 1, pl, ws, ws);
-}
-
-// the MSM result point as the reduction left it in the pinned host buffer
-template <class F>
-static XYZZ<F> msm_finish(uint32_t n, const MsmWorkspace &ws, int j = 0) {  // j: proof of a fused batch
-  if (n == 0) return XYZZ<F>::inf();
-  return ((const XYZZ<F> *)ws.h_result)[j];
+  if ((rc = msm_digits_enqueue(pf, s, scalars, n_scalars, 1, pl, m.dig))) return rc;
+  if ((rc = msm_sort_enqueue(pf, s, rank, m.dig, n_scalars, n, 1, pl, m.sort))) return rc;
+  if ((rc = msm_big_enqueue(pf, s, g2, pts, m.sort, m.big_partials))) return rc;
+  if ((rc = msm_accum_enqueue(pf, s, g2, pts, 1, pl, m.sort, m.chain.buckets))) return rc;
+  if ((rc = msm_big_finish_enqueue(pf, s, g2, m.sort, m.big_partials, m.chain.buckets))) return rc;
+  return msm_reduce_enqueue(pf, s, 1, pl, m.chain);
 }
 
 static int draw_blinding(uint8_t out[32]) {
@@ -675,24 +674,16 @@ static int prove_submit_enqueue(zkr_key *k, ProofSlot &sl, const Fr *const *d_ws
     ZKR_HIP_CHECK(hipEventRecord(sl.ev_w, sp));  // the ingested witness (and the cleared counters of its digit records)
     ZKR_HIP_CHECK(hipStreamWaitEvent(sw, sl.ev_w, 0));
   }
-  auto sort_table = [&](int t) -> int {
+  auto sort_table = [&](int t) -> int {  // a table that owns its sort; an empty one has none
+    if (!h.npts[t]) return 0;
     const uint32_t *rank = h.rank_identity[t] ? nullptr : (const uint32_t *)(ar + h.off_rank[t]);
     hipStream_t st = t == T_H ? sp : sw;
-    int rc = msm_sort_enqueue(pf, st, rank, *dig[t], rank_entries(h, t), h.npts[t], nbat, k->plan[t], sl.ws[t]);
+    int rc = msm_sort_enqueue(pf, st, rank, *dig[t], rank_entries(h, t), h.npts[t], nbat, k->plan[t], sl.sort[t]);
     if (rc) return rc;
     ZKR_HIP_CHECK(hipEventRecord(sl.ev_sorted[t], st));
     return 0;
   };
-  // which bucket set each table's sums land in and which chain reduces them: H onto C's set (merge_ch), A behind B1's sets (joint_ab);
-  // the rules and their reasons: zkr_key.hip proof_layout
-  const bool merge_ch = lay.merge_ch, joint_ab = lay.joint_ab;
-  for (int t = 0; t < N_TABLES; t++) sl.res_pending[t] = false;
-  auto result_event = [&](int t, hipStream_t rs, int rc) -> int {  // after a table's reduction chain (its D2H copy is the last thing enqueued)
-    if (rc) return rc;
-    ZKR_HIP_CHECK(hipEventRecord(sl.ev_res[t], rs));
-    sl.res_pending[t] = true;
-    return 0;
-  };
+  for (int c = 0; c < N_TABLES; c++) sl.res_pending[c] = false;
   // part of a sharded proof whose calcH is split over the shards (calc_h_split: host barriers in the middle of this enqueue): the
   // chains of the four w tables are handed over BEFORE it, so that they run while the threads wait for one another.  Everywhere
   // else the accumulations are handed over after the whole preparation chain: started early they fill the chip's wavefront slots
@@ -701,69 +692,48 @@ static int prove_submit_enqueue(zkr_key *k, ProofSlot &sl, const Fr *const *d_ws
   ShardGroup *const group = shard_group;
   const bool split_h = group && group->split_h && !serial && nbat == 1 && h.shard_parts == group->parts && h.shard_part == shard_group_part;
   // C's oversized-bucket sums on the auxiliary stream for ONE proof of a key that can fuse batches (the latency case; c_big below)
-  const bool c_big_first = merge_ch && !serial && nbat == 1 && sl.cap > 1;
+  const bool c_big_first = lay.flags[T_C] == ACC_ZERO_BIG && !serial && nbat == 1 && sl.cap > 1;
   // nothing else of this key in flight (the caller holds the key's lock: with_free_slot): this proof's last chain is latency
   bool alone = !serial;
   for (const ProofSlot &o : k->slot)
     if (&o != &sl && o.busy) alone = false;
   const bool early = split_h;  // (for a lone 2^20 / 2^22 proof the early hand-over measures the same: profiles/r6_16_lone_proof_early_handover.txt)
-  hipStream_t last = s;
-  // One table: (1) its chain's stream waits for the table's sort and takes its oversized buckets (they need only the sort and run
-  // beside the accumulation), (2) the accumulation on the accumulation stream, (3) oversized-bucket sums into the buckets and
-  // the bucket reduction, on the chain's stream again.
+  bool big_sent[N_TABLES] = {false, false, false, false, false};  // the table's oversized-bucket sums are enqueued already (c_big below)
+  // One table, where the layout (msm_plan.hpp proof_layout: the rules and their reasons) says it lands: (1) its chain's stream waits
+  // for the table's sort and takes its oversized buckets (they need only the sort and run beside the accumulation), (2) the
+  // accumulation on the accumulation stream, into the table's set of the chain, (3) after the chain's LAST table, on the chain's
+  // stream again: every member's oversized-bucket sums into its set and ONE bucket reduction over all the sets.
   auto accum_table = [&](int t) -> int {
+    if (lay.chain[t] < 0) return 0;  // an empty table
     int rc;
-    const hipStream_t rs = t == T_B2 ? s_g2 : s_g1;
-    last = rs;
-    const MsmWorkspace &srt = sl.ws[sort_src[t]];
+    const ChainLayout &cl = lay.chains[lay.chain[t]];
+    const MsmChain &ch = sl.chain[lay.chain[t]];
+    const hipStream_t rs = cl.g2 ? s_g2 : s_g1;
+    const size_t set_bytes = (size_t)nbat * k->plan[cl.geom].nb * (cl.g2 ? sizeof(G2XYZZ) : sizeof(G1XYZZ));  // one set of the chain, the fused proofs end to end
     const void *pts = ar + h.off_pts[t];
     ZKR_HIP_CHECK(hipStreamWaitEvent(rs, sl.ev_sorted[sort_src[t]], 0));
-    // partial sums into the table's OWN partials buffer.  C's, when C shares H's bucket set, may have been enqueued in front of
-    // every chain (c_big_first)
-    if (!(t == T_C && c_big_first)) {
-      if (t == T_B2) rc = msm_big_enqueue<Fq2>(pf, rs, (const G2Affine *)pts, h.npts[t], k->plan[t], srt, sl.ws[t]);
-      else rc = msm_big_enqueue<Fq>(pf, rs, (const G1Affine *)pts, h.npts[t], k->plan[t], srt, sl.ws[t]);
-      if (rc) return rc;
-      if (t == T_C && merge_ch) ZKR_HIP_CHECK(hipEventRecord(sl.ev_h, rs));  // C's partial sums are on their way: H's chain adds them in
+    if (!big_sent[t]) {  // partial sums into the table's OWN partials buffer
+      if ((rc = msm_big_enqueue(pf, rs, cl.g2, pts, sl.sort[sort_src[t]], sl.big_partials[t]))) return rc;
+      if (lay.flags[t] == ACC_ZERO_BIG) ZKR_HIP_CHECK(hipEventRecord(sl.ev_h, rs));  // the first table of a shared set: its partial sums are on their way, the chain's end adds them in
     }
     ZKR_HIP_CHECK(hipStreamWaitEvent(s, sl.ev_sorted[sort_src[t]], 0));
-    // whose bucket set the table lands in: H onto C's (merge_ch), A behind B1's sets (joint chain); its oversized-bucket sums stay its
-    // own.  Shared set: C's accumulation clears the slots of ITS oversized buckets (their sums are added after H's accumulation, so
-    // H's accumulation waits for nothing but C's, in front of it on the same stream)
-    void *buckets = t == T_H && merge_ch ? sl.ws[T_C].buckets : sl.ws[t].buckets;
-    if (joint_ab && t == T_A) buckets = (char *)sl.ws[T_B1].buckets + (size_t)nbat * k->plan[T_B1].nb * sizeof(G1XYZZ);
-    const int flags = t == T_H && merge_ch ? ACC_ONTO : (t == T_C && merge_ch ? ACC_ZERO_BIG : 0);
-    if (t == T_B2) rc = msm_accum_enqueue<Fq2>(pf, s, (const G2Affine *)pts, h.npts[t], nbat, k->plan[t], srt, buckets);
-    else rc = msm_accum_enqueue<Fq>(pf, s, (const G1Affine *)pts, h.npts[t], nbat, k->plan[t], srt, buckets, flags);
-    if (rc) return rc;
+    // Shared set (ACC_ZERO_BIG, then ACC_ONTO): the first table's accumulation clears the slots of ITS oversized buckets (their sums
+    // are added after the last accumulation, so that one waits for nothing but the first, in front of it on the same stream)
+    if ((rc = msm_accum_enqueue(pf, s, cl.g2, pts, nbat, k->plan[t], sl.sort[sort_src[t]], (char *)ch.buckets + lay.set[t] * set_bytes, lay.flags[t]))) return rc;
     ZKR_HIP_CHECK(hipEventRecord(sl.ev_done[t], s));
-    if (t == T_C && merge_ch) return 0;             // reduced with H
-    if (joint_ab && t == T_B1) return 0;            // reduced with A, by A's turn on this stream (B1's oversized-bucket sums are on their way on it)
+    if (!lay.last_of_chain(t)) return 0;  // reduced with the tables behind it, at the last one's turn on this stream
+    // the stream is in order: the earlier members' partial sums (enqueued at their turns) are done; the accumulations ran on the one
+    // accumulation stream, this table's last
     ZKR_HIP_CHECK(hipStreamWaitEvent(rs, sl.ev_done[t], 0));
-    if (t == T_B2) {
-      if ((rc = msm_big_finish_enqueue<Fq2>(pf, rs, h.npts[t], srt, sl.ws[t]))) return rc;
-      return result_event(t, rs, msm_reduce_enqueue<Fq2>(pf, rs, h.npts[t], nbat, 1, k->plan[t], srt, sl.ws[t]));
+    for (int i = 0; i < cl.n_members; i++) {  // a shared set: every table's oversized buckets are ADDED to what it holds
+      const int u = cl.members[i];
+      if (lay.flags[u] == ACC_ZERO_BIG) ZKR_HIP_CHECK(hipStreamWaitEvent(rs, sl.ev_h, 0));
+      if ((rc = msm_big_finish_enqueue(pf, rs, cl.g2, sl.sort[sort_src[u]], sl.big_partials[u], (char *)ch.buckets + lay.set[u] * set_bytes, lay.flags[u] != 0))) return rc;
     }
-    if (t == T_H && merge_ch) {  // both tables' oversized buckets are ADDED to what the shared set holds: C's partial sums (its own sort's list), then H's
-      ZKR_HIP_CHECK(hipStreamWaitEvent(rs, sl.ev_h, 0));
-      MsmWorkspace mixc = sl.ws[T_C];   // C's workspace: its partials, its buckets
-      if ((rc = msm_big_finish_enqueue<Fq>(pf, rs, h.npts[T_C], sl.ws[sort_src[T_C]], mixc, true))) return rc;
-      MsmWorkspace mix = sl.ws[T_C];
-      mix.big_partials = sl.ws[t].big_partials;
-      if ((rc = msm_big_finish_enqueue<Fq>(pf, rs, h.npts[t], srt, mix, true))) return rc;
-      return result_event(t, rs, msm_reduce_enqueue<Fq>(pf, rs, h.npts[t], nbat, 1, k->plan[t], srt, mixc, alone));
-    }
-    if (joint_ab && t == T_A) {
-      // the stream is in order: B1's partial sums (enqueued at B1's turn) are done; both accumulations ran on the one accumulation
-      // stream, A's last (ev_done[T_A] is waited for above)
-      MsmWorkspace dst = sl.ws[t];
-      dst.buckets = buckets;
-      if ((rc = msm_big_finish_enqueue<Fq>(pf, rs, h.npts[T_B1], sl.ws[sort_src[T_B1]], sl.ws[T_B1]))) return rc;
-      if ((rc = msm_big_finish_enqueue<Fq>(pf, rs, h.npts[T_A], srt, dst))) return rc;
-      return result_event(T_A, rs, msm_reduce_enqueue<Fq>(pf, rs, h.npts[T_B1], nbat, 2, k->plan[T_B1], sl.ws[sort_src[T_B1]], sl.ws[T_B1]));
-    }
-    if ((rc = msm_big_finish_enqueue<Fq>(pf, rs, h.npts[t], srt, sl.ws[t]))) return rc;
-    return result_event(t, rs, msm_reduce_enqueue<Fq>(pf, rs, h.npts[t], nbat, 1, k->plan[t], srt, sl.ws[t], alone && t == T_H));
+    if ((rc = msm_reduce_enqueue(pf, rs, nbat, k->plan[cl.geom], ch, alone && cl.latency))) return rc;
+    ZKR_HIP_CHECK(hipEventRecord(sl.ev_res[lay.chain[t]], rs));  // the chain's D2H copy is the last thing enqueued
+    sl.res_pending[lay.chain[t]] = true;
+    return 0;
   };
   auto chains = [&](std::initializer_list<int> ts) -> int {
     for (int t : ts)
@@ -780,9 +750,10 @@ static int prove_submit_enqueue(zkr_key *k, ProofSlot &sl, const Fr *const *d_ws
   auto c_big = [&]() -> int {
     if (!c_big_first) return 0;
     ZKR_HIP_CHECK(hipStreamWaitEvent(aux, sl.ev_sorted[sort_src[T_C]], 0));
-    int rc = msm_big_enqueue<Fq>(pf, aux, (const G1Affine *)(ar + h.off_pts[T_C]), h.npts[T_C], k->plan[T_C], sl.ws[sort_src[T_C]], sl.ws[T_C]);
+    int rc = msm_big_enqueue(pf, aux, false, ar + h.off_pts[T_C], sl.sort[sort_src[T_C]], sl.big_partials[T_C]);
     if (rc) return rc;
     ZKR_HIP_CHECK(hipEventRecord(sl.ev_h, aux));
+    big_sent[T_C] = true;
     return 0;
   };
   // preparation chain
@@ -806,7 +777,7 @@ static int prove_submit_enqueue(zkr_key *k, ProofSlot &sl, const Fr *const *d_ws
   if (rc) return rc;
   // completion = the chain and auxiliary streams done (prove_collect waits for the events on the host).  No stream is made
   // to wait for another, so nothing of the next proof queues behind this one's tail.
-  prof_end(pf, last, tot);
+  prof_end(pf, s_g1, tot);  // the proof's last table, H, belongs to a G1 chain
   const hipStream_t ends[3] = {s_g2, s_g1, aux};  // sl.ev_end's order
   for (int j = 0; j < 3; j++) ZKR_HIP_CHECK(hipEventRecord(sl.ev_end[j], ends[j]));
   sl.busy = true;
@@ -874,24 +845,27 @@ static int prove_collect(zkr_key *k, ProofSlot &sl, uint8_t *proofs_out, Partial
     }
   } release{k, sl};
   ZKR_HIP_CHECK(hipSetDevice(k->device));
-  const ArenaHeader &h = k->h;
   const ProofLayout &lay = k->layout;
   // Everything that needs A, B1, B2 only (assemble_ab: all the scalar multiplications) is done while the LAST chains (C, H: H's
   // sort only starts after calcH) still run on the GPU; when C + H lands, one addition and one inversion finish pi_c.
   // Single-proof latency: ~0.35 ms of host work off the critical path (with two proofs in flight it was hidden already).
-  auto wait_table = [&](int t) -> int {
-    if (sl.res_pending[t]) ZKR_HIP_CHECK(hipEventSynchronize(sl.ev_res[t]));
+  auto wait_table = [&](int t) -> int {  // for the chain the table was reduced in
+    const int c = lay.chain[t];
+    if (c >= 0 && sl.res_pending[c]) { ZKR_HIP_CHECK(hipEventSynchronize(sl.ev_res[c])); sl.res_pending[c] = false; }
     return 0;
+  };
+  // the sum of table t in proof j of the group as its chain's reduction left it in the pinned host buffer (set-major); infinity for an
+  // empty table and for one that landed ONTO another's set: that table's result holds both
+  auto g1_result = [&](int t, int j) {
+    return lay.own_result(t) ? ((const G1XYZZ *)sl.chain[lay.chain[t]].h_result)[lay.set[t] * sl.nbat + j] : G1XYZZ::inf();
   };
   int rcw;
   if ((rcw = wait_table(T_A)) || (rcw = wait_table(T_B1)) || (rcw = wait_table(T_B2))) return rcw;
   std::vector<G1XYZZ> pic_part((size_t)sl.nbat);
   int status = 0;
   for (int j = 0; j < sl.nbat; j++) {
-    // joint chain of A and B1 (prove_submit_enqueue): B1's workspace holds both results, B1's nbat first
-    G1XYZZ A = lay.joint_ab ? msm_finish<Fq>(h.npts[T_A], sl.ws[T_B1], sl.nbat + j) : msm_finish<Fq>(h.npts[T_A], sl.ws[T_A], j);
-    G1XYZZ B1 = msm_finish<Fq>(h.npts[T_B1], sl.ws[T_B1], j);
-    G2XYZZ B2 = msm_finish<Fq2>(h.npts[T_B2], sl.ws[T_B2], j);
+    G1XYZZ A = g1_result(T_A, j), B1 = g1_result(T_B1, j);
+    G2XYZZ B2 = lay.own_result(T_B2) ? ((const G2XYZZ *)sl.chain[lay.chain[T_B2]].h_result)[j] : G2XYZZ::inf();
     if (partials_out) { partials_out[j].A = A; partials_out[j].B1 = B1; partials_out[j].B2 = B2; continue; }
     int rc = assemble_ab(k, A, B1, B2, &sl.rb[32 * j], &sl.sb[32 * j], proofs_out + 256 * j, pic_part[j]);
     if (rc) status = rc;
@@ -900,9 +874,7 @@ static int prove_collect(zkr_key *k, ProofSlot &sl, uint8_t *proofs_out, Partial
   for (hipEvent_t e : sl.ev_end) ZKR_HIP_CHECK(hipEventSynchronize(e));  // every stream of the slot is idle (all of it precedes the table events)
   if (k->prof_on) { std::lock_guard<std::mutex> lk(k->mu); prof_collect(k, sl); }
   for (int j = 0; j < sl.nbat && !status; j++) {
-    // merged bucket sets (prove_submit_enqueue): the one reduction result, C + H, sits in C's workspace
-    G1XYZZ C = msm_finish<Fq>(h.npts[T_C], sl.ws[T_C], j);
-    G1XYZZ H = lay.merge_ch ? G1XYZZ::inf() : msm_finish<Fq>(h.npts[T_H], sl.ws[T_H], j);
+    G1XYZZ C = g1_result(T_C, j), H = g1_result(T_H, j);
     if (partials_out) { partials_out[j].CH = add_full(C, H); continue; }
     status = assemble_c(add_full(C, H), pic_part[j], proofs_out + 256 * j);
   }
@@ -1281,12 +1253,9 @@ static int msm_hook(const void *points_mont, const void *scalars_std, size_t n, 
   XYZZ<F> res = XYZZ<F>::inf();
   if (np) {
     MsmPlan pl = msm_plan(n, np);
-    struct WsGuard {  // the sort / bucket workspace goes with the scope as well
-      MsmWorkspace ws;
-      ~WsGuard() { msm_ws_free(ws); }
-    } g;
-    MsmWorkspace &ws = g.ws;
-    int rc = msm_ws_alloc(ws, np, pl, sizeof(XYZZ<F>));
+    constexpr bool g2 = sizeof(F) != 32;
+    MsmScratch ms;
+    int rc = msm_scratch_alloc(ms, n, np, pl, g2);
     if (rc) return rc;
     DevBuf bpts, brank, bsc, bsc2;
     if ((rc = bpts.alloc(compact.size() * pl.K)) || (rc = brank.alloc(n * 4)) || (rc = bsc.alloc(n * 32)) || (rc = bsc2.alloc(n * 32))) return rc;  // K window levels
@@ -1296,13 +1265,13 @@ static int msm_hook(const void *points_mont, const void *scalars_std, size_t n, 
     ZKR_HIP_CHECK(hipMemcpy(d_pts, compact.data(), compact.size(), hipMemcpyHostToDevice));
     ZKR_HIP_CHECK(hipMemcpy(d_rank, rank.data(), n * 4, hipMemcpyHostToDevice));
     ZKR_HIP_CHECK(hipMemcpy(d_sc, scalars_std, n * 32, hipMemcpyHostToDevice));
-    if ((rc = msm_precompute(device, sizeof(F) != 32, d_pts, np, pl))) return rc;
+    if ((rc = msm_precompute(device, g2, d_pts, np, pl))) return rc;
     ingest_kernel<<<(unsigned)((n + 255) / 256), 256>>>(d_sc, d_sc2, n);
-    rc = msm_enqueue<F>(Prof{nullptr, nullptr}, nullptr, d_pts, d_rank, d_sc2, (uint32_t)n, np, pl, ws);
+    rc = msm_enqueue(Prof{nullptr, nullptr}, nullptr, g2, d_pts, d_rank, d_sc2, (uint32_t)n, np, pl, ms);
     hipError_t e = hipDeviceSynchronize();  // also after a failed enqueue: nothing may still run on buffers that are about to go
     if (!rc && e != hipSuccess) { set_error("msm failed: %s", hipGetErrorString(e)); rc = ZKR_ERR_HIP; }
     if (rc) return rc;
-    res = msm_finish<F>(np, ws);
+    res = *(const XYZZ<F> *)ms.chain.h_result;
   }
   *is_inf = res.is_inf() ? 1 : 0;
   memset(out, 0, pb);
@@ -1321,18 +1290,15 @@ int key_table_msm(const zkr_key *k, int t, const Fr *d_scalars, G1XYZZ *out) {
   const ArenaHeader &h = k->h;
   *out = G1XYZZ::inf();
   if (!h.npts[t]) return 0;
-  struct WsGuard {
-    MsmWorkspace ws;
-    ~WsGuard() { msm_ws_free(ws); }
-  } g;
-  int rc = msm_ws_alloc(g.ws, h.npts[t], k->plan[t], sizeof(G1XYZZ));
+  MsmScratch ms;
+  int rc = msm_scratch_alloc(ms, rank_entries(h, t), h.npts[t], k->plan[t], false);
   if (rc) return rc;
-  rc = msm_enqueue<Fq>(Prof{nullptr, nullptr}, nullptr, (const G1Affine *)(k->arena + h.off_pts[t]), (const uint32_t *)(k->arena + h.off_rank[t]), d_scalars,
-                       rank_entries(h, t), h.npts[t], k->plan[t], g.ws);
+  rc = msm_enqueue(Prof{nullptr, nullptr}, nullptr, false, k->arena + h.off_pts[t], (const uint32_t *)(k->arena + h.off_rank[t]), d_scalars,
+                   rank_entries(h, t), h.npts[t], k->plan[t], ms);
   hipError_t e = hipDeviceSynchronize();  // also after a failed enqueue: the workspace goes with this scope
   if (!rc && e != hipSuccess) { set_error("msm over a key table failed: %s", hipGetErrorString(e)); rc = ZKR_ERR_HIP; }
   if (rc) return rc;
-  *out = msm_finish<Fq>(h.npts[t], g.ws);
+  *out = *(const G1XYZZ *)ms.chain.h_result;
   return 0;
 }
 }  // namespace zkr

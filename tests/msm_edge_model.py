@@ -1,4 +1,4 @@
-"""Integer model of the MSM's digit recoding and bucket geometry (csrc/kernels_msm.hpp, csrc/zkr_key.hip), for the edge tests.
+"""Integer model of the MSM's digit recoding and bucket geometry (csrc/kernels_msm.hpp, csrc/msm_plan.hpp), for the edge tests.
 
 tests/test_gpu_msm_edges.py builds witnesses and scalar vectors that are meant to reach particular paths of the MSM: buckets
 over `big_thresh`, more of them than BIG_CAP lists, more than BIG_SLOTS of them, buckets in the top size class, the
@@ -14,9 +14,9 @@ from bn254 import R
 BIG_CAP = 1024            # kernels_msm.hpp: oversized buckets listed per MSM (the rest stay with msm_accum_kernel)
 BIG_SLOTS = 64            # kernels_msm.hpp: oversized buckets per round of msm_big_body
 SIZE_BINS = 1024          # kernels_msm.hpp: buckets of >= SIZE_BINS - 1 entries share the top size class
-MAX_RANGES = 256          # kernels_msm.hpp
-SORT_RANGE_DEFAULT = 2048  # kernels_msm.hpp
-SORT_CHUNK_RECORDS = 3328  # kernels_msm.hpp
+MAX_RANGES = 256          # msm_plan.hpp
+SORT_RANGE_DEFAULT = 2048  # msm_plan.hpp
+SORT_CHUNK_RECORDS = 3328  # msm_plan.hpp
 MAX_FUSE = 16             # proofs one submit fuses at most (zkr_key_fuse of a 2^16 key)
 
 
@@ -36,7 +36,7 @@ def spread_tmax(c, K):
 
 
 def big_threshold(n, K, nbw, nbat=1):
-    """big_threshold (zkr_key.hip): occupancy above which a bucket goes to msm_big_kernel."""
+    """big_threshold (msm_plan.hpp): occupancy above which a bucket goes to msm_big_kernel."""
     mean = n * K // nbw + 1
     by_bulk = (n * K * max(nbat, 1)) >> 17
     thr = min(by_bulk, mean * 8)

@@ -35,7 +35,7 @@ def test_sharded_proof_equals_whole_key_proof_and_closed_form(log_m, parts):
         cover_h += si["h_n"]
         for t in pts:
             pts[t] += sh.info()[t]
-        # a shard picks its window from ITS scalar counts, as a key of that size would (csrc/zkr_key.hip msm_plan)
+        # a shard picks its window from ITS scalar counts, as a key of that size would (csrc/msm_plan.hpp msm_plan)
         c_of = lambda nsc: min(20, max(4, (nsc - 1).bit_length()))
         win = sh.windows()
         assert all(win[t][0] == c_of(si["w_n"]) for t in ("A", "B1", "B2", "C")) and win["H"][0] == c_of(si["h_n"]) and sh.fuse() == 1
@@ -66,6 +66,22 @@ def test_sharded_proof_equals_whole_key_proof_and_closed_form(log_m, parts):
     # the whole key may go: shards own their memory
     key.close()
     assert zkr_hip.prove_sharded(shards, wb, r, s) == whole
+
+
+def test_shards_with_a_points_and_no_b_point():
+    """A key whose B side reads its first eight signals only (tests/layout_cases.py), cut in four: shards 1..3 own A and C points but
+    no B point, so there is no B1 chain for A to land behind and A is reduced by a chain of its own (csrc/msm_plan.hpp proof_layout)."""
+    import zkr_hip
+    from layout_cases import b_side_on_the_first_signals
+    c = b_side_on_the_first_signals()
+    key = zkr_hip.ProvingKey.load_websnark(c["pkb"])
+    shards = [key.shard(i, 4) for i in range(4)]
+    infos = [sh.info() for sh in shards]
+    assert infos[0]["ptsB1"] > 0 and all(i["ptsB1"] == i["ptsB2"] == 0 and i["ptsA"] > 0 and i["ptsC"] > 0 for i in infos[1:])
+    whole = key.prove(c["wb"], 71, 72)
+    assert whole == coracle.prove(c["pkb"], c["wb"], 71, 72)
+    assert zkr_hip.prove_sharded(shards, c["wb"], 71, 72) == whole
+    assert key.prove_combine([sh.prove_partial(c["wb"]) for sh in shards], 71, 72) == whole
 
 
 @pytest.mark.parametrize("log_m,parts", [(12, 3), (12, 5), (12, 7), (18, 6), (22, 8)])

@@ -494,6 +494,27 @@ def test_prove_batch_from_host_buffers_equals_single_proofs(small_case):
     assert key.prove(wits[1], 5, 6) == coracle.prove(c["pkb"], wits[1], 5, 6)      # the key is still usable
 
 
+@pytest.mark.parametrize("count", [1, 4])
+def test_c_and_h_in_chains_of_their_own(count):
+    """A circuit with far fewer signals than constraints (100 under a domain of 2^8: tests/layout_cases.py): C's window follows the
+    signals, H's the domain, so H cannot land on C's bucket set and each is reduced by a chain of its own, H's last (csrc/msm_plan.hpp
+    proof_layout).  One proof alone and a fused batch of four, unsatisfied witnesses among them, against the oracle."""
+    import zkr_hip
+    from layout_cases import few_signals_many_constraints
+    c = few_signals_many_constraints()
+    key = zkr_hip.ProvingKey.load_websnark(c["pkb"])
+    info, win = key.info(), key.windows()
+    assert (info["nVars"], info["domainSize"]) == (100, 256) and info["ptsC"] > 0 and info["ptsH"] > 0
+    assert win["C"][0] == win["A"][0] == 7 and win["H"][0] == 8 and key.fuse() >= 4
+    rnd = random.Random(count)
+    wits = [c["wb"]] + [g.binarify_witness([1] + [rnd.randrange(R) for _ in range(99)]) for _ in range(count - 1)]
+    rs, ss = [rnd.randrange(R) for _ in wits], [rnd.randrange(R) for _ in wits]
+    want = [coracle.prove(c["pkb"], wb, r, s) for wb, r, s in zip(wits, rs, ss)]
+    assert want[0] == g.proof_bytes(g.proof_from_toxic(c["circ"], g.toxic_from_seed(0x5A4B00FF), c["w"], rs[0], ss[0]))
+    got = key.prove_batch(wits, rs, ss) if count > 1 else [key.prove(wits[0], rs[0], ss[0])]
+    assert got == want
+
+
 _SORT_KNOB_CHILD = r"""
 import random, sys
 sys.path[:0] = %r

@@ -73,7 +73,7 @@ def test_edge_scalars_are_what_they_claim(c):
 
 def test_occupancy_and_thresholds_on_small_cases():
     """occupancy() against a plain digit count; big_threshold / plan / group_sizes against values worked out by hand from the
-    C++ (zkr_key.hip big_threshold and msm_plan, zkr_prove.hip group_count)."""
+    C++ (msm_plan.hpp big_threshold and msm_plan, zkr_prove.hip group_count)."""
     rnd = random.Random(9)
     for c in (2, 3, 5, 9, 16):
         K = em.windows(c)
