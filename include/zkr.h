@@ -289,6 +289,22 @@ int zkr_synth_witness(unsigned log_m, unsigned n_public, uint64_t circuit_seed, 
  * delta (5 x 32 B, non-zero, < r) for reproducible test setups, or NULL to draw them from the OS CSPRNG inside the call
  * (they are wiped before it returns).  domainSize = smallest power of two >= nConstraints + nPublic + 1. */
 int zkr_setup_r1cs(const void *r1cs_bin, size_t r1cs_len, const uint8_t *toxic160, int device, zkr_key **key_out, void **vk_out, size_t *vk_len);
+/* H in evaluation form.  A builder that knows the key's scalars (zkr_setup_r1cs with toxic scalars or its own, zkr_synth_key) also
+ * builds two side tables beside the arena, with the window plans of C and H: C' = C + 1/2 C^T F over all nVars signals and
+ * E' = -1/2 E over the domain, the H table moved to the evaluations on the coset by two transforms of its scalars.  A whole-key proof
+ * of its own launches then runs four transforms instead of six: the H multiexp takes the coset products A(g w^j) B(g w^j) as they
+ * are, the C multiexp takes the witness over C'.  That rests on a o b = C w, so every such proof also counts the rows where it
+ * fails, and a witness with such rows is proved again through the coefficient form, in its place in the caller's order: the proof
+ * is the same bytes for every witness.  The tables cost about as much device memory as C and H themselves (2 x 0.87 GB at 2^20);
+ * when they cannot be allocated, or a signal of C' has no point in the layout C shares, the key simply keeps the coefficient
+ * form (ZKR_H_FORM=coefficients asks for that).  They are not part of the arena: key files, replicas, shards, contributed keys
+ * (zkr_key_contribute changes C and H), websnark-loaded and transcript keys prove through the coefficient form.
+ * zkr_key_h_form: *evaluation = 1 when the key has the tables; *retries = proofs of this key proved again so far (either may be NULL).
+ * zkr_setup_r1cs_opts: zkr_setup_r1cs with flags; ZKR_SETUP_NO_SIDE_TABLES refuses the side tables' allocation (a test hook for
+ * the fall-back). */
+#define ZKR_SETUP_NO_SIDE_TABLES 1u
+int zkr_setup_r1cs_opts(const void *r1cs_bin, size_t r1cs_len, const uint8_t *toxic160, int device, unsigned flags, zkr_key **key_out, void **vk_out, size_t *vk_len);
+int zkr_key_h_form(const zkr_key *key, int *evaluation, uint64_t *retries);
 /* The same setup, delivering the proving key as the bytes `binarifyProvingKey(provingKey)` produces from snarkjs' JSON key
  * (binarify.ts:143-206; malloc'ed, free with zkr_free; at most 4 GiB, the format's u32 offsets) instead of a device key:
  * the provingKeyBin an UNCHANGED reference caller passes to groth16GenProof on every call (common.ts:28-29). */

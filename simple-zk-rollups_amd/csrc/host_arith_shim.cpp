@@ -5,6 +5,7 @@
 #include "pairing.hpp"
 #include "curve29.hpp"
 #include "msm_plan.hpp"
+#include "eval_h.hpp"
 using namespace zkr;
 
 // ---- the 29-bit-limb hot-path arithmetic (field29.hpp, curve29.hpp) compiled for the host
@@ -214,6 +215,30 @@ int zkt_proof_layout(uint32_t n, uint32_t m, const uint32_t npts[5], const uint3
 }
 int zkr_host_shard_group_selftest(unsigned parts, unsigned rounds, unsigned fail_part, unsigned fail_round) {
   return shard_group_selftest(parts, rounds, fail_part, fail_round);
+}
+// eval_h.hpp: host_ntt on 2^logn standard-form values in place (natural order in and out)
+void zkt_host_ntt(uint8_t *data, unsigned logn, int inverse) {
+  std::vector<Fr> x((size_t)1 << logn);
+  for (size_t i = 0; i < x.size(); i++) x[i] = to_mont(load_fp<FrParams>(data + 32 * i));
+  host_ntt(x, logn, inverse != 0);
+  for (size_t i = 0; i < x.size(); i++) store_fp(data + 32 * i, from_mont(x[i]));
+}
+// eval_h.hpp: eval_h_scalars with every value in standard form, 32 B each (hx, f, e, eprime: 2^logm; coefC: one per term of C;
+// cpriv: n - p - 1; cfold: n)
+void zkt_eval_h_scalars(const uint8_t *hx, unsigned logm, const uint32_t *rowC, const uint32_t *sigC, const uint8_t *coefC, uint32_t nC, uint32_t n, uint32_t p,
+                        const uint8_t *cpriv, uint8_t *f, uint8_t *e, uint8_t *cfold, uint8_t *eprime) {
+  auto load = [](const uint8_t *b, size_t cnt) {
+    std::vector<Fr> v(cnt);
+    for (size_t i = 0; i < cnt; i++) v[i] = to_mont(load_fp<FrParams>(b + 32 * i));
+    return v;
+  };
+  auto store = [](const std::vector<Fr> &v, uint8_t *b) {
+    for (size_t i = 0; i < v.size(); i++) store_fp(b + 32 * i, from_mont(v[i]));
+  };
+  const std::vector<Fr> vhx = load(hx, (size_t)1 << logm), vco = load(coefC, rowC[nC]), vcp = load(cpriv, n - p - 1);
+  EvalHScalars sc;
+  eval_h_scalars(vhx.data(), logm, rowC, sigC, vco.data(), nC, n, p, vcp.data(), sc);
+  store(sc.f, f); store(sc.e, e); store(sc.cfold, cfold); store(sc.eprime, eprime);
 }
 // field 0 = Fq, 1 = Fr; ops: see f29_op above; inputs / outputs standard form
 void zkt29_fp(int field, int op, const uint8_t *a, const uint8_t *b, uint8_t *out) {

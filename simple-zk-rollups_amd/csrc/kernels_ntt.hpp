@@ -341,11 +341,14 @@ static __global__ void ingest_kernel(const Fr *in, Fr *out, size_t n, uint32_t *
 // occasional wide row (64-term bit-packing rows, a handful per few thousand), which would leave 63 lanes of its
 // wavefront waiting for one; rows wider than SPMV_WIDE are left to spmv_wide_kernel (one wavefront per row).
 constexpr uint32_t SPMV_WIDE = 8;
-// blockIdx.z = 1: the B side of the QAP in the same launch (its CSR arrays and output vector)
+// blockIdx.z = 1: the B side of the QAP in the same launch (its CSR arrays and output vector); 2: the C side of a key that proves
+// with H in evaluation form (gridDim.z = 3; everybody else passes an empty third side and gridDim.z = 2)
 struct SpmvSide { const uint32_t *row_ptr, *col; const Fr *coef; Fr *out; const uint32_t *wide; uint32_t n_wide; };
 // row0 / row1: the rows wanted (a shard of a split calcH evaluates its block of the domain; otherwise 0 and m)
-static __global__ void spmv_kernel(SpmvSide sa, SpmvSide sb, const Fr *w, uint32_t m, uint32_t n, uint32_t row0, uint32_t row1) {
-  const SpmvSide &sd = blockIdx.z ? sb : sa;
+// zero: one word a LATER kernel of the stream counts into (eval_unsatisfied_kernel), cleared here; null: none
+static __global__ void spmv_kernel(SpmvSide sa, SpmvSide sb, SpmvSide sc, const Fr *w, uint32_t m, uint32_t n, uint32_t row0, uint32_t row1, uint32_t *zero) {
+  const SpmvSide &sd = blockIdx.z == 0 ? sa : blockIdx.z == 1 ? sb : sc;
+  if (zero && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) *zero = 0;
   const uint32_t *row_ptr = sd.row_ptr, *col = sd.col;
   const Fr *coef = sd.coef;
   Fr *out = sd.out;
@@ -360,9 +363,9 @@ static __global__ void spmv_kernel(SpmvSide sa, SpmvSide sb, const Fr *w, uint32
   store_fr(out + c, acc);
 }
 // wide[i] = index of the i-th row wider than SPMV_WIDE; one wavefront per row, terms strided over the lanes, LDS tree
-static __global__ __launch_bounds__(64) void spmv_wide_kernel(SpmvSide sa, SpmvSide sb, const Fr *w, uint32_t m, uint32_t n, uint32_t row0, uint32_t row1) {
+static __global__ __launch_bounds__(64) void spmv_wide_kernel(SpmvSide sa, SpmvSide sb, SpmvSide sc, const Fr *w, uint32_t m, uint32_t n, uint32_t row0, uint32_t row1) {
   __shared__ uint32_t sh[8 * 64];
-  const SpmvSide &sd = blockIdx.z ? sb : sa;
+  const SpmvSide &sd = blockIdx.z == 0 ? sa : blockIdx.z == 1 ? sb : sc;
   const uint32_t *row_ptr = sd.row_ptr, *col = sd.col, *wide = sd.wide;
   const Fr *coef = sd.coef;
   Fr *out = sd.out;
@@ -407,6 +410,24 @@ static __global__ void combine_h_kernel(const Fr *S, const Fr *D, Fr *h, const F
   Fr s = mul(load_fr(S + pos), c1);
   Fr d = mul(mul(load_fr(D + pos), ginv), c2);
   store_fr(h + pos, sub(s, d));
+}
+
+// H in evaluation form (eval_h.hpp), two element-wise kernels.
+// Rows with a_j b_j != c_j: the identity behind the folded C table needs a o b = C w on the whole domain.  a, b: the QAP row sums
+// in standard form; c_over_r: C's row sums made with standard-form coefficients, i.e. c_j / R -- what one product of a_j and b_j
+// leaves.  All three canonical.  A satisfying witness adds nothing, so the good path has no atomic at all.
+static __global__ void eval_unsatisfied_kernel(const Fr *a, const Fr *b, const Fr *c_over_r, uint32_t m, uint32_t *bad) {
+  uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= m) return;
+  if (!(mul(load_fr(a + j), load_fr(b + j)) == load_fr(c_over_r + j))) atomicAdd(bad, 1u);
+}
+// d_j = ao_j bo_j / R from the canonical coset evaluations: the scalars of the E' table (whose points carry R / m^2 and the rest)
+static __global__ void eval_product_kernel(const Fr *ao, const Fr *bo, Fr *d, uint32_t m, uint32_t *zero, uint32_t zero_words) {
+  if (blockIdx.x == 0)  // see ingest_kernel: the counters of h's digit records
+    for (uint32_t k = threadIdx.x; k < zero_words; k += blockDim.x) zero[k] = 0;
+  uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= m) return;
+  store_fr(d + j, mul(load_fr(ao + j), load_fr(bo + j)));
 }
 
 // out[i] = in[bitrev(i)]  (test hooks only)

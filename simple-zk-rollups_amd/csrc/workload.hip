@@ -9,6 +9,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <map>
+#include "eval_h.hpp"
 #include "zkr_internal.hpp"
 
 namespace zkr {
@@ -345,6 +346,85 @@ static int build_key_from_generated(const Generated &g, int device, zkr_key **ke
   return build_key_from_tables(g.circ, keep, g.d_tbl, 0, g.consts, device, key_out);
 }
 
+// The side tables of H in evaluation form (zkr_internal.hpp EvalTables; the algebra: eval_h.hpp) for a key this setup has just
+// built: the scalars of C' and E' from the setup's own, their points by the fixed-base kernel, their window levels with the plans
+// of C and H, C by QAP row for the prover's third row sum, and a counter per proof slot.  Returns 0 with the key unchanged -- it
+// proves through the coefficient form -- when an allocation fails (refuse: the test hook that says so), when ZKR_H_FORM=coefficients
+// asks for it, or when the tables would not fit the layout the key's proofs run on: the H table dropped a point, or a signal with a
+// C' point has no place among the points of C (of A's sort, when the two share one).  Below zero only for a failed kernel.
+static int key_build_eval_tables(zkr_key *k, const Generated &g, bool refuse) {
+  const ArenaHeader &h = k->h;
+  const Circuit &c = g.circ;
+  const uint32_t n = h.n, m = h.m, p = h.p;
+  if (const char *e = getenv("ZKR_H_FORM"); e && !strcmp(e, "coefficients")) return 0;
+  if (refuse || h.shard_parts != 1 || !h.npts[T_C] || h.npts[T_H] != m) return 0;
+  ZKR_HIP_CHECK(hipSetDevice(k->device));
+  struct Secret {  // scalars that reveal t or delta go the way the setup's own do
+    EvalHScalars es;
+    std::vector<Fr> c_sc;
+    std::vector<uint8_t> bytes;
+    bool wipe;
+    ~Secret() { if (wipe) { wipe_vector(es.f); wipe_vector(es.e); wipe_vector(es.cfold); wipe_vector(es.eprime); wipe_vector(c_sc); wipe_vector(bytes); } }
+  } sec{{}, {}, {}, g.secret};
+  std::vector<uint32_t> sig(c.tC.size());
+  std::vector<Fr> coef(c.tC.size());
+  for (size_t i = 0; i < c.tC.size(); i++) { sig[i] = c.tC[i].sig; coef[i] = c.tC[i].coef; }
+  eval_h_scalars(g.sc.hx.data(), h.logm, c.rowC.data(), sig.data(), coef.data(), c.nC, n, p, g.sc.cpriv.data(), sec.es);
+  // C' over the points of the table whose sort C's accumulation reads
+  const int lt = k->layout.sort_src[T_C];
+  const uint32_t np_c = h.npts[lt];
+  std::vector<uint32_t> rank(n);
+  if (h.rank_identity[lt]) for (uint32_t s = 0; s < n; s++) rank[s] = s;
+  else ZKR_HIP_CHECK(hipMemcpy(rank.data(), k->arena + h.off_rank[lt], (size_t)n * 4, hipMemcpyDeviceToHost));
+  sec.c_sc.assign(np_c, Fr::zero());
+  for (uint32_t s = 0; s < n; s++) {
+    if (sec.es.cfold[s].is_zero()) continue;
+    if (rank[s] >= np_c) return 0;  // no point for this signal in the layout (0xffffffff: dropped)
+    sec.c_sc[rank[s]] = sec.es.cfold[s];
+  }
+  EvalTables &ev = k->eval;
+  auto give_up = [&](bool hip_failed) { if (hip_failed) (void)hipGetLastError(); key_eval_tables_free(k); return 0; };
+  // level 0 from the scalars, then the window levels in place (msm_precompute), in a buffer sized as arena_layout sizes a table's
+  auto table = [&](const std::vector<Fr> &scalars, const MsmPlan &pl, void **out) -> int {
+    const size_t np = scalars.size();
+    if (hipMalloc(out, np * pl.K * 64 + 64) != hipSuccess) { *out = nullptr; return 1; }
+    to_std_bytes(scalars, sec.bytes);
+    void *lvl0 = nullptr;
+    if (int rc = fixed_base_points(k->device, false, sec.bytes.data(), np, &lvl0, g.secret)) return rc;
+    hipError_t e = hipMemcpy(*out, lvl0, np * 64, hipMemcpyDeviceToDevice);
+    hipFree(lvl0);
+    if (e != hipSuccess) { set_error("copy of a side table's base points failed: %s", hipGetErrorString(e)); return ZKR_ERR_HIP; }
+    return msm_precompute(k->device, false, *out, (uint32_t)np, pl);
+  };
+  int rc;
+  if ((rc = table(sec.c_sc, k->plan[T_C], &ev.c_pts)) > 0) return give_up(true);
+  if (rc) { give_up(false); return rc; }
+  if ((rc = table(sec.es.eprime, k->plan[T_H], &ev.e_pts)) > 0) return give_up(true);
+  if (rc) { give_up(false); return rc; }
+  // C by row over the whole domain (rows from nConstraints on are empty), STANDARD-form coefficients: with the standard-form
+  // witness the row sums come out as c_j / R, which is what one product of a_j and b_j leaves (kernels_ntt.hpp eval_unsatisfied_kernel)
+  std::vector<uint32_t> rowptr(m + 1), wide;
+  for (uint32_t r = 0; r <= m; r++) rowptr[r] = c.rowC[r < c.nC ? r : c.nC];
+  for (uint32_t r = 0; r < c.nC; r++)
+    if (rowptr[r + 1] - rowptr[r] > 8) wide.push_back(r);  // kernels_ntt.hpp SPMV_WIDE
+  for (Fr &x : coef) x = from_mont(x);
+  ev.nnz = (uint32_t)sig.size();
+  ev.n_wide = (uint32_t)wide.size();
+  bool ok = hipMalloc(&ev.c_rowptr, rowptr.size() * 4) == hipSuccess && hipMalloc(&ev.c_col, sig.size() * 4 + 4) == hipSuccess &&
+            hipMalloc(&ev.c_coef, coef.size() * 32 + 32) == hipSuccess && hipMalloc(&ev.c_wide, wide.size() * 4 + 4) == hipSuccess;
+  for (ProofSlot &sl : k->slot)
+    ok = ok && hipMalloc(&sl.d_bad, 4) == hipSuccess && hipHostMalloc(&sl.h_bad, 4, hipHostMallocDefault) == hipSuccess;
+  if (!ok) return give_up(true);
+  for (ProofSlot &sl : k->slot) *sl.h_bad = 0;
+  hipError_t e = hipMemcpy(ev.c_rowptr, rowptr.data(), rowptr.size() * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess && !sig.empty()) e = hipMemcpy(ev.c_col, sig.data(), sig.size() * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess && !coef.empty()) e = hipMemcpy(ev.c_coef, coef.data(), coef.size() * 32, hipMemcpyHostToDevice);
+  if (e == hipSuccess && !wide.empty()) e = hipMemcpy(ev.c_wide, wide.data(), wide.size() * 4, hipMemcpyHostToDevice);
+  if (e != hipSuccess) { set_error("upload of the C rows failed: %s", hipGetErrorString(e)); give_up(false); return ZKR_ERR_HIP; }
+  ev.ready = true;
+  return 0;
+}
+
 // vk_bin (zkr_verify layout) from the setup's own data
 static void vk_from_generated(const Generated &g, std::vector<uint8_t> &vk) {
   const size_t nic = g.ic_std.size() / 64;
@@ -444,14 +524,18 @@ static void vk_to_malloc(const Generated &g, void **vk_out, size_t *vk_len) {
   *vk_len = vk.size();
 }
 
-int zkr_setup_r1cs(const void *r1cs_bin, size_t r1cs_len, const uint8_t *toxic160, int device, zkr_key **key_out, void **vk_out, size_t *vk_len) {
+int zkr_setup_r1cs_opts(const void *r1cs_bin, size_t r1cs_len, const uint8_t *toxic160, int device, unsigned flags, zkr_key **key_out, void **vk_out, size_t *vk_len) {
   if (!r1cs_bin || !key_out || !vk_out || !vk_len) { set_error("null argument"); return ZKR_ERR_ARG; }
   Generated g;
   int rc = setup_parse_and_run(r1cs_bin, r1cs_len, toxic160, device, g);
   if (!rc) rc = build_key_from_generated(g, device, key_out);
   if (rc) return rc;
+  if ((rc = key_build_eval_tables(*key_out, g, (flags & ZKR_SETUP_NO_SIDE_TABLES) != 0))) { zkr_key_free(*key_out); *key_out = nullptr; return rc; }
   vk_to_malloc(g, vk_out, vk_len);
   return 0;
+}
+int zkr_setup_r1cs(const void *r1cs_bin, size_t r1cs_len, const uint8_t *toxic160, int device, zkr_key **key_out, void **vk_out, size_t *vk_len) {
+  return zkr_setup_r1cs_opts(r1cs_bin, r1cs_len, toxic160, device, 0, key_out, vk_out, vk_len);
 }
 
 // The same key from a powers-of-tau transcript instead of toxic scalars (zkr_ptau.hip): nobody knows t, alfa, beta; delta = gamma = 1
@@ -537,6 +621,7 @@ int zkr_synth_key(unsigned log_m, unsigned n_public, uint64_t circuit_seed, uint
   if (rc) return rc;
   rc = build_key_from_generated(g, device, key_out);
   if (rc) return rc;
+  if ((rc = key_build_eval_tables(*key_out, g, false))) { zkr_key_free(*key_out); *key_out = nullptr; return rc; }
   const Circuit &c = g.circ;
   uint32_t n = c.n;
   std::vector<uint8_t> wb;

@@ -186,10 +186,31 @@ struct ProofSlot {
   int nbat = 0;   // proofs of the group in flight
   std::vector<uint8_t> rb, sb;  // blinding scalars of the proofs in flight, cap x 32 B each
   bool busy = false, collecting = false;
+  // H in evaluation form (EvalTables): the proof in flight took that path; rows of its witness with a_j b_j != c_j, counted on the
+  // device and copied to the pinned word before the sort of H (so it has landed when the proof's last chain has)
+  bool eval = false;
+  uint32_t *d_bad = nullptr, *h_bad = nullptr;
   std::vector<ProfSpan> spans;
   std::vector<hipEvent_t> event_pool;
   size_t event_next = 0;
 };
+}  // namespace zkr
+
+namespace zkr {
+// Side tables of a key whose builder knew its scalars (workload.hip key_build_eval_tables; eval_h.hpp has the algebra): the H
+// multiexp over E' = -1/2 E with the coset products d_j as scalars, the C multiexp over C' = C + 1/2 C^T F.  Outside the arena: key
+// files, replicas, shards and contributed keys do not carry them and prove through the coefficient form.  Both tables have the
+// plans and the point layout of the tables they stand in for (C': the points of C, or of A's sort when the two share it, infinity
+// where a scalar is zero; E': m points in natural order), so a proof uses the same sorts, bucket sets and chains either way.
+struct EvalTables {
+  bool ready = false;
+  void *c_pts = nullptr, *e_pts = nullptr;
+  uint32_t *c_rowptr = nullptr, *c_col = nullptr, *c_wide = nullptr;  // C by QAP row, as the arena holds A and B, but with
+  Fr *c_coef = nullptr;                                               // STANDARD-form coefficients: the row sums come out as c_j / R
+  uint32_t n_wide = 0, nnz = 0;
+  std::atomic<uint64_t> retries{0};  // proofs proved again through the coefficient form (their witness did not satisfy the R1CS)
+};
+int key_eval_tables_free(zkr_key *k);  // zkr_key.hip
 }  // namespace zkr
 
 struct zkr_key {
@@ -223,6 +244,7 @@ struct zkr_key {
   std::condition_variable slot_freed;
   zkr::MsmPlan plan[zkr::N_TABLES];
   zkr::ProofLayout layout;
+  zkr::EvalTables eval;
   // proof assembly on the host: 4-bit window tables of delta_1 / delta_2 (built on first use)
   zkr::Tw29 *tw29 = nullptr, *twl29 = nullptr;  // butterfly twiddles, derived from the arena's tables when the key is set up (not part of the arena)
   std::once_flag delta_once;

@@ -10,6 +10,7 @@
 #include "kernels_ntt.hpp"
 #include "kernels_group.hpp"  // group_on_curve_launch for ZKR_CHECK_POINTS
 #include "hostops.hpp"
+#include "eval_h.hpp"  // fr_root_of_unity
 #include <map>
 #include "zkr_internal.hpp"
 
@@ -34,24 +35,6 @@ int os_random(void *out, size_t bytes) {
 
 static inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 
-// w_{2^k} in Montgomery form: 5^((r-1)/2^k) (5 = smallest quadratic non-residue mod r)
-static Fr fr_root_of_unity(unsigned k) {
-  Fr five = Fr::zero();
-  five.v[0] = 5;
-  Fr g = to_mont(five);
-  uint32_t e[8];
-  for (int i = 0; i < 8; i++) e[i] = FrParams::P[i];
-  e[0] -= 1;
-  // e >>= 28
-  for (int i = 0; i < 8; i++) e[i] = (e[i] >> 28) | (i < 7 ? e[i + 1] << 4 : 0);
-  Fr r = Fr::one(), b = g;
-  for (int i = 0; i < 256; i++) {
-    if ((e[i >> 5] >> (i & 31)) & 1) r = mul(r, b);
-    b = sqr(b);
-  }
-  for (unsigned j = k; j < 28; j++) r = sqr(r);
-  return r;
-}
 Fr host_root_of_unity(unsigned k) { return fr_root_of_unity(k); }
 
 // The arena's layout: header, twiddles, the two QAP sides (CSR), then per table its K window levels and its rank map.
@@ -300,6 +283,22 @@ int key_alloc_workspace(zkr_key *k) {
     k->delta1_tab = fixed_base_table(load_g1(h.delta1));
     k->delta2_tab = fixed_base_table(load_g2(h.delta2));
   });
+  return 0;
+}
+
+// the side tables of the evaluation form and what the slots hold for them; the key's proofs must have been collected
+int key_eval_tables_free(zkr_key *k) {
+  EvalTables &ev = k->eval;
+  ev.ready = false;
+  hipFree(ev.c_pts); hipFree(ev.e_pts); hipFree(ev.c_rowptr); hipFree(ev.c_col); hipFree(ev.c_coef); hipFree(ev.c_wide);
+  ev.c_pts = ev.e_pts = nullptr;
+  ev.c_rowptr = ev.c_col = ev.c_wide = nullptr;
+  ev.c_coef = nullptr;
+  for (ProofSlot &sl : k->slot) {
+    hipFree(sl.d_bad);
+    if (sl.h_bad) hipHostFree(sl.h_bad);
+    sl.d_bad = sl.h_bad = nullptr;
+  }
   return 0;
 }
 
@@ -674,6 +673,7 @@ void zkr_key_free(zkr_key *k) {
     if (ws.d_w) hipFree(ws.d_w);
     if (ws.ev_up) hipEventDestroy(ws.ev_up);
   }
+  key_eval_tables_free(k);
   hipFree(k->tw29);
   hipFree(k->twl29);
   if (k->owns_arena) hipFree(k->arena);
@@ -685,6 +685,13 @@ int zkr_key_info(const zkr_key *k, uint64_t out[10]) {
   if (!k || !out) { set_error("null argument"); return ZKR_ERR_ARG; }
   out[0] = k->h.n; out[1] = k->h.p; out[2] = k->h.m; out[3] = k->h.nnzA; out[4] = k->h.nnzB;
   for (int t = 0; t < N_TABLES; t++) out[5 + t] = k->h.npts[t];
+  return 0;
+}
+
+int zkr_key_h_form(const zkr_key *k, int *evaluation, uint64_t *retries) {
+  if (!k) { set_error("null argument"); return ZKR_ERR_ARG; }
+  if (evaluation) *evaluation = k->eval.ready ? 1 : 0;
+  if (retries) *retries = k->eval.retries.load();
   return 0;
 }
 

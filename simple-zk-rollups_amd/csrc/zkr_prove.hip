@@ -185,21 +185,27 @@ static Fr fr_from_u64(uint64_t x) {
 
 // QAP rows [lo, hi) of nbat witnesses end to end (sl.d_w -> sl.va, sl.vb): both sides in one launch (blockIdx.z; one launch fewer in
 // the chain, twice the workgroups), then the rows wider than SPMV_WIDE terms
-static void spmv_enqueue(zkr_key *k, ProofSlot &sl, hipStream_t s, uint32_t lo, uint32_t hi, int nbat) {
+// with_c (H in evaluation form): the C side too, into sl.d_h (free until the coset products land there), and the slot's counter of
+// unsatisfied rows cleared for the check that follows
+static void spmv_enqueue(zkr_key *k, ProofSlot &sl, hipStream_t s, uint32_t lo, uint32_t hi, int nbat, bool with_c = false) {
   const Prof pf{k, &sl};
   const ArenaHeader &h = k->h;
   const unsigned char *ar = k->arena;
   const int sp = prof_begin(pf, s, "spmv");
-  SpmvSide side[2];
+  SpmvSide side[3] = {};
   Fr *evals[2] = {sl.va, sl.vb};
   for (int i = 0; i < 2; i++)
     side[i] = SpmvSide{(const uint32_t *)(ar + h.off_rowptr[i]), (const uint32_t *)(ar + h.off_col[i]), (const Fr *)(ar + h.off_coef[i]), evals[i],
                        (const uint32_t *)(ar + h.off_wide[i]), h.n_wide[i]};
+  const EvalTables &ev = k->eval;
+  if (with_c) side[2] = SpmvSide{ev.c_rowptr, ev.c_col, ev.c_coef, sl.d_h, ev.c_wide, ev.n_wide};
+  const unsigned sides = with_c ? 3 : 2;
   const int sa = prof_begin(pf, s, "spmv_a");
-  spmv_kernel<<<dim3((hi - lo + 255) / 256, nbat, 2), 256, 0, s>>>(side[0], side[1], sl.d_w, h.m, h.n, lo, hi);
+  spmv_kernel<<<dim3((hi - lo + 255) / 256, nbat, sides), 256, 0, s>>>(side[0], side[1], side[2], sl.d_w, h.m, h.n, lo, hi, with_c ? sl.d_bad : nullptr);
   prof_end(pf, s, sa);
-  const uint32_t nw = h.n_wide[0] > h.n_wide[1] ? h.n_wide[0] : h.n_wide[1];
-  if (nw) spmv_wide_kernel<<<dim3(nw, nbat, 2), 64, 0, s>>>(side[0], side[1], sl.d_w, h.m, h.n, lo, hi);
+  uint32_t nw = h.n_wide[0] > h.n_wide[1] ? h.n_wide[0] : h.n_wide[1];
+  if (with_c && ev.n_wide > nw) nw = ev.n_wide;
+  if (nw) spmv_wide_kernel<<<dim3(nw, nbat, sides), 64, 0, s>>>(side[0], side[1], side[2], sl.d_w, h.m, h.n, lo, hi);
   prof_end(pf, s, sp);
 }
 
@@ -241,6 +247,31 @@ int calc_h_device(zkr_key *k, ProofSlot &sl, hipStream_t s, int nbat) {
   const int csp = prof_begin(pf, s, "combine_h");
   const uint32_t pos0 = ranged ? h_lo : 0, pos1 = ranged ? h_lo + h_n : m;
   combine_h_kernel<<<dim3((pos1 - pos0 + 255) / 256, nbat), 256, 0, s>>>(sl.va, sl.ca, sl.d_h, tw, tlog, L, c1v, c2v, sl.dig_h.rng, DIGIT_CLEAR_WORDS, pos0, pos1);  // + the counters of h's digit records
+  prof_end(pf, s, csp);
+  prof_end(pf, s, sp);
+  ZKR_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// H in evaluation form (a key with side tables, EvalTables; eval_h.hpp): d_w -> the coset products d_j in sl.d_h, natural order.
+// Four transforms instead of six and no combination: QAP rows of A, B and C in one launch, the count of rows with a_j b_j != c_j
+// into the slot's pinned word (prove_collect reads it with the proof's results), the two coefficient transforms, the two coset
+// transforms (canonical stores on their last pass), one product per row.
+static int calc_h_eval(zkr_key *k, ProofSlot &sl, hipStream_t s) {
+  const Prof pf{k, &sl};
+  const ArenaHeader &h = k->h;
+  const int L = (int)h.logm;
+  const NttTables tb{(const Fr *)(k->arena + h.off_tw), k->tw29, k->twl29, (int)h.tlog};
+  const uint32_t m = h.m;
+  spmv_enqueue(k, sl, s, 0, m, 1, true);
+  eval_unsatisfied_kernel<<<(m + 255) / 256, 256, 0, s>>>(sl.va, sl.vb, sl.d_h, m, sl.d_bad);
+  ZKR_HIP_CHECK(hipMemcpyAsync(sl.h_bad, sl.d_bad, 4, hipMemcpyDeviceToHost, s));
+  const int sp = prof_begin(pf, s, "ntt");
+  int rc;
+  if ((rc = run_ntt(s, sl.va, nullptr, sl.ca, tb, L, true, true, PRE_NONE, 1, pf, sl.vb, nullptr, sl.cb))) return rc;
+  if ((rc = run_ntt(s, sl.ca, nullptr, sl.ca, tb, L, false, false, PRE_COSET, 1, pf, sl.cb, nullptr, sl.cb))) return rc;
+  const int csp = prof_begin(pf, s, "combine_h");  // the stage record keeps its keys: the product stands where the combination stood
+  eval_product_kernel<<<(m + 255) / 256, 256, 0, s>>>(sl.ca, sl.cb, sl.d_h, m, sl.dig_h.rng, DIGIT_CLEAR_WORDS);
   prof_end(pf, s, csp);
   prof_end(pf, s, sp);
   ZKR_HIP_CHECK(hipGetLastError());
@@ -597,7 +628,8 @@ static int take_blinding(const uint8_t *r32, const uint8_t *s32, uint8_t rb[32],
   return 0;
 }
 
-static int prove_submit_enqueue(zkr_key *k, ProofSlot &sl, const Fr *const *d_wsrcs, int nbat, const uint8_t *r32s, const uint8_t *s32s, hipStream_t caller, const hipEvent_t *readies);
+static int prove_submit_enqueue(zkr_key *k, ProofSlot &sl, const Fr *const *d_wsrcs, int nbat, const uint8_t *r32s, const uint8_t *s32s, hipStream_t caller, const hipEvent_t *readies,
+                                bool coefficients = false);
 
 // Enqueue the whole GPU side of one proof on the slot's buffers; returns without waiting.  If the enqueue fails part
 // way, kernels already launched still use the slot's buffers while the slot stays marked free: the key's streams are
@@ -605,8 +637,11 @@ static int prove_submit_enqueue(zkr_key *k, ProofSlot &sl, const Fr *const *d_ws
 // nbat witnesses (1 <= nbat <= sl.cap: a fused batch shares every launch); r32s / s32s: nbat x 32 B or both
 // null (drawn per proof).  readies[j]: the event after which witness j is in place (a staged upload); readies == null:
 // whatever is enqueued on `caller` now.
-static int prove_submit_group(zkr_key *k, ProofSlot &sl, const Fr *const *d_wsrcs, int nbat, const uint8_t *r32s, const uint8_t *s32s, hipStream_t caller, const hipEvent_t *readies = nullptr) {
-  int rc = prove_submit_enqueue(k, sl, d_wsrcs, nbat, r32s, s32s, caller, readies);
+// coefficients: H in coefficient form even if the key has the side tables of the evaluation form (prove_collect's second run of a
+// witness that does not satisfy the R1CS)
+static int prove_submit_group(zkr_key *k, ProofSlot &sl, const Fr *const *d_wsrcs, int nbat, const uint8_t *r32s, const uint8_t *s32s, hipStream_t caller, const hipEvent_t *readies = nullptr,
+                              bool coefficients = false) {
+  int rc = prove_submit_enqueue(k, sl, d_wsrcs, nbat, r32s, s32s, caller, readies, coefficients);
   if (rc && rc != ZKR_ERR_ARG) {  // ZKR_ERR_ARG: refused before the first launch
     key_streams_sync(k);
     sl.spans.clear();
@@ -615,7 +650,8 @@ static int prove_submit_group(zkr_key *k, ProofSlot &sl, const Fr *const *d_wsrc
   return rc;
 }
 
-static int prove_submit_enqueue(zkr_key *k, ProofSlot &sl, const Fr *const *d_wsrcs, int nbat, const uint8_t *r32s, const uint8_t *s32s, hipStream_t caller, const hipEvent_t *readies) {
+static int prove_submit_enqueue(zkr_key *k, ProofSlot &sl, const Fr *const *d_wsrcs, int nbat, const uint8_t *r32s, const uint8_t *s32s, hipStream_t caller, const hipEvent_t *readies,
+                                bool coefficients) {
   ZKR_HIP_CHECK(hipSetDevice(k->device));
   const ArenaHeader &h = k->h;
   const ProofLayout &lay = k->layout;
@@ -663,6 +699,19 @@ static int prove_submit_enqueue(zkr_key *k, ProofSlot &sl, const Fr *const *d_ws
   for (int j = 0; j < nbat; j++)  // the last one also clears the counters of w's digit records (msm_digits_enqueue below)
     ingest_kernel<<<(h.n + 255) / 256, 256, 0, sp>>>(d_wsrcs[j], sl.d_w + (size_t)j * h.n, h.n, j == nbat - 1 ? sl.dig_w.rng : nullptr, j == nbat - 1 ? DIGIT_CLEAR_WORDS : 0u);
   prof_end(pf, sp, spn);
+  // part of a sharded proof whose calcH is split over the shards (calc_h_split: host barriers in the middle of this enqueue): the
+  // chains of the four w tables are handed over BEFORE it, so that they run while the threads wait for one another.  Everywhere
+  // else the accumulations are handed over after the whole preparation chain: started early they fill the chip's wavefront slots
+  // and the preparation stream -- whose end, the sort of H, the last accumulation waits for -- waits for its dispatches
+  // (HISTORY.md 7b / 13: a tx proof 2.13-2.40 against 1.98 ms, 2^20 the same).
+  ShardGroup *const group = shard_group;
+  const bool split_h = group && group->split_h && !serial && nbat == 1 && h.shard_parts == group->parts && h.shard_part == shard_group_part;
+  // H in evaluation form: a whole-key proof of its own launches on a key that has the side tables.  Fused batches, shards and the
+  // split calcH keep the coefficient form.  C and H then gather from C' and E', which have the layouts and plans of the tables
+  // they stand in for (EvalTables): the sorts, bucket sets and chains below do not change.
+  const bool eval = k->eval.ready && !coefficients && nbat == 1 && h.shard_parts == 1 && !split_h;
+  sl.eval = eval;
+  auto table_points = [&](int t) -> const void * { return eval && t == T_C ? k->eval.c_pts : eval && t == T_H ? k->eval.e_pts : ar + h.off_pts[t]; };
   const DigitLists *dig[N_TABLES] = {&sl.dig_w, &sl.dig_w, &sl.dig_w, &sl.dig_w, &sl.dig_h};
   const int *sort_src = lay.sort_src;
   // A shard key's proof is as long as its replicated calcH plus what follows it (digits and sort of h, H's accumulation, the
@@ -676,7 +725,7 @@ static int prove_submit_enqueue(zkr_key *k, ProofSlot &sl, const Fr *const *d_ws
   }
   auto sort_table = [&](int t) -> int {  // a table that owns its sort; an empty one has none
     if (!h.npts[t]) return 0;
-    const uint32_t *rank = h.rank_identity[t] ? nullptr : (const uint32_t *)(ar + h.off_rank[t]);
+    const uint32_t *rank = h.rank_identity[t] || (eval && t == T_H) ? nullptr : (const uint32_t *)(ar + h.off_rank[t]);  // E' is in the order of its scalars
     hipStream_t st = t == T_H ? sp : sw;
     int rc = msm_sort_enqueue(pf, st, rank, *dig[t], rank_entries(h, t), h.npts[t], nbat, k->plan[t], sl.sort[t]);
     if (rc) return rc;
@@ -684,13 +733,6 @@ static int prove_submit_enqueue(zkr_key *k, ProofSlot &sl, const Fr *const *d_ws
     return 0;
   };
   for (int c = 0; c < N_TABLES; c++) sl.res_pending[c] = false;
-  // part of a sharded proof whose calcH is split over the shards (calc_h_split: host barriers in the middle of this enqueue): the
-  // chains of the four w tables are handed over BEFORE it, so that they run while the threads wait for one another.  Everywhere
-  // else the accumulations are handed over after the whole preparation chain: started early they fill the chip's wavefront slots
-  // and the preparation stream -- whose end, the sort of H, the last accumulation waits for -- waits for its dispatches
-  // (HISTORY.md 7b / 13: a tx proof 2.13-2.40 against 1.98 ms, 2^20 the same).
-  ShardGroup *const group = shard_group;
-  const bool split_h = group && group->split_h && !serial && nbat == 1 && h.shard_parts == group->parts && h.shard_part == shard_group_part;
   // C's oversized-bucket sums on the auxiliary stream for ONE proof of a key that can fuse batches (the latency case; c_big below)
   const bool c_big_first = lay.flags[T_C] == ACC_ZERO_BIG && !serial && nbat == 1 && sl.cap > 1;
   // nothing else of this key in flight (the caller holds the key's lock: with_free_slot): this proof's last chain is latency
@@ -710,7 +752,7 @@ static int prove_submit_enqueue(zkr_key *k, ProofSlot &sl, const Fr *const *d_ws
     const MsmChain &ch = sl.chain[lay.chain[t]];
     const hipStream_t rs = cl.g2 ? s_g2 : s_g1;
     const size_t set_bytes = (size_t)nbat * k->plan[cl.geom].nb * (cl.g2 ? sizeof(G2XYZZ) : sizeof(G1XYZZ));  // one set of the chain, the fused proofs end to end
-    const void *pts = ar + h.off_pts[t];
+    const void *pts = table_points(t);
     ZKR_HIP_CHECK(hipStreamWaitEvent(rs, sl.ev_sorted[sort_src[t]], 0));
     if (!big_sent[t]) {  // partial sums into the table's OWN partials buffer
       if ((rc = msm_big_enqueue(pf, rs, cl.g2, pts, sl.sort[sort_src[t]], sl.big_partials[t]))) return rc;
@@ -750,7 +792,7 @@ static int prove_submit_enqueue(zkr_key *k, ProofSlot &sl, const Fr *const *d_ws
   auto c_big = [&]() -> int {
     if (!c_big_first) return 0;
     ZKR_HIP_CHECK(hipStreamWaitEvent(aux, sl.ev_sorted[sort_src[T_C]], 0));
-    int rc = msm_big_enqueue(pf, aux, false, ar + h.off_pts[T_C], sl.sort[sort_src[T_C]], sl.big_partials[T_C]);
+    int rc = msm_big_enqueue(pf, aux, false, table_points(T_C), sl.sort[sort_src[T_C]], sl.big_partials[T_C]);
     if (rc) return rc;
     ZKR_HIP_CHECK(hipEventRecord(sl.ev_h, aux));
     big_sent[T_C] = true;
@@ -766,6 +808,7 @@ static int prove_submit_enqueue(zkr_key *k, ProofSlot &sl, const Fr *const *d_ws
   if (!lay.share_ac && (rc = sort_table(T_C))) return rc;
   if (early && ((rc = c_big()) || (rc = chains({T_A, T_C})))) return rc;
   if (split_h) rc = calc_h_split(k, sl, sp, *group, shard_group_part, enqueue_lock);
+  else if (eval) rc = calc_h_eval(k, sl, sp);
   else rc = calc_h_device(k, sl, sp, nbat);
   if (rc) return rc;
   if ((rc = msm_digits_enqueue(pf, sp, sl.d_h + h.sc_lo[1], h.sc_n[1], nbat, k->plan[T_H], sl.dig_h, true))) return rc;
@@ -860,9 +903,10 @@ static int prove_collect(zkr_key *k, ProofSlot &sl, uint8_t *proofs_out, Partial
     return lay.own_result(t) ? ((const G1XYZZ *)sl.chain[lay.chain[t]].h_result)[lay.set[t] * sl.nbat + j] : G1XYZZ::inf();
   };
   int rcw;
-  if ((rcw = wait_table(T_A)) || (rcw = wait_table(T_B1)) || (rcw = wait_table(T_B2))) return rcw;
   std::vector<G1XYZZ> pic_part((size_t)sl.nbat);
   int status = 0;
+again:
+  if ((rcw = wait_table(T_A)) || (rcw = wait_table(T_B1)) || (rcw = wait_table(T_B2))) return rcw;
   for (int j = 0; j < sl.nbat; j++) {
     G1XYZZ A = g1_result(T_A, j), B1 = g1_result(T_B1, j);
     G2XYZZ B2 = lay.own_result(T_B2) ? ((const G2XYZZ *)sl.chain[lay.chain[T_B2]].h_result)[j] : G2XYZZ::inf();
@@ -873,6 +917,25 @@ static int prove_collect(zkr_key *k, ProofSlot &sl, uint8_t *proofs_out, Partial
   if ((rcw = wait_table(T_C)) || (rcw = wait_table(T_H))) return rcw;
   for (hipEvent_t e : sl.ev_end) ZKR_HIP_CHECK(hipEventSynchronize(e));  // every stream of the slot is idle (all of it precedes the table events)
   if (k->prof_on) { std::lock_guard<std::mutex> lk(k->mu); prof_collect(k, sl); }
+  // H in evaluation form stands on a o b = C w (eval_h.hpp).  The count of rows where it fails was copied out in front of the sort
+  // of H, so it has landed with the chains.  A witness that leaves rows unsatisfied is proved AGAIN through the coefficient form,
+  // which is exact for every witness, in this slot (its ingested witness and blinding are still here) and in this proof's place in
+  // the caller's order; what the other slot has in flight is not touched.
+  if (sl.eval && *sl.h_bad) {
+    k->eval.retries.fetch_add(1);
+    uint8_t rb[32], sb[32];
+    memcpy(rb, sl.rb.data(), 32); memcpy(sb, sl.sb.data(), 32);
+    const Fr *w = sl.d_w;
+    int rc;
+    {
+      std::lock_guard<std::mutex> lk(k->mu);
+      rc = prove_submit_group(k, sl, &w, 1, rb, sb, k->prep_stream, nullptr, true);
+    }
+    explicit_bzero(rb, 32); explicit_bzero(sb, 32);
+    if (rc) return rc;
+    status = 0;
+    goto again;
+  }
   for (int j = 0; j < sl.nbat && !status; j++) {
     G1XYZZ C = g1_result(T_C, j), H = g1_result(T_H, j);
     if (partials_out) { partials_out[j].CH = add_full(C, H); continue; }

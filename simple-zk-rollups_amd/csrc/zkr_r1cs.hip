@@ -377,9 +377,9 @@ int zkr_r1cs_matches_key(zkr_r1cs *cs, const zkr_key *key, int *same) {
   for (int i = 0; i < 2; i++)
     side[i] = SpmvSide{(const uint32_t *)(ar + h.off_rowptr[i]), (const uint32_t *)(ar + h.off_col[i]), (const Fr *)(ar + h.off_coef[i]), eval[i],
                        (const uint32_t *)(ar + h.off_wide[i]), h.n_wide[i]};
-  spmv_kernel<<<dim3((m + 255) / 256, 1, 2), 256, 0, st>>>(side[0], side[1], v, m, n, 0, m);
+  spmv_kernel<<<dim3((m + 255) / 256, 1, 2), 256, 0, st>>>(side[0], side[1], SpmvSide{}, v, m, n, 0, m, nullptr);
   const uint32_t nw = h.n_wide[0] > h.n_wide[1] ? h.n_wide[0] : h.n_wide[1];
-  if (nw) spmv_wide_kernel<<<dim3(nw, 1, 2), 64, 0, st>>>(side[0], side[1], v, m, n, 0, m);
+  if (nw) spmv_wide_kernel<<<dim3(nw, 1, 2), 64, 0, st>>>(side[0], side[1], SpmvSide{}, v, m, n, 0, m);
   const unsigned long long none[4] = {0, NONE64, 0, NONE64};
   unsigned long long res[4];
   ZKR_HIP_CHECK(hipMemcpyAsync(d_rep.p, none, sizeof(none), hipMemcpyHostToDevice, st));

@@ -102,6 +102,8 @@ def lib():
                                      c.POINTER(vp), c.POINTER(sz)]
     L.zkr_synth_witness.argtypes = [c.c_uint, c.c_uint, c.c_uint64, c.c_uint64, c.POINTER(vp), c.POINTER(sz)]
     L.zkr_setup_r1cs.argtypes = [u8p, sz, u8p, i, c.POINTER(vp), c.POINTER(vp), c.POINTER(sz)]
+    L.zkr_setup_r1cs_opts.argtypes = [u8p, sz, u8p, i, c.c_uint, c.POINTER(vp), c.POINTER(vp), c.POINTER(sz)]
+    L.zkr_key_h_form.argtypes = [vp, c.POINTER(i), c.POINTER(c.c_uint64)]
     L.zkr_setup_r1cs_websnark.argtypes = [u8p, sz, u8p, i, c.POINTER(vp), c.POINTER(sz), c.POINTER(vp), c.POINTER(sz)]
     L.zkr_synth_vk.argtypes = [vp, u8p, sz, c.POINTER(vp), c.POINTER(sz)]
     L.zkr_synth_set_shape.argtypes = [c.c_uint]
@@ -195,12 +197,16 @@ class ProvingKey:
         return cls(h, device)
 
     @classmethod
-    def setup_r1cs(cls, r1cs_bin: bytes, toxic=None, device=0):
+    def setup_r1cs(cls, r1cs_bin: bytes, toxic=None, device=0, side_tables=True):
         """Groth16 setup of an R1CS on the GPU (zkr_setup_r1cs; `snarkjs setup --protocol groth`).  toxic: None (OS
-        CSPRNG) or five ints (t, alfa, beta, gamma, delta) for reproducible tests.  Returns (key, vk_bin)."""
+        CSPRNG) or five ints (t, alfa, beta, gamma, delta) for reproducible tests.  side_tables=False refuses the allocation of
+        the evaluation-form side tables (zkr_setup_r1cs_opts: a test hook for the fall-back).  Returns (key, vk_bin)."""
         tb = None if toxic is None else b"".join(int(x).to_bytes(32, "little") for x in toxic)
         h, vk, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_size_t()
-        _check(lib().zkr_setup_r1cs(bytes(r1cs_bin), len(r1cs_bin), tb, device, ctypes.byref(h), ctypes.byref(vk), ctypes.byref(n)))
+        if side_tables:
+            _check(lib().zkr_setup_r1cs(bytes(r1cs_bin), len(r1cs_bin), tb, device, ctypes.byref(h), ctypes.byref(vk), ctypes.byref(n)))
+        else:
+            _check(lib().zkr_setup_r1cs_opts(bytes(r1cs_bin), len(r1cs_bin), tb, device, 1, ctypes.byref(h), ctypes.byref(vk), ctypes.byref(n)))
         try:
             return cls(h, device), ctypes.string_at(vk, n.value)
         finally:
@@ -325,6 +331,14 @@ class ProvingKey:
         _check(lib().zkr_key_info(self._h, out))
         names = ("nVars", "nPublic", "domainSize", "nnzA", "nnzB", "ptsA", "ptsB1", "ptsB2", "ptsC", "ptsH")
         return dict(zip(names, [int(x) for x in out]))
+
+    def h_form(self):
+        """How this key's own proofs form the H term -- not part of info(), which describes the arena and is equal for a key and
+        its replicas, while the side tables of the evaluation form stay with the key that was built with them.  {'form': 'evaluation' | 'coefficients', 'retries': proofs proved again through the coefficient form because their
+        witness left constraints unsatisfied} (zkr_key_h_form)."""
+        ev, n = ctypes.c_int(), ctypes.c_uint64()
+        _check(lib().zkr_key_h_form(self._h, ctypes.byref(ev), ctypes.byref(n)))
+        return {"form": "evaluation" if ev.value else "coefficients", "retries": int(n.value)}
 
     def arena(self):
         p, n = ctypes.c_void_p(), ctypes.c_size_t()
