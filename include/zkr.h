@@ -298,13 +298,40 @@ int zkr_setup_r1cs(const void *r1cs_bin, size_t r1cs_len, const uint8_t *toxic16
  * is the same bytes for every witness.  The tables cost about as much device memory as C and H themselves (2 x 0.87 GB at 2^20);
  * when they cannot be allocated, or a signal of C' has no point in the layout C shares, the key simply keeps the coefficient
  * form (ZKR_H_FORM=coefficients asks for that).  They are not part of the arena: key files, replicas, shards, contributed keys
- * (zkr_key_contribute changes C and H), websnark-loaded and transcript keys prove through the coefficient form.
+ * (zkr_key_contribute changes C and H), websnark-loaded and transcript keys come without them and prove through the coefficient
+ * form until zkr_key_eval_tables (below) derives the tables from the key's own points.
  * zkr_key_h_form: *evaluation = 1 when the key has the tables; *retries = proofs of this key proved again so far (either may be NULL).
  * zkr_setup_r1cs_opts: zkr_setup_r1cs with flags; ZKR_SETUP_NO_SIDE_TABLES refuses the side tables' allocation (a test hook for
  * the fall-back). */
 #define ZKR_SETUP_NO_SIDE_TABLES 1u
 int zkr_setup_r1cs_opts(const void *r1cs_bin, size_t r1cs_len, const uint8_t *toxic160, int device, unsigned flags, zkr_key **key_out, void **vk_out, size_t *vk_len);
 int zkr_key_h_form(const zkr_key *key, int *evaluation, uint64_t *retries);
+/* The same side tables for ANY whole key -- loaded from websnark bytes or a file, made from a transcript, replicated, contributed to --
+ * from the key's own points and the circuit's C side; no scalar of the setup is needed.  Both tables are linear images of points the
+ * key holds: E'_j = ke 1/m sum_i (g w^j)^(-i) H_i (ke = -1/2 R / m^2) is the H points scaled one by one and taken through one inverse
+ * NTT over points; C'_s = C_s + 1/2 sum_j C_js F_j, F_j = 1/m sum_i w^(-ij) H_i, is a second such transform, one sparse combination
+ * over the columns of C and one addition per signal.  All on the key's device, once per key (the cost is that of two G1 transforms
+ * over the domain).  The tables are the bytes of the ones zkr_setup_r1cs builds for the same key.
+ * r1cs_bin: the layout of zkr_setup_r1cs; it is parsed before any device call.  ZKR_ERR_ARG: a null pointer, flags other than 0, a
+ * malformed system, a shard key, a system whose nVars, nPublic or domain differ from the key's, a key with a proof in flight (a slot
+ * submitted and not collected).  *built = 1: the key has the tables, and zkr_key_h_form reports evaluation from then on.
+ * ZKR_OK with *built = 0 and a one-line reason in zkr_last_error where the setup's builder gives up as well: ZKR_H_FORM=coefficients,
+ * an H table that dropped a point, a signal with a finite C' point and no slot among the points C's accumulation reads, no memory
+ * for the tables.  A status below zero otherwise only for a failed kernel or copy.  A key that has tables drops them first.
+ * WHICH C matrix: the identity the tables rest on holds for any matrix M with M w = a o b, and every evaluation-form proof checks
+ * exactly that of its witness.  A wrong or stale C side therefore gives no wrong proof: it makes every proof take the retry path
+ * (slower; `retries` of zkr_key_h_form counts them).  Nothing binds r1cs_bin to the key beyond its geometry.
+ * Loading, saving, replicating, sharding and contributing carry no tables, as before: derive again on the key such a step returns.
+ * zkr_key_eval_tables_drop: back to the coefficient form; frees the tables (ZKR_ERR_ARG with a proof in flight).
+ * zkr_key_eval_tables_equal (test hook): *same = 1 iff both keys, on one device, have tables and their C' and E' tables at every window
+ * level and their C rows are equal byte for byte.
+ * zkr_points_add_each (stage hook, as zkr_points_scale_each below): points[i] <- points[i] + addends[i], n points in host memory,
+ * Montgomery affine (64 B G1 / 128 B G2; x == 0 encodes infinity, which either side, or both, may be; equal and opposite points are
+ * handled); an infinite sum is written as all zeros. */
+int zkr_key_eval_tables(zkr_key *key, const void *r1cs_bin, size_t r1cs_len, unsigned flags, int *built);
+int zkr_key_eval_tables_drop(zkr_key *key);
+int zkr_key_eval_tables_equal(const zkr_key *a, const zkr_key *b, int *same);
+int zkr_points_add_each(void *points_mont, const void *addends_mont, size_t n, int g2, int device);
 /* The same setup, delivering the proving key as the bytes `binarifyProvingKey(provingKey)` produces from snarkjs' JSON key
  * (binarify.ts:143-206; malloc'ed, free with zkr_free; at most 4 GiB, the format's u32 offsets) instead of a device key:
  * the provingKeyBin an UNCHANGED reference caller passes to groth16GenProof on every call (common.ts:28-29). */

@@ -1,7 +1,8 @@
 // kernels_group.hpp -- arithmetic on VECTORS OF GROUP ELEMENTS, which the proving path never needs (its points are fixed, its
 // scalars vary) and a powers-of-tau transcript is made of: every point multiplied by a scalar of its own, and the radix-2 NTT
 // whose coefficients are points (the Lagrange-basis form of tau^i G).  The delta contribution's kernel (every point times ONE
-// scalar, zkr_contribute.hip) and the curve-equation check of the key loader are here too: one home for them all.  Templated over the coordinate families of curve29.hpp
+// scalar, zkr_contribute.hip), the curve-equation check of the key loader and the slot-by-slot addition of the side tables a key
+// derives from its own points (zkr_eval_tables.hip) are here too: one home for them all.  Templated over the coordinate families of curve29.hpp
 // (G1C over Fq, G2C over Fq2); the group law is the hot path's (XYZZ accumulator, dbl_xyzz29, add_mixed29).
 //
 // Points are affine in the key's boundary radix (x 2^256; x == 0 = infinity) in memory, in and out, as zkr_msm_g1 / g2 take them.
@@ -272,6 +273,45 @@ static __global__ __launch_bounds__(GROUP_THREADS) void group_diff_kernel(Affine
   auto prod = C::one().template to<4>();
   group_store_unnormalised<C>(out, ztmp, n, i, add_mixed29<C>(make_xyzz<C>(qa.x, qa.y, C::one(), C::one()), qb, true), prod);
   group_normalise_own<C>(out, ztmp, n, i, 0, 1, prod);
+}
+
+// out[o] = a[o] + b[i], o = dst[i] (dst null: o = i), for EVERY input: either side at infinity (under a shared support the `a`
+// side is, for public signals and placeholders), both, P + P and P + (-P) (add_affine_affine29 has the last two).  An entry whose
+// slot is outside the n_out points of `out` (RANK_NONE: the layout has no point for it) is skipped, and tallied in `bad` when its
+// addend is finite.  The slots of a launch are distinct; out may be a.  ztmp: 2 n_out coordinates.
+template <class C>
+static __global__ __launch_bounds__(GROUP_THREADS) void group_add_each_kernel(Affine<typename C::W> *out, const Affine<typename C::W> *a, const Affine<typename C::W> *b, uint32_t n,
+                                                                               const uint32_t *dst, uint32_t n_out, typename C::W *ztmp, uint32_t *bad) {
+  const uint32_t i = blockIdx.x * GROUP_THREADS + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t o = dst ? dst[i] : i;
+  const Affine<typename C::W> pb = load_pod(b + i);
+  if (o >= n_out) {
+    if (!pb.is_inf()) group_note_bad(bad, i);
+    return;
+  }
+  const Affine<typename C::W> pa = load_pod(a + o);
+  XYZZ29<C> acc = XYZZ29<C>::inf();
+  if (pa.is_inf() || pb.is_inf()) {
+    if (!pa.is_inf() || !pb.is_inf()) {
+      const Affine29<C> q = group_affine_in<C>(pa.is_inf() ? pb : pa);
+      acc = make_xyzz<C>(q.x, q.y, C::one(), C::one());
+    }
+  } else {
+    acc = add_affine_affine29<C>(group_affine_in<C>(pa), false, group_affine_in<C>(pb), false);
+  }
+  auto prod = C::one().template to<4>();
+  group_store_unnormalised<C>(out, ztmp, n_out, o, acc, prod);
+  group_normalise_own<C>(out, ztmp, n_out, o, 0, 1, prod);
+}
+
+// Infinity as the fixed-base setup writes it (the websnark wire form: x = 0, y = one) where the kernels above leave all zeros, so
+// that a table derived from points is the bytes of the table made from scalars.
+template <class W>
+static __global__ void group_inf_wire_kernel(Affine<W> *pts, uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  if (load_pod(&pts[i].x).is_zero()) store_pod(&pts[i].y, W::one());
 }
 
 // Montgomery -> standard form, in place (the ladders read plain bits)

@@ -401,27 +401,39 @@ static int key_build_eval_tables(zkr_key *k, const Generated &g, bool refuse) {
   if (rc) { give_up(false); return rc; }
   if ((rc = table(sec.es.eprime, k->plan[T_H], &ev.e_pts)) > 0) return give_up(true);
   if (rc) { give_up(false); return rc; }
-  // C by row over the whole domain (rows from nConstraints on are empty), STANDARD-form coefficients: with the standard-form
-  // witness the row sums come out as c_j / R, which is what one product of a_j and b_j leaves (kernels_ntt.hpp eval_unsatisfied_kernel)
+  if ((rc = key_eval_rows(k, c)) > 0) return give_up(true);
+  if (rc) { give_up(false); return rc; }
+  ev.ready = true;
+  return 0;
+}
+
+// What a key's side tables need beside their points, whoever made those (above; zkr_eval_tables.hip): C by row over the whole
+// domain (rows from nConstraints on are empty), STANDARD-form coefficients -- with the standard-form witness the row sums come out
+// as c_j / R, which is what one product of a_j and b_j leaves (kernels_ntt.hpp eval_unsatisfied_kernel) -- and a counter per
+// proof slot.  Above zero: an allocation failed (the caller gives the tables up); below: a failed copy.
+int key_eval_rows(zkr_key *k, const Circuit &c) {
+  const uint32_t m = k->h.m;
+  EvalTables &ev = k->eval;
+  std::vector<uint32_t> sig(c.tC.size());
+  std::vector<Fr> coef(c.tC.size());
+  for (size_t i = 0; i < c.tC.size(); i++) { sig[i] = c.tC[i].sig; coef[i] = from_mont(c.tC[i].coef); }
   std::vector<uint32_t> rowptr(m + 1), wide;
   for (uint32_t r = 0; r <= m; r++) rowptr[r] = c.rowC[r < c.nC ? r : c.nC];
   for (uint32_t r = 0; r < c.nC; r++)
     if (rowptr[r + 1] - rowptr[r] > 8) wide.push_back(r);  // kernels_ntt.hpp SPMV_WIDE
-  for (Fr &x : coef) x = from_mont(x);
   ev.nnz = (uint32_t)sig.size();
   ev.n_wide = (uint32_t)wide.size();
   bool ok = hipMalloc(&ev.c_rowptr, rowptr.size() * 4) == hipSuccess && hipMalloc(&ev.c_col, sig.size() * 4 + 4) == hipSuccess &&
             hipMalloc(&ev.c_coef, coef.size() * 32 + 32) == hipSuccess && hipMalloc(&ev.c_wide, wide.size() * 4 + 4) == hipSuccess;
   for (ProofSlot &sl : k->slot)
     ok = ok && hipMalloc(&sl.d_bad, 4) == hipSuccess && hipHostMalloc(&sl.h_bad, 4, hipHostMallocDefault) == hipSuccess;
-  if (!ok) return give_up(true);
+  if (!ok) return 1;
   for (ProofSlot &sl : k->slot) *sl.h_bad = 0;
   hipError_t e = hipMemcpy(ev.c_rowptr, rowptr.data(), rowptr.size() * 4, hipMemcpyHostToDevice);
   if (e == hipSuccess && !sig.empty()) e = hipMemcpy(ev.c_col, sig.data(), sig.size() * 4, hipMemcpyHostToDevice);
   if (e == hipSuccess && !coef.empty()) e = hipMemcpy(ev.c_coef, coef.data(), coef.size() * 32, hipMemcpyHostToDevice);
   if (e == hipSuccess && !wide.empty()) e = hipMemcpy(ev.c_wide, wide.data(), wide.size() * 4, hipMemcpyHostToDevice);
-  if (e != hipSuccess) { set_error("upload of the C rows failed: %s", hipGetErrorString(e)); give_up(false); return ZKR_ERR_HIP; }
-  ev.ready = true;
+  if (e != hipSuccess) { set_error("upload of the C rows failed: %s", hipGetErrorString(e)); return ZKR_ERR_HIP; }
   return 0;
 }
 
@@ -475,6 +487,30 @@ int parse_r1cs(const void *r1cs_bin, size_t r1cs_len, Circuit &c) {
   }
   if (b != end) { set_error("R1CS has %zu trailing bytes", (size_t)(end - b)); return ZKR_ERR_ARG; }
   return 0;
+}
+
+// One side of the QAP (0 = A with its input-consistency rows, 1 = B, 2 = C) by signal, constraint index ascending, coefficients in
+// standard form
+void qap_columns(const Circuit &c, int side, QapColumns &q) {
+  const uint32_t n = c.n, p = c.p;
+  const std::vector<uint32_t> &rp = side == 0 ? c.rowA : side == 1 ? c.rowB : c.rowC;
+  const std::vector<Term> &tt = side == 0 ? c.tA : side == 1 ? c.tB : c.tC;
+  q.colptr.assign(n + 1, 0);
+  for (const Term &t : tt) q.colptr[t.sig + 1]++;
+  if (side == 0) for (uint32_t i = 0; i <= p; i++) q.colptr[i + 1]++;
+  for (uint32_t s = 0; s < n; s++) q.colptr[s + 1] += q.colptr[s];
+  q.row.resize(q.colptr[n]);
+  q.coef.resize((size_t)q.colptr[n] * 32);
+  std::vector<uint32_t> fill(q.colptr.begin(), q.colptr.end() - 1);
+  auto put = [&](uint32_t sig, uint32_t row, const Fr &coef_mont) {
+    const uint32_t e = fill[sig]++;
+    const Fr std_form = from_mont(coef_mont);
+    q.row[e] = row;
+    memcpy(&q.coef[(size_t)e * 32], std_form.v, 32);
+  };
+  for (uint32_t r = 0; r < c.nC; r++)
+    for (uint32_t e = rp[r]; e < rp[r + 1]; e++) put(tt[e].sig, r, tt[e].coef);
+  if (side == 0) for (uint32_t i = 0; i <= p; i++) put(i, c.nC + i, Fr::one());
 }
 
 }  // namespace zkr
@@ -546,29 +582,8 @@ int zkr_setup_r1cs_ptau(const void *r1cs_bin, size_t r1cs_len, const void *ptau,
   int rc = parse_r1cs(r1cs_bin, r1cs_len, c);
   if (rc) return rc;
   const uint32_t n = c.n, p = c.p, m = c.m;
-  // the QAP by signal, constraint index ascending (A with its input-consistency rows), coefficients in standard form
   QapColumns cols[3];
-  const std::vector<uint32_t> *rp[3] = {&c.rowA, &c.rowB, &c.rowC};
-  const std::vector<Term> *tt[3] = {&c.tA, &c.tB, &c.tC};
-  for (int k = 0; k < 3; k++) {
-    QapColumns &q = cols[k];
-    q.colptr.assign(n + 1, 0);
-    for (const Term &t : *tt[k]) q.colptr[t.sig + 1]++;
-    if (k == 0) for (uint32_t i = 0; i <= p; i++) q.colptr[i + 1]++;
-    for (uint32_t s = 0; s < n; s++) q.colptr[s + 1] += q.colptr[s];
-    q.row.resize(q.colptr[n]);
-    q.coef.resize((size_t)q.colptr[n] * 32);
-    std::vector<uint32_t> fill(q.colptr.begin(), q.colptr.end() - 1);
-    auto put = [&](uint32_t sig, uint32_t row, const Fr &coef_mont) {
-      const uint32_t e = fill[sig]++;
-      const Fr std_form = from_mont(coef_mont);
-      q.row[e] = row;
-      memcpy(&q.coef[(size_t)e * 32], std_form.v, 32);
-    };
-    for (uint32_t r = 0; r < c.nC; r++)
-      for (uint32_t e = (*rp[k])[r]; e < (*rp[k])[r + 1]; e++) put((*tt[k])[e].sig, r, (*tt[k])[e].coef);
-    if (k == 0) for (uint32_t i = 0; i <= p; i++) put(i, c.nC + i, Fr::one());
-  }
+  for (int k = 0; k < 3; k++) qap_columns(c, k, cols[k]);
   if ((rc = ptau_key_tables(ptau, ptau_len, device, m, n, cols, g.d_tbl, g.consts))) return rc;
   // a table entry is dropped exactly when its point is infinity; the IC points for the verifying key
   KeptPoints keep;

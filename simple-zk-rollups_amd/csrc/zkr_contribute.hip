@@ -123,6 +123,14 @@ int scale_table(G1Affine *pts, uint32_t n, const uint32_t *d_naf, int top, Fq *z
 }
 
 }  // namespace
+
+// two device buffers of `bytes` (a multiple of 16) hold the same bytes: the compare kernel over one range (zkr_internal.hpp)
+int device_bytes_equal(int device, const void *a, const void *b, size_t bytes, bool *same) {
+  uint32_t first = 0;
+  if (int rc = compare_ranges(device, (const unsigned char *)a, (const unsigned char *)b, {CmpRange{0, 0, bytes / 16, 0, 0}}, &first)) return rc;
+  *same = first == 0xffffffffu;
+  return 0;
+}
 }  // namespace zkr
 
 using namespace zkr;

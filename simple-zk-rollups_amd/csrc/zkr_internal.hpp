@@ -197,9 +197,11 @@ struct ProofSlot {
 }  // namespace zkr
 
 namespace zkr {
-// Side tables of a key whose builder knew its scalars (workload.hip key_build_eval_tables; eval_h.hpp has the algebra): the H
+// Side tables of the evaluation form (eval_h.hpp has the algebra), made from the scalars by a builder that knew them (workload.hip
+// key_build_eval_tables) or from the key's own points for any whole key (zkr_eval_tables.hip zkr_key_eval_tables): the H
 // multiexp over E' = -1/2 E with the coset products d_j as scalars, the C multiexp over C' = C + 1/2 C^T F.  Outside the arena: key
-// files, replicas, shards and contributed keys do not carry them and prove through the coefficient form.  Both tables have the
+// files, replicas, shards and contributed keys do not carry them and prove through the coefficient form until they are derived
+// again.  Both tables have the
 // plans and the point layout of the tables they stand in for (C': the points of C, or of A's sort when the two share it, infinity
 // where a scalar is zero; E': m points in natural order), so a proof uses the same sorts, bucket sets and chains either way.
 struct EvalTables {
@@ -311,6 +313,12 @@ struct QapColumns {
 // (ZKR_ERR_BAD_KEY).  d_tbl (device, Montgomery affine, infinity where a signal's polynomial vanishes; the caller hipFree's them):
 // [T_A], [T_B1], [T_B2]: n points; [T_C]: the n points K[s] = beta A_s + alfa B_s + C_s (IC for s <= nPublic, C above); [T_H]: m
 int ptau_key_tables(const void *ptau, size_t len, int device, uint32_t m, uint32_t n, const QapColumns cols[3], void *d_tbl[N_TABLES], uint8_t consts448[448]);
+// zkr_ptau.hip: its launches over vectors of G1 points, for the side tables derived from a key's own points (zkr_eval_tables.hip).
+// On the current device and its null stream; points Montgomery affine x 2^256, x == 0 = infinity; ztmp: 2 n coordinates.
+int g1_scale_each(G1Affine *pts, size_t n, const Fr *d_scalars, uint32_t sc_stride, void *ztmp);  // pts[i] <- s[i] pts[i]; scalars standard form, one per point (stride 1) or one for all (0)
+int g1_group_ntt(G1Affine *pts, G1Affine *tmp, unsigned logn, bool inverse, Fr *tw, void *ztmp);  // natural order in and out, the inverse with 1 / n; tmp: n points, tw: n / 2 + 1 scalars
+// *out (a fresh allocation the caller hipFree's): point s < n = sum over column s of coefficient x pts[row]; partial sums lie behind
+int g1_combine_columns(uint32_t n, const QapColumns &cols, const G1Affine *pts, void **out);
 // workload.hip: a rank-1 constraint system as the setups and zkr_r1cs.hip take it, rows in CSR
 struct Term { uint32_t sig; Fr coef; };  // coef Montgomery
 struct Circuit {
@@ -320,6 +328,9 @@ struct Circuit {
   std::vector<Fr> w;  // Montgomery
 };
 int parse_r1cs(const void *r1cs_bin, size_t r1cs_len, Circuit &c);  // r1cs_bin (include/zkr.h) -> the circuit, with its domain; host only; ZKR_ERR_ARG with a message
+int device_bytes_equal(int device, const void *a, const void *b, size_t bytes, bool *same);  // zkr_contribute.hip: its compare kernel over one range; bytes a multiple of 16
+void qap_columns(const Circuit &c, int side, QapColumns &q);  // one side of the QAP (0 = A with its input-consistency rows, 1 = B, 2 = C) by signal
+int key_eval_rows(zkr_key *k, const Circuit &c);  // C by row and the slots' counters of a key's side tables; above zero: an allocation failed
 int digit_lists_alloc(DigitLists &dl, size_t n_scalars, const MsmPlan &pl);
 void digit_lists_free(DigitLists &dl);
 int msm_scratch_alloc(MsmScratch &m, size_t n_scalars, size_t n_points, const MsmPlan &pl, bool g2);  // for one proof of one table

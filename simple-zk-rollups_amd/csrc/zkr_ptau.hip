@@ -641,6 +641,22 @@ int ptau_key_tables(const void *ptau, size_t len, int device, uint32_t m, uint32
   return 0;
 }
 
+// the same launches for the side tables a key derives from its own points (zkr_internal.hpp)
+int g1_scale_each(G1Affine *pts, size_t n, const Fr *d_scalars, uint32_t sc_stride, void *ztmp) { return scale_each_launch<G1C>(pts, n, d_scalars, sc_stride, ztmp); }
+int g1_group_ntt(G1Affine *pts, G1Affine *tmp, unsigned logn, bool inverse, Fr *tw, void *ztmp) { return group_ntt_launch<G1C>(pts, tmp, logn, inverse, tw, ztmp); }
+int g1_combine_columns(uint32_t n, const QapColumns &cols, const G1Affine *pts, void **out) {
+  CombinePlan pl;
+  const QapColumns *src[1] = {&cols};
+  const uint32_t zero[1] = {0};
+  combine_plan(n, src, zero, 1, pl);
+  DeviceCombinePlan dp;
+  DevBuf ztmp;
+  int rc;
+  if ((rc = dp.upload(pl)) || (rc = ztmp.alloc(2 * pl.n_out * sizeof(Fq))) || (rc = combine_run<G1C>(dp, pts, ztmp.p, out))) return rc;
+  if ((rc = sync_or_fail("combining the points"))) { hipFree(*out); *out = nullptr; }
+  return rc;
+}
+
 }  // namespace zkr
 
 using namespace zkr;

@@ -26,6 +26,9 @@ export interface Bn128 {
   /** A further party's contribution to the held key's delta (zkr_key_contribute): the object's key becomes the contributed one;
    *  returns the 352-byte record.  opts.d: the secret (1 < d < r) for reproducible tests; by default drawn inside the library. */
   contribute(opts?: { d?: bigint | string }): { record: Uint8Array };
+  /** Evaluation-form side tables for the held key from its own points and the circuit's C side (zkr_key_eval_tables): true when
+   *  its proofs run four transforms instead of six from now on.  contribute, saveKey / loadKeyFile and replicas carry no tables. */
+  evalTables(r1csBin: Uint8Array): boolean;
   saveKey(path: string): void;
   loadKeyFile(path: string): void;
   /** What the held key's arena contains (zkr_key_check): every index the kernels follow stays inside its section; with
@@ -93,6 +96,8 @@ export function keyCacheStats(): { loads: number; hits: number; replications: nu
 export interface ShardedForm { form: "none" | "split" | "replicated"; reason: string }
 export function shardedLastForm(): ShardedForm;
 /** How a native key handle came to its device: loaded there ("none") or copied device to device (zkr_key_replicate) in the full or the compact form. */
+/** zkr_key_eval_tables for a key handle: true when the key proves through the evaluation form from now on. */
+export function keyEvalTables(key: unknown, r1csBin: Uint8Array): boolean;
 export function keyReplication(key: unknown): { mode: "none" | "full" | "base"; peerDirect: boolean };
 export function keyFingerprint(provingKeyBin: ArrayBuffer | Uint8Array, full?: boolean): string;
 export function clearKeyCache(): void;

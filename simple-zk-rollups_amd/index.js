@@ -280,6 +280,10 @@ class Bn128 {
     this._key = key; this._fp = "contributed"; this._replicas = null;
     return { record: new Uint8Array(record) };
   }
+  // The evaluation-form side tables for the held key, whatever it came from, derived from its own points and the circuit's C side
+  // (zkr_key_eval_tables; r1csBin: binarifyR1cs(circuitDef) or RollupCircuit.r1cs()).  true: its proofs run four transforms instead
+  // of six from now on; false: it keeps the coefficient form.  contribute, saveKey / loadKeyFile and replicas carry no tables: call again.
+  evalTables(r1csBin) { if (!this._key) throw new Error("no key loaded"); return native().keyEvalTables(this._key, r1csBin); }
   saveKey(path) { if (!this._key) throw new Error("no key loaded"); native().keySave(this._key, path); }
   loadKeyFile(path) { this._key = native().keyLoadFile(path, this.device); this._fp = "file:" + path; }
   // what the held key's arena contains (zkr_key_check): the structure, and with { deep: true } the values as well (every point of
@@ -538,6 +542,8 @@ module.exports = {
   binarifyR1cs, verifyingKeyFromBytes, solidityVerifyingKey, solidityVerifyingKeySource,
   // which form the last sharded proof took and why ({form: "split" | "replicated" | "none", reason}); how a key handle came to its device
   shardedLastForm: () => native().shardedLastForm(), keyReplication: (key) => native().keyReplication(key),
+  // the same for a key handle: true when the key proves through the evaluation form from now on (zkr_key_eval_tables)
+  keyEvalTables: (key, r1csBin) => native().keyEvalTables(key, r1csBin),
   keyCacheStats: () => Object.assign({ shardedLastForm: addon ? native().shardedLastForm() : { form: "none", reason: "" } }, { entries: keyCache.size, handles: Array.from(keyCache.values()).reduce((a, e) => a + Array.from(e.entries()).reduce((b, [k, v]) => b + (k === "ref" || k === "src" ? 0 : Array.isArray(v) ? v.length : 1), 0), 0) }, keyCacheStats), clearKeyCache, keyFingerprint,
   _cacheEntry: cacheEntry,  // the cache's lookup alone (no device involved): tests/test_node_host.py
   multiHash, multiHashBatch, buildBalanceTree, hashLeftRight, genPublicKey, formatPrivKeyForBabyJub, sign, verify, RollupCircuit, WithdrawCircuit,

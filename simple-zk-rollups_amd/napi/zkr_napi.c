@@ -52,6 +52,7 @@ static struct {
   int (*key_contribute)(const zkr_key *, const uint8_t *, zkr_key **, uint8_t *);
   int (*contribution_check)(const uint8_t *, int *);
   int (*vk_contribute)(const void *, size_t, const uint8_t *, void **, size_t *);
+  int (*key_eval_tables)(zkr_key *, const void *, size_t, unsigned, int *); /* optional: NULL with a library older than the call */
 } Z;
 /* which form the last sharded proof took (zkr_prove_sharded_last_form, read on the worker thread that ran it, published on the JS
  * thread when its promise settles) */
@@ -99,6 +100,7 @@ static napi_value js_load(napi_env env, napi_callback_info info) {
     SYM(rollup_info, "zkr_rollup_info") SYM(rollup_r1cs, "zkr_rollup_r1cs") SYM(rollup_witness, "zkr_rollup_witness")
     SYM(sharded_last_form, "zkr_prove_sharded_last_form") SYM(key_replication, "zkr_key_replication")
     SYM(key_contribute, "zkr_key_contribute") SYM(contribution_check, "zkr_contribution_check") SYM(vk_contribute, "zkr_vk_contribute")
+    *(void **)(&Z.key_eval_tables) = dlsym(h, "zkr_key_eval_tables"); /* looked up optionally: an older library still loads */
     Z.handle = h;
   }
   napi_value out;
@@ -291,6 +293,25 @@ static napi_value js_vk_contribute(napi_env env, napi_callback_info info) {
   void *copy;
   NAPI_OK(napi_create_buffer_copy(env, out_len, out_vk, &copy, &out));
   Z.free_(out_vk);
+  return out;
+}
+
+/* keyEvalTables(key, r1csBin) -> boolean: the evaluation-form side tables from the key's own points and the circuit's C side
+ * (zkr_key_eval_tables; synchronous, once per key).  false: the key keeps the coefficient form. */
+static napi_value js_key_eval_tables(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (!Z.handle) return throw_msg(env, "libzkr_hip.so not loaded");
+  if (!Z.key_eval_tables) return throw_msg(env, "this libzkr_hip.so has no zkr_key_eval_tables");
+  zkr_key *key = NULL;
+  const uint8_t *r1cs;
+  size_t len;
+  if (argc < 2 || napi_get_value_external(env, argv[0], (void **)&key) != napi_ok || !get_bytes(env, argv[1], &r1cs, &len)) return throw_msg(env, "keyEvalTables(key, r1csBin)");
+  int built = 0;
+  if (Z.key_eval_tables(key, r1cs, len, 0, &built)) return throw_msg(env, Z.last_error());
+  napi_value out;
+  NAPI_OK(napi_get_boolean(env, built != 0, &out));
   return out;
 }
 
@@ -843,6 +864,7 @@ static napi_value init(napi_env env, napi_value exports) {
       {"keyContribute", NULL, js_key_contribute, NULL, NULL, NULL, napi_default, NULL},
       {"contributionCheck", NULL, js_contribution_check, NULL, NULL, NULL, napi_default, NULL},
       {"vkContribute", NULL, js_vk_contribute, NULL, NULL, NULL, napi_default, NULL},
+      {"keyEvalTables", NULL, js_key_eval_tables, NULL, NULL, NULL, napi_default, NULL},
   };
   napi_define_properties(env, exports, sizeof(props) / sizeof(props[0]), props);
   return exports;

@@ -104,6 +104,10 @@ def lib():
     L.zkr_setup_r1cs.argtypes = [u8p, sz, u8p, i, c.POINTER(vp), c.POINTER(vp), c.POINTER(sz)]
     L.zkr_setup_r1cs_opts.argtypes = [u8p, sz, u8p, i, c.c_uint, c.POINTER(vp), c.POINTER(vp), c.POINTER(sz)]
     L.zkr_key_h_form.argtypes = [vp, c.POINTER(i), c.POINTER(c.c_uint64)]
+    L.zkr_key_eval_tables.argtypes = [vp, u8p, sz, c.c_uint, c.POINTER(i)]
+    L.zkr_key_eval_tables_drop.argtypes = [vp]
+    L.zkr_key_eval_tables_equal.argtypes = [vp, vp, c.POINTER(i)]
+    L.zkr_points_add_each.argtypes = [u8p, u8p, sz, i, i]
     L.zkr_setup_r1cs_websnark.argtypes = [u8p, sz, u8p, i, c.POINTER(vp), c.POINTER(sz), c.POINTER(vp), c.POINTER(sz)]
     L.zkr_synth_vk.argtypes = [vp, u8p, sz, c.POINTER(vp), c.POINTER(sz)]
     L.zkr_synth_set_shape.argtypes = [c.c_uint]
@@ -339,6 +343,25 @@ class ProvingKey:
         ev, n = ctypes.c_int(), ctypes.c_uint64()
         _check(lib().zkr_key_h_form(self._h, ctypes.byref(ev), ctypes.byref(n)))
         return {"form": "evaluation" if ev.value else "coefficients", "retries": int(n.value)}
+
+    def eval_tables(self, r1cs_bin: bytes) -> bool:
+        """The side tables of the evaluation form from this key's own points and the circuit's C side (zkr_key_eval_tables): any
+        whole key -- websnark bytes, a file, a transcript, a replica, a contributed key.  True: h_form() says 'evaluation' from
+        now on.  False: the key keeps the coefficient form and zkr_hip.lib().zkr_last_error() says why.  Saving, replicating,
+        sharding and contributing carry no tables: derive again on the key they return."""
+        built = ctypes.c_int(0)
+        _check(lib().zkr_key_eval_tables(self._h, bytes(r1cs_bin), len(r1cs_bin), 0, ctypes.byref(built)))
+        return bool(built.value)
+
+    def drop_eval_tables(self):
+        """Back to the coefficient form; frees the side tables (zkr_key_eval_tables_drop)."""
+        _check(lib().zkr_key_eval_tables_drop(self._h))
+
+    def eval_tables_equal(self, other) -> bool:
+        """Both keys have side tables and they are equal byte for byte (zkr_key_eval_tables_equal, a test hook)."""
+        same = ctypes.c_int(0)
+        _check(lib().zkr_key_eval_tables_equal(self._h, other._h, ctypes.byref(same)))
+        return bool(same.value)
 
     def arena(self):
         p, n = ctypes.c_void_p(), ctypes.c_size_t()
@@ -696,6 +719,17 @@ def points_scale_each(points: bytes, scalars: bytes, g2=False, device=0) -> byte
         raise ValueError("points/scalars length mismatch")
     buf = ctypes.create_string_buffer(bytes(points), len(points))
     _check(lib().zkr_points_scale_each(ctypes.cast(buf, ctypes.c_char_p), bytes(scalars), n, 1 if g2 else 0, device))
+    return buf.raw
+
+
+def points_add_each(points: bytes, addends: bytes, g2=False, device=0) -> bytes:
+    """zkr_points_add_each: points[i] <- points[i] + addends[i] (Montgomery affine points; x == 0 is infinity, on either side)."""
+    pb = 128 if g2 else 64
+    n = len(points) // pb
+    if len(points) != n * pb or len(addends) != len(points):
+        raise ValueError("points/addends length mismatch")
+    buf = ctypes.create_string_buffer(bytes(points), len(points))
+    _check(lib().zkr_points_add_each(ctypes.cast(buf, ctypes.c_char_p), bytes(addends), n, 1 if g2 else 0, device))
     return buf.raw
 
 
