@@ -162,7 +162,9 @@ int zkr_prove_batch(zkr_key *key, const void *const *witnesses_std, size_t witne
  * the chip (the reference's tx circuit, 2^17 constraints) runs every kernel over up to zkr_key_fuse(key) witnesses at once
  * (vectors end to end, one bucket set per proof and table), so a launch carries about the work of one 2^20 proof and the
  * fixed latency tail of the bucket reduction is paid once per group; two groups are in flight.  Proofs are the same bytes as
- * from zkr_prove_device. */
+ * from zkr_prove_device.  A key with the side tables of the evaluation form (zkr_key_h_form below) runs every group through the
+ * four-transform form; a group in which a witness leaves constraints unsatisfied is proved again, whole, through the coefficient
+ * form, in its slot and in its proofs' places in the caller's order. */
 int zkr_prove_batch_device(zkr_key *key, const void *const *d_witnesses_std, size_t count, const uint8_t *r32s, const uint8_t *s32s, void *stream,
                            uint8_t *proofs_out);
 /* A batch over SEVERAL GPUs of the node from one process (BASELINE config 4: 64 independent proofs, 8 per GPU): keys[j] are
@@ -292,15 +294,18 @@ int zkr_setup_r1cs(const void *r1cs_bin, size_t r1cs_len, const uint8_t *toxic16
 /* H in evaluation form.  A builder that knows the key's scalars (zkr_setup_r1cs with toxic scalars or its own, zkr_synth_key) also
  * builds two side tables beside the arena, with the window plans of C and H: C' = C + 1/2 C^T F over all nVars signals and
  * E' = -1/2 E over the domain, the H table moved to the evaluations on the coset by two transforms of its scalars.  A whole-key proof
- * of its own launches then runs four transforms instead of six: the H multiexp takes the coset products A(g w^j) B(g w^j) as they
+ * -- of its own launches, or in a fused group of the batch calls -- then runs four transforms instead of six: the H multiexp takes the coset products A(g w^j) B(g w^j) as they
  * are, the C multiexp takes the witness over C'.  That rests on a o b = C w, so every such proof also counts the rows where it
- * fails, and a witness with such rows is proved again through the coefficient form, in its place in the caller's order: the proof
- * is the same bytes for every witness.  The tables cost about as much device memory as C and H themselves (2 x 0.87 GB at 2^20);
+ * fails (one count per proof of a fused group), and a witness with such rows is proved again through the coefficient form, in its
+ * place in the caller's order -- with the rest of its group, when it came in one: the proof is the same bytes for every witness.
+ * Shards, the split calcH of a sharded proof and the stage hooks (zkr_calc_h) keep the coefficient form.  The tables cost about as much device memory as C and H themselves (2 x 0.87 GB at 2^20);
  * when they cannot be allocated, or a signal of C' has no point in the layout C shares, the key simply keeps the coefficient
  * form (ZKR_H_FORM=coefficients asks for that).  They are not part of the arena: key files, replicas, shards, contributed keys
  * (zkr_key_contribute changes C and H), websnark-loaded and transcript keys come without them and prove through the coefficient
  * form until zkr_key_eval_tables (below) derives the tables from the key's own points.
- * zkr_key_h_form: *evaluation = 1 when the key has the tables; *retries = proofs of this key proved again so far (either may be NULL).
+ * zkr_key_h_form: *evaluation = 1 when the key has the tables; *retries = witnesses of this key that left rows unsatisfied and were
+ * proved again so far -- the witnesses that failed, not the proofs of their groups that went again with them, so the count does not
+ * depend on how a batch was cut into groups (either may be NULL).
  * zkr_setup_r1cs_opts: zkr_setup_r1cs with flags; ZKR_SETUP_NO_SIDE_TABLES refuses the side tables' allocation (a test hook for
  * the fall-back). */
 #define ZKR_SETUP_NO_SIDE_TABLES 1u
@@ -320,7 +325,7 @@ int zkr_key_h_form(const zkr_key *key, int *evaluation, uint64_t *retries);
  * for the tables.  A status below zero otherwise only for a failed kernel or copy.  A key that has tables drops them first.
  * WHICH C matrix: the identity the tables rest on holds for any matrix M with M w = a o b, and every evaluation-form proof checks
  * exactly that of its witness.  A wrong or stale C side therefore gives no wrong proof: it makes every proof take the retry path
- * (slower; `retries` of zkr_key_h_form counts them).  Nothing binds r1cs_bin to the key beyond its geometry.
+ * (slower; `retries` of zkr_key_h_form counts them), alone or as fused groups.  Nothing binds r1cs_bin to the key beyond its geometry.
  * Loading, saving, replicating, sharding and contributing carry no tables, as before: derive again on the key such a step returns.
  * zkr_key_eval_tables_drop: back to the coefficient form; frees the tables (ZKR_ERR_ARG with a proof in flight).
  * zkr_key_eval_tables_equal (test hook): *same = 1 iff both keys, on one device, have tables and their C' and E' tables at every window

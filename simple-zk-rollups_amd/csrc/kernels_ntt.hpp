@@ -345,10 +345,12 @@ constexpr uint32_t SPMV_WIDE = 8;
 // with H in evaluation form (gridDim.z = 3; everybody else passes an empty third side and gridDim.z = 2)
 struct SpmvSide { const uint32_t *row_ptr, *col; const Fr *coef; Fr *out; const uint32_t *wide; uint32_t n_wide; };
 // row0 / row1: the rows wanted (a shard of a split calcH evaluates its block of the domain; otherwise 0 and m)
-// zero: one word a LATER kernel of the stream counts into (eval_unsatisfied_kernel), cleared here; null: none
+// zero: gridDim.y words, one per witness of the batch, that a LATER kernel of the stream counts into (eval_unsatisfied_kernel),
+// cleared here by ONE workgroup; null: none
 static __global__ void spmv_kernel(SpmvSide sa, SpmvSide sb, SpmvSide sc, const Fr *w, uint32_t m, uint32_t n, uint32_t row0, uint32_t row1, uint32_t *zero) {
   const SpmvSide &sd = blockIdx.z == 0 ? sa : blockIdx.z == 1 ? sb : sc;
-  if (zero && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) *zero = 0;
+  if (zero && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0)
+    for (uint32_t k = threadIdx.x; k < gridDim.y; k += blockDim.x) zero[k] = 0;
   const uint32_t *row_ptr = sd.row_ptr, *col = sd.col;
   const Fr *coef = sd.coef;
   Fr *out = sd.out;
@@ -416,18 +418,22 @@ static __global__ void combine_h_kernel(const Fr *S, const Fr *D, Fr *h, const F
 // Rows with a_j b_j != c_j: the identity behind the folded C table needs a o b = C w on the whole domain.  a, b: the QAP row sums
 // in standard form; c_over_r: C's row sums made with standard-form coefficients, i.e. c_j / R -- what one product of a_j and b_j
 // leaves.  All three canonical.  A satisfying witness adds nothing, so the good path has no atomic at all.
+// blockIdx.y: proof of a fused batch -- its vectors at stride m, its own word of `bad` (the host learns WHICH witnesses failed)
 static __global__ void eval_unsatisfied_kernel(const Fr *a, const Fr *b, const Fr *c_over_r, uint32_t m, uint32_t *bad) {
   uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= m) return;
-  if (!(mul(load_fr(a + j), load_fr(b + j)) == load_fr(c_over_r + j))) atomicAdd(bad, 1u);
+  const size_t i = (size_t)blockIdx.y * m + j;
+  if (!(mul(load_fr(a + i), load_fr(b + i)) == load_fr(c_over_r + i))) atomicAdd(bad + blockIdx.y, 1u);
 }
 // d_j = ao_j bo_j / R from the canonical coset evaluations: the scalars of the E' table (whose points carry R / m^2 and the rest)
+// blockIdx.y: proof of a fused batch, vectors at stride m
 static __global__ void eval_product_kernel(const Fr *ao, const Fr *bo, Fr *d, uint32_t m, uint32_t *zero, uint32_t zero_words) {
-  if (blockIdx.x == 0)  // see ingest_kernel: the counters of h's digit records
+  if (blockIdx.x == 0 && blockIdx.y == 0)  // see ingest_kernel: the counters of h's digit records, once per launch
     for (uint32_t k = threadIdx.x; k < zero_words; k += blockDim.x) zero[k] = 0;
   uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= m) return;
-  store_fr(d + j, mul(load_fr(ao + j), load_fr(bo + j)));
+  const size_t i = (size_t)blockIdx.y * m + j;
+  store_fr(d + i, mul(load_fr(ao + i), load_fr(bo + i)));
 }
 
 // out[i] = in[bitrev(i)]  (test hooks only)

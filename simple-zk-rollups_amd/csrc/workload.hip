@@ -409,8 +409,8 @@ static int key_build_eval_tables(zkr_key *k, const Generated &g, bool refuse) {
 
 // What a key's side tables need beside their points, whoever made those (above; zkr_eval_tables.hip): C by row over the whole
 // domain (rows from nConstraints on are empty), STANDARD-form coefficients -- with the standard-form witness the row sums come out
-// as c_j / R, which is what one product of a_j and b_j leaves (kernels_ntt.hpp eval_unsatisfied_kernel) -- and a counter per
-// proof slot.  Above zero: an allocation failed (the caller gives the tables up); below: a failed copy.
+// as c_j / R, which is what one product of a_j and b_j leaves (kernels_ntt.hpp eval_unsatisfied_kernel) -- and, per proof
+// slot, a counter for each proof of a fused group (the slot's capacity).  Above zero: an allocation failed (the caller gives the tables up); below: a failed copy.
 int key_eval_rows(zkr_key *k, const Circuit &c) {
   const uint32_t m = k->h.m;
   EvalTables &ev = k->eval;
@@ -426,9 +426,9 @@ int key_eval_rows(zkr_key *k, const Circuit &c) {
   bool ok = hipMalloc(&ev.c_rowptr, rowptr.size() * 4) == hipSuccess && hipMalloc(&ev.c_col, sig.size() * 4 + 4) == hipSuccess &&
             hipMalloc(&ev.c_coef, coef.size() * 32 + 32) == hipSuccess && hipMalloc(&ev.c_wide, wide.size() * 4 + 4) == hipSuccess;
   for (ProofSlot &sl : k->slot)
-    ok = ok && hipMalloc(&sl.d_bad, 4) == hipSuccess && hipHostMalloc(&sl.h_bad, 4, hipHostMallocDefault) == hipSuccess;
+    ok = ok && hipMalloc(&sl.d_bad, (size_t)sl.cap * 4) == hipSuccess && hipHostMalloc(&sl.h_bad, (size_t)sl.cap * 4, hipHostMallocDefault) == hipSuccess;
   if (!ok) return 1;
-  for (ProofSlot &sl : k->slot) *sl.h_bad = 0;
+  for (ProofSlot &sl : k->slot) memset(sl.h_bad, 0, (size_t)sl.cap * 4);
   hipError_t e = hipMemcpy(ev.c_rowptr, rowptr.data(), rowptr.size() * 4, hipMemcpyHostToDevice);
   if (e == hipSuccess && !sig.empty()) e = hipMemcpy(ev.c_col, sig.data(), sig.size() * 4, hipMemcpyHostToDevice);
   if (e == hipSuccess && !coef.empty()) e = hipMemcpy(ev.c_coef, coef.data(), coef.size() * 32, hipMemcpyHostToDevice);

@@ -185,8 +185,8 @@ static Fr fr_from_u64(uint64_t x) {
 
 // QAP rows [lo, hi) of nbat witnesses end to end (sl.d_w -> sl.va, sl.vb): both sides in one launch (blockIdx.z; one launch fewer in
 // the chain, twice the workgroups), then the rows wider than SPMV_WIDE terms
-// with_c (H in evaluation form): the C side too, into sl.d_h (free until the coset products land there), and the slot's counter of
-// unsatisfied rows cleared for the check that follows
+// with_c (H in evaluation form): the C side too -- witness j's row sums into sl.d_h + j m, free until the coset products land there --
+// and the slot's nbat counters of unsatisfied rows cleared for the check that follows
 static void spmv_enqueue(zkr_key *k, ProofSlot &sl, hipStream_t s, uint32_t lo, uint32_t hi, int nbat, bool with_c = false) {
   const Prof pf{k, &sl};
   const ArenaHeader &h = k->h;
@@ -255,23 +255,24 @@ int calc_h_device(zkr_key *k, ProofSlot &sl, hipStream_t s, int nbat) {
 
 // H in evaluation form (a key with side tables, EvalTables; eval_h.hpp): d_w -> the coset products d_j in sl.d_h, natural order.
 // Four transforms instead of six and no combination: QAP rows of A, B and C in one launch, the count of rows with a_j b_j != c_j
-// into the slot's pinned word (prove_collect reads it with the proof's results), the two coefficient transforms, the two coset
-// transforms (canonical stores on their last pass), one product per row.
-static int calc_h_eval(zkr_key *k, ProofSlot &sl, hipStream_t s) {
+// into the slot's pinned words (prove_collect reads them with the proofs' results), the two coefficient transforms, the two coset
+// transforms (canonical stores on their last pass), one product per row.  nbat witnesses end to end (a fused group) share every
+// launch: vectors at stride m, one counter word per witness, ONE copy of the nbat words.
+static int calc_h_eval(zkr_key *k, ProofSlot &sl, hipStream_t s, int nbat) {
   const Prof pf{k, &sl};
   const ArenaHeader &h = k->h;
   const int L = (int)h.logm;
   const NttTables tb{(const Fr *)(k->arena + h.off_tw), k->tw29, k->twl29, (int)h.tlog};
   const uint32_t m = h.m;
-  spmv_enqueue(k, sl, s, 0, m, 1, true);
-  eval_unsatisfied_kernel<<<(m + 255) / 256, 256, 0, s>>>(sl.va, sl.vb, sl.d_h, m, sl.d_bad);
-  ZKR_HIP_CHECK(hipMemcpyAsync(sl.h_bad, sl.d_bad, 4, hipMemcpyDeviceToHost, s));
+  spmv_enqueue(k, sl, s, 0, m, nbat, true);
+  eval_unsatisfied_kernel<<<dim3((m + 255) / 256, nbat), 256, 0, s>>>(sl.va, sl.vb, sl.d_h, m, sl.d_bad);
+  ZKR_HIP_CHECK(hipMemcpyAsync(sl.h_bad, sl.d_bad, (size_t)nbat * 4, hipMemcpyDeviceToHost, s));
   const int sp = prof_begin(pf, s, "ntt");
   int rc;
-  if ((rc = run_ntt(s, sl.va, nullptr, sl.ca, tb, L, true, true, PRE_NONE, 1, pf, sl.vb, nullptr, sl.cb))) return rc;
-  if ((rc = run_ntt(s, sl.ca, nullptr, sl.ca, tb, L, false, false, PRE_COSET, 1, pf, sl.cb, nullptr, sl.cb))) return rc;
+  if ((rc = run_ntt(s, sl.va, nullptr, sl.ca, tb, L, true, true, PRE_NONE, nbat, pf, sl.vb, nullptr, sl.cb))) return rc;
+  if ((rc = run_ntt(s, sl.ca, nullptr, sl.ca, tb, L, false, false, PRE_COSET, nbat, pf, sl.cb, nullptr, sl.cb))) return rc;
   const int csp = prof_begin(pf, s, "combine_h");  // the stage record keeps its keys: the product stands where the combination stood
-  eval_product_kernel<<<(m + 255) / 256, 256, 0, s>>>(sl.ca, sl.cb, sl.d_h, m, sl.dig_h.rng, DIGIT_CLEAR_WORDS);
+  eval_product_kernel<<<dim3((m + 255) / 256, nbat), 256, 0, s>>>(sl.ca, sl.cb, sl.d_h, m, sl.dig_h.rng, DIGIT_CLEAR_WORDS);
   prof_end(pf, s, csp);
   prof_end(pf, s, sp);
   ZKR_HIP_CHECK(hipGetLastError());
@@ -638,7 +639,7 @@ static int prove_submit_enqueue(zkr_key *k, ProofSlot &sl, const Fr *const *d_ws
 // null (drawn per proof).  readies[j]: the event after which witness j is in place (a staged upload); readies == null:
 // whatever is enqueued on `caller` now.
 // coefficients: H in coefficient form even if the key has the side tables of the evaluation form (prove_collect's second run of a
-// witness that does not satisfy the R1CS)
+// group with a witness that does not satisfy the R1CS)
 static int prove_submit_group(zkr_key *k, ProofSlot &sl, const Fr *const *d_wsrcs, int nbat, const uint8_t *r32s, const uint8_t *s32s, hipStream_t caller, const hipEvent_t *readies = nullptr,
                               bool coefficients = false) {
   int rc = prove_submit_enqueue(k, sl, d_wsrcs, nbat, r32s, s32s, caller, readies, coefficients);
@@ -706,10 +707,10 @@ static int prove_submit_enqueue(zkr_key *k, ProofSlot &sl, const Fr *const *d_ws
   // (HISTORY.md 7b / 13: a tx proof 2.13-2.40 against 1.98 ms, 2^20 the same).
   ShardGroup *const group = shard_group;
   const bool split_h = group && group->split_h && !serial && nbat == 1 && h.shard_parts == group->parts && h.shard_part == shard_group_part;
-  // H in evaluation form: a whole-key proof of its own launches on a key that has the side tables.  Fused batches, shards and the
-  // split calcH keep the coefficient form.  C and H then gather from C' and E', which have the layouts and plans of the tables
-  // they stand in for (EvalTables): the sorts, bucket sets and chains below do not change.
-  const bool eval = k->eval.ready && !coefficients && nbat == 1 && h.shard_parts == 1 && !split_h;
+  // H in evaluation form: a whole-key proof, alone or in a fused group, on a key that has the side tables.  Shards and the split
+  // calcH keep the coefficient form.  C and H then gather from C' and E', which have the layouts and plans of the tables they
+  // stand in for (EvalTables): the sorts, bucket sets (one per proof and table) and chains below do not change.
+  const bool eval = k->eval.ready && !coefficients && h.shard_parts == 1 && !split_h;
   sl.eval = eval;
   auto table_points = [&](int t) -> const void * { return eval && t == T_C ? k->eval.c_pts : eval && t == T_H ? k->eval.e_pts : ar + h.off_pts[t]; };
   const DigitLists *dig[N_TABLES] = {&sl.dig_w, &sl.dig_w, &sl.dig_w, &sl.dig_w, &sl.dig_h};
@@ -808,7 +809,7 @@ static int prove_submit_enqueue(zkr_key *k, ProofSlot &sl, const Fr *const *d_ws
   if (!lay.share_ac && (rc = sort_table(T_C))) return rc;
   if (early && ((rc = c_big()) || (rc = chains({T_A, T_C})))) return rc;
   if (split_h) rc = calc_h_split(k, sl, sp, *group, shard_group_part, enqueue_lock);
-  else if (eval) rc = calc_h_eval(k, sl, sp);
+  else if (eval) rc = calc_h_eval(k, sl, sp, nbat);
   else rc = calc_h_device(k, sl, sp, nbat);
   if (rc) return rc;
   if ((rc = msm_digits_enqueue(pf, sp, sl.d_h + h.sc_lo[1], h.sc_n[1], nbat, k->plan[T_H], sl.dig_h, true))) return rc;
@@ -917,21 +918,30 @@ again:
   if ((rcw = wait_table(T_C)) || (rcw = wait_table(T_H))) return rcw;
   for (hipEvent_t e : sl.ev_end) ZKR_HIP_CHECK(hipEventSynchronize(e));  // every stream of the slot is idle (all of it precedes the table events)
   if (k->prof_on) { std::lock_guard<std::mutex> lk(k->mu); prof_collect(k, sl); }
-  // H in evaluation form stands on a o b = C w (eval_h.hpp).  The count of rows where it fails was copied out in front of the sort
-  // of H, so it has landed with the chains.  A witness that leaves rows unsatisfied is proved AGAIN through the coefficient form,
-  // which is exact for every witness, in this slot (its ingested witness and blinding are still here) and in this proof's place in
-  // the caller's order; what the other slot has in flight is not touched.
-  if (sl.eval && *sl.h_bad) {
-    k->eval.retries.fetch_add(1);
-    uint8_t rb[32], sb[32];
-    memcpy(rb, sl.rb.data(), 32); memcpy(sb, sl.sb.data(), 32);
-    const Fr *w = sl.d_w;
+  // H in evaluation form stands on a o b = C w (eval_h.hpp).  The counts of rows where it fails, one per witness of the group, were
+  // copied out in front of the sort of H, so they have landed with the chains.  A group with a witness that leaves rows unsatisfied
+  // is proved AGAIN through the coefficient form, which is exact for every witness, in this slot (its ingested witnesses, sl.d_w +
+  // j n, and blinding pairs are still here) and in its proofs' places in the caller's order; what the other slot has in flight is not
+  // touched.  The WHOLE group goes again, not the failing witnesses compacted into a smaller one: a resubmit overwrites the chains'
+  // pinned result buffers, so the good proofs' sums would have to be set aside first, and an unsatisfying witness is the rare case.
+  // `retries` counts the witnesses that failed -- what it means for lone proofs, whatever the groups a batch was cut into.
+  int n_bad = 0;
+  if (sl.eval)
+    for (int j = 0; j < sl.nbat; j++) n_bad += sl.h_bad[j] != 0;
+  if (n_bad) {
+    k->eval.retries.fetch_add((uint64_t)n_bad);
+    const int nbat = sl.nbat;
+    const size_t bl = (size_t)nbat * 32;
+    uint8_t rb[32 * MAX_FUSE], sb[32 * MAX_FUSE];
+    memcpy(rb, sl.rb.data(), bl); memcpy(sb, sl.sb.data(), bl);
+    const Fr *w[MAX_FUSE];
+    for (int j = 0; j < nbat; j++) w[j] = sl.d_w + (size_t)j * k->h.n;
     int rc;
     {
       std::lock_guard<std::mutex> lk(k->mu);
-      rc = prove_submit_group(k, sl, &w, 1, rb, sb, k->prep_stream, nullptr, true);
+      rc = prove_submit_group(k, sl, w, nbat, rb, sb, k->prep_stream, nullptr, true);
     }
-    explicit_bzero(rb, 32); explicit_bzero(sb, 32);
+    explicit_bzero(rb, sizeof rb); explicit_bzero(sb, sizeof sb);
     if (rc) return rc;
     status = 0;
     goto again;

@@ -27,7 +27,7 @@ export interface Bn128 {
    *  returns the 352-byte record.  opts.d: the secret (1 < d < r) for reproducible tests; by default drawn inside the library. */
   contribute(opts?: { d?: bigint | string }): { record: Uint8Array };
   /** Evaluation-form side tables for the held key from its own points and the circuit's C side (zkr_key_eval_tables): true when
-   *  its proofs run four transforms instead of six from now on.  contribute, saveKey / loadKeyFile and replicas carry no tables. */
+   *  its proofs run four transforms instead of six from now on (the fused groups of proveBatch included).  contribute, saveKey / loadKeyFile and replicas carry no tables. */
   evalTables(r1csBin: Uint8Array): boolean;
   saveKey(path: string): void;
   loadKeyFile(path: string): void;

@@ -282,7 +282,7 @@ class Bn128 {
   }
   // The evaluation-form side tables for the held key, whatever it came from, derived from its own points and the circuit's C side
   // (zkr_key_eval_tables; r1csBin: binarifyR1cs(circuitDef) or RollupCircuit.r1cs()).  true: its proofs run four transforms instead
-  // of six from now on; false: it keeps the coefficient form.  contribute, saveKey / loadKeyFile and replicas carry no tables: call again.
+  // of six from now on, the fused groups of proveBatch included; false: it keeps the coefficient form.  contribute, saveKey / loadKeyFile and replicas carry no tables: call again.
   evalTables(r1csBin) { if (!this._key) throw new Error("no key loaded"); return native().keyEvalTables(this._key, r1csBin); }
   saveKey(path) { if (!this._key) throw new Error("no key loaded"); native().keySave(this._key, path); }
   loadKeyFile(path) { this._key = native().keyLoadFile(path, this.device); this._fp = "file:" + path; }

@@ -338,8 +338,9 @@ class ProvingKey:
 
     def h_form(self):
         """How this key's own proofs form the H term -- not part of info(), which describes the arena and is equal for a key and
-        its replicas, while the side tables of the evaluation form stay with the key that was built with them.  {'form': 'evaluation' | 'coefficients', 'retries': proofs proved again through the coefficient form because their
-        witness left constraints unsatisfied} (zkr_key_h_form)."""
+        its replicas, while the side tables of the evaluation form stay with the key that was built with them.  {'form': 'evaluation' | 'coefficients', 'retries': witnesses proved again through the coefficient form because they
+        left constraints unsatisfied -- lone proofs and fused groups alike; a group goes again as a whole and counts the witnesses
+        that failed} (zkr_key_h_form)."""
         ev, n = ctypes.c_int(), ctypes.c_uint64()
         _check(lib().zkr_key_h_form(self._h, ctypes.byref(ev), ctypes.byref(n)))
         return {"form": "evaluation" if ev.value else "coefficients", "retries": int(n.value)}
@@ -418,7 +419,8 @@ class ProvingKey:
 
     def prove_batch_device(self, d_witness_ptrs, rs=None, ss=None, stream=None, depth=None):
         """Independent proofs of one batch from witnesses resident in HBM (zkr_prove_batch_device): two submits in flight,
-        proofs of small circuits fused into shared launches (fuse() per submit).  depth (or env ZKR_PIPELINE_DEPTH) selects
+        proofs of small circuits fused into shared launches (fuse() per submit), in the four-transform form when the key has the side
+        tables (h_form()).  depth (or env ZKR_PIPELINE_DEPTH) selects
         the unfused submit / collect loop with that many single proofs in flight instead."""
         import collections
         import os
