@@ -566,6 +566,15 @@ const char *zkr_rollup_statement_text(uint32_t stmt);
  * lazily reduced).  field 0 = Fq, 1 = Fr.  The host build of the same header (libzkr_hostarith.so zkt29_raw_forms) must
  * give the same limbs bit for bit: tests/test_gpu_stages.py. */
 int zkr_selftest_f29_forms(int device, int field, int form, const uint32_t *records, size_t n, uint32_t *out);
+/* The same one layer up: the group law of the hot path (csrc/curve29.hpp) on raw limbs as the device compiles it, one thread per
+ * record.  g2: 0 = G1 over Fq (9 limbs per coordinate), 1 = G2 over Fq2 (18: re, im); the low eight limbs of a value below 2^29,
+ * the top limb = value >> 232, values x 2^261, nothing reduced on the way in or out.  op and record (csrc/curve29_raw.hpp):
+ * 0 add_mixed29 (X Y ZZ ZZZ, qx qy; flag neg_q), 1 add_affine_affine29 (ax ay, bx by; flags neg_a, neg_b), 2 add_full29 (two
+ * XYZZ; the second is read again for the doubling), 3 dbl_xyzz29, 4 dbl_affine29 (x y), 5 dbl_jac29 (X Y Z), 6 pack_xyzz and
+ * unpack_xyzz of the result; a record = its coordinates, then two flag words.  out: n x (4 coordinates; op 5: 3; op 6: the 4
+ * packed coordinates of 8 / 16 words, then the 4 read back as limbs); inf: n bytes, 1 = the point at infinity.  The host build
+ * of the same header (libzkr_hostarith.so zkt29_curve_raw) must give the same limbs: tests/test_gpu_group_law.py. */
+int zkr_selftest_curve29(int device, int g2, int op, const uint32_t *records, size_t n, uint32_t *out, uint8_t *inf);
 int zkr_bench_fq_mul(int device, double *gmuls_per_s);
 int zkr_bench_fq_mul_legacy(int device, double *gmuls_per_s);
 

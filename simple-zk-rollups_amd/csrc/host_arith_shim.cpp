@@ -4,6 +4,7 @@
 #include "hostops.hpp"
 #include "pairing.hpp"
 #include "curve29.hpp"
+#include "curve29_raw.hpp"
 #include "msm_plan.hpp"
 #include "eval_h.hpp"
 using namespace zkr;
@@ -159,6 +160,23 @@ template <class C> static int affine_affine29(const uint8_t *a, int neg_a, const
   return xyzz_out<C>(add_affine_affine29<C>(pa, neg_a != 0, pb, neg_b != 0), out);
 }
 
+// the group law on raw limbs (curve29_raw.hpp), one operation over n records
+template <class C, int OP> static void curve_raw_run(const uint32_t *records, size_t n, uint32_t *out, uint8_t *inf) {
+  constexpr int RW = curve29_record_words(Raw29<C>::g2, OP), OW = curve29_out_words(Raw29<C>::g2, OP);
+  for (size_t i = 0; i < n; i++) curve29_raw_op<C, OP>(records + i * RW, out + i * OW, inf + i);
+}
+template <class C> static void curve_raw(int op, const uint32_t *records, size_t n, uint32_t *out, uint8_t *inf) {
+  switch (op) {
+    case 0: curve_raw_run<C, 0>(records, n, out, inf); break;
+    case 1: curve_raw_run<C, 1>(records, n, out, inf); break;
+    case 2: curve_raw_run<C, 2>(records, n, out, inf); break;
+    case 3: curve_raw_run<C, 3>(records, n, out, inf); break;
+    case 4: curve_raw_run<C, 4>(records, n, out, inf); break;
+    case 5: curve_raw_run<C, 5>(records, n, out, inf); break;
+    default: curve_raw_run<C, 6>(records, n, out, inf);
+  }
+}
+
 #include <atomic>
 #include <thread>
 #include "shard_group.hpp"
@@ -288,6 +306,16 @@ void zkt29_loose(int field, const uint32_t *a9, const uint32_t *b9, uint32_t *nl
     auto n = neg_loose(b); auto d = sub_loose(a, b);
     memcpy(nl, n.v, 36); memcpy(sl, d.v, 36); *k_neg = decltype(n)::bound / 2; *k_sub = (decltype(d)::bound - 4) / 2;
   }
+}
+// the group law of curve29.hpp on raw limbs, nothing reduced on the way in or out: records, operations and results as
+// curve29_raw.hpp lays them out (and as zkr_selftest_curve29 runs them on the device); inf[i] = 1 for the point at infinity
+void zkt29_curve_raw(int g2, int op, const uint32_t *records, size_t n, uint32_t *out, uint8_t *inf) {
+  if (g2) curve_raw<G2C>(op, records, n, out, inf); else curve_raw<G1C>(op, records, n, out, inf);
+}
+// the bounds (half moduli) the register forms of curve29.hpp declare: HX, HY, JX, JY, JZ
+void zkt29_curve_bounds(int out[5]) {
+  const int b[5] = {HX, HY, JX, JY, JZ};
+  memcpy(out, b, sizeof b);
 }
 void zkt29_g1_levels(const uint8_t *pt, int c, int levels, uint8_t *out) { jac_levels29<Fq>(pt, c, levels, out); }
 void zkt29_g2_levels(const uint8_t *pt, int c, int levels, uint8_t *out) { jac_levels29<Fq2>(pt, c, levels, out); }

@@ -116,6 +116,7 @@ def lib():
     L.zkr_bench_fq_mul.argtypes = [i, c.POINTER(c.c_double)]
     L.zkr_bench_fq_mul_legacy.argtypes = [i, c.POINTER(c.c_double)]
     L.zkr_selftest_f29_forms.argtypes = [i, i, i, c.POINTER(c.c_uint32), sz, c.POINTER(c.c_uint32)]
+    L.zkr_selftest_curve29.argtypes = [i, i, i, c.POINTER(c.c_uint32), sz, c.POINTER(c.c_uint32), c.POINTER(c.c_uint8)]
     L.zkr_mimcsponge_multihash.argtypes = [u8p, sz, u8p]
     L.zkr_babyjub_pubkey.argtypes = [u8p, u8p]
     L.zkr_eddsa_sign.argtypes = [u8p, u8p, sz, u8p]
@@ -829,6 +830,30 @@ def selftest_f29_forms(field, form, records, device=0):
     out = (ctypes.c_uint32 * (9 * n))()
     _check(lib().zkr_selftest_f29_forms(device, field, form, flat, n, out))
     return [list(out[9 * k:9 * k + 9]) for k in range(n)]
+
+
+CURVE29_COORDS_IN = (6, 4, 8, 4, 2, 3, 4)  # coordinates of one record per op of zkr_selftest_curve29 (csrc/curve29_raw.hpp)
+
+
+def curve29_words(g2, op):
+    """(words of one record, words of one result) of zkr_selftest_curve29."""
+    nl = 18 if g2 else 9
+    return CURVE29_COORDS_IN[op] * nl + 2, 3 * nl if op == 5 else 4 * nl + (4 * (16 if g2 else 8) if op == 6 else 0)
+
+
+def selftest_curve29(g2, op, records, device=0):
+    """zkr_selftest_curve29: records = a flat sequence of uint32 words (n records of curve29_words(g2, op)[0] words: raw 29-bit
+    limbs of the operation's coordinates, then two flag words); returns (the result words of every record, flat; the n infinity
+    flags) as the device computes the group law of csrc/curve29.hpp."""
+    rw, ow = curve29_words(g2, op)
+    if len(records) % rw:
+        raise ValueError("records are not a whole number of %d-word records" % rw)
+    n = len(records) // rw
+    flat = records if isinstance(records, ctypes.Array) else (ctypes.c_uint32 * len(records))(*records)
+    out = (ctypes.c_uint32 * max(1, ow * n))()
+    inf = (ctypes.c_uint8 * max(1, n))()
+    _check(lib().zkr_selftest_curve29(device, int(bool(g2)), op, flat, n, out, inf))
+    return list(out[:ow * n]), list(inf[:n])
 
 
 def bench_fq_mul(device=0, legacy=False) -> float:

@@ -15,6 +15,7 @@ import pytest
 
 import bn254 as bn
 from bn254 import Q
+from curve29_cases import F1, F2, affine_affine_model, dbl_affine_model  # the fields as integers and the forms' integer models
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHIM = os.environ.get("ZKR_HOSTARITH_LIB") or os.path.join(ROOT, "simple-zk-rollups_amd", "csrc", "libzkr_hostarith.so")
@@ -27,34 +28,6 @@ def L():
     return ctypes.CDLL(SHIM)
 
 
-class F1:
-    """Fq as integers."""
-    g2, size = 0, 32
-    zero, one = 0, 1
-    add = staticmethod(lambda a, b: (a + b) % Q)
-    sub = staticmethod(lambda a, b: (a - b) % Q)
-    mul = staticmethod(lambda a, b: a * b % Q)
-    neg = staticmethod(lambda a: -a % Q)
-    inv = staticmethod(lambda a: pow(a, Q - 2, Q))
-    enc = staticmethod(lambda a: int(a).to_bytes(32, "little"))
-    dec = staticmethod(lambda b: int.from_bytes(b, "little"))
-    rand = staticmethod(lambda rnd: rnd.randrange(Q))
-    edges = [0, 1, 2, Q - 1, Q - 2, Q >> 1, (1 << 253) - 1, ((1 << 254) - 1) % Q, int("1" * 254, 2) % Q]
-    gen, padd, pmul, pneg = bn.G1_GEN, staticmethod(bn.g1_add), staticmethod(bn.g1_mul), staticmethod(bn.g1_neg)
-
-
-class F2:
-    """Fq2 as pairs (re, im)."""
-    g2, size = 1, 64
-    zero, one = (0, 0), (1, 0)
-    add, sub, mul, neg, inv = (staticmethod(f) for f in (bn.f2add, bn.f2sub, bn.f2mul, bn.f2neg, bn.f2inv))
-    enc = staticmethod(lambda a: int(a[0]).to_bytes(32, "little") + int(a[1]).to_bytes(32, "little"))
-    dec = staticmethod(lambda b: (int.from_bytes(b[:32], "little"), int.from_bytes(b[32:], "little")))
-    rand = staticmethod(lambda rnd: (rnd.randrange(Q), rnd.randrange(Q)))
-    edges = [(0, 0), (1, 0), (0, 1), (Q - 1, Q - 1), (Q - 1, 0), (0, Q - 1), (Q - 2, 1), (Q >> 1, (1 << 253) - 1)]
-    gen, padd, pmul, pneg = bn.G2_GEN, staticmethod(bn.g2_add), staticmethod(bn.g2_mul), staticmethod(bn.g2_neg)
-
-
 def _xyzz(F, raw, inf):
     return None if inf else tuple(F.dec(raw[i * F.size:(i + 1) * F.size]) for i in range(4))
 
@@ -63,25 +36,6 @@ def affine_affine(L, F, a, neg_a, b, neg_b):
     o = ctypes.create_string_buffer(4 * F.size)
     inf = L.zkt29_affine_affine(F.g2, F.enc(a[0]) + F.enc(a[1]), int(neg_a), F.enc(b[0]) + F.enc(b[1]), int(neg_b), o)
     return _xyzz(F, o.raw, inf)
-
-
-def dbl_affine_model(F, x, y):
-    u = F.add(y, y); v = F.mul(u, u); w = F.mul(u, v); s = F.mul(x, v)
-    xx = F.mul(x, x); m = F.add(F.add(xx, xx), xx)
-    x3 = F.sub(F.mul(m, m), F.add(s, s))
-    return x3, F.sub(F.mul(m, F.sub(s, x3)), F.mul(w, y)), v, w
-
-
-def affine_affine_model(F, a, neg_a, b, neg_b):
-    """The formulas of add_affine_affine29 on integers, special cases included."""
-    x1, y1 = a[0], F.neg(a[1]) if neg_a else a[1]
-    x2, y2 = b[0], F.neg(b[1]) if neg_b else b[1]
-    p, r = F.sub(x2, x1), F.sub(y2, y1)
-    if p == F.zero:
-        return dbl_affine_model(F, x1, y1) if r == F.zero else None
-    pp = F.mul(p, p); ppp = F.mul(p, pp); q = F.mul(x1, pp)
-    x3 = F.sub(F.sub(F.mul(r, r), ppp), F.add(q, q))
-    return x3, F.sub(F.mul(r, F.sub(q, x3)), F.mul(y1, ppp)), pp, ppp
 
 
 def to_affine(F, P):

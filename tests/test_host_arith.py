@@ -149,6 +149,48 @@ def _raw_records(rnd, n):
     return recs
 
 
+# The weight patterns of the sweep-less (U29) factors that the call sites of field29.hpp / curve29.hpp instantiate, per operand
+# position a b c d e f g h of a form (1: normalised; 2: neg_loose / cneg_loose, low limbs below 2^30; 3: sub_loose, below 3 * 2^29).
+# One factor of every product is normalised and the weight products of a form sum to at most 6 (f29_column_fits: 9 * (1 + 6) = 63
+# of the 64 units of 2^58 a column's 64-bit accumulator holds).  The square (form 1) takes normalised operands only.
+LOOSE_PATTERNS = (
+    (0, (1, 2)),                      # mul(a, neg_loose / cneg_loose): the sign of a table point folded into Y2 ZZZ1
+    (0, (1, 3)),                      # mul(a, sub_loose)
+    (2, (1, 1, 2, 1)),                # products weighted (1, 2): Fq2 mul / sqr, mul_sub over Fq with a normalised factor
+    (2, (1, 3, 2, 1)),                # (3, 2): the Y coordinate over Fq, R (Q - X3) - Y1 P^3
+    (2, (1, 2, 1, 2)),                # (2, 2): the Fq2 mul_cneg
+    (3, (1, 1, 2, 1, 2, 1, 1, 1)),    # (1, 2, 2, 1): the real part of the Fq2 mul_sub
+    (3, (1, 1, 1, 1, 2, 1, 2, 1)),    # (1, 1, 2, 2): its imaginary part
+)
+
+
+def _raw_records_loose(rnd, n):
+    """{(form, weights): n records} with the operands of weight 2 / 3 as neg_loose / sub_loose leave them: low eight limbs up to
+    2^30 - 1 resp. 3 * 2^29 - 1, top limb below 2^28; the normalised operands as in _raw_records.  Record 0 of every pattern has
+    every limb at its ceiling."""
+    M = (1 << 29) - 1
+    out = {}
+    for form, weights in LOOSE_PATTERNS:
+        pairs = [weights[i] * weights[i + 1] for i in range(0, len(weights), 2)]
+        assert sum(pairs) <= 6 and all(1 in weights[i:i + 2] for i in range(0, len(weights), 2)) and form != 1
+        w8 = tuple(weights) + (1,) * (8 - len(weights))
+        recs = []
+        for k in range(n):
+            rec = []
+            for w in w8:
+                top = (w << 29) - 1
+                if w == 1:
+                    rec.append([M] * 9 if rnd.random() < 0.3 else [rnd.randrange(1 << 29) for _ in range(9)])
+                else:
+                    kind = rnd.random()
+                    low = [top] * 8 if kind < 0.25 else [top if rnd.random() < 0.5 else rnd.randrange(top + 1) for _ in range(8)] if kind < 0.5 else [rnd.randrange(top + 1) for _ in range(8)]
+                    rec.append(low + [rnd.choice([(1 << 28) - 1, rnd.randrange(1 << 28)])])
+            recs.append(rec)
+        recs[0] = [[M] * 9 if w == 1 else [(w << 29) - 1] * 8 + [(1 << 28) - 1] for w in w8]
+        out[(form, weights)] = recs
+    return out
+
+
 def _limbs_value(l):
     return sum(int(x) << (29 * i) for i, x in enumerate(l))
 
@@ -178,6 +220,24 @@ def test_field29_product_forms_on_raw_limbs(L):
                 got = _limbs_value(o)
                 assert got % P == t * rinv % P, (field, form)
                 assert all(x < (1 << 29) for x in o[:8]) and got <= (t >> 261) + P, (field, form)
+
+
+def test_field29_product_forms_with_loose_factors_at_their_limb_ceilings(L):
+    """The same recursion with the factors the group law really feeds it: differences WITHOUT their carry sweep (U29), limbs up to
+    2^30 - 1 (neg_loose, cneg_loose) and 3 * 2^29 - 1 (sub_loose), in exactly the weight patterns the call sites instantiate -- up to
+    the Fq2 mul_sub's sum of four products with weights 1 + 2 + 2 + 1 = 6, 63 of the 64 units a column may hold.  Agreement with
+    Python's integers is what shows that no 64-bit column wrapped; the device's forms are compared with these limbs in
+    tests/test_gpu_stages.py."""
+    for (form, weights), recs in _raw_records_loose(random.Random(3030), 120).items():
+        for field, P in ((0, Q), (1, R)):
+            rinv = pow(1 << 261, -1, P)
+            outs = raw_forms_host(L, field, form, recs)
+            for k, (rec, o) in enumerate(zip(recs, outs)):
+                v = [_limbs_value(x) for x in rec]
+                t = [v[0] * v[1], None, v[0] * v[1] + v[2] * v[3], v[0] * v[1] + v[2] * v[3] + v[4] * v[5] + v[6] * v[7]][form]
+                got = _limbs_value(o)
+                assert got % P == t * rinv % P, (field, form, weights, k)
+                assert all(x < (1 << 29) for x in o[:8]) and got <= (t >> 261) + P, (field, form, weights, k)
 
 
 def test_sweepless_differences_on_raw_limbs(L):
