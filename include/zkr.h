@@ -194,6 +194,20 @@ int zkr_prove_batch_multi_device(zkr_key *const *keys, size_t n_keys, const void
  * shard (shards[i] = part i of `parts`; _device: d_witnesses_std[i] = the full witness resident on shard i's device). */
 #define ZKR_PARTIAL_BYTES 640
 int zkr_key_shard(const zkr_key *key, unsigned part, unsigned parts, int device, zkr_key **out);
+/* zkr_key_shard with flags (zkr_key_shard is flags = 0; unknown flags: ZKR_ERR_ARG, before any device call).
+ * ZKR_SHARD_SIDE_TABLES: when the whole key has the side tables of the evaluation form (zkr_key_h_form), the shard gets its own on
+ * `device`, cut as its point tables are -- E' over its range of the domain (natural order: the range of the whole table), C' over
+ * the point range of the table whose digit sort C's accumulation reads, window levels copied when the shard keeps the whole key's
+ * window and rebuilt from level 0 otherwise, C by row whole.  zkr_key_h_form then says evaluation for the shard.  The shard is a
+ * valid coefficient-form shard all the same (ZKR_OK, zkr_key_h_form says 0, one line in zkr_last_error) when the whole key has no
+ * tables, the device has no memory for them, ZKR_H_FORM=coefficients is set, or the shard's C table reads another digit sort than
+ * the whole key's.  zkr_key_eval_tables_drop takes a shard; zkr_key_eval_tables does not (derive on the whole key, then cut);
+ * zkr_key_eval_tables_equal compares two shards that are the same part of the same cut.
+ * Side tables change ONLY zkr_prove_sharded(_device): a shard's partial sums differ between the two forms of H and only their sum
+ * over all shards agrees, so zkr_prove_partial(_device) called on its own keeps the coefficient form and its records stay
+ * combinable with any shard's.  See zkr_prove_sharded_last_h_form. */
+#define ZKR_SHARD_SIDE_TABLES 1u
+int zkr_key_shard_opts(const zkr_key *key, unsigned part, unsigned parts, int device, unsigned flags, zkr_key **out);
 int zkr_prove_partial(zkr_key *shard, const void *witness_std, size_t witness_len, uint8_t partial_out[ZKR_PARTIAL_BYTES]);
 int zkr_prove_partial_device(zkr_key *shard, const void *d_witness_std, void *stream, uint8_t partial_out[ZKR_PARTIAL_BYTES]);
 int zkr_prove_combine(zkr_key *key, const uint8_t *partials, size_t parts, const uint8_t *r32, const uint8_t *s32, uint8_t proof_out[256]);
@@ -218,6 +232,17 @@ int zkr_prove_sharded_split_stats(unsigned *parts_out, double phase_ms_out[64]);
  * agree (a warning on stderr and replicated calcH from then on otherwise).  ZKR_SHARD_SPLIT_H=1 skips that check. */
 enum { ZKR_SHARDED_NONE = 0, ZKR_SHARDED_SPLIT_H = 1, ZKR_SHARDED_REPLICATED_H = 2 };
 int zkr_prove_sharded_last_form(int *form_out, char *reason_out, size_t reason_len);
+/* WHICH form of H the calling thread's last zkr_prove_sharded(_device) took (thread-local, as zkr_prove_sharded_last_form;
+ * ZKR_H_NONE before any sharded proof on the thread).  Evaluation form -- four transforms instead of six per proof; with a split
+ * calcH two cross passes instead of three in phase 2, no cross inverse transform in phase 4, the product on the block in phase 5
+ * -- runs iff EVERY shard has side tables (ZKR_SHARD_SIDE_TABLES) and ZKR_H_FORM=coefficients is not set; the first-use check
+ * compares split against replicated in the same form.  reason_out, one line: "every shard has side tables", "shard 2 has no side
+ * tables", "ZKR_H_FORM=coefficients", or "witness left 3 rows unsatisfied: proved again through the coefficient form" -- the shards
+ * count the rows with a_j b_j != c_j (each its block with a split calcH, each all of them otherwise), the counts are summed after the
+ * shards' threads have joined, and a witness with such rows is proved again on every shard through the coefficient form: the proof
+ * is the same bytes for every witness, and `retries` (zkr_key_h_form) of EVERY shard of the set grows by one. */
+enum { ZKR_H_NONE = 0, ZKR_H_COEFFICIENTS = 1, ZKR_H_EVALUATION = 2 };
+int zkr_prove_sharded_last_h_form(int *form_out, char *reason_out, size_t reason_len);
 /* Measurement only (bench.py's shard leg on a one-GPU box): ONE shard runs its share of a proof with a split calcH ALONE, its own
  * buffers standing in for the other shards' -- the time a shard takes with a GPU to itself and no exchange (*ms_out); what it
  * computes is meaningless and is discarded. */
@@ -298,7 +323,8 @@ int zkr_setup_r1cs(const void *r1cs_bin, size_t r1cs_len, const uint8_t *toxic16
  * are, the C multiexp takes the witness over C'.  That rests on a o b = C w, so every such proof also counts the rows where it
  * fails (one count per proof of a fused group), and a witness with such rows is proved again through the coefficient form, in its
  * place in the caller's order -- with the rest of its group, when it came in one: the proof is the same bytes for every witness.
- * Shards, the split calcH of a sharded proof and the stage hooks (zkr_calc_h) keep the coefficient form.  The tables cost about as much device memory as C and H themselves (2 x 0.87 GB at 2^20);
+ * A shard proving on its own (zkr_prove_partial) and the stage hooks (zkr_calc_h) keep the coefficient form; a sharded proof takes the
+ * evaluation form when every shard was cut with side tables (zkr_key_shard_opts).  The tables cost about as much device memory as C and H themselves (2 x 0.87 GB at 2^20);
  * when they cannot be allocated, or a signal of C' has no point in the layout C shares, the key simply keeps the coefficient
  * form (ZKR_H_FORM=coefficients asks for that).  They are not part of the arena: key files, replicas, shards, contributed keys
  * (zkr_key_contribute changes C and H), websnark-loaded and transcript keys come without them and prove through the coefficient
@@ -326,7 +352,8 @@ int zkr_key_h_form(const zkr_key *key, int *evaluation, uint64_t *retries);
  * WHICH C matrix: the identity the tables rest on holds for any matrix M with M w = a o b, and every evaluation-form proof checks
  * exactly that of its witness.  A wrong or stale C side therefore gives no wrong proof: it makes every proof take the retry path
  * (slower; `retries` of zkr_key_h_form counts them), alone or as fused groups.  Nothing binds r1cs_bin to the key beyond its geometry.
- * Loading, saving, replicating, sharding and contributing carry no tables, as before: derive again on the key such a step returns.
+ * Loading, saving, replicating and contributing carry no tables, as before: derive again on the key such a step returns; a shard
+ * gets its part of them only through zkr_key_shard_opts with ZKR_SHARD_SIDE_TABLES.
  * zkr_key_eval_tables_drop: back to the coefficient form; frees the tables (ZKR_ERR_ARG with a proof in flight).
  * zkr_key_eval_tables_equal (test hook): *same = 1 iff both keys, on one device, have tables and their C' and E' tables at every window
  * level and their C rows are equal byte for byte.

@@ -209,7 +209,28 @@ static int shard_group_selftest(unsigned parts, unsigned rounds, unsigned fail_p
   return bad.load();
 }
 
+// ShardGroup::unsatisfied on the host: `parts` threads meet at a barrier, then each writes its count (counts[part]) as a shard's
+// thread does when it collects its proof; the sum is taken after the threads have joined.  Returns the sum, or ~0 when a thread was
+// refused at the barrier.
+static unsigned long long shard_group_count_selftest(unsigned parts, const unsigned *counts) {
+  zkr::ShardGroup g;
+  g.parts = parts;
+  g.vecs.resize(parts);
+  g.unsatisfied.assign(parts, 0);
+  std::atomic<int> bad{0};
+  auto work = [&](unsigned i) {
+    if (!g.barrier()) { bad++; return; }
+    g.unsatisfied[i] = counts[i];
+  };
+  std::vector<std::thread> thr;
+  for (unsigned i = 1; i < parts; i++) thr.emplace_back(work, i);
+  work(0);
+  for (auto &t : thr) t.join();
+  return bad.load() ? ~0ull : g.unsatisfied_sum();
+}
+
 extern "C" {
+unsigned long long zkr_host_shard_group_count_selftest(unsigned parts, const unsigned *counts) { return shard_group_count_selftest(parts, counts); }
 // msm_plan(n_scalars, n_points, c_fixed) as ten words: c, K, glog, nbw, nb, big_thresh, nR, nbl, J, S
 void zkt_msm_plan(size_t n_scalars, size_t n_points, int c_fixed, uint32_t out[10]) {
   const MsmPlan p = msm_plan(n_scalars, n_points, c_fixed);

@@ -419,19 +419,21 @@ static __global__ void combine_h_kernel(const Fr *S, const Fr *D, Fr *h, const F
 // in standard form; c_over_r: C's row sums made with standard-form coefficients, i.e. c_j / R -- what one product of a_j and b_j
 // leaves.  All three canonical.  A satisfying witness adds nothing, so the good path has no atomic at all.
 // blockIdx.y: proof of a fused batch -- its vectors at stride m, its own word of `bad` (the host learns WHICH witnesses failed)
-static __global__ void eval_unsatisfied_kernel(const Fr *a, const Fr *b, const Fr *c_over_r, uint32_t m, uint32_t *bad) {
-  uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= m) return;
+// row0 / row1: the rows wanted (a shard of a split calcH checks its block of the domain; otherwise 0 and m)
+static __global__ void eval_unsatisfied_kernel(const Fr *a, const Fr *b, const Fr *c_over_r, uint32_t m, uint32_t *bad, uint32_t row0, uint32_t row1) {
+  uint32_t j = row0 + blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= row1) return;
   const size_t i = (size_t)blockIdx.y * m + j;
   if (!(mul(load_fr(a + i), load_fr(b + i)) == load_fr(c_over_r + i))) atomicAdd(bad + blockIdx.y, 1u);
 }
 // d_j = ao_j bo_j / R from the canonical coset evaluations: the scalars of the E' table (whose points carry R / m^2 and the rest)
 // blockIdx.y: proof of a fused batch, vectors at stride m
-static __global__ void eval_product_kernel(const Fr *ao, const Fr *bo, Fr *d, uint32_t m, uint32_t *zero, uint32_t zero_words) {
+// row0 / row1: the rows wanted (a shard: its range of d, the scalars its part of E' takes; otherwise 0 and m)
+static __global__ void eval_product_kernel(const Fr *ao, const Fr *bo, Fr *d, uint32_t m, uint32_t *zero, uint32_t zero_words, uint32_t row0, uint32_t row1) {
   if (blockIdx.x == 0 && blockIdx.y == 0)  // see ingest_kernel: the counters of h's digit records, once per launch
     for (uint32_t k = threadIdx.x; k < zero_words; k += blockDim.x) zero[k] = 0;
-  uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= m) return;
+  uint32_t j = row0 + blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= row1) return;
   const size_t i = (size_t)blockIdx.y * m + j;
   store_fr(d + i, mul(load_fr(ao + i), load_fr(bo + i)));
 }

@@ -19,6 +19,16 @@ struct ShardGroup {
   bool solo = false;                  // measurement only (zkr_bench_shard_split_solo): ONE shard runs its phases with its own buffers
                                       // standing in for the others' -- the time of a shard alone on its GPU, the result meaningless
   double phase_ms[8][8] = {};         // [part][phase]: host time enqueue -> stream idle of the split's phases (bench / tests)
+  bool eval_h = false;                // the proof runs with H in evaluation form: every shard has side tables (zkr_multi.hip run_sharded)
+  // [part]: rows with a_j b_j != c_j that the part's proof counted (evaluation form: of its block with a split calcH, of the whole
+  // domain otherwise), written by the part's thread when it collects its proof and read after the threads have joined -- no shard
+  // waits at a barrier for the sum
+  std::vector<unsigned> unsatisfied;
+  unsigned long long unsatisfied_sum() const {
+    unsigned long long s = 0;
+    for (unsigned c : unsatisfied) s += c;
+    return s;
+  }
   std::mutex mu;
   std::condition_variable cv;
   unsigned waiting = 0, generation = 0;

@@ -186,6 +186,8 @@ int zkr_key_eval_tables_equal(const zkr_key *a, const zkr_key *b, int *same) {
   const EvalTables &x = a->eval, &y = b->eval;
   if (!x.ready || !y.ready) return 0;
   const int lt = a->layout.sort_src[T_C];
+  // two shards: the same part of the same cut (their tables hold the shards' ranges, sized by the shards' own point counts)
+  if (a->h.shard_parts != b->h.shard_parts || a->h.shard_part != b->h.shard_part || a->h.npts[T_H] != b->h.npts[T_H]) return 0;
   if (a->h.m != b->h.m || b->layout.sort_src[T_C] != lt || a->h.npts[lt] != b->h.npts[lt] || a->plan[T_C].K != b->plan[T_C].K || a->plan[T_H].K != b->plan[T_H].K ||
       x.nnz != y.nnz || x.n_wide != y.n_wide)
     return 0;
@@ -193,7 +195,7 @@ int zkr_key_eval_tables_equal(const zkr_key *a, const zkr_key *b, int *same) {
   bool eq = false;
   if (int rc = device_bytes_equal(a->device, x.c_pts, y.c_pts, (size_t)a->h.npts[lt] * a->plan[T_C].K * 64, &eq)) return rc;
   if (!eq) return 0;
-  if (int rc = device_bytes_equal(a->device, x.e_pts, y.e_pts, (size_t)a->h.m * a->plan[T_H].K * 64, &eq)) return rc;
+  if (int rc = device_bytes_equal(a->device, x.e_pts, y.e_pts, (size_t)a->h.npts[T_H] * a->plan[T_H].K * 64, &eq)) return rc;
   if (!eq) return 0;
   // the C rows: small beside the tables, compared on the host
   const struct { const void *p, *q; size_t bytes; } rows[4] = {{x.c_rowptr, y.c_rowptr, ((size_t)a->h.m + 1) * 4}, {x.c_col, y.c_col, (size_t)x.nnz * 4},

@@ -200,8 +200,9 @@ namespace zkr {
 // Side tables of the evaluation form (eval_h.hpp has the algebra), made from the scalars by a builder that knew them (workload.hip
 // key_build_eval_tables) or from the key's own points for any whole key (zkr_eval_tables.hip zkr_key_eval_tables): the H
 // multiexp over E' = -1/2 E with the coset products d_j as scalars, the C multiexp over C' = C + 1/2 C^T F.  Outside the arena: key
-// files, replicas, shards and contributed keys do not carry them and prove through the coefficient form until they are derived
-// again.  Both tables have the
+// files, replicas and contributed keys do not carry them and prove through the coefficient form until they are derived
+// again; a shard gets its ranges of a whole key's tables when it is cut with ZKR_SHARD_SIDE_TABLES (zkr_multi.hip shard_eval_tables:
+// E' over its range of the domain, C' over its point range, both with the shard's plans).  Both tables have the
 // plans and the point layout of the tables they stand in for (C': the points of C, or of A's sort when the two share it, infinity
 // where a scalar is zero; E': m points in natural order), so a proof uses the same sorts, bucket sets and chains either way.
 struct EvalTables {
@@ -287,8 +288,9 @@ int run_ntt(hipStream_t s, const Fr *in0, const Fr *in1, Fr *out, const NttTable
 int calc_h_device(zkr_key *k, ProofSlot &sl, hipStream_t s, int nbat = 1);  // sl.d_w -> sl.d_h (bit-reversed), nbat vectors end to end
 
 // ShardGroup (the shards of one proof running concurrently; barrier + abort): shard_group.hpp, no HIP in it
-// set by run_sharded's worker threads around zkr_prove_partial(_device): the proof this thread enqueues is part `shard_group_part`
-// of that group (null: a shard proving on its own -- replicated calcH)
+// set by run_sharded's worker threads around zkr_prove_partial(_device): the proof this thread enqueues -- and collects -- is part
+// `shard_group_part` of that group, which says whether calcH is split and whether H goes in evaluation form (null: a shard proving
+// on its own -- replicated calcH, coefficient form)
 extern thread_local ShardGroup *shard_group;
 extern thread_local unsigned shard_group_part;
 extern thread_local bool shard_turn_held;  // the caller of this thread's zkr_prove_partial(_device) holds the shard's split_mu already (run_sharded with a split calcH)

@@ -195,8 +195,79 @@ int zkr_key_shard_info(const zkr_key *key, uint32_t out[6]) {
   return 0;
 }
 
-int zkr_key_shard(const zkr_key *src, unsigned part, unsigned parts, int device, zkr_key **out) {
+}  // extern "C"
+
+namespace {
+
+// Points [pt_lo, pt_lo + np) of a table of src_np points per window level (pb bytes each, window src_c) on src_dev -> a table of np
+// points per level at dst on dst_dev, with the levels of plan pl.  The same window: level k of the range is copied, 2^(ck) P_i for
+// the range's points.  Another one: level 0 of the range back in the key's wire radix, then the levels of pl built on dst_dev
+// (msm_precompute, as a key load does).  The arena's five tables and the side tables of the evaluation form are cut this way.
+int cut_table(void *dst, int dst_dev, const void *src, int src_dev, bool g2, uint32_t src_np, uint32_t src_c, uint32_t pt_lo, uint32_t np, const MsmPlan &pl) {
+  if (!np) return 0;
+  const size_t pb = g2 ? 128 : 64;
+  const char *from = (const char *)src;
+  if ((uint32_t)pl.c == src_c) {
+    int rc = 0;
+    for (size_t k = 0; k < (size_t)pl.K && !rc; k++)
+      rc = copy_between_devices((char *)dst + k * np * pb, dst_dev, from + (k * src_np + pt_lo) * pb, src_dev, (size_t)np * pb);
+    return rc;
+  }
+  int rc = copy_between_devices(dst, dst_dev, from + (size_t)pt_lo * pb, src_dev, (size_t)np * pb);
+  if (!rc) rc = radix_convert(dst_dev, g2, dst, np, false);
+  if (!rc) rc = msm_precompute(dst_dev, g2, dst, np, pl);
+  return rc;
+}
+
+// The side tables of the evaluation form for a shard `k` of `src` (zkr_key_shard_opts with ZKR_SHARD_SIDE_TABLES): E' over the
+// shard's range of d -- natural order, so the range [sc_lo[1], sc_lo[1] + sc_n[1]) of the whole key's table -- and C' over the point
+// range [c_lo, c_lo + npts[lt]) of the table lt whose sort C's accumulation reads, both with the shard's plans; C by row and the
+// slots' counters whole, as the shard holds A and B.  0 with *why = null: k->eval is ready; 0 with a reason: the shard keeps the
+// coefficient form and nothing is left allocated; below zero: a failed copy or kernel.
+int shard_eval_tables(zkr_key *k, const zkr_key *src, uint32_t c_lo, const char **why) {
+  *why = nullptr;
+  const ArenaHeader &h = k->h, &sh = src->h;
+  const EvalTables &sv = src->eval;
+  EvalTables &ev = k->eval;
+  if (!sv.ready) { *why = "the whole key has no side tables"; return 0; }
+  if (const char *e = getenv("ZKR_H_FORM"); e && !strcmp(e, "coefficients")) { *why = "ZKR_H_FORM=coefficients"; return 0; }
+  const int lt = src->layout.sort_src[T_C];
+  if (k->layout.sort_src[T_C] != lt) { *why = "the shard's C table reads another digit sort than the whole key's"; return 0; }
+  if (h.npts[T_H] != h.sc_n[1] || sh.npts[T_H] != sh.m) { *why = "the H table dropped a point"; return 0; }
+  ZKR_HIP_CHECK(hipSetDevice(k->device));
+  auto give_up = [&](const char *reason) { (void)hipGetLastError(); key_eval_tables_free(k); *why = reason; return 0; };
+  const char *const no_memory = "the device has no memory for the side tables";
+  const uint32_t np_c = h.npts[lt], np_e = h.npts[T_H];
+  const size_t rows = ((size_t)sh.m + 1) * 4;
+  bool ok = hipMalloc(&ev.e_pts, (size_t)np_e * k->plan[T_H].K * 64 + 64) == hipSuccess && hipMalloc(&ev.c_pts, (size_t)np_c * k->plan[T_C].K * 64 + 64) == hipSuccess &&
+            hipMalloc(&ev.c_rowptr, rows) == hipSuccess && hipMalloc(&ev.c_col, (size_t)sv.nnz * 4 + 4) == hipSuccess &&
+            hipMalloc(&ev.c_coef, (size_t)sv.nnz * 32 + 32) == hipSuccess && hipMalloc(&ev.c_wide, (size_t)sv.n_wide * 4 + 4) == hipSuccess;
+  for (ProofSlot &sl : k->slot)
+    ok = ok && hipMalloc(&sl.d_bad, (size_t)sl.cap * 4) == hipSuccess && hipHostMalloc(&sl.h_bad, (size_t)sl.cap * 4, hipHostMallocDefault) == hipSuccess;
+  if (!ok) return give_up(no_memory);
+  for (ProofSlot &sl : k->slot) memset(sl.h_bad, 0, (size_t)sl.cap * 4);
+  ev.nnz = sv.nnz; ev.n_wide = sv.n_wide;
+  int rc = cut_table(ev.e_pts, k->device, sv.e_pts, src->device, false, sh.npts[T_H], sh.win_c[T_H], h.sc_lo[1], np_e, k->plan[T_H]);
+  if (!rc) rc = cut_table(ev.c_pts, k->device, sv.c_pts, src->device, false, sh.npts[lt], sh.win_c[T_C], c_lo, np_c, k->plan[T_C]);
+  auto cp = [&](void *dst, const void *from, size_t bytes) { return bytes ? copy_between_devices(dst, k->device, from, src->device, bytes) : 0; };
+  if (!rc) rc = cp(ev.c_rowptr, sv.c_rowptr, rows);
+  if (!rc) rc = cp(ev.c_col, sv.c_col, (size_t)sv.nnz * 4);
+  if (!rc) rc = cp(ev.c_coef, sv.c_coef, (size_t)sv.nnz * 32);
+  if (!rc) rc = cp(ev.c_wide, sv.c_wide, (size_t)sv.n_wide * 4);
+  if (rc) { key_eval_tables_free(k); return rc; }
+  ev.ready = true;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int zkr_key_shard(const zkr_key *src, unsigned part, unsigned parts, int device, zkr_key **out) { return zkr_key_shard_opts(src, part, parts, device, 0, out); }
+
+int zkr_key_shard_opts(const zkr_key *src, unsigned part, unsigned parts, int device, unsigned flags, zkr_key **out) {
   if (!src || !out) { set_error("null argument"); return ZKR_ERR_ARG; }
+  if (flags & ~ZKR_SHARD_SIDE_TABLES) { set_error("zkr_key_shard_opts: unknown flags %#x", flags); return ZKR_ERR_ARG; }
   if (parts < 1 || parts > 64 || part >= parts) { set_error("shard %u of %u: parts must be 1..64 and part below it", part, parts); return ZKR_ERR_ARG; }
   if (src->h.shard_parts != 1) { set_error("the key is itself a shard (%u of %u): shard the whole key", src->h.shard_part, src->h.shard_parts); return ZKR_ERR_ARG; }
   if (zkr_device_count() <= device || device < 0) { set_error("no HIP device %d (found %d)", device, zkr_device_count()); return ZKR_ERR_NO_DEVICE; }
@@ -241,12 +312,7 @@ int zkr_key_shard(const zkr_key *src, unsigned part, unsigned parts, int device,
   // table (3 entries each) and then walks four reduction chains over all of them -- the chains were 2/3 of such a shard's 4.1 ms.
   // At c = 17 it is an ordinary 2^17-point key (2^16 buckets).  The levels 2^(ck) P are then rebuilt from level 0 on the shard's
   // device (msm_precompute, as a key load does); tables whose window does not change are copied level by level.
-  bool rebuild[N_TABLES];
-  for (int t = 0; t < N_TABLES; t++) {
-    const uint32_t c = (uint32_t)msm_plan(rank_entries(h, t), h.npts[t], 0).c;
-    rebuild[t] = c != sh.win_c[t];
-    h.win_c[t] = c;
-  }
+  for (int t = 0; t < N_TABLES; t++) h.win_c[t] = (uint32_t)msm_plan(rank_entries(h, t), h.npts[t], 0).c;
   arena_layout(h);
   // peer access between the shard's device and every other one, both ways, BEFORE anything of the shard is allocated: its
   // siblings' kernels read and write its vectors directly when a sharded proof splits calcH (zkr_prove.hip calc_h_split)
@@ -269,15 +335,8 @@ int zkr_key_shard(const zkr_key *src, unsigned part, unsigned parts, int device,
     if (!rc) rc = cp(h.off_wide[s], sh.off_wide[s], (size_t)sh.n_wide[s] * 4);
   }
   for (int t = 0; t < N_TABLES && !rc; t++) {
-    const size_t pb = t == T_B2 ? 128 : 64, K = (255 + sh.win_c[t] - 1) / sh.win_c[t];
-    if (rebuild[t]) {  // level 0 of the range back in the key's wire radix, then the shard's own levels
-      rc = cp(h.off_pts[t], sh.off_pts[t] + (size_t)pt_lo[t] * pb, (size_t)h.npts[t] * pb);
-      if (!rc) rc = radix_convert(device, t == T_B2, arena + h.off_pts[t], h.npts[t], false);
-      if (!rc) rc = msm_precompute(device, t == T_B2, arena + h.off_pts[t], h.npts[t], msm_plan(rank_entries(h, t), h.npts[t], (int)h.win_c[t]));
-    } else {
-      for (size_t k = 0; k < K && !rc; k++)  // level k of the range: 2^(ck) P_i for the shard's points
-        rc = cp(h.off_pts[t] + k * h.npts[t] * pb, sh.off_pts[t] + (k * sh.npts[t] + pt_lo[t]) * pb, (size_t)h.npts[t] * pb);
-    }
+    rc = cut_table(arena + h.off_pts[t], device, src->arena + sh.off_pts[t], src->device, t == T_B2, sh.npts[t], sh.win_c[t], pt_lo[t], h.npts[t],
+                   msm_plan(rank_entries(h, t), h.npts[t], (int)h.win_c[t]));
     if (!rc && !rank[t].empty()) {
       ZKR_HIP_CHECK(hipSetDevice(device));
       ZKR_HIP_CHECK(hipMemcpy(arena + h.off_rank[t], rank[t].data(), rank[t].size() * 4, hipMemcpyHostToDevice));
@@ -289,6 +348,12 @@ int zkr_key_shard(const zkr_key *src, unsigned part, unsigned parts, int device,
   if (rc) return rc;
   k->owns_arena = true;
   buf.release();
+  if (flags & ZKR_SHARD_SIDE_TABLES) {
+    const char *why = nullptr;
+    rc = shard_eval_tables(k, src, pt_lo[src->layout.sort_src[T_C]], &why);
+    if (rc) { zkr_key_free(k); return rc; }
+    if (why) set_error("zkr_key_shard_opts: shard %u of %u keeps the coefficient form: %s", part, parts, why);
+  }
   *out = k;
   return 0;
 }
@@ -302,6 +367,16 @@ thread_local unsigned last_split_parts = 0;
 // which form the calling thread's last sharded proof took, and why (zkr_prove_sharded_last_form)
 thread_local int last_form = ZKR_SHARDED_NONE;
 thread_local char last_reason[256] = "";
+// ... and whether H went in evaluation form (zkr_prove_sharded_last_h_form)
+thread_local int last_h_form = ZKR_H_NONE;
+thread_local char last_h_reason[256] = "";
+void set_h_form(int form, const char *fmt, ...) {
+  last_h_form = form;
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(last_h_reason, sizeof(last_h_reason), fmt, ap);
+  va_end(ap);
+}
 void set_form(int form, const char *fmt, ...) {
   last_form = form;
   va_list ap;
@@ -322,9 +397,12 @@ void drain_shards(zkr_key *const *shards, size_t parts) {
 
 // One pass over the shards, one host thread each: split = calcH split over them (the caller has checked the preconditions and
 // holds the shards' turns), else every shard computes h for itself.  *ran_split: whether the split really ran (false when a
-// thread could not be started).
+// thread could not be started).  eval_h: H in evaluation form (the caller has seen side tables on every shard); *bad_rows: the rows
+// the witness leaves unsatisfied as the shards counted them -- with a split calcH each its own block, so the sum; otherwise every
+// shard all of them, so any one's count, and they must agree.  Above zero the partial sums mean nothing.
 template <class Partial>
-int run_shards_once(zkr_key *const *shards, size_t parts, bool split, int klog, std::vector<uint8_t> &partials, Partial partial, bool *ran_split, bool turns_held) {
+int run_shards_once(zkr_key *const *shards, size_t parts, bool split, int klog, std::vector<uint8_t> &partials, Partial partial, bool *ran_split, bool turns_held,
+                    bool eval_h, uint64_t *bad_rows) {
   std::vector<int> rcs(parts, 0);
   std::vector<std::string> errs(parts);
   ShardGroup group;
@@ -332,9 +410,12 @@ int run_shards_once(zkr_key *const *shards, size_t parts, bool split, int klog, 
   group.vecs.resize(parts);
   group.klog = klog;
   group.split_h = split;
+  group.eval_h = eval_h;
+  group.unsatisfied.assign(parts, 0);
+  *bad_rows = 0;
   std::vector<char> threaded(parts, 0);
   auto work = [&](size_t i) {
-    shard_group = group.split_h && threaded[i] ? &group : nullptr;  // a shard run inline after the others cannot meet them at a barrier
+    shard_group = &group;  // split_h is off by now when a shard runs inline after the others: it could not meet them at a barrier
     shard_group_part = (unsigned)i;
     shard_turn_held = turns_held;  // the caller holds every shard's turn (a split pass, also when the split is then given up: no thread; the first-use check's second pass)
     try {
@@ -379,12 +460,29 @@ int run_shards_once(zkr_key *const *shards, size_t parts, bool split, int klog, 
         set_error("shard %zu (device %d): %s", i, shards[i]->device, errs[i].c_str());
         return rcs[i];
       }
+  if (eval_h) {
+    if (group.split_h) *bad_rows = group.unsatisfied_sum();
+    else {
+      for (size_t i = 1; i < parts; i++)
+        if (group.unsatisfied[i] != group.unsatisfied[0]) {
+          set_error("shards 0 and %zu count %u and %u unsatisfied rows of the same witness", i, group.unsatisfied[0], group.unsatisfied[i]);
+          return ZKR_ERR_HIP;
+        }
+      *bad_rows = group.unsatisfied[0];
+    }
+  }
   return 0;
 }
 
 template <class Partial>
+int run_sharded_form(zkr_key *const *shards, size_t parts, const uint8_t *r32, const uint8_t *s32, uint8_t *proof_out, Partial partial, std::vector<uint8_t> &partials,
+                     bool ok, bool check, int klog, int policy, bool distinct, int force_check, const char *why,
+                     std::vector<std::unique_lock<std::shared_mutex>> &turn, bool eval_h, uint64_t *bad_rows);
+
+template <class Partial>
 int run_sharded(zkr_key *const *shards, size_t parts, const uint8_t *r32, const uint8_t *s32, uint8_t *proof_out, Partial partial) {
   set_form(ZKR_SHARDED_NONE, "");
+  set_h_form(ZKR_H_NONE, "");
   last_split_parts = 0;
   if (!shards || parts == 0 || !proof_out) { set_error("null argument"); return ZKR_ERR_ARG; }
   for (size_t i = 0; i < parts; i++) {
@@ -438,7 +536,36 @@ int run_sharded(zkr_key *const *shards, size_t parts, const uint8_t *r32, const 
     if (st == 0) state = 0;
   }
   if (ok && policy == 2 && state == 2) { ok = false; turn.clear(); snprintf(why, sizeof(why), "the split form failed its first-use check on these shards (it disagreed with the replicated one)"); }
-  const bool check = ok && policy == 2 && state == 0 && (distinct || force_check);
+  bool check = ok && policy == 2 && state == 0 && (distinct || force_check);
+  // H in evaluation form iff EVERY shard has side tables (zkr_key_shard_opts): a shard's partial sums differ between the two forms,
+  // only the sums over all shards agree, and the record has no room for a tag -- so the form is decided here, per proof, for the whole
+  // set.  A witness that leaves rows unsatisfied (the shards' counts, summed after their threads have joined) goes again on every
+  // shard through the coefficient form, which is exact for every witness.
+  bool eval_h = true;
+  if (const char *fe = getenv("ZKR_H_FORM"); fe && !strcmp(fe, "coefficients")) { eval_h = false; set_h_form(ZKR_H_COEFFICIENTS, "ZKR_H_FORM=coefficients"); }
+  for (size_t i = 0; i < parts && eval_h; i++)
+    if (!shards[i]->eval.ready) { eval_h = false; set_h_form(ZKR_H_COEFFICIENTS, "shard %zu has no side tables", i); }
+  if (eval_h) set_h_form(ZKR_H_EVALUATION, "every shard has side tables");
+  for (;;) {
+    uint64_t bad_rows = 0;
+    const int rc = run_sharded_form(shards, parts, r32, s32, proof_out, partial, partials, ok, check, klog, policy, distinct, force_check, why, turn, eval_h, &bad_rows);
+    if (rc || !bad_rows) return rc;
+    for (size_t i = 0; i < parts; i++) shards[i]->eval.retries.fetch_add(1);
+    set_h_form(ZKR_H_COEFFICIENTS, "witness left %llu rows unsatisfied: proved again through the coefficient form", (unsigned long long)bad_rows);
+    eval_h = false;
+    if (check && shards[0]->split_checked.load() == 2) {  // the first-use check has just condemned the split on these shards
+      ok = check = false;
+      turn.clear();  // every shard then takes its own turn, as in any replicated pass
+      snprintf(why, sizeof(why), "the split form failed its first-use check on these shards (it disagreed with the replicated one)");
+    }
+  }
+}
+
+// One sharded proof in one H form.  *bad_rows above zero (evaluation form only): nothing was assembled, no state was kept.
+template <class Partial>
+int run_sharded_form(zkr_key *const *shards, size_t parts, const uint8_t *r32, const uint8_t *s32, uint8_t *proof_out, Partial partial, std::vector<uint8_t> &partials,
+                     bool ok, bool check, int klog, int policy, bool distinct, int force_check, const char *why,
+                     std::vector<std::unique_lock<std::shared_mutex>> &turn, bool eval_h, uint64_t *bad_rows) {
   bool ran_split = false;
   int rc;
   if (check) {
@@ -447,13 +574,23 @@ int run_sharded(zkr_key *const *shards, size_t parts, const uint8_t *r32, const 
     // the XYZZ coordinates of a sum depend on the order of additions)
     std::vector<uint8_t> split_partials(parts * ZKR_PARTIAL_BYTES);
     uint8_t one[32] = {1}, pa[256], pb[256];
-    rc = run_shards_once(shards, parts, true, klog, split_partials, partial, &ran_split, true);
+    uint64_t bad_split = 0;
+    rc = run_shards_once(shards, parts, true, klog, split_partials, partial, &ran_split, true, eval_h, &bad_split);
     double keep_ms[8][8];
     memcpy(keep_ms, last_split_phase_ms, sizeof(keep_ms));
     const bool split_ran = rc == 0 && ran_split;
     bool dummy = false;
-    int rc2 = run_shards_once(shards, parts, false, klog, partials, partial, &dummy, true);
+    int rc2 = run_shards_once(shards, parts, false, klog, partials, partial, &dummy, true, eval_h, bad_rows);  // the same H form: the forms' sums differ shard by shard
     if (rc2) return rc2;
+    if (*bad_rows || bad_split) {  // sums of an unsatisfying witness decide nothing: the set stays unchecked ...
+      if (split_ran && bad_split != *bad_rows) {  // ... unless the two forms do not even count the same rows: that IS a disagreement
+        for (size_t i = 0; i < parts; i++) shards[i]->split_checked.store(2);
+        fprintf(stderr, "zkr: sharded proof: the split calcH counts %llu unsatisfied rows, the replicated form %llu, on first use over devices %d..%d -- every shard computes h for itself from now on\n",
+                (unsigned long long)bad_split, (unsigned long long)*bad_rows, shards[0]->device, shards[parts - 1]->device);
+      }
+      if (!*bad_rows) *bad_rows = bad_split;
+      return 0;
+    }
     // compared: the split pass ran and both sets of sums assemble; a pass that could not run (a transient HIP failure, no thread)
     // or sums that do not assemble with r = s = 1 decide nothing -- the set stays unchecked and the next proof tries again
     bool compared = false, same = false;
@@ -479,8 +616,8 @@ int run_sharded(zkr_key *const *shards, size_t parts, const uint8_t *r32, const 
     turn.clear();
     return zkr_prove_combine(shards[0], partials.data(), parts, r32, s32, proof_out);  // the replicated pass' sums either way
   }
-  rc = run_shards_once(shards, parts, ok, klog, partials, partial, &ran_split, ok);
-  if (rc) return rc;
+  rc = run_shards_once(shards, parts, ok, klog, partials, partial, &ran_split, ok, eval_h, bad_rows);
+  if (rc || *bad_rows) return rc;
   if (ran_split) set_form(ZKR_SHARDED_SPLIT_H, "split calcH: %s", policy == 1 ? "ZKR_SHARD_SPLIT_H=1" : distinct ? "checked against the replicated form on first use" : "all shards on one device");
   else set_form(ZKR_SHARDED_REPLICATED_H, "replicated calcH: %s", ok ? "a shard's host thread could not be started" : why);
   return zkr_prove_combine(shards[0], partials.data(), parts, r32, s32, proof_out);
@@ -504,6 +641,12 @@ int zkr_prove_sharded_last_form(int *form_out, char *reason_out, size_t reason_l
   if (!form_out) { set_error("null argument"); return ZKR_ERR_ARG; }
   *form_out = last_form;
   if (reason_out && reason_len) { strncpy(reason_out, last_reason, reason_len - 1); reason_out[reason_len - 1] = 0; }
+  return 0;
+}
+int zkr_prove_sharded_last_h_form(int *form_out, char *reason_out, size_t reason_len) {
+  if (!form_out) { set_error("null argument"); return ZKR_ERR_ARG; }
+  *form_out = last_h_form;
+  if (reason_out && reason_len) { strncpy(reason_out, last_h_reason, reason_len - 1); reason_out[reason_len - 1] = 0; }
   return 0;
 }
 int zkr_key_replication(const zkr_key *key, int *mode_out, int *peer_direct_out) {

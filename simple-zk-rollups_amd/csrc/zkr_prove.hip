@@ -258,6 +258,9 @@ int calc_h_device(zkr_key *k, ProofSlot &sl, hipStream_t s, int nbat) {
 // into the slot's pinned words (prove_collect reads them with the proofs' results), the two coefficient transforms, the two coset
 // transforms (canonical stores on their last pass), one product per row.  nbat witnesses end to end (a fused group) share every
 // launch: vectors at stride m, one counter word per witness, ONE copy of the nbat words.
+// A shard with side tables (zkr_key_shard_opts) in a sharded proof that computes h on every shard: the same sequence over the whole
+// domain -- every shard counts all the rows -- but the product is made over the shard's range of d only, the scalars its part of E'
+// takes (natural order: the range is contiguous).
 static int calc_h_eval(zkr_key *k, ProofSlot &sl, hipStream_t s, int nbat) {
   const Prof pf{k, &sl};
   const ArenaHeader &h = k->h;
@@ -265,14 +268,15 @@ static int calc_h_eval(zkr_key *k, ProofSlot &sl, hipStream_t s, int nbat) {
   const NttTables tb{(const Fr *)(k->arena + h.off_tw), k->tw29, k->twl29, (int)h.tlog};
   const uint32_t m = h.m;
   spmv_enqueue(k, sl, s, 0, m, nbat, true);
-  eval_unsatisfied_kernel<<<dim3((m + 255) / 256, nbat), 256, 0, s>>>(sl.va, sl.vb, sl.d_h, m, sl.d_bad);
+  eval_unsatisfied_kernel<<<dim3((m + 255) / 256, nbat), 256, 0, s>>>(sl.va, sl.vb, sl.d_h, m, sl.d_bad, 0, m);
   ZKR_HIP_CHECK(hipMemcpyAsync(sl.h_bad, sl.d_bad, (size_t)nbat * 4, hipMemcpyDeviceToHost, s));
+  const uint32_t d0 = h.sc_lo[1], d1 = h.sc_lo[1] + h.sc_n[1];  // a whole key: 0 and m
   const int sp = prof_begin(pf, s, "ntt");
   int rc;
   if ((rc = run_ntt(s, sl.va, nullptr, sl.ca, tb, L, true, true, PRE_NONE, nbat, pf, sl.vb, nullptr, sl.cb))) return rc;
   if ((rc = run_ntt(s, sl.ca, nullptr, sl.ca, tb, L, false, false, PRE_COSET, nbat, pf, sl.cb, nullptr, sl.cb))) return rc;
   const int csp = prof_begin(pf, s, "combine_h");  // the stage record keeps its keys: the product stands where the combination stood
-  eval_product_kernel<<<dim3((m + 255) / 256, nbat), 256, 0, s>>>(sl.ca, sl.cb, sl.d_h, m, sl.dig_h.rng, DIGIT_CLEAR_WORDS);
+  eval_product_kernel<<<dim3((d1 - d0 + 255) / 256, nbat), 256, 0, s>>>(sl.ca, sl.cb, sl.d_h, m, sl.dig_h.rng, DIGIT_CLEAR_WORDS, d0, d1);
   prof_end(pf, s, csp);
   prof_end(pf, s, sp);
   ZKR_HIP_CHECK(hipGetLastError());
@@ -326,13 +330,22 @@ static int run_ntt_cross(hipStream_t s, const NttTables &tb, int L, int klog, bo
 //      their product; CROSS top stages of iNTT(product)                       -> ca (this shard's columns of every block)
 //   5  the block's own stages of that; h = combination on the block           -> d_h (block j).  No barrier: the rest is the shard's own
 // The enqueue lock of the device is released while the thread waits (shards on one device share its streams and its lock).
-static int calc_h_split_phases(zkr_key *k, ProofSlot &sl, hipStream_t s, ShardGroup &g, unsigned part, std::unique_lock<std::mutex> &lock);
-static int calc_h_split(zkr_key *k, ProofSlot &sl, hipStream_t s, ShardGroup &g, unsigned part, std::unique_lock<std::mutex> &lock) {
-  const int rc = calc_h_split_phases(k, sl, s, g, part, lock);
+// eval -- H in evaluation form, every shard of the group with side tables (calc_h_eval has the sequence): the same five phases and
+// four barriers with a third less in them.  The product of the coset evaluations is the end, so iNTT(a.b) and the last inverse
+// transform go, and what block j must hold is d in NATURAL order:
+//   1  QAP rows of the block for A, B and C (C's into the block of d_h, free until 5) and the count of its unsatisfied rows
+//   2  CROSS top stages of iNTT(a), iNTT(b)              [all blocks' va, vb] -> ca, cb (this shard's columns of every block)
+//   3  the blocks' own stages of the two; the coset transforms up to their top stages
+//   4  CROSS top stages of the coset transforms, canonical, IN PLACE: this shard's columns of every block's ca, cb -- which no
+//      other shard touches -- so that after the barrier block j of ca, cb on shard j holds the evaluations in natural order
+//   5  d = their product on the block                                          -> d_h (block j)
+static int calc_h_split_phases(zkr_key *k, ProofSlot &sl, hipStream_t s, ShardGroup &g, unsigned part, std::unique_lock<std::mutex> &lock, bool eval);
+static int calc_h_split(zkr_key *k, ProofSlot &sl, hipStream_t s, ShardGroup &g, unsigned part, std::unique_lock<std::mutex> &lock, bool eval) {
+  const int rc = calc_h_split_phases(k, sl, s, g, part, lock, eval);
   if (rc) g.abort();  // whoever waits for this shard (now or at a later barrier) gives up too
   return rc;
 }
-static int calc_h_split_phases(zkr_key *k, ProofSlot &sl, hipStream_t s, ShardGroup &g, unsigned part, std::unique_lock<std::mutex> &lock) {
+static int calc_h_split_phases(zkr_key *k, ProofSlot &sl, hipStream_t s, ShardGroup &g, unsigned part, std::unique_lock<std::mutex> &lock, bool eval) {
   const Prof pf{k, &sl};
   const ArenaHeader &h = k->h;
   const Fr *tw = (const Fr *)(k->arena + h.off_tw);
@@ -365,7 +378,11 @@ static int calc_h_split_phases(zkr_key *k, ProofSlot &sl, hipStream_t s, ShardGr
     for (unsigned b = 0; b < P; b++) g.vecs[b] = g.vecs[part];
   // 1: QAP rows of the block
   phase_begin();
-  spmv_enqueue(k, sl, s, blk, blk + Bk, 1);
+  spmv_enqueue(k, sl, s, blk, blk + Bk, 1, eval);
+  if (eval) {  // the block's rows with a_j b_j != c_j; the count has landed when the phase ends (its stream is idle then)
+    eval_unsatisfied_kernel<<<dim3((Bk + 255) / 256, 1), 256, 0, s>>>(sl.va, sl.vb, sl.d_h, m, sl.d_bad, blk, blk + Bk);
+    ZKR_HIP_CHECK(hipMemcpyAsync(sl.h_bad, sl.d_bad, 4, hipMemcpyDeviceToHost, s));
+  }
   if ((rc = phase_end())) return rc;
   const Fr *r_va[8], *r_vb[8], *r_ca[8], *r_cb[8], *r_ga[8], *r_gb[8];
   Fr *w_ca[8], *w_cb[8], *w_dh[8], *w_ga[8], *w_gb[8];
@@ -382,7 +399,7 @@ static int calc_h_split_phases(zkr_key *k, ProofSlot &sl, hipStream_t s, ShardGr
   phase_begin();
   if ((rc = run_ntt_cross(s, tb, L, klog, true, true, PRE_NONE, false, r_va, nullptr, w_ca, 0, 0, col_lo, cols, pf))) return rc;
   if ((rc = run_ntt_cross(s, tb, L, klog, true, true, PRE_NONE, false, r_vb, nullptr, w_cb, 0, 0, col_lo, cols, pf))) return rc;
-  if ((rc = run_ntt_cross(s, tb, L, klog, true, true, PRE_MUL, false, r_va, r_vb, w_dh, 0, 0, col_lo, cols, pf))) return rc;
+  if (!eval && (rc = run_ntt_cross(s, tb, L, klog, true, true, PRE_MUL, false, r_va, r_vb, w_dh, 0, 0, col_lo, cols, pf))) return rc;
   if ((rc = phase_end())) return rc;
   // 3: the block's own stages
   phase_begin();
@@ -392,11 +409,27 @@ static int calc_h_split_phases(zkr_key *k, ProofSlot &sl, hipStream_t s, ShardGr
     for (int i = 0; i < klog; i++) rev |= ((part >> i) & 1u) << (klog - 1 - i);
     if ((rc = run_ntt(s, ca, nullptr, ca, tb, Lb, true, true, PRE_NONE, 1, pf, cb, nullptr, cb))) return rc;              // coefficients of a, b (x m, bit-reversed)
     if ((rc = run_ntt(s, ca, nullptr, ca, tb, Lb, false, false, PRE_COSET, 1, pf, cb, nullptr, cb, 0, 0, (uint32_t)klog, rev))) return rc;  // coset transforms below their top stages
-    if ((rc = run_ntt(s, dh, nullptr, dh, tb, Lb, true, true, PRE_NONE, 1, pf))) return rc;                             // S' on the block
+    if (!eval && (rc = run_ntt(s, dh, nullptr, dh, tb, Lb, true, true, PRE_NONE, 1, pf))) return rc;                    // S' on the block
   }
   if ((rc = phase_end())) return rc;
   // 4: top stages of the coset transforms into local columns, product, top stages of the last inverse transform
   phase_begin();
+  if (eval) {
+    if ((rc = run_ntt_cross(s, tb, L, klog, false, false, PRE_NONE, true, r_ca, nullptr, w_ca, 0, 0, col_lo, cols, pf))) return rc;
+    if ((rc = run_ntt_cross(s, tb, L, klog, false, false, PRE_NONE, true, r_cb, nullptr, w_cb, 0, 0, col_lo, cols, pf))) return rc;
+    if ((rc = phase_end())) return rc;
+    // 5: d on the block
+    phase_begin();
+    const int psp = prof_begin(pf, s, "combine_h");  // as in calc_h_eval: the product stands where the combination stood
+    eval_product_kernel<<<dim3((Bk + 255) / 256, 1), 256, 0, s>>>(sl.ca, sl.cb, sl.d_h, m, sl.dig_h.rng, DIGIT_CLEAR_WORDS, blk, blk + Bk);
+    prof_end(pf, s, psp);
+    prof_end(pf, s, ntt_span);
+    ZKR_HIP_CHECK(hipGetLastError());
+    struct timespec t1;
+    clock_gettime(CLOCK_MONOTONIC, &t1);
+    if (phase < 8) g.phase_ms[part][phase] = (t1.tv_sec - t0.tv_sec) * 1e3 + (t1.tv_nsec - t0.tv_nsec) * 1e-6;  // enqueue time only: nothing waits here
+    return 0;
+  }
   if ((rc = run_ntt_cross(s, tb, L, klog, false, false, PRE_NONE, true, r_ca, nullptr, w_ga, 0, col_lo, col_lo, cols, pf))) return rc;
   if ((rc = run_ntt_cross(s, tb, L, klog, false, false, PRE_NONE, true, r_cb, nullptr, w_gb, 0, col_lo, col_lo, cols, pf))) return rc;
   if ((rc = run_ntt_cross(s, tb, L, klog, true, true, PRE_MUL, false, r_ga, r_gb, w_ca, col_lo, 0, col_lo, cols, pf))) return rc;
@@ -707,10 +740,13 @@ static int prove_submit_enqueue(zkr_key *k, ProofSlot &sl, const Fr *const *d_ws
   // (HISTORY.md 7b / 13: a tx proof 2.13-2.40 against 1.98 ms, 2^20 the same).
   ShardGroup *const group = shard_group;
   const bool split_h = group && group->split_h && !serial && nbat == 1 && h.shard_parts == group->parts && h.shard_part == shard_group_part;
-  // H in evaluation form: a whole-key proof, alone or in a fused group, on a key that has the side tables.  Shards and the split
-  // calcH keep the coefficient form.  C and H then gather from C' and E', which have the layouts and plans of the tables they
-  // stand in for (EvalTables): the sorts, bucket sets (one per proof and table) and chains below do not change.
-  const bool eval = k->eval.ready && !coefficients && h.shard_parts == 1 && !split_h;
+  // H in evaluation form: a whole-key proof, alone or in a fused group, on a key that has the side tables; a shard with side tables
+  // only as part of a sharded proof whose caller has seen that EVERY shard has them (ShardGroup::eval_h: the partial sums of the
+  // two forms differ shard by shard, only their sums over all shards agree).  A shard proving on its own keeps the coefficient
+  // form.  C and H then gather from C' and E', which have the layouts and plans of the tables they stand in for (EvalTables): the
+  // sorts, bucket sets (one per proof and table) and chains below do not change.
+  const bool group_eval = group && group->eval_h && nbat == 1 && h.shard_parts == group->parts && h.shard_part == shard_group_part;
+  const bool eval = k->eval.ready && !coefficients && (h.shard_parts == 1 ? !split_h : group_eval);
   sl.eval = eval;
   auto table_points = [&](int t) -> const void * { return eval && t == T_C ? k->eval.c_pts : eval && t == T_H ? k->eval.e_pts : ar + h.off_pts[t]; };
   const DigitLists *dig[N_TABLES] = {&sl.dig_w, &sl.dig_w, &sl.dig_w, &sl.dig_w, &sl.dig_h};
@@ -808,7 +844,7 @@ static int prove_submit_enqueue(zkr_key *k, ProofSlot &sl, const Fr *const *d_ws
   if ((rc = sort_table(T_A))) return rc;
   if (!lay.share_ac && (rc = sort_table(T_C))) return rc;
   if (early && ((rc = c_big()) || (rc = chains({T_A, T_C})))) return rc;
-  if (split_h) rc = calc_h_split(k, sl, sp, *group, shard_group_part, enqueue_lock);
+  if (split_h) rc = calc_h_split(k, sl, sp, *group, shard_group_part, enqueue_lock, eval);
   else if (eval) rc = calc_h_eval(k, sl, sp, nbat);
   else rc = calc_h_device(k, sl, sp, nbat);
   if (rc) return rc;
@@ -925,8 +961,12 @@ again:
   // touched.  The WHOLE group goes again, not the failing witnesses compacted into a smaller one: a resubmit overwrites the chains'
   // pinned result buffers, so the good proofs' sums would have to be set aside first, and an unsatisfying witness is the rare case.
   // `retries` counts the witnesses that failed -- what it means for lone proofs, whatever the groups a batch was cut into.
+  // A shard's count goes to its group instead (this thread's: run_sharded started it): whether the witness satisfies the system is
+  // known from the counts of ALL shards, and the proof goes again on every one of them (zkr_multi.hip run_sharded).
   int n_bad = 0;
-  if (sl.eval)
+  if (sl.eval && k->h.shard_parts > 1) {
+    if (shard_group && shard_group_part < shard_group->unsatisfied.size()) shard_group->unsatisfied[shard_group_part] = sl.h_bad[0];
+  } else if (sl.eval)
     for (int j = 0; j < sl.nbat; j++) n_bad += sl.h_bad[j] != 0;
   if (n_bad) {
     k->eval.retries.fetch_add((uint64_t)n_bad);

@@ -92,12 +92,15 @@ export class WithdrawCircuit {
 // ---- process-level key cache (the reference builds a new Bn128 per proof: common.ts:23) and verifier constants
 /** Device keys loaded / found in the cache by groth16GenProof so far in this process. */
 export function keyCacheStats(): { loads: number; hits: number; replications: number; shardings?: number; entries: number; handles: number; shardedLastForm: ShardedForm };
-/** Which form the last sharded proof (groth16GenProof with opts.devices) took and why: calcH split over the shards, or computed by every shard for itself. */
-export interface ShardedForm { form: "none" | "split" | "replicated"; reason: string }
+/** Which form the last sharded proof (groth16GenProof with opts.devices) took and why: calcH split over the shards, or computed by every shard for itself;
+ *  hForm / hReason: H in evaluation form (every shard was cut with side tables: the cached key had them) or in coefficient form. */
+export interface ShardedForm { form: "none" | "split" | "replicated"; reason: string; hForm: "none" | "coefficients" | "evaluation"; hReason: string }
 export function shardedLastForm(): ShardedForm;
 /** How a native key handle came to its device: loaded there ("none") or copied device to device (zkr_key_replicate) in the full or the compact form. */
 /** zkr_key_eval_tables for a key handle: true when the key proves through the evaluation form from now on. */
 export function keyEvalTables(key: unknown, r1csBin: Uint8Array): boolean;
+/** zkr_key_h_form for a key handle (a whole key or a shard): whether it has the side tables, and the witnesses proved again so far. */
+export function keyHForm(key: unknown): { form: "coefficients" | "evaluation"; retries: number };
 export function keyReplication(key: unknown): { mode: "none" | "full" | "base"; peerDirect: boolean };
 export function keyFingerprint(provingKeyBin: ArrayBuffer | Uint8Array, full?: boolean): string;
 export function clearKeyCache(): void;

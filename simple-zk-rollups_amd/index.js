@@ -152,14 +152,19 @@ function cachedReplicas(provingKeyBin, devices) {
   return keys;
 }
 // the shards of a key over `devices` (one shard per entry, shard i = part i of devices.length on devices[i]): built once from the
-// cached whole key (zkr_key_shard: window levels copied device to device) and kept with it in the cache entry
+// cached whole key (zkr_key_shard: window levels copied device to device) and kept with it in the cache entry.  A cached key that has
+// the side tables of the evaluation form (keyEvalTables on its handle) is cut WITH them (zkr_key_shard_opts): the sharded proof then
+// runs four transforms instead of six.  Sets cut with and without tables are different sets: tables derived after a first sharded
+// proof take effect with the next one.
 function cachedShards(provingKeyBin, devices) {
-  const ent = cacheEntry(provingKeyBin), slot = "shards:" + devices.join(",");
+  const ent = cacheEntry(provingKeyBin);
+  let whole = anyReplica(ent);
+  const tables = whole !== undefined && native().keyHForm(whole).form === "evaluation";
+  const slot = "shards:" + devices.join(",") + (tables ? ":eval" : "");
   let shards = ent.get(slot);
   if (shards !== undefined) { keyCacheStats.hits++; ent.delete(slot); ent.set(slot, shards); return shards; }
-  let whole = anyReplica(ent);
   if (whole === undefined) { whole = native().keyLoad(provingKeyBin, devices[0]); keyCacheStats.loads++; ent.set(devices[0] + "#0", whole); }
-  shards = devices.map((d, i) => native().keyShard(whole, i, devices.length, d));
+  shards = devices.map((d, i) => native().keyShard(whole, i, devices.length, d, tables));
   keyCacheStats.shardings = (keyCacheStats.shardings || 0) + 1;
   const sets = Array.from(ent.keys()).filter((k) => k.startsWith("shards:"));
   while (sets.length >= MAX_SHARD_SETS) ent.delete(sets.shift());  // bounded: a caller cycling through device lists does not pile up shard sets
@@ -540,11 +545,14 @@ module.exports = {
   buildBn128, genProof, binarifyWitness, binarifyProvingKey, solidityProof, proofFromBytes, isValid, isValidBatch, binarifyVerifyingKey,
   contributionCheck, vkContribute,
   binarifyR1cs, verifyingKeyFromBytes, solidityVerifyingKey, solidityVerifyingKeySource,
-  // which form the last sharded proof took and why ({form: "split" | "replicated" | "none", reason}); how a key handle came to its device
+  // which form the last sharded proof took and why ({form: "split" | "replicated" | "none", reason, hForm: "evaluation" | "coefficients" |
+  // "none", hReason}); how a key handle came to its device
   shardedLastForm: () => native().shardedLastForm(), keyReplication: (key) => native().keyReplication(key),
   // the same for a key handle: true when the key proves through the evaluation form from now on (zkr_key_eval_tables)
   keyEvalTables: (key, r1csBin) => native().keyEvalTables(key, r1csBin),
-  keyCacheStats: () => Object.assign({ shardedLastForm: addon ? native().shardedLastForm() : { form: "none", reason: "" } }, { entries: keyCache.size, handles: Array.from(keyCache.values()).reduce((a, e) => a + Array.from(e.entries()).reduce((b, [k, v]) => b + (k === "ref" || k === "src" ? 0 : Array.isArray(v) ? v.length : 1), 0), 0) }, keyCacheStats), clearKeyCache, keyFingerprint,
+  // whether a key handle (a whole key or a shard) has them: {form: "evaluation" | "coefficients", retries} (zkr_key_h_form)
+  keyHForm: (key) => native().keyHForm(key),
+  keyCacheStats: () => Object.assign({ shardedLastForm: addon ? native().shardedLastForm() : { form: "none", reason: "", hForm: "none", hReason: "" } }, { entries: keyCache.size, handles: Array.from(keyCache.values()).reduce((a, e) => a + Array.from(e.entries()).reduce((b, [k, v]) => b + (k === "ref" || k === "src" ? 0 : Array.isArray(v) ? v.length : 1), 0), 0) }, keyCacheStats), clearKeyCache, keyFingerprint,
   _cacheEntry: cacheEntry,  // the cache's lookup alone (no device involved): tests/test_node_host.py
   multiHash, multiHashBatch, buildBalanceTree, hashLeftRight, genPublicKey, formatPrivKeyForBabyJub, sign, verify, RollupCircuit, WithdrawCircuit,
   deviceCount: () => { native(); return deviceCount; },

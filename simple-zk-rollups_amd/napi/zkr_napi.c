@@ -53,11 +53,15 @@ static struct {
   int (*contribution_check)(const uint8_t *, int *);
   int (*vk_contribute)(const void *, size_t, const uint8_t *, void **, size_t *);
   int (*key_eval_tables)(zkr_key *, const void *, size_t, unsigned, int *); /* optional: NULL with a library older than the call */
+  /* optional as well: shards with the side tables of the evaluation form, and which form of H a sharded proof took */
+  int (*key_shard_opts)(const zkr_key *, unsigned, unsigned, int, unsigned, zkr_key **);
+  int (*sharded_last_h_form)(int *, char *, size_t);
+  int (*key_h_form)(const zkr_key *, int *, uint64_t *);
 } Z;
 /* which form the last sharded proof took (zkr_prove_sharded_last_form, read on the worker thread that ran it, published on the JS
  * thread when its promise settles) */
-static int g_sharded_form = 0;
-static char g_sharded_reason[256] = "";
+static int g_sharded_form = 0, g_sharded_h_form = 0;
+static char g_sharded_reason[256] = "", g_sharded_h_reason[256] = "";
 
 #define NAPI_OK(call)                                                     \
   do {                                                                    \
@@ -101,6 +105,9 @@ static napi_value js_load(napi_env env, napi_callback_info info) {
     SYM(sharded_last_form, "zkr_prove_sharded_last_form") SYM(key_replication, "zkr_key_replication")
     SYM(key_contribute, "zkr_key_contribute") SYM(contribution_check, "zkr_contribution_check") SYM(vk_contribute, "zkr_vk_contribute")
     *(void **)(&Z.key_eval_tables) = dlsym(h, "zkr_key_eval_tables"); /* looked up optionally: an older library still loads */
+    *(void **)(&Z.key_shard_opts) = dlsym(h, "zkr_key_shard_opts");
+    *(void **)(&Z.sharded_last_h_form) = dlsym(h, "zkr_prove_sharded_last_h_form");
+    *(void **)(&Z.key_h_form) = dlsym(h, "zkr_key_h_form");
     Z.handle = h;
   }
   napi_value out;
@@ -171,11 +178,13 @@ static napi_value js_key_replicate(napi_env env, napi_callback_info info) {
   NAPI_OK(napi_create_external(env, key, key_finalize, NULL, &ext));
   return ext;
 }
-/* keyShard(key, part, parts, device) -> external handle of shard `part` of `parts` of the whole key on `device` (zkr_key_shard: one
- * contiguous range of every MSM of a proof, all window levels copied device to device, plus the whole QAP).  Synchronous. */
+/* keyShard(key, part, parts, device[, sideTables]) -> external handle of shard `part` of `parts` of the whole key on `device`
+ * (zkr_key_shard: one contiguous range of every MSM of a proof, all window levels copied device to device, plus the whole QAP).
+ * sideTables: true asks for the shard's range of the side tables of the evaluation form as well (zkr_key_shard_opts with
+ * ZKR_SHARD_SIDE_TABLES; a key without tables gives a coefficient-form shard all the same).  Synchronous. */
 static napi_value js_key_shard(napi_env env, napi_callback_info info) {
-  size_t argc = 4;
-  napi_value argv[4];
+  size_t argc = 5;
+  napi_value argv[5];
   NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
   if (!Z.handle) return throw_msg(env, "libzkr_hip.so not loaded");
   zkr_key *src = NULL, *key = NULL;
@@ -184,7 +193,10 @@ static napi_value js_key_shard(napi_env env, napi_callback_info info) {
   if (argc < 4 || napi_get_value_external(env, argv[0], (void **)&src) != napi_ok || napi_get_value_uint32(env, argv[1], &part) != napi_ok ||
       napi_get_value_uint32(env, argv[2], &parts) != napi_ok || napi_get_value_int32(env, argv[3], &dev) != napi_ok)
     return throw_msg(env, "keyShard(key, part, parts, device)");
-  if (Z.key_shard(src, part, parts, dev, &key)) return throw_msg(env, Z.last_error());
+  bool side_tables = false;
+  if (argc >= 5 && napi_get_value_bool(env, argv[4], &side_tables) != napi_ok) return throw_msg(env, "keyShard: sideTables must be a boolean");
+  if (side_tables && !Z.key_shard_opts) return throw_msg(env, "this libzkr_hip.so has no zkr_key_shard_opts");
+  if (side_tables ? Z.key_shard_opts(src, part, parts, dev, 1u /* ZKR_SHARD_SIDE_TABLES */, &key) : Z.key_shard(src, part, parts, dev, &key)) return throw_msg(env, Z.last_error());
   napi_value ext;
   NAPI_OK(napi_create_external(env, key, key_finalize, NULL, &ext));
   return ext;
@@ -400,6 +412,8 @@ typedef struct {
   char err[512];
   int form;            /* proveSharded: split / replicated calcH and why */
   char reason[256];
+  int h_form;          /* ... and H in coefficient / evaluation form and why */
+  char h_reason[256];
 } prove_job;
 
 static void prove_execute(napi_env env, void *data) {  /* libuv worker thread: the event loop is not blocked */
@@ -409,12 +423,16 @@ static void prove_execute(napi_env env, void *data) {  /* libuv worker thread: t
                     : Z.prove(j->key, j->wit, j->wit_len, j->have_rs ? j->r : NULL, j->have_rs ? j->s : NULL, j->proof, NULL);
   if (j->rc) { strncpy(j->err, Z.last_error(), sizeof(j->err) - 1); j->err[sizeof(j->err) - 1] = 0; }
   if (j->shards) Z.sharded_last_form(&j->form, j->reason, sizeof(j->reason));  /* thread-local in the library: this thread ran the proof */
+  if (j->shards && Z.sharded_last_h_form) Z.sharded_last_h_form(&j->h_form, j->h_reason, sizeof(j->h_reason));
 }
 
 static void prove_complete(napi_env env, napi_status status, void *data) {
   prove_job *j = (prove_job *)data;
   napi_value v;
-  if (j->shards && status == napi_ok) { g_sharded_form = j->form; memcpy(g_sharded_reason, j->reason, sizeof(g_sharded_reason)); }
+  if (j->shards && status == napi_ok) {
+    g_sharded_form = j->form; memcpy(g_sharded_reason, j->reason, sizeof(g_sharded_reason));
+    g_sharded_h_form = j->h_form; memcpy(g_sharded_h_reason, j->h_reason, sizeof(g_sharded_h_reason));
+  }
   if (status == napi_ok && j->rc == 0) {
     void *out;
     napi_create_buffer_copy(env, 256, j->proof, &out, &v);
@@ -481,16 +499,43 @@ static napi_value prove_common(napi_env env, napi_callback_info info, int sharde
   }
   return promise;
 }
-/* shardedLastForm() -> {form: "none" | "split" | "replicated", reason}: of the last proveSharded whose promise has settled */
+/* shardedLastForm() -> {form: "none" | "split" | "replicated", reason, hForm: "none" | "coefficients" | "evaluation", hReason}: of the
+ * last proveSharded whose promise has settled */
 static napi_value js_sharded_last_form(napi_env env, napi_callback_info info) {
   (void)info;
   static const char *names[] = {"none", "split", "replicated"};
-  napi_value out, f, r;
+  static const char *h_names[] = {"none", "coefficients", "evaluation"};
+  napi_value out, f, r, hf, hr;
   NAPI_OK(napi_create_object(env, &out));
   NAPI_OK(napi_create_string_utf8(env, names[g_sharded_form >= 0 && g_sharded_form <= 2 ? g_sharded_form : 0], NAPI_AUTO_LENGTH, &f));
   NAPI_OK(napi_create_string_utf8(env, g_sharded_reason, NAPI_AUTO_LENGTH, &r));
+  NAPI_OK(napi_create_string_utf8(env, h_names[g_sharded_h_form >= 0 && g_sharded_h_form <= 2 ? g_sharded_h_form : 0], NAPI_AUTO_LENGTH, &hf));
+  NAPI_OK(napi_create_string_utf8(env, g_sharded_h_reason, NAPI_AUTO_LENGTH, &hr));
   NAPI_OK(napi_set_named_property(env, out, "form", f));
   NAPI_OK(napi_set_named_property(env, out, "reason", r));
+  NAPI_OK(napi_set_named_property(env, out, "hForm", hf));
+  NAPI_OK(napi_set_named_property(env, out, "hReason", hr));
+  return out;
+}
+/* keyHForm(key) -> {form: "coefficients" | "evaluation", retries}: whether the key (a whole key or a shard) has the side tables of the
+ * evaluation form, and the witnesses proved again so far (zkr_key_h_form) */
+static napi_value js_key_h_form(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (!Z.handle) return throw_msg(env, "libzkr_hip.so not loaded");
+  if (!Z.key_h_form) return throw_msg(env, "this libzkr_hip.so has no zkr_key_h_form");
+  zkr_key *key = NULL;
+  if (argc < 1 || napi_get_value_external(env, argv[0], (void **)&key) != napi_ok) return throw_msg(env, "keyHForm(key)");
+  int ev = 0;
+  uint64_t retries = 0;
+  if (Z.key_h_form(key, &ev, &retries)) return throw_msg(env, Z.last_error());
+  napi_value out, f, n;
+  NAPI_OK(napi_create_object(env, &out));
+  NAPI_OK(napi_create_string_utf8(env, ev ? "evaluation" : "coefficients", NAPI_AUTO_LENGTH, &f));
+  NAPI_OK(napi_create_double(env, (double)retries, &n));
+  NAPI_OK(napi_set_named_property(env, out, "form", f));
+  NAPI_OK(napi_set_named_property(env, out, "retries", n));
   return out;
 }
 /* keyReplication(key) -> {mode: "none" | "full" | "base", peerDirect}: how the key came to its device (zkr_key_replication) */
@@ -865,6 +910,7 @@ static napi_value init(napi_env env, napi_value exports) {
       {"contributionCheck", NULL, js_contribution_check, NULL, NULL, NULL, napi_default, NULL},
       {"vkContribute", NULL, js_vk_contribute, NULL, NULL, NULL, napi_default, NULL},
       {"keyEvalTables", NULL, js_key_eval_tables, NULL, NULL, NULL, napi_default, NULL},
+      {"keyHForm", NULL, js_key_h_form, NULL, NULL, NULL, napi_default, NULL},
   };
   napi_define_properties(env, exports, sizeof(props) / sizeof(props[0]), props);
   return exports;

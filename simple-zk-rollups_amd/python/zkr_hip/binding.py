@@ -6,6 +6,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ZKR_HIP_LIB") or os.path.normpath(os.path.join(_HERE, "..", "..", "csrc", "libzkr_hip.so"))  # same override as index.js
 PROOF_BYTES = 256
 PARTIAL_BYTES = 640   # zkr.h ZKR_PARTIAL_BYTES
+SHARD_SIDE_TABLES = 1  # ZKR_SHARD_SIDE_TABLES
 CONTRIBUTION_BYTES = 352   # zkr.h ZKR_CONTRIBUTION_BYTES
 PTAU_RECORD_BYTES = 928   # zkr.h ZKR_PTAU_RECORD_BYTES
 REPLICATE_MODES = {"auto": 0, "full": 1, "base": 2}   # zkr.h ZKR_REPLICATE_*
@@ -76,6 +77,8 @@ def lib():
     L.zkr_prove_batch_multi.argtypes = [c.POINTER(vp), sz, c.POINTER(c.c_char_p), sz, sz, u8p, u8p, u8p]
     L.zkr_prove_batch_multi_device.argtypes = [c.POINTER(vp), sz, c.POINTER(vp), sz, u8p, u8p, u8p]
     L.zkr_key_shard.argtypes = [vp, c.c_uint, c.c_uint, i, c.POINTER(vp)]
+    L.zkr_key_shard_opts.argtypes = [vp, c.c_uint, c.c_uint, i, c.c_uint, c.POINTER(vp)]
+    L.zkr_prove_sharded_last_h_form.argtypes = [c.POINTER(i), c.c_char_p, sz]
     L.zkr_key_shard_info.argtypes = [vp, c.POINTER(c.c_uint32)]
     L.zkr_prove_partial.argtypes = [vp, u8p, sz, u8p]
     L.zkr_prove_partial_device.argtypes = [vp, vp, vp, u8p]
@@ -281,12 +284,15 @@ class ProvingKey:
         _check(lib().zkr_key_replication(self._h, ctypes.byref(mode), ctypes.byref(direct)))
         return {"mode": {0: "none", 1: "full", 2: "base"}[mode.value], "peer_direct": bool(direct.value)}
 
-    def shard(self, part, parts, device=None):
+    def shard(self, part, parts, device=None, side_tables=False):
         """Shard `part` of `parts` of this (whole) key on `device` (default: the key's own): the points of one contiguous range
-        of every MSM of a proof, all window levels, plus the whole QAP (zkr_key_shard)."""
+        of every MSM of a proof, all window levels, plus the whole QAP (zkr_key_shard).
+        side_tables: also the shard's range of the side tables of the evaluation form, when this key has them
+        (zkr_key_shard_opts with ZKR_SHARD_SIDE_TABLES): prove_sharded over shards that ALL have them runs H in evaluation
+        form.  A shard that could not get them is a coefficient-form shard (h_form() says so, zkr_last_error() why)."""
         h = ctypes.c_void_p()
         dev = self.device if device is None else device
-        _check(lib().zkr_key_shard(self._h, part, parts, dev, ctypes.byref(h)))
+        _check(lib().zkr_key_shard_opts(self._h, part, parts, dev, SHARD_SIDE_TABLES if side_tables else 0, ctypes.byref(h)))
         return ProvingKey(h, dev)
 
     def bench_split_solo(self, d_witness_ptr) -> float:
@@ -349,8 +355,8 @@ class ProvingKey:
     def eval_tables(self, r1cs_bin: bytes) -> bool:
         """The side tables of the evaluation form from this key's own points and the circuit's C side (zkr_key_eval_tables): any
         whole key -- websnark bytes, a file, a transcript, a replica, a contributed key.  True: h_form() says 'evaluation' from
-        now on.  False: the key keeps the coefficient form and zkr_hip.lib().zkr_last_error() says why.  Saving, replicating,
-        sharding and contributing carry no tables: derive again on the key they return."""
+        now on.  False: the key keeps the coefficient form and zkr_hip.lib().zkr_last_error() says why.  Saving, replicating
+        and contributing carry no tables: derive again on the key they return; shard(side_tables=True) cuts them with the shard."""
         built = ctypes.c_int(0)
         _check(lib().zkr_key_eval_tables(self._h, bytes(r1cs_bin), len(r1cs_bin), 0, ctypes.byref(built)))
         return bool(built.value)
@@ -640,6 +646,7 @@ def sharded_split_stats():
 
 
 SHARDED_FORMS = {0: "none", 1: "split", 2: "replicated"}
+SHARDED_H_FORMS = {0: "none", 1: "coefficients", 2: "evaluation"}
 
 
 def sharded_last_form():
@@ -649,6 +656,15 @@ def sharded_last_form():
     buf = ctypes.create_string_buffer(256)
     _check(lib().zkr_prove_sharded_last_form(ctypes.byref(form), buf, 256))
     return {"form": SHARDED_FORMS.get(form.value, str(form.value)), "reason": buf.value.decode()}
+
+
+def sharded_last_h_form():
+    """Which form of H this thread's last sharded proof took and why (zkr_prove_sharded_last_h_form): {"form": "evaluation" |
+    "coefficients" | "none", "reason": one line}.  Evaluation form runs when every shard was cut with side_tables=True."""
+    form = ctypes.c_int(0)
+    buf = ctypes.create_string_buffer(256)
+    _check(lib().zkr_prove_sharded_last_h_form(ctypes.byref(form), buf, 256))
+    return {"form": SHARDED_H_FORMS.get(form.value, str(form.value)), "reason": buf.value.decode()}
 
 
 def verify(vk_bin: bytes, proof: bytes, public_signals) -> bool:
