@@ -267,10 +267,59 @@ int zkr_verify(const void *vk_bin, size_t vk_len, const uint8_t proof[256], cons
 /* n_proofs proofs (n_proofs x 256 B) with their public signals (n_proofs x n_public x 32 B) under one key, merged by a
  * random linear combination (128-bit coefficients from the OS CSPRNG) into ONE product of n_proofs + 3 pairings with one
  * final exponentiation: *all_valid = 1 iff every proof verifies (an invalid one slips through with
- * probability 2^-128); about 0.5 ms per proof instead of 3.7.  Use zkr_verify to locate a failing proof. */
+ * probability 2^-128); about 0.5 ms per proof instead of 3.7.  Use zkr_verify to locate a failing proof, or
+ * zkr_verify_each (below) for a verdict per proof. */
 int zkr_verify_batch(const void *vk_bin, size_t vk_len, const uint8_t *proofs, const void *publics_std, size_t n_proofs, size_t n_public, int *all_valid);
 
+/* ---- acceptance check on the GPU: a verdict per proof -----------------------------------------------
+ * The same equation (common.ts:30-38, TxVerifier.sol:258-276), one proof per lane, where a batch's witnesses already live:
+ * zkr_rollup_witness_batch_device -> zkr_r1cs_check_device -> zkr_prove_batch_device -> zkr_verify_each_device.  No random
+ * combination: every proof gets its own product of four pairings and its own final exponentiation, so the answer is
+ * deterministic and names the proofs that fail.  For every input, verdicts[i] == 0 exactly when zkr_verify on the same key,
+ * proof and signals sets *valid = 1.
+ *
+ * zkr_vk_load: vk_bin in the layout of zkr_verify, read by the same parser with the same bounds and messages, BEFORE any device
+ * call: a malformed key is ZKR_ERR_BAD_KEY (ZKR_ERR_ARG for a key without an IC point) on a machine without a GPU too, a
+ * well-formed one without a device ZKR_ERR_NO_DEVICE (no CPU fallback).  nPublic is the key's IC count less one.  The handle
+ * owns, on `device`: the 8-bit window table of the IC points (255 affine multiples each), the prepared lines of beta, gamma
+ * and delta, the Miller value of (alfa, beta), the constants of the pairing, one stream, and per-batch buffers that grow to
+ * the largest batch seen (about 4 KiB + nPublic x 32 B per proof).  One zkr_vk serves ONE call at a time, as a zkr_r1cs does;
+ * two handles (of the same key too) run concurrently.
+ * zkr_vk_info: out[0] = nPublic, out[1] = device. */
+typedef struct zkr_vk zkr_vk;
+int zkr_vk_load(const void *vk_bin, size_t vk_len, int device, zkr_vk **out);
+void zkr_vk_free(zkr_vk *vk);
+int zkr_vk_info(const zkr_vk *vk, uint64_t out[2]);
+/* The first check that fails, in the order zkr_verify makes them:
+ *   BAD_G1     A or C: a coordinate not below q, the point at infinity, off the curve;
+ *   BAD_INPUT  a public signal not below r (TxVerifier.sol:265);
+ *   BAD_G2     B: a coordinate not below q, infinity, off the twist, or outside the order-r subgroup;
+ *   EQUATION   e(-A, B) e(alfa, beta) e(vk_x, gamma) e(C, delta) != 1. */
+enum { ZKR_VERDICT_VALID = 0, ZKR_VERDICT_BAD_G1 = 1, ZKR_VERDICT_BAD_INPUT = 2, ZKR_VERDICT_BAD_G2 = 3, ZKR_VERDICT_EQUATION = 4 };
+#define ZKR_VERIFY_PIECE 4096 /* proofs per set of launches: a larger batch is cut into pieces of this size inside the call */
+/* proofs: n_proofs x 256 B in HOST memory (where zkr_prove_batch* leave them).  publics_std: n_proofs x nPublic x 32 B in host
+ * memory (may be NULL when nPublic == 0).  verdicts: n_proofs bytes, may be NULL.  *all_valid = 1 iff every verdict is 0;
+ * n_proofs == 0 is ZKR_OK with *all_valid = 1.  An invalid proof is NOT an error status: ZKR_OK, and zkr_last_error names the
+ * first one ("proof 17: pairing equation fails", "proof 3: B is not in the order-r subgroup").  A status below zero only for
+ * null pointers (ZKR_ERR_ARG) or a HIP failure. */
+int zkr_verify_each(zkr_vk *vk, const uint8_t *proofs, const void *publics_std, size_t n_proofs, uint8_t *verdicts, int *all_valid);
+/* The same with the public signals read in place: d_witnesses_std holds n_proofs device pointers on the key's device (a host
+ * array), proof i's signals are words 1..nPublic of witness i.  Nothing comes back to the host but the verdicts.  A witness word
+ * is judged as it stands and NOT reduced: a word >= r is BAD_INPUT, which is what the contract answers (zkr_r1cs_check_device
+ * reduces it first and may accept the same witness).  stream: as for zkr_prove_device and zkr_r1cs_check_device -- the check
+ * starts after the work already queued there and runs on the handle's own stream; the call returns when the verdicts are on the
+ * host.  A null witness pointer is ZKR_ERR_ARG. */
+int zkr_verify_each_device(zkr_vk *vk, const uint8_t *proofs, const void *const *d_witnesses_std, size_t n_proofs, void *stream,
+                           uint8_t *verdicts, int *all_valid);
+
 /* ---- stage hooks (tests, profiling) ----------------------------------------------------------- */
+/* e(P_i, Q_i) after the final exponentiation, one pair per lane (the arithmetic of zkr_verify_each by itself).  g1_std: n x 64 B,
+ * g2_std: n x 128 B (x.re, x.im, y.re, y.im), standard-form affine; an all-zero point is infinity and gives one.  The points are
+ * taken as given: the caller vouches for curve and subgroup.  out: n x 384 B, the twelve Fq coefficients in standard form in the
+ * tower's order Fq12 = c0 + c1 w, Fq6 = c0 + c1 v + c2 v^2, Fq2 = a + b u:
+ *   c0.c0.a, c0.c0.b, c0.c1.a, c0.c1.b, c0.c2.a, c0.c2.b, c1.c0.a, ..., c1.c2.b    (w^2 = v, v^3 = 9 + u, u^2 = -1).
+ * degenerate[i] (may be NULL) = 1 when the projective Miller loop of pair i met Z = 0 (impossible for a Q of order r). */
+int zkr_pairing_device(const void *g1_std, const void *g2_std, size_t n, void *out, uint8_t *degenerate, int device);
 /* In-place NTT of n = 2^logn standard-form elements in host memory; natural order in and out (words >= r are reduced first). */
 int zkr_ntt(void *data_std, unsigned logn, int inverse, int device);
 /* sum_i scalars[i] * points[i].  points: Montgomery affine as in the key sections (64 B G1 / 128 B G2;

@@ -466,6 +466,27 @@ int zkt_miller_loops_agree(const uint8_t *g1, const uint8_t *g2, uint64_t seed, 
   }
   return agree;
 }
+// The host twin of zkr_pairing_device (include/zkr.h): e(P_i, Q_i) after the final exponentiation through the header code the
+// device kernel runs (miller_loop_proj, final_exponentiation with an explicit Consts), same input and output layout: g1 n x 64 B,
+// g2 n x 128 B standard form (an all-zero point: infinity -> one), out n x 384 B, the twelve coefficients in the tower's order.
+int zkt_pairing(const uint8_t *g1, const uint8_t *g2, size_t n, uint8_t *out, uint8_t *degenerate) {
+  using namespace zkr::pairing;
+  const Consts &k = host_consts();
+  for (size_t i = 0; i < n; i++) {
+    const uint8_t *a = g1 + 64 * i, *b = g2 + 128 * i;
+    G1Affine P{to_mont(load_fp<FqParams>(a)), to_mont(load_fp<FqParams>(a + 32))};
+    G2Affine Q{Fq2{to_mont(load_fp<FqParams>(b)), to_mont(load_fp<FqParams>(b + 32))}, Fq2{to_mont(load_fp<FqParams>(b + 64)), to_mont(load_fp<FqParams>(b + 96))}};
+    bool ok = true;
+    const Fq12 e = final_exponentiation(miller_loop_proj(P, Q, k, &ok), k);
+    const Fq2 *co[6] = {&e.c0.c0, &e.c0.c1, &e.c0.c2, &e.c1.c0, &e.c1.c1, &e.c1.c2};
+    for (int t = 0; t < 6; t++) {
+      store_fp(out + 384 * i + 64 * t, from_mont(co[t]->a));
+      store_fp(out + 384 * i + 64 * t + 32, from_mont(co[t]->b));
+    }
+    if (degenerate) degenerate[i] = ok ? 0 : 1;
+  }
+  return 0;
+}
 // the two G2 membership tests on one twist point (128 B standard form: x.re, x.im, y.re, y.im): bit 0 = the definition
 // ([r]Q == infinity), bit 1 = the endomorphism test the verifier runs (psi(Q) == [6x^2]Q), bit 2 = the point is on the twist
 int zkt_g2_membership(const uint8_t *pt) {

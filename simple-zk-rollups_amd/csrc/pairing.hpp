@@ -11,10 +11,27 @@
 // Affine Miller loops over 6x+2 (all pairs in lockstep, one shared inversion per step) with the two Frobenius
 // correction steps, final exponentiation by plain square-and-multiply -- the same mathematics as the checker in
 // oracle/bn254.py, kept simple on purpose.
+//
+// Host AND device: everything a kernel of zkr_verify_gpu.hip needs (the tower, the line products, the projective steps, the
+// prepared-line loop, the final exponentiation, the curve and subgroup tests) is ZKR_PAIRING_FN: static inline on the host, as it
+// always was, and a REAL CALL on the device.  ZKR_HD is __forceinline__; one Fq12 product is 54 Fq products of ~300 VALU
+// instructions, so a Miller loop inlined through would be many times the instruction cache.  On the device the call boundaries
+// sit at the Fq2 product (m2 / s2 / mul_fq) and at every Fq6 / Fq12 function above it; the frames live in private memory.
+// What the host derived on first use (function-local statics) the device reads from a Consts built once by the host
+// (make_consts) and handed to every function that needs it; the host forms without that argument use the host's own copy.
 #pragma once
 #include "curve.hpp"
 
 #include <vector>
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#define ZKR_PAIRING_FN static __host__ __device__ __noinline__
+#elif defined(__HIPCC__) || defined(__HIP__)
+#define ZKR_PAIRING_FN static inline __host__ __device__
+#else
+#define ZKR_PAIRING_FN static inline
+#endif
+
 namespace zkr {
 namespace pairing {
 
@@ -28,62 +45,66 @@ static inline Fq fq_small(uint32_t x) {
   r.v[0] = x;
   return to_mont(r);
 }
-static inline Fq2 conj(const Fq2 &a) { return Fq2{a.a, neg(a.b)}; }
-static inline Fq2 mul_fq(const Fq2 &a, const Fq &k) { return Fq2{mul(a.a, k), mul(a.b, k)}; }
-static inline Fq2 mul_xi(const Fq2 &a) {  // (a0 + a1 u)(9 + u) = 9 a0 - a1 + (a0 + 9 a1) u
+ZKR_PAIRING_FN Fq2 conj(const Fq2 &a) { return Fq2{a.a, neg(a.b)}; }
+ZKR_PAIRING_FN Fq2 mul_fq(const Fq2 &a, const Fq &k) { return Fq2{mul(a.a, k), mul(a.b, k)}; }
+ZKR_PAIRING_FN Fq2 mul_xi(const Fq2 &a) {  // (a0 + a1 u)(9 + u) = 9 a0 - a1 + (a0 + 9 a1) u
   Fq a8 = dbl(dbl(dbl(a.a))), b8 = dbl(dbl(dbl(a.b)));
   return Fq2{sub(add(a8, a.a), a.b), add(add(b8, a.b), a.a)};
 }
 
+// the Fq2 product and square of the tower: zkr::mul / zkr::sqr, out of line on the device
+ZKR_PAIRING_FN Fq2 m2(const Fq2 &a, const Fq2 &b) { return mul(a, b); }
+ZKR_PAIRING_FN Fq2 s2(const Fq2 &a) { return sqr(a); }
+
 struct Fq6 {
   Fq2 c0, c1, c2;
-  static Fq6 zero() { return Fq6{Fq2::zero(), Fq2::zero(), Fq2::zero()}; }
-  static Fq6 one() { return Fq6{Fq2::one(), Fq2::zero(), Fq2::zero()}; }
-  bool operator==(const Fq6 &o) const { return c0 == o.c0 && c1 == o.c1 && c2 == o.c2; }
+  static ZKR_HD Fq6 zero() { return Fq6{Fq2::zero(), Fq2::zero(), Fq2::zero()}; }
+  static ZKR_HD Fq6 one() { return Fq6{Fq2::one(), Fq2::zero(), Fq2::zero()}; }
+  ZKR_HD bool operator==(const Fq6 &o) const { return c0 == o.c0 && c1 == o.c1 && c2 == o.c2; }
 };
-static inline Fq6 add(const Fq6 &a, const Fq6 &b) { return Fq6{add(a.c0, b.c0), add(a.c1, b.c1), add(a.c2, b.c2)}; }
-static inline Fq6 sub(const Fq6 &a, const Fq6 &b) { return Fq6{sub(a.c0, b.c0), sub(a.c1, b.c1), sub(a.c2, b.c2)}; }
-static inline Fq6 neg(const Fq6 &a) { return Fq6{neg(a.c0), neg(a.c1), neg(a.c2)}; }
-static inline Fq6 mul(const Fq6 &a, const Fq6 &b) {
-  Fq2 t0 = mul(a.c0, b.c0), t1 = mul(a.c1, b.c1), t2 = mul(a.c2, b.c2);
-  Fq2 c0 = add(t0, mul_xi(sub(sub(mul(add(a.c1, a.c2), add(b.c1, b.c2)), t1), t2)));
-  Fq2 c1 = add(sub(sub(mul(add(a.c0, a.c1), add(b.c0, b.c1)), t0), t1), mul_xi(t2));
-  Fq2 c2 = add(sub(sub(mul(add(a.c0, a.c2), add(b.c0, b.c2)), t0), t2), t1);
+ZKR_PAIRING_FN Fq6 add(const Fq6 &a, const Fq6 &b) { return Fq6{add(a.c0, b.c0), add(a.c1, b.c1), add(a.c2, b.c2)}; }
+ZKR_PAIRING_FN Fq6 sub(const Fq6 &a, const Fq6 &b) { return Fq6{sub(a.c0, b.c0), sub(a.c1, b.c1), sub(a.c2, b.c2)}; }
+ZKR_PAIRING_FN Fq6 neg(const Fq6 &a) { return Fq6{neg(a.c0), neg(a.c1), neg(a.c2)}; }
+ZKR_PAIRING_FN Fq6 mul(const Fq6 &a, const Fq6 &b) {
+  Fq2 t0 = m2(a.c0, b.c0), t1 = m2(a.c1, b.c1), t2 = m2(a.c2, b.c2);
+  Fq2 c0 = add(t0, mul_xi(sub(sub(m2(add(a.c1, a.c2), add(b.c1, b.c2)), t1), t2)));
+  Fq2 c1 = add(sub(sub(m2(add(a.c0, a.c1), add(b.c0, b.c1)), t0), t1), mul_xi(t2));
+  Fq2 c2 = add(sub(sub(m2(add(a.c0, a.c2), add(b.c0, b.c2)), t0), t2), t1);
   return Fq6{c0, c1, c2};
 }
-static inline Fq6 mul_v(const Fq6 &a) { return Fq6{mul_xi(a.c2), a.c0, a.c1}; }  // (c0 + c1 v + c2 v^2) v
-static inline Fq6 inv(const Fq6 &a) {
-  Fq2 t0 = sub(sqr(a.c0), mul_xi(mul(a.c1, a.c2)));
-  Fq2 t1 = sub(mul_xi(sqr(a.c2)), mul(a.c0, a.c1));
-  Fq2 t2 = sub(sqr(a.c1), mul(a.c0, a.c2));
-  Fq2 d = inv(add(mul(a.c0, t0), mul_xi(add(mul(a.c2, t1), mul(a.c1, t2)))));
-  return Fq6{mul(t0, d), mul(t1, d), mul(t2, d)};
+ZKR_PAIRING_FN Fq6 mul_v(const Fq6 &a) { return Fq6{mul_xi(a.c2), a.c0, a.c1}; }  // (c0 + c1 v + c2 v^2) v
+ZKR_PAIRING_FN Fq6 inv(const Fq6 &a) {
+  Fq2 t0 = sub(s2(a.c0), mul_xi(m2(a.c1, a.c2)));
+  Fq2 t1 = sub(mul_xi(s2(a.c2)), m2(a.c0, a.c1));
+  Fq2 t2 = sub(s2(a.c1), m2(a.c0, a.c2));
+  Fq2 d = inv(add(m2(a.c0, t0), mul_xi(add(m2(a.c2, t1), m2(a.c1, t2)))));
+  return Fq6{m2(t0, d), m2(t1, d), m2(t2, d)};
 }
 
 struct Fq12 {
   Fq6 c0, c1;  // c0 + c1 w
-  static Fq12 one() { return Fq12{Fq6::one(), Fq6::zero()}; }
-  bool operator==(const Fq12 &o) const { return c0 == o.c0 && c1 == o.c1; }
+  static ZKR_HD Fq12 one() { return Fq12{Fq6::one(), Fq6::zero()}; }
+  ZKR_HD bool operator==(const Fq12 &o) const { return c0 == o.c0 && c1 == o.c1; }
 };
-static inline Fq12 mul(const Fq12 &a, const Fq12 &b) {
+ZKR_PAIRING_FN Fq12 mul(const Fq12 &a, const Fq12 &b) {
   Fq6 t0 = mul(a.c0, b.c0), t1 = mul(a.c1, b.c1);
   return Fq12{add(t0, mul_v(t1)), sub(sub(mul(add(a.c0, a.c1), add(b.c0, b.c1)), t0), t1)};
 }
 // (a0 + a1 w)^2 = a0^2 + v a1^2 + 2 a0 a1 w with two Fq6 products: (a0 + a1)(a0 + v a1) - a0 a1 - v a0 a1 is the first part
-static inline Fq12 sqr(const Fq12 &a) {
+ZKR_PAIRING_FN Fq12 sqr(const Fq12 &a) {
   Fq6 ab = mul(a.c0, a.c1);
   Fq6 t = mul(add(a.c0, a.c1), add(a.c0, mul_v(a.c1)));
   return Fq12{sub(sub(t, ab), mul_v(ab)), add(ab, ab)};
 }
 // x * (b0 + b1 v): an Fq6 product whose second factor has no v^2 term (five Fq2 products instead of six)
-static inline Fq6 mul_sparse01(const Fq6 &x, const Fq2 &b0, const Fq2 &b1) {
-  Fq2 t0 = mul(x.c0, b0), t1 = mul(x.c1, b1);
-  Fq2 c1 = sub(sub(mul(add(x.c0, x.c1), add(b0, b1)), t0), t1);
-  return Fq6{add(t0, mul_xi(mul(x.c2, b1))), c1, add(t1, mul(x.c2, b0))};
+ZKR_PAIRING_FN Fq6 mul_sparse01(const Fq6 &x, const Fq2 &b0, const Fq2 &b1) {
+  Fq2 t0 = m2(x.c0, b0), t1 = m2(x.c1, b1);
+  Fq2 c1 = sub(sub(m2(add(x.c0, x.c1), add(b0, b1)), t0), t1);
+  return Fq6{add(t0, mul_xi(m2(x.c2, b1))), c1, add(t1, m2(x.c2, b0))};
 }
 // f * (a + (b0 + b1 v) w) for a in Fq: the line functions of the Miller loop (line() below builds exactly this shape): six Fq
 // and ten Fq2 products instead of the eighteen Fq2 products of a general Fq12 product
-static inline Fq12 mul_by_line(const Fq12 &f, const Fq &a, const Fq2 &b0, const Fq2 &b1) {
+ZKR_PAIRING_FN Fq12 mul_by_line(const Fq12 &f, const Fq &a, const Fq2 &b0, const Fq2 &b1) {
   Fq6 t0{mul_fq(f.c0.c0, a), mul_fq(f.c0.c1, a), mul_fq(f.c0.c2, a)};
   Fq6 t1 = mul_sparse01(f.c1, b0, b1);
   Fq6 m = mul_sparse01(add(f.c0, f.c1), Fq2{add(b0.a, a), b0.b}, b1);
@@ -91,19 +112,19 @@ static inline Fq12 mul_by_line(const Fq12 &f, const Fq &a, const Fq2 &b0, const 
 }
 // a^2 for a in the cyclotomic subgroup (anything after the easy part of the final exponentiation): Granger-Scott, three
 // Fq4 squarings = six Fq2 products instead of twelve
-static inline Fq12 cyclotomic_sqr(const Fq12 &a) {
+ZKR_PAIRING_FN void fq4_sqr(const Fq2 &x, const Fq2 &y, Fq2 &r0, Fq2 &r1) {  // (x + y s)^2 with s^2 = xi
+  Fq2 tmp = m2(x, y);
+  r0 = sub(sub(m2(add(x, y), add(x, mul_xi(y))), tmp), mul_xi(tmp));
+  r1 = add(tmp, tmp);
+}
+ZKR_PAIRING_FN Fq2 three_minus_two(const Fq2 &t, const Fq2 &z) { Fq2 d = sub(t, z); return add(add(d, d), t); }  // 3 t - 2 z
+ZKR_PAIRING_FN Fq2 three_plus_two(const Fq2 &t, const Fq2 &z) { Fq2 d = add(t, z); return add(add(d, d), t); }    // 3 t + 2 z
+ZKR_PAIRING_FN Fq12 cyclotomic_sqr(const Fq12 &a) {
   Fq2 z0 = a.c0.c0, z4 = a.c0.c1, z3 = a.c0.c2, z2 = a.c1.c0, z1 = a.c1.c1, z5 = a.c1.c2;
-  auto fq4_sqr = [](const Fq2 &x, const Fq2 &y, Fq2 &r0, Fq2 &r1) {  // (x + y s)^2 with s^2 = xi
-    Fq2 tmp = mul(x, y);
-    r0 = sub(sub(mul(add(x, y), add(x, mul_xi(y))), tmp), mul_xi(tmp));
-    r1 = add(tmp, tmp);
-  };
   Fq2 t0, t1, t2, t3, t4, t5;
   fq4_sqr(z0, z1, t0, t1);
   fq4_sqr(z2, z3, t2, t3);
   fq4_sqr(z4, z5, t4, t5);
-  auto three_minus_two = [](const Fq2 &t, const Fq2 &z) { Fq2 d = sub(t, z); return add(add(d, d), t); };  // 3 t - 2 z
-  auto three_plus_two = [](const Fq2 &t, const Fq2 &z) { Fq2 d = add(t, z); return add(add(d, d), t); };    // 3 t + 2 z
   z0 = three_minus_two(t0, z0);
   z1 = three_plus_two(t1, z1);
   z2 = three_plus_two(mul_xi(t5), z2);
@@ -112,8 +133,8 @@ static inline Fq12 cyclotomic_sqr(const Fq12 &a) {
   z5 = three_plus_two(t3, z5);
   return Fq12{Fq6{z0, z4, z3}, Fq6{z2, z1, z5}};
 }
-static inline Fq12 conj(const Fq12 &a) { return Fq12{a.c0, neg(a.c1)}; }
-static inline Fq12 inv(const Fq12 &a) {
+ZKR_PAIRING_FN Fq12 conj(const Fq12 &a) { return Fq12{a.c0, neg(a.c1)}; }
+ZKR_PAIRING_FN Fq12 inv(const Fq12 &a) {
   Fq6 d = inv(sub(mul(a.c0, a.c0), mul_v(mul(a.c1, a.c1))));
   return Fq12{mul(a.c0, d), neg(mul(a.c1, d))};
 }
@@ -123,18 +144,6 @@ static inline Fq12 pow(const Fq12 &a, const uint32_t (&e)[N]) {
   bool started = false;
   for (int i = 32 * N - 1; i >= 0; i--) {
     if (started) r = sqr(r);
-    if ((e[i >> 5] >> (i & 31)) & 1) { r = started ? mul(r, a) : a; started = true; }
-  }
-  return r;
-}
-
-// the same for an element of the cyclotomic subgroup
-template <int N>
-static inline Fq12 pow_cyclotomic(const Fq12 &a, const uint32_t (&e)[N]) {
-  Fq12 r = Fq12::one();
-  bool started = false;
-  for (int i = 32 * N - 1; i >= 0; i--) {
-    if (started) r = cyclotomic_sqr(r);
     if ((e[i >> 5] >> (i & 31)) & 1) { r = started ? mul(r, a) : a; started = true; }
   }
   return r;
@@ -157,12 +166,28 @@ static const uint32_t FROB_Y1[8] = {0x2623b0e3u, 0x82d37f63u, 0x8fa25bd2u, 0x218
 static const uint32_t TWIST_B0[8] = {0x24a138e5u, 0x3267e6dcu, 0x59dbefa3u, 0xb5b4c5e5u, 0x1be06ac3u, 0x81be1899u, 0xceb8aaaeu, 0x2b149d40u};
 static const uint32_t TWIST_B1[8] = {0x85c315d2u, 0xe4a2bd06u, 0xe52d1852u, 0xa74fa084u, 0xeed8fdf4u, 0xcd2cafadu, 0x3af0fed4u, 0x009713b0u};
 
-static inline bool g1_on_curve(const G1Affine &p) {  // y^2 = x^3 + 3 (TxVerifier.sol:24-26 generator (1, 2))
-  return sqr(p.y) == add(mul(sqr(p.x), p.x), fq_small(3));
+// The loop counts again as words a kernel can hold in registers: bit b of ATE_LOOP below its leading one, 6 x^2 and x
+constexpr uint64_t ATE_LOW64 = 0x9d797039be763ba8ull;
+constexpr uint64_t SIX_X_SQ_LO = 0xf83e9682e87cfd46ull, SIX_X_SQ_HI = 0x6f4d8248eeb859fbull;
+constexpr uint64_t BN_X64 = 0x44e992b44a6909f1ull;
+constexpr int N_LINES = 64 + __builtin_popcountll(ATE_LOW64) + 2;  // steps of one Miller loop: the entries of a prepared-line table
+
+// Every derived constant of this file in Montgomery form: what the host computes on first use, built once (make_consts)
+// and copied to the device with a verifying key.  Plain data.
+struct Consts {
+  Fq three;          // the curve constant of G1
+  Fq half;           // 1 / 2
+  Fq2 twist_b;       // b' = 3 / xi
+  Fq2 frob_x, frob_y;  // xi^((q-1)/3), xi^((q-1)/2): Frobenius on the twist
+  Fq2 g1[6];         // xi^(i (q-1)/6): Frobenius on Fq12
+  Fq g2[6];          // their norms: the q^2-power
+};
+
+ZKR_PAIRING_FN bool g1_on_curve(const G1Affine &p, const Consts &k) {  // y^2 = x^3 + 3 (TxVerifier.sol:24-26 generator (1, 2))
+  return sqr(p.y) == add(mul(sqr(p.x), p.x), k.three);
 }
-static inline bool g2_on_curve(const G2Affine &p) {
-  Fq2 b{fq_from_limbs(TWIST_B0), fq_from_limbs(TWIST_B1)};
-  return sqr(p.y) == add(mul(sqr(p.x), p.x), b);
+ZKR_PAIRING_FN bool g2_on_curve(const G2Affine &p, const Consts &k) {
+  return s2(p.y) == add(m2(s2(p.x), p.x), k.twist_b);
 }
 
 // Q is in the order-r subgroup G2 of the twist: [r]Q == infinity.  The twist's group order is r (2q - r) and the
@@ -179,9 +204,8 @@ static inline bool g2_in_subgroup_plain(const G2Affine &p) {
   return acc.is_inf();
 }
 
-static inline G2Affine g2_frobenius(const G2Affine &p) {
-  Fq2 gx{fq_from_limbs(FROB_X0), fq_from_limbs(FROB_X1)}, gy{fq_from_limbs(FROB_Y0), fq_from_limbs(FROB_Y1)};
-  return G2Affine{mul(conj(p.x), gx), mul(conj(p.y), gy)};
+ZKR_PAIRING_FN G2Affine g2_frobenius(const G2Affine &p, const Consts &k) {
+  return G2Affine{m2(conj(p.x), k.frob_x), m2(conj(p.y), k.frob_y)};
 }
 
 // The same membership through the twist's Frobenius endomorphism psi (untwist, q-power, twist = g2_frobenius): on G2 psi acts
@@ -189,19 +213,29 @@ static inline G2Affine g2_frobenius(const G2Affine &p) {
 // ONLY on G2 (Scott, "A note on group membership tests for G1, G2 and GT on BLS pairing-friendly curves", and the BN case
 // as implemented in gnark-crypto's bn254 G2 IsInSubGroup): a 127-bit multiplication instead of a 254-bit one.  Compared
 // with the plain definition on subgroup points, on-curve points outside it and their sums in tests/test_host_arith.py.
-static const uint32_t SIX_X_SQ[4] = {0xe87cfd46u, 0xf83e9682u, 0xeeb859fbu, 0x6f4d8248u};  // 6 x^2 = 147946756881789318990833708069417712966 = q - r
-static inline bool g2_in_subgroup(const G2Affine &p) {
+// 6 x^2 = 147946756881789318990833708069417712966 = q - r: SIX_X_SQ_HI : SIX_X_SQ_LO above
+ZKR_PAIRING_FN bool g2_in_subgroup(const G2Affine &p, const Consts &k) {
   if (p.is_inf()) return true;
   G2XYZZ base = to_xyzz(p), acc = G2XYZZ::inf();
   for (int i = 126; i >= 0; i--) {  // 6 x^2 < 2^127
     acc = dbl_xyzz(acc);
-    if ((SIX_X_SQ[i >> 5] >> (i & 31)) & 1) acc = add_full(acc, base);
+    if (((i < 64 ? SIX_X_SQ_LO : SIX_X_SQ_HI) >> (i & 63)) & 1) acc = add_full(acc, base);
   }
   if (acc.is_inf()) return false;
-  const G2Affine lhs = g2_frobenius(p);
+  const G2Affine lhs = g2_frobenius(p, k);
   // [6x^2]Q == psi(Q) without leaving XYZZ: X == x ZZ and Y == y ZZZ
-  return mul(lhs.x, acc.zz) == acc.x && mul(lhs.y, acc.zzz) == acc.y;
+  return m2(lhs.x, acc.zz) == acc.x && m2(lhs.y, acc.zzz) == acc.y;
 }
+// ---- the host's own copy of the constants, and the forms without a Consts argument (host only)
+static inline Consts make_consts();
+static inline const Consts &host_consts() {
+  static const Consts k = make_consts();
+  return k;
+}
+static inline bool g1_on_curve(const G1Affine &p) { return g1_on_curve(p, host_consts()); }
+static inline bool g2_on_curve(const G2Affine &p) { return g2_on_curve(p, host_consts()); }
+static inline G2Affine g2_frobenius(const G2Affine &p) { return g2_frobenius(p, host_consts()); }
+static inline bool g2_in_subgroup(const G2Affine &p) { return g2_in_subgroup(p, host_consts()); }
 
 static inline Fq12 line(const G2Affine &t, const Fq2 &lam, const G1Affine &p) {
   Fq6 c0{Fq2{p.y, Fq::zero()}, Fq2::zero(), Fq2::zero()};
@@ -318,41 +352,75 @@ static inline bool g2_prepare(const G2Affine &q, G2Prepared &out) {
   return step(&q1) && step(&q2);
 }
 // f * (a + (b0 + b1 v) w) with a in Fq2: thirteen Fq2 products
-static inline Fq12 mul_by_line2(const Fq12 &f, const Fq2 &a, const Fq2 &b0, const Fq2 &b1) {
-  Fq6 t0{mul(f.c0.c0, a), mul(f.c0.c1, a), mul(f.c0.c2, a)};
+ZKR_PAIRING_FN Fq12 mul_by_line2(const Fq12 &f, const Fq2 &a, const Fq2 &b0, const Fq2 &b1) {
+  Fq6 t0{m2(f.c0.c0, a), m2(f.c0.c1, a), m2(f.c0.c2, a)};
   Fq6 t1 = mul_sparse01(f.c1, b0, b1);
   Fq6 m = mul_sparse01(add(f.c0, f.c1), add(a, b0), b1);
   return Fq12{add(t0, mul_v(t1)), sub(sub(m, t0), t1)};
 }
 struct G2Proj { Fq2 x, y, z; };
-static inline const Fq2 &twist_b() {
-  static const Fq2 b{fq_from_limbs(TWIST_B0), fq_from_limbs(TWIST_B1)};
-  return b;
-}
-static inline const Fq &fq_half() {
-  static const Fq h = inv(fq_small(2));
-  return h;
-}
 // T <- 2T; f <- f * line_{T,T}(P)
-static inline void proj_double_step(G2Proj &t, const G1Affine &p, Fq12 &f) {
-  const Fq2 xx = sqr(t.x), b = sqr(t.y), c = sqr(t.z);
-  const Fq2 e = mul(twist_b(), add(dbl(c), c));                 // 3 b' Z^2
+ZKR_PAIRING_FN void proj_double_step(G2Proj &t, const G1Affine &p, Fq12 &f, const Consts &k) {
+  const Fq2 xx = s2(t.x), b = s2(t.y), c = s2(t.z);
+  const Fq2 e = m2(k.twist_b, add(dbl(c), c));                  // 3 b' Z^2
   const Fq2 f3 = add(dbl(e), e);                                // 9 b' Z^2
-  const Fq2 a = mul_fq(mul(t.x, t.y), fq_half());               // X Y / 2
-  const Fq2 g = mul_fq(add(b, f3), fq_half());                  // (Y^2 + 9 b' Z^2) / 2
-  const Fq2 h = sub(sqr(add(t.y, t.z)), add(b, c));             // 2 Y Z
-  const Fq2 e2 = sqr(e);
+  const Fq2 a = mul_fq(m2(t.x, t.y), k.half);                   // X Y / 2
+  const Fq2 g = mul_fq(add(b, f3), k.half);                     // (Y^2 + 9 b' Z^2) / 2
+  const Fq2 h = sub(s2(add(t.y, t.z)), add(b, c));              // 2 Y Z
+  const Fq2 e2 = s2(e);
   f = mul_by_line2(f, mul_fq(h, p.y), mul_fq(add(dbl(xx), xx), neg(p.x)), sub(b, e));
-  t = G2Proj{mul(a, sub(b, f3)), sub(sqr(g), add(dbl(e2), e2)), mul(b, h)};
+  t = G2Proj{m2(a, sub(b, f3)), sub(s2(g), add(dbl(e2), e2)), m2(b, h)};
 }
 // T <- T + Q (Q affine, T != +-Q); f <- f * line_{T,Q}(P)
-static inline void proj_add_step(G2Proj &t, const G2Affine &q, const G1Affine &p, Fq12 &f) {
-  const Fq2 theta = sub(t.y, mul(q.y, t.z)), lam = sub(t.x, mul(q.x, t.z));
-  const Fq2 c = sqr(theta), d = sqr(lam), e = mul(lam, d), ff = mul(t.z, c), g = mul(t.x, d);
+ZKR_PAIRING_FN void proj_add_step(G2Proj &t, const G2Affine &q, const G1Affine &p, Fq12 &f) {
+  const Fq2 theta = sub(t.y, m2(q.y, t.z)), lam = sub(t.x, m2(q.x, t.z));
+  const Fq2 c = s2(theta), d = s2(lam), e = m2(lam, d), ff = m2(t.z, c), g = m2(t.x, d);
   const Fq2 h = sub(add(e, ff), dbl(g));
-  f = mul_by_line2(f, mul_fq(lam, p.y), mul_fq(theta, neg(p.x)), sub(mul(theta, q.x), mul(lam, q.y)));
-  t = G2Proj{mul(lam, h), sub(mul(theta, sub(g, h)), mul(e, t.y)), mul(t.z, e)};
+  f = mul_by_line2(f, mul_fq(lam, p.y), mul_fq(theta, neg(p.x)), sub(m2(theta, q.x), m2(lam, q.y)));
+  t = G2Proj{m2(lam, h), sub(m2(theta, sub(g, h)), m2(e, t.y)), m2(t.z, e)};
 }
+// f_{6x+2,Q}(P) with the two Frobenius lines for ONE pair with an arbitrary second argument: the projective steps above, as
+// miller_loop_mixed runs them for its first kind of pair.  One when either point is infinity.  *ok is cleared when the projective
+// point degenerates (Z = 0: impossible for a Q of order r).
+ZKR_PAIRING_FN Fq12 miller_loop_proj(const G1Affine &p, const G2Affine &q, const Consts &k, bool *ok) {
+  Fq12 f = Fq12::one();
+  *ok = true;
+  if (p.is_inf() || q.is_inf()) return f;
+  G2Proj t{q.x, q.y, Fq2::one()};
+  for (int b = 63; b >= 0; b--) {
+    f = sqr(f);
+    proj_double_step(t, p, f, k);
+    if ((ATE_LOW64 >> b) & 1) proj_add_step(t, q, p, f);
+  }
+  const G2Affine q1 = g2_frobenius(q, k);
+  G2Affine q2 = g2_frobenius(q1, k);
+  q2.y = neg(q2.y);
+  proj_add_step(t, q1, p, f);
+  proj_add_step(t, q2, p, f);
+  *ok = !t.z.is_zero();
+  return f;
+}
+// One prepared line per step of the loop (g2_prepare): slope, slope * x_T - y_T.  N_LINES of them make a table.
+struct Line { Fq2 lam, c; };
+// The same Miller value for ONE pair whose second argument is a table of prepared lines: the second kind of pair of
+// miller_loop_mixed.  Every caller reads the table at the same index in the same step.
+ZKR_PAIRING_FN Fq12 miller_loop_prepared(const G1Affine &p, const Line *lines) {
+  Fq12 f = Fq12::one();
+  if (p.is_inf()) return f;
+  const Fq nx = neg(p.x);
+  int at = 0;
+  for (int b = 63; b >= 0; b--) {
+    f = sqr(f);
+    f = mul_by_line(f, p.y, mul_fq(lines[at].lam, nx), lines[at].c);
+    at++;
+    if ((ATE_LOW64 >> b) & 1) { f = mul_by_line(f, p.y, mul_fq(lines[at].lam, nx), lines[at].c); at++; }
+  }
+  f = mul_by_line(f, p.y, mul_fq(lines[at].lam, nx), lines[at].c);
+  at++;
+  return mul_by_line(f, p.y, mul_fq(lines[at].lam, nx), lines[at].c);
+}
+
+static inline void proj_double_step(G2Proj &t, const G1Affine &p, Fq12 &f) { proj_double_step(t, p, f, host_consts()); }
 // prod_i f_{6x+2,ql_i}(pl_i) * prod_j f_{6x+2,qf_j}(pf_j): nl pairs with arbitrary second arguments (projective steps), nf pairs
 // with prepared ones.  Pairs with a point at infinity contribute 1.  *ok is cleared when a projective point degenerates (Z = 0:
 // impossible for second arguments of order r, which the callers check).
@@ -434,40 +502,55 @@ struct FrobConst {
     for (int i = 0; i < 6; i++) g2[i] = sub(mul(g1[i].a, g1[i].a), neg(mul(g1[i].b, g1[i].b)));  // norm a^2 + b^2
   }
 };
-static inline const FrobConst &frob_const() {
-  static const FrobConst k;
+static inline Consts make_consts() {
+  Consts k;
+  k.three = fq_small(3);
+  k.half = inv(fq_small(2));
+  k.twist_b = Fq2{fq_from_limbs(TWIST_B0), fq_from_limbs(TWIST_B1)};
+  k.frob_x = Fq2{fq_from_limbs(FROB_X0), fq_from_limbs(FROB_X1)};
+  k.frob_y = Fq2{fq_from_limbs(FROB_Y0), fq_from_limbs(FROB_Y1)};
+  const FrobConst fc;
+  for (int i = 0; i < 6; i++) { k.g1[i] = fc.g1[i]; k.g2[i] = fc.g2[i]; }
   return k;
 }
 // coefficient of w^i: i = 0, 2, 4 -> c0.{c0, c1, c2}; i = 1, 3, 5 -> c1.{c0, c1, c2}   (v = w^2)
-static inline Fq12 frobenius(const Fq12 &a) {
-  const FrobConst &k = frob_const();
-  return Fq12{Fq6{conj(a.c0.c0), mul(conj(a.c0.c1), k.g1[2]), mul(conj(a.c0.c2), k.g1[4])},
-              Fq6{mul(conj(a.c1.c0), k.g1[1]), mul(conj(a.c1.c1), k.g1[3]), mul(conj(a.c1.c2), k.g1[5])}};
+ZKR_PAIRING_FN Fq12 frobenius(const Fq12 &a, const Consts &k) {
+  return Fq12{Fq6{conj(a.c0.c0), m2(conj(a.c0.c1), k.g1[2]), m2(conj(a.c0.c2), k.g1[4])},
+              Fq6{m2(conj(a.c1.c0), k.g1[1]), m2(conj(a.c1.c1), k.g1[3]), m2(conj(a.c1.c2), k.g1[5])}};
 }
-static inline Fq12 frobenius2(const Fq12 &a) {
-  const FrobConst &k = frob_const();
+ZKR_PAIRING_FN Fq12 frobenius2(const Fq12 &a, const Consts &k) {
   return Fq12{Fq6{a.c0.c0, mul_fq(a.c0.c1, k.g2[2]), mul_fq(a.c0.c2, k.g2[4])},
               Fq6{mul_fq(a.c1.c0, k.g2[1]), mul_fq(a.c1.c1, k.g2[3]), mul_fq(a.c1.c2, k.g2[5])}};
 }
-// the curve parameter x = 4965661367192848881 (ATE_LOOP = 6x + 2)
-static const uint32_t BN_X[2] = {0x4a6909f1u, 0x44e992b4u};
+static inline Fq12 frobenius(const Fq12 &a) { return frobenius(a, host_consts()); }
+static inline Fq12 frobenius2(const Fq12 &a) { return frobenius2(a, host_consts()); }
+// a^x for a in the cyclotomic subgroup: pow_cyclotomic over the 63 bits of the curve parameter
+ZKR_PAIRING_FN Fq12 pow_x(const Fq12 &a) {
+  Fq12 r = a;  // bit 62, the leading one
+  for (int i = 61; i >= 0; i--) {
+    r = cyclotomic_sqr(r);
+    if ((BN_X64 >> i) & 1) r = mul(r, a);
+  }
+  return r;
+}
+// (BN_X64 above: the curve parameter x = 4965661367192848881, ATE_LOOP = 6x + 2)
 
 // The same value with the structure of the exponent: q^6 - 1 by conjugation and one inversion, q^2 + 1 by a Frobenius
 // map, the hard part (q^4 - q^2 + 1)/r as lambda_3 q^3 + lambda_2 q^2 + lambda_1 q + lambda_0 with the lambda_i
 // polynomials in x (Scott, Benger, Charlemagne, Dominguez Perez, Kachisa: three powers by x, Frobenius maps and the
 // addition chain y0 y1^2 y2^6 y3^12 y4^18 y5^30 y6^36; inverses are conjugates after the easy part).
-static inline Fq12 final_exponentiation(const Fq12 &f0) {
+ZKR_PAIRING_FN Fq12 final_exponentiation(const Fq12 &f0, const Consts &k) {
   Fq12 f = mul(conj(f0), inv(f0));  // ^(q^6 - 1)
-  f = mul(frobenius2(f), f);        // ^(q^2 + 1)
-  Fq12 fx = pow_cyclotomic(f, BN_X), fx2 = pow_cyclotomic(fx, BN_X), fx3 = pow_cyclotomic(fx2, BN_X);
-  Fq12 fp = frobenius(f), fp2 = frobenius2(f), fp3 = frobenius(fp2);
+  f = mul(frobenius2(f, k), f);     // ^(q^2 + 1)
+  Fq12 fx = pow_x(f), fx2 = pow_x(fx), fx3 = pow_x(fx2);
+  Fq12 fp = frobenius(f, k), fp2 = frobenius2(f, k), fp3 = frobenius(fp2, k);
   Fq12 y0 = mul(mul(fp, fp2), fp3);
   Fq12 y1 = conj(f);
-  Fq12 y2 = frobenius2(fx2);
-  Fq12 y3 = conj(frobenius(fx));
-  Fq12 y4 = conj(mul(fx, frobenius(fx2)));
+  Fq12 y2 = frobenius2(fx2, k);
+  Fq12 y3 = conj(frobenius(fx, k));
+  Fq12 y4 = conj(mul(fx, frobenius(fx2, k)));
   Fq12 y5 = conj(fx2);
-  Fq12 y6 = conj(mul(fx3, frobenius(fx3)));
+  Fq12 y6 = conj(mul(fx3, frobenius(fx3, k)));
   Fq12 t0 = mul(mul(cyclotomic_sqr(y6), y4), y5);
   Fq12 t1 = mul(mul(y3, y5), t0);
   t0 = mul(t0, y2);
@@ -476,6 +559,7 @@ static inline Fq12 final_exponentiation(const Fq12 &f0) {
   t1 = mul(t1, y0);
   return mul(cyclotomic_sqr(t0), t1);
 }
+static inline Fq12 final_exponentiation(const Fq12 &f0) { return final_exponentiation(f0, host_consts()); }
 
 // prod_i e(P_i, Q_i) == 1  -- the bn256 pairing precompile's check (TxVerifier.sol:91-115)
 static inline bool pairing_product_is_one(const G1Affine *ps, const G2Affine *qs, int n) {

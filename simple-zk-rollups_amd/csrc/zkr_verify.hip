@@ -15,58 +15,11 @@
 #include <system_error>
 #include <thread>
 #include "zkr_internal.hpp"
+#include "verify_key.hpp"
 
 using namespace zkr;
 
-static bool fq_lt_q(const uint8_t *p) {
-  uint32_t v[8];
-  memcpy(v, p, 32);
-  return words_below(v, FqParams::P);
-}
-static bool fr_lt_r(const uint8_t *p) {
-  uint32_t v[8];
-  memcpy(v, p, 32);
-  return words_below(v, FrParams::P);
-}
-// standard-form bytes -> Montgomery affine; false when a coordinate is >= q or the point is off the curve
-static bool read_g1(const uint8_t *p, G1Affine &out) {
-  if (!fq_lt_q(p) || !fq_lt_q(p + 32)) return false;
-  out = G1Affine{to_mont(load_fp<FqParams>(p)), to_mont(load_fp<FqParams>(p + 32))};
-  return !out.is_inf() && pairing::g1_on_curve(out);
-}
-static bool read_g2(const uint8_t *p, G2Affine &out) {
-  for (int i = 0; i < 4; i++)
-    if (!fq_lt_q(p + 32 * i)) return false;
-  out = G2Affine{Fq2{to_mont(load_fp<FqParams>(p)), to_mont(load_fp<FqParams>(p + 32))},
-                 Fq2{to_mont(load_fp<FqParams>(p + 64)), to_mont(load_fp<FqParams>(p + 96))}};
-  // on the twist AND in the order-r subgroup (the twist has cofactor 2q - r): what precompile 8 accepts
-  return !out.is_inf() && pairing::g2_on_curve(out) && pairing::g2_in_subgroup(out);
-}
-
 namespace {
-struct ParsedVk {
-  G1Affine alfa1, ic0;
-  G2Affine beta2, gamma2, delta2;
-  std::vector<G1Affine> ics;  // IC_1 .. IC_nPublic
-};
-// the whole key is checked before any proof is looked at: a malformed key is an error, whatever the proofs
-int parse_vk(const void *vk_bin, size_t vk_len, size_t n_public, ParsedVk &k) {
-  const uint8_t *vk = (const uint8_t *)vk_bin;
-  const size_t fixed = 64 + 3 * 128 + 4;
-  if (vk_len < fixed) { set_error("verifying key shorter than its fixed part (%zu bytes)", fixed); return ZKR_ERR_BAD_KEY; }
-  uint32_t n_ic;
-  memcpy(&n_ic, vk + 64 + 3 * 128, 4);
-  if (vk_len != fixed + 64ull * n_ic) { set_error("verifying key length %zu does not match %u IC points", vk_len, n_ic); return ZKR_ERR_BAD_KEY; }
-  if (n_ic != n_public + 1) { set_error("%zu public signals for a key with %u IC points (needs nPublic + 1, TxVerifier.sol:261)", n_public, n_ic); return ZKR_ERR_ARG; }
-  if (!read_g1(vk, k.alfa1) || !read_g2(vk + 64, k.beta2) || !read_g2(vk + 192, k.gamma2) || !read_g2(vk + 320, k.delta2) || !read_g1(vk + fixed, k.ic0)) {
-    set_error("verifying key holds a point that is not on the curve (or a G2 point outside the order-r subgroup)");
-    return ZKR_ERR_BAD_KEY;
-  }
-  k.ics.resize(n_public);
-  for (size_t i = 0; i < n_public; i++)
-    if (!read_g1(vk + fixed + 64 * (i + 1), k.ics[i])) { set_error("verifying key IC[%zu] is not on the curve", i + 1); return ZKR_ERR_BAD_KEY; }
-  return 0;
-}
 // sum_i scalar_i * IC_{i+1}, scalars standard 32 B each: interleaved 4-bit windows (Straus), one shared chain of 252
 // doublings, one addition per scalar and window
 G1XYZZ ic_combination(const ParsedVk &k, const uint8_t *scalars) {
@@ -106,30 +59,6 @@ struct VkEntry {
 std::mutex vk_mu;
 std::list<std::shared_ptr<VkEntry>> vk_cache;
 
-void build_win8(VkEntry &e) {
-  const size_t n = e.k.ics.size();
-  std::vector<G1XYZZ> pts(n * 255);
-  for (size_t i = 0; i < n; i++) {
-    G1XYZZ base = to_xyzz(e.k.ics[i]), cur = base;
-    for (int d = 0; d < 255; d++) { pts[i * 255 + d] = cur; cur = add_mixed(cur, e.k.ics[i]); }
-  }
-  // affine with ONE inversion: x = X / ZZ, y = Y / ZZZ, and 1 / ZZ = ZZ^2 / ZZZ^2 (ZZ^3 = ZZZ^2), so only the ZZZ are inverted
-  std::vector<Fq> pre(pts.size());
-  Fq run = Fq::one();
-  for (size_t j = 0; j < pts.size(); j++) {
-    pre[j] = run;
-    if (!pts[j].is_inf()) run = mul(run, pts[j].zzz);
-  }
-  Fq iv = inv(run);
-  e.win8.assign(pts.size(), G1Affine{Fq::zero(), Fq::one()});
-  for (size_t j = pts.size(); j-- > 0;) {
-    if (pts[j].is_inf()) continue;  // d * IC = infinity cannot happen for a point of prime order r > 255; kept for safety
-    Fq izzz = mul(iv, pre[j]);
-    iv = mul(iv, pts[j].zzz);
-    Fq izz = mul(sqr(pts[j].zz), sqr(izzz));
-    e.win8[j] = G1Affine{mul(pts[j].x, izz), mul(pts[j].y, izzz)};
-  }
-}
 // the parsed key for these bytes (ZKR_ERR_* through *rc when they are not a well-formed key for n_public inputs)
 std::shared_ptr<const VkEntry> cached_vk(const void *vk_bin, size_t vk_len, size_t n_public, int *rc) {
   *rc = 0;
@@ -151,7 +80,7 @@ std::shared_ptr<const VkEntry> cached_vk(const void *vk_bin, size_t vk_len, size
   }
   if (upgrade) {
     std::shared_ptr<VkEntry> e2 = copy;
-    build_win8(*e2);
+    build_win8(e2->k.ics, e2->win8);
     std::lock_guard<std::mutex> lk(vk_mu);  // publish: the new entry replaces the old one where it still sits (readers keep theirs)
     for (auto &slot : vk_cache)
       if (slot == upgrade) { e2->uses = upgrade->uses; slot = e2; break; }

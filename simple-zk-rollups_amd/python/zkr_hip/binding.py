@@ -92,6 +92,13 @@ def lib():
     L.zkr_prove_batch.argtypes = [vp, c.POINTER(c.c_char_p), sz, sz, u8p, u8p, u8p]
     L.zkr_verify.argtypes = [u8p, sz, u8p, u8p, sz, c.POINTER(i)]
     L.zkr_verify_batch.argtypes = [u8p, sz, u8p, u8p, sz, sz, c.POINTER(i)]
+    L.zkr_vk_load.argtypes = [u8p, sz, i, c.POINTER(vp)]
+    L.zkr_vk_free.argtypes = [vp]
+    L.zkr_vk_free.restype = None
+    L.zkr_vk_info.argtypes = [vp, c.POINTER(c.c_uint64)]
+    L.zkr_verify_each.argtypes = [vp, u8p, u8p, sz, vp, c.POINTER(i)]
+    L.zkr_verify_each_device.argtypes = [vp, u8p, c.POINTER(vp), sz, vp, vp, c.POINTER(i)]
+    L.zkr_pairing_device.argtypes = [u8p, u8p, sz, vp, vp, i]
     L.zkr_ntt.argtypes = [u8p, c.c_uint, i, i]
     L.zkr_msm_g1.argtypes = [u8p, u8p, sz, u8p, c.POINTER(i), i]
     L.zkr_msm_g2.argtypes = [u8p, u8p, sz, u8p, c.POINTER(i), i]
@@ -561,6 +568,87 @@ class ConstraintSystem:
             self.close()
         except Exception:
             pass
+
+
+VERDICTS = ("valid", "bad G1 point", "public signal not below r", "bad G2 point", "pairing equation fails")   # zkr.h ZKR_VERDICT_*
+
+
+class VerifyingKey:
+    """A verifying key resident on the device (zkr_vk*): the Groth16 acceptance check with one verdict per proof (0 = valid,
+    else the first failing check: VERDICTS).  vk_bin: the layout of zkr_hip.verify (binarify_verifying_key).  A failing proof
+    raises nothing; zkr_hip.lib().zkr_last_error() names the first one, and .all_valid holds the call's *all_valid.  One VerifyingKey
+    serves one call at a time."""
+
+    def __init__(self, vk_bin: bytes, device=0):
+        self._h = None
+        h = ctypes.c_void_p()
+        _check(lib().zkr_vk_load(bytes(vk_bin), len(vk_bin), device, ctypes.byref(h)))
+        self._h = h
+        self.device = device
+        self.all_valid = None   # of the last verify_each* call
+        out = (ctypes.c_uint64 * 2)()
+        _check(lib().zkr_vk_info(self._h, out))
+        self.n_public = int(out[0])
+
+    def _proofs(self, proofs):
+        pb = b"".join(bytes(p) for p in proofs)
+        if len(pb) != PROOF_BYTES * len(proofs):
+            raise ValueError("every proof is %d bytes" % PROOF_BYTES)
+        return pb
+
+    def verify_each(self, proofs, public_signals):
+        """zkr_verify_each: proofs (256 B each) and one list of n_public ints per proof, both from the host -> one verdict per proof."""
+        n = len(proofs)
+        if len(public_signals) != n or any(len(p) != self.n_public for p in public_signals):
+            raise ValueError("one list of %d public signals per proof" % self.n_public)
+        sb = b"".join(int(v).to_bytes(32, "little") for p in public_signals for v in p)
+        verdicts = ctypes.create_string_buffer(max(n, 1))
+        ok = ctypes.c_int(0)
+        _check(lib().zkr_verify_each(self._h, self._proofs(proofs), sb, n, verdicts, ctypes.byref(ok)))
+        self.all_valid = bool(ok.value)
+        return list(verdicts.raw[:n])
+
+    def verify_each_device(self, proofs, d_witness_ptrs, stream=None):
+        """zkr_verify_each_device: the public signals are words 1..n_public of the witnesses where they live (device pointers on
+        the key's device, as ProvingKey.prove_batch_device takes them); stream as for ProvingKey.prove_device."""
+        n = len(proofs)
+        if len(d_witness_ptrs) != n:
+            raise ValueError("one witness pointer per proof")
+        arr = (ctypes.c_void_p * max(n, 1))(*[ctypes.c_void_p(p) for p in d_witness_ptrs])
+        verdicts = ctypes.create_string_buffer(max(n, 1))
+        ok = ctypes.c_int(0)
+        _check(lib().zkr_verify_each_device(self._h, self._proofs(proofs), arr, n, ctypes.c_void_p(stream or 0), verdicts, ctypes.byref(ok)))
+        self.all_valid = bool(ok.value)
+        return list(verdicts.raw[:n])
+
+    def close(self):
+        if self._h:
+            lib().zkr_vk_free(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def pairing_device(g1: bytes, g2: bytes, device=0):
+    """zkr_pairing_device: e(P_i, Q_i) for n pairs of standard-form affine points (64 B / 128 B each, all zero = infinity) ->
+    (n x 384 B of Fq12 coefficients in the tower's order, n degenerate flags)."""
+    n = len(g1) // 64
+    if len(g1) != 64 * n or len(g2) != 128 * n:
+        raise ValueError("g1 is n x 64 bytes and g2 n x 128 bytes")
+    out = ctypes.create_string_buffer(max(384 * n, 1))
+    deg = ctypes.create_string_buffer(max(n, 1))
+    _check(lib().zkr_pairing_device(bytes(g1), bytes(g2), n, out, deg, device))
+    return out.raw[:384 * n], list(deg.raw[:n])
 
 
 def _blinding_bytes(rs, ss, n=None):
