@@ -631,6 +631,61 @@ int zkr_rollup_witness_batch_device(uint32_t batch, uint32_t depth, const uint8_
  * with the host builder signal for signal. */
 int zkr_rollup_witness_program_host(uint32_t batch, uint32_t depth, const uint8_t *inputs, size_t n_inputs, uint8_t *witness_out, uint32_t *stmt, uint32_t *tx);
 const char *zkr_rollup_statement_text(uint32_t stmt);
+/* zkr_rollup_witness_batch_device with the inputs already in device memory (same kernels, same errors, same bytes): d_inputs =
+ * n_batches x n_inputs x 32 B as zkr_ledger_sequence leaves them.  The kernels run on `stream` (NULL: the default stream), the
+ * one the inputs were written on; the call returns when the witnesses are complete. */
+int zkr_rollup_witness_batch_from_device(uint32_t batch, uint32_t depth, const void *d_inputs, size_t n_inputs, size_t n_batches,
+                                         void *d_witnesses, int device, void *stream);
+
+/* ---- the operator's ledger on the GPU: a queue of signed transactions -> a status each and the circuit inputs of every whole
+ * batch, in device memory (csrc/zkr_sequencer.hip).  Stands in for the per-transaction loop of
+ * operator/src/routes/send.ts:72-135 and the tree updates of operator/src/routes/pubsub.ts:19-66.  The ledger holds the account
+ * records (host) and the whole balance tree (device, 2^(depth+1) - 1 nodes).  No CPU fallback (ZKR_ERR_NO_DEVICE). ---- */
+typedef struct zkr_ledger zkr_ledger;
+int zkr_ledger_new(unsigned depth, int device, zkr_ledger **out); /* empty tree, zero leaves; depth 1..24 */
+void zkr_ledger_free(zkr_ledger *l);
+/* onEventUpdateMerkleTree (pubsub.ts:19-66): insert (index == accounts so far) or overwrite (index below it); an index above it
+ * is ZKR_ERR_ARG ("out of sync").  records: n x 4 x 32 B  pubX pubY balance nonce, standard form; every element below r, balance
+ * and nonce below 2^250 (the circuit's range checks), ZKR_ERR_ARG otherwise.  A refused call leaves the ledger as it was. */
+int zkr_ledger_deposit(zkr_ledger *l, const uint32_t *indices, const uint8_t *records, size_t n);
+int zkr_ledger_info(const zkr_ledger *l, uint64_t out[4]); /* depth, accounts, transactions applied, batches emitted */
+int zkr_ledger_root(const zkr_ledger *l, uint8_t root[32]);
+int zkr_ledger_account(const zkr_ledger *l, uint32_t index, uint8_t record[128], uint8_t *path /* depth x 32 B, may be NULL */);
+/* verify (crypto.ts:170-177) for n signatures at once, one verdict byte each; equals zkr_eddsa_verify bit for bit.  msgs: n x
+ * arity x 32 B (elements of any size are taken mod r, as zkr_mimcsponge_multihash takes them), sigs: n x 96 B, pubs: n x 64 B. */
+int zkr_eddsa_verify_batch(const uint8_t *msgs, unsigned arity, const uint8_t *sigs, const uint8_t *pubs, size_t n, uint8_t *verdicts, int device);
+/* txs: n_txs x 8 x 32 B, the txData row of batchprocesstx.circom (from to amount fee nonce R8x R8y S).
+ * status: n_txs bytes.  d_inputs: device memory for (n_txs / batch) x (n_public - 1) x 32 B.
+ * *n_batches: batches written.  *consumed: transactions decided (the caller resubmits txs[consumed..]).
+ *
+ * The queue is gone through in order against the ledger's state.  A status is the first rule of this list the transaction
+ * breaks, 0 = accepted:
+ *    1  `from` is an account of the ledger (send.ts:76)          2  `to` is an account of the ledger (send.ts:82)
+ *    3  every element is below r; amount, fee and nonce are below 2^250
+ *    4  amount > 0                                                5  fee > 0
+ *    6  sender balance > amount + fee (the circuit's strict comparison; send.ts:91 is laxer, what it admits beyond cannot be proved)
+ *    7  fee >= (amount div 1000) * 3 (send.ts:101)                8  nonce = sender's nonce + 1 (send.ts:112)
+ *    9  the recipient's new balance stays below 2^250
+ *   10  the signature over multiHash([from, to, amount, fee, nonce]) verifies under the sender's stored key, as the circuit
+ *       checks it (a key whose order divides 8 fails here)
+ * With A transactions accepted in the whole queue only the first A - (A mod batch) of them are applied; *consumed is the position
+ * just behind the last of them, and every transaction from there on has status 255 ("not reached").  Batch b's inputs are those
+ * of its `batch` applied transactions in the order zkr_rollup_witness takes them.  Everything runs on `stream` (NULL: the default
+ * stream); the call returns when the statuses are final and d_inputs is complete.  On any error return the ledger is unchanged. */
+int zkr_ledger_sequence(zkr_ledger *l, const uint8_t *txs, size_t n_txs, uint32_t batch, uint8_t *status, void *d_inputs,
+                        size_t *n_batches, size_t *consumed, void *stream);
+/* Wall milliseconds of the last zkr_ledger_sequence call's stages -- signatures, host pass, leaf hashes, tree levels, assembly --
+ * recorded only while the environment variable ZKR_SEQUENCER_STAGES is set (the call then waits for the stream after each stage). */
+int zkr_ledger_stage_times(const zkr_ledger *l, double ms[5]);
+/* host only */
+/* Test hook: the host pass of zkr_ledger_sequence (rules 1-9 and the arithmetic; rule 10 from sig_verdicts, one byte per
+ * transaction) over records = n_accounts x 128 B.  prev (may be NULL): int32 [3][depth][2T], T = the number of status-0
+ * transactions, room for 3 x depth x 2 x n_txs: table 0 [l][u] = the latest update u' < u under the sibling of update u's node
+ * of level l, or -1 (the stored node); table 1 [l][2k] the same for the recipient's node asked before update 2k (odd entries
+ * -1); table 2 [l][u] = 1 when update u holds the last version of its node of level l.  Update 2k is transaction k's sender
+ * leaf, 2k + 1 its recipient leaf. */
+int zkr_sequence_plan_host(unsigned depth, const uint8_t *records, size_t n_accounts, const uint8_t *txs, size_t n_txs,
+                           const uint8_t *sig_verdicts, uint32_t batch, uint8_t *status, size_t *consumed, int32_t *prev);
 
 /* Integer-ALU microbenchmark: sustained Fq Montgomery multiplications per second on `device` with the multiplier of the
  * hot path (9 x 29-bit limbs, 162 multiply-adds without carry words, csrc/field29.hpp); used for the secondary (VALU)

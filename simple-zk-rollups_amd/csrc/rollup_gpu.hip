@@ -10,50 +10,13 @@
 #include <thread>
 #include "zkr_internal.hpp"
 #include "rollup_witness.hpp"
+#include "mimc_device.hpp"
 
 namespace zkr {
-const Fr *mimc_round_constants();  // rollup.cpp
 void rollup_device_constants(Fr *a, Fr *d, uint32_t suborder_m1[8], Fr *b8x253, Fr *b8y253);
 uint32_t rollup_tx_private_count(uint32_t depth);
 uint32_t rollup_n_public(uint32_t batch, uint32_t depth);
 int rollup_check_geometry(uint32_t batch, uint32_t depth);
-
-__constant__ uint32_t c_mimc[MIMC_ROUNDS * 8];
-
-__device__ __forceinline__ Fr mimc_const(int i) {
-  Fr k;
-#pragma unroll
-  for (int j = 0; j < 8; j++) k.v[j] = c_mimc[8 * i + j];
-  return k;
-}
-__device__ __forceinline__ void mimc_feistel(Fr &xl, Fr &xr) {  // key 0 (hasher.circom:21)
-  for (int i = 0; i < MIMC_ROUNDS; i++) {
-    Fr t = add(xl, mimc_const(i));
-    Fr t2 = sqr(t);
-    Fr t5 = mul(sqr(t2), t);
-    if (i < MIMC_ROUNDS - 1) {
-      Fr nl = add(xr, t5);
-      xr = xl;
-      xl = nl;
-    } else {
-      xr = add(xr, t5);
-    }
-  }
-}
-__device__ __forceinline__ Fr load_std_as_mont(const Fr *p) {
-  Fr a = *p;
-  // operands of any size are taken mod r as the reference's field operations do: 2^256 < 6 r
-  for (int k = 0; k < 5; k++) {
-    bool ge = true;
-    for (int i = 7; i >= 0; i--)
-      if (a.v[i] != FrParams::P[i]) { ge = a.v[i] > FrParams::P[i]; break; }
-    if (!ge) break;
-    uint32_t br = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) a.v[i] = __builtin_subc(a.v[i], FrParams::P[i], br, &br);
-  }
-  return to_mont(a);
-}
 
 // out[t] = multiHash(in[t * arity .. t * arity + arity))   (standard form in and out)
 static __global__ __launch_bounds__(256) void mimc_multihash_kernel(const Fr *in, size_t count, uint32_t arity, Fr *out) {
@@ -67,15 +30,7 @@ static __global__ __launch_bounds__(256) void mimc_multihash_kernel(const Fr *in
   out[t] = from_mont(r);
 }
 
-static int upload_constants(int device) {
-  static std::mutex mu;
-  static bool done[64] = {false};
-  std::lock_guard<std::mutex> lk(mu);
-  if (device < 64 && done[device]) return 0;
-  ZKR_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(c_mimc), mimc_round_constants(), MIMC_ROUNDS * 32));
-  if (device < 64) done[device] = true;
-  return 0;
-}
+static int upload_constants(int device) { return upload_mimc_constants(device); }
 
 // ------------------------------------------------------------------------------------------------ witnesses on the GPU
 // SURVEY 8(f-3) "batch-parallel across txs on GPU": the witness of BatchProcessTx(batch, depth) for MANY rollup batches at
@@ -250,8 +205,11 @@ int zkr_mimcsponge_multihash_batch(const void *inputs_std, size_t count, unsigne
   return ZKR_OK;
 }
 
-int zkr_rollup_witness_batch_device(uint32_t batch, uint32_t depth, const uint8_t *inputs, size_t n_inputs, size_t n_batches, void *d_witnesses, int device) {
-  if ((!inputs && n_batches) || !d_witnesses) { set_error("null argument"); return ZKR_ERR_ARG; }
+// The body of zkr_rollup_witness_batch_device and of zkr_rollup_witness_batch_from_device.  inputs: host memory, copied into the
+// builder's scratch on the builder's own stream; or d_inputs: device memory, read in place, and then `stream` (the one the
+// inputs were written on) carries the kernels instead of the builder's own.
+static int witness_batch(uint32_t batch, uint32_t depth, const uint8_t *inputs, const void *d_inputs, size_t n_inputs, size_t n_batches, void *d_witnesses, int device, hipStream_t stream) {
+  if ((!inputs && !d_inputs && n_batches) || !d_witnesses) { set_error("null argument"); return ZKR_ERR_ARG; }
   int rc = rollup_check_geometry(batch, depth);
   if (rc) return rc;
   if (zkr_device_count() <= device || device < 0) { set_error("no HIP device %d; the batch witness builder runs on the GPU (zkr_rollup_witness is the host call)", device); return ZKR_ERR_NO_DEVICE; }
@@ -288,7 +246,7 @@ int zkr_rollup_witness_batch_device(uint32_t batch, uint32_t depth, const uint8_
   static std::mutex scratch_mu[64];
   std::lock_guard<std::mutex> scratch_lock(scratch_mu[device]);
   const uint32_t ROWS = TX_PARTS + 1;  // a row of statement codes per part, one for tx_finish
-  const size_t want[4] = {n_batches * (size_t)(p - 1) * 32, n_tx * (size_t)TX_WS_ELEMS * 32, n_tx * 32, (ROWS * n_tx + n_batches) * 4};
+  const size_t want[4] = {d_inputs ? 0 : n_batches * (size_t)(p - 1) * 32, n_tx * (size_t)TX_WS_ELEMS * 32, n_tx * 32, (ROWS * n_tx + n_batches) * 4};
   for (int j = 0; j < 4; j++) {
     Scratch &sc = scratch[device][j];
     if (sc.cap >= want[j]) continue;
@@ -297,20 +255,21 @@ int zkr_rollup_witness_batch_device(uint32_t batch, uint32_t depth, const uint8_
     ZKR_HIP_CHECK(hipMalloc(&sc.p, want[j] + want[j] / 2));
     sc.cap = want[j] + want[j] / 2;
   }
-  const DevView b_in{scratch[device][0].p}, b_ws{scratch[device][1].p}, b_roots{scratch[device][2].p}, b_errs{scratch[device][3].p};
+  const DevView b_in{d_inputs ? const_cast<void *>(d_inputs) : scratch[device][0].p}, b_ws{scratch[device][1].p}, b_roots{scratch[device][2].p}, b_errs{scratch[device][3].p};
   // Its own stream (non-blocking, highest priority): the builder is a handful of long-running wavefronts that must neither wait
   // for nor hold up the proofs in flight on the key's streams; nothing here synchronises the device.
   // Made once per device and kept (the scratch lock above serialises the calls): streams that come and go reshuffle the
   // runtime's hardware queues under the provers' streams (zkr_key.hip DeviceStreams).
   struct StreamRef { hipStream_t s = nullptr; };
   static StreamRef kept[64];
-  StreamRef &sg = kept[device];
-  if (!sg.s) {
+  if (!d_inputs && !kept[device].s) {
     int prio_lo = 0, prio_hi = 0;
     ZKR_HIP_CHECK(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
-    ZKR_HIP_CHECK(hipStreamCreateWithPriority(&sg.s, hipStreamNonBlocking, prio_hi));
+    ZKR_HIP_CHECK(hipStreamCreateWithPriority(&kept[device].s, hipStreamNonBlocking, prio_hi));
   }
-  ZKR_HIP_CHECK(hipMemcpyAsync(b_in.p, inputs, n_batches * (size_t)(p - 1) * 32, hipMemcpyHostToDevice, sg.s));
+  StreamRef sg = kept[device];
+  if (d_inputs) sg.s = stream;
+  else ZKR_HIP_CHECK(hipMemcpyAsync(b_in.p, inputs, n_batches * (size_t)(p - 1) * 32, hipMemcpyHostToDevice, sg.s));
   uint32_t *d_errs = b_errs.as<uint32_t>(), *d_chain = d_errs + ROWS * n_tx;
   rollup_witness_tx_kernel<<<dim3((unsigned)((n_tx + 63) / 64), TX_PARTS), 64, 0, sg.s>>>(b_in.as<Fr>(), (uint32_t)n_batches, batch, depth, K, k, (Fr *)d_witnesses, b_ws.as<Fr>(), b_roots.as<Fr>(), d_errs);
   ZKR_HIP_CHECK(hipGetLastError());
@@ -337,6 +296,15 @@ int zkr_rollup_witness_batch_device(uint32_t batch, uint32_t depth, const uint8_
     }
   }
   return ZKR_OK;
+}
+
+int zkr_rollup_witness_batch_device(uint32_t batch, uint32_t depth, const uint8_t *inputs, size_t n_inputs, size_t n_batches, void *d_witnesses, int device) {
+  if (!inputs && n_batches) { set_error("null argument"); return ZKR_ERR_ARG; }
+  return witness_batch(batch, depth, inputs, nullptr, n_inputs, n_batches, d_witnesses, device, nullptr);
+}
+int zkr_rollup_witness_batch_from_device(uint32_t batch, uint32_t depth, const void *d_inputs, size_t n_inputs, size_t n_batches, void *d_witnesses, int device, void *stream) {
+  if (!d_inputs && n_batches) { set_error("null argument"); return ZKR_ERR_ARG; }
+  return witness_batch(batch, depth, nullptr, d_inputs, n_inputs, n_batches, d_witnesses, device, (hipStream_t)stream);
 }
 
 // The same value program run on the HOST for one batch (test hook: no device involved): witness_out = nVars x 32 B laid out as

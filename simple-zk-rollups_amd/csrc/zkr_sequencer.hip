@@ -1,0 +1,552 @@
+// zkr_sequencer.hip -- the operator's ledger on the GPU: a queue of signed transactions in, a status per transaction and the
+// input signals of every whole batch out, in device memory, laid out as zkr_rollup_witness_batch_device takes them.
+// Replaces the per-transaction host loop of /root/reference/operator/src/routes/send.ts:72-135 (account, balance, fee and nonce
+// checks, `verify(formatTx(tx), signature, publicKey)`) and the two leaf moves per transaction of
+// operator/src/utils/merkletree.ts:44-83 / operator/src/routes/pubsub.ts:19-66.
+//
+//   a  signatures     one thread per transaction: S * BASE8 - h * (8A) as ONE projective double-and-add chain over a four-entry
+//                     table, compared with R8 by cross-multiplication (no inversion, no signal store: this is not the witness
+//                     program of rollup_witness.hpp, which proves the same equation signal by signal)
+//   b  ledger pass    on the host (sequencer_plan.cpp): the rules, the 256-bit balance arithmetic, the look-up tables
+//   c  leaf hashes    one launch, 2T hashes of four elements
+//   d  tree levels    one launch per level, 2T independent hashes each: val[l+1][u] = H(ordered(val[l][u], sib[l][u]))
+//   e  assembly       one kernel writes the input signals, a second one the touched nodes' last versions into the ledger's tree
+// The field is field.hpp's 8 x 32 limbs throughout, as in the other cold-side kernels.
+#include <chrono>
+#include <mutex>
+#include <vector>
+#include "zkr_internal.hpp"
+#include "rollup_witness.hpp"
+#include "mimc_device.hpp"
+#include "sequencer_plan.hpp"
+
+namespace zkr {
+void rollup_device_constants(Fr *a, Fr *d, uint32_t suborder_m1[8], Fr *b8x253, Fr *b8y253);  // rollup.cpp
+int rollup_check_geometry(uint32_t batch, uint32_t depth);
+
+// ------------------------------------------------------------------------------------------------ a. signatures
+struct SigConsts {
+  Fr a, d, b8x, b8y;     // Montgomery
+  uint32_t suborder[8];  // eddsa.circom:32 (+ 1)
+};
+struct SeqPt { Fr x, y, z; };
+
+__device__ __forceinline__ SeqPt seq_add(const SigConsts &k, const SeqPt &p, const SeqPt &q) {  // add-2008-bbjlp, complete on BabyJub
+  Fr A = mul(p.z, q.z), B = sqr(A), C = mul(p.x, q.x), D = mul(p.y, q.y);
+  Fr E = mul(k.d, mul(C, D)), F = sub(B, E), G = add(B, E);
+  Fr x3 = mul(mul(A, F), sub(sub(mul(add(p.x, p.y), add(q.x, q.y)), C), D));
+  Fr y3 = mul(mul(A, G), sub(D, mul(k.a, C)));
+  return SeqPt{x3, y3, mul(F, G)};
+}
+__device__ __forceinline__ SeqPt seq_dbl(const SigConsts &k, const SeqPt &p) {  // dbl-2008-bbjlp
+  Fr B = sqr(add(p.x, p.y)), C = sqr(p.x), D = sqr(p.y), E = mul(k.a, C), F = add(E, D), H = sqr(p.z);
+  Fr J = sub(F, dbl(H));
+  return SeqPt{mul(sub(sub(B, C), D), J), mul(F, sub(E, D)), mul(F, J)};
+}
+__device__ __forceinline__ bool seq_on_curve(const SigConsts &k, const Fr &x, const Fr &y) {  // a x^2 + y^2 = 1 + d x^2 y^2
+  Fr x2 = sqr(x), y2 = sqr(y);
+  return add(mul(k.a, x2), y2) == add(Fr::one(), mul(k.d, mul(x2, y2)));
+}
+// standard form -> Montgomery; false when the words are not below r
+__device__ __forceinline__ bool seq_read(const Fr *p, Fr &out) {
+  Fr a = *p;
+  out = to_mont(a);
+  return words_below(a.v, FrParams::P);
+}
+// the top bit of a 256-bit number, which then moves up by one: a scalar's bits from the top without an indexed register array
+__device__ __forceinline__ uint32_t seq_take_top_bit(uint32_t (&w)[8]) {
+  const uint32_t b = w[7] >> 31;
+#pragma unroll
+  for (int i = 7; i > 0; i--) w[i] = (w[i] << 1) | (w[i - 1] >> 31);
+  w[0] <<= 1;
+  return b;
+}
+// entry `sel` of four, by masks: the entries stay in registers (a chain of selects becomes an indexed table in scratch)
+__device__ __forceinline__ Fr seq_pick(uint32_t sel, const Fr &e0, const Fr &e1, const Fr &e2, const Fr &e3) {
+  const uint32_t m0 = 0u - (uint32_t)(sel == 0), m1 = 0u - (uint32_t)(sel == 1), m2 = 0u - (uint32_t)(sel == 2), m3 = 0u - (uint32_t)(sel == 3);
+  Fr r;
+#pragma unroll
+  for (int i = 0; i < 8; i++) r.v[i] = (e0.v[i] & m0) | (e1.v[i] & m1) | (e2.v[i] & m2) | (e3.v[i] & m3);
+  return r;
+}
+
+// verdicts[t] = 1 when signature t verifies: R8 and A on the curve, S below the subgroup order, every word below r, and
+// S * BASE8 == R8 + h * (8A) with h = multiHash(R8x, R8y, Ax, Ay, multiHash(message)) -- circomlib's verifyMiMCSponge
+// (crypto.ts:170-177), the answer of zkr_eddsa_verify.  strict: also refuse a key whose order divides 8 (4A has x = 0), which
+// the circuit refuses (eddsa.circom's patched verifier, ST_SMALL_ORDER in rollup_witness.hpp).
+// msgs / sigs / pubs: standard form, element t at t * stride; message elements of any size are taken mod r.
+static __global__ __launch_bounds__(64) void seq_verify_kernel(const Fr *msgs, size_t msg_stride, uint32_t arity, const Fr *sigs, size_t sig_stride, const Fr *pubs,
+                                                               size_t n, SigConsts k, uint32_t strict, uint8_t *verdicts) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  verdicts[t] = 0;
+  Fr r8x, r8y, S, ax, ay;
+  bool ok = seq_read(sigs + t * sig_stride, r8x);
+  ok = seq_read(sigs + t * sig_stride + 1, r8y) && ok;
+  ok = seq_read(sigs + t * sig_stride + 2, S) && ok;
+  ok = seq_read(pubs + 2 * t, ax) && ok;
+  ok = seq_read(pubs + 2 * t + 1, ay) && ok;
+  uint32_t sw[8], hw[8];
+  {
+    const Fr s = sigs[t * sig_stride + 2];
+#pragma unroll
+    for (int i = 0; i < 8; i++) sw[i] = s.v[i];
+  }
+  ok = ok && words_below(sw, k.suborder);
+  ok = ok && seq_on_curve(k, r8x, r8y) && seq_on_curve(k, ax, ay);
+  if (!ok) return;
+  {  // h = multiHash(R8x, R8y, Ax, Ay, multiHash(message))
+    Fr r = Fr::zero(), c = Fr::zero();
+    for (uint32_t i = 0; i < arity; i++) {
+      r = add(r, load_std_as_mont(msgs + t * msg_stride + i));
+      mimc_feistel(r, c);
+    }
+    const Fr m = r;
+    r = r8x, c = Fr::zero();
+    mimc_feistel(r, c);
+    r = add(r, r8y);
+    mimc_feistel(r, c);
+    r = add(r, ax);
+    mimc_feistel(r, c);
+    r = add(r, ay);
+    mimc_feistel(r, c);
+    r = add(r, m);
+    mimc_feistel(r, c);
+    const Fr h = from_mont(r);
+#pragma unroll
+    for (int i = 0; i < 8; i++) hw[i] = h.v[i];
+  }
+  // the table: 0 the identity, 1 BASE8, 2 -(8A), 3 BASE8 - 8A
+  const Fr one = Fr::one(), zero = Fr::zero();
+  SeqPt t2{ax, ay, one};
+  bool small_order = false;
+#pragma unroll 1
+  for (int i = 0; i < 3; i++) {
+    t2 = seq_dbl(k, t2);
+    if (i == 1) small_order = t2.x.is_zero();
+  }
+  if (strict && small_order) return;
+  t2.x = neg(t2.x);
+  const SeqPt t1{k.b8x, k.b8y, one};
+  const SeqPt t3 = seq_add(k, t1, t2);
+  // S < 2^251 and h < 2^254: 254 steps from bit 253 down
+  seq_take_top_bit(sw), seq_take_top_bit(sw);
+  seq_take_top_bit(hw), seq_take_top_bit(hw);
+  SeqPt acc{zero, one, one};
+#pragma unroll 1
+  for (int i = 0; i < 254; i++) {
+    acc = seq_dbl(k, acc);
+    const uint32_t sel = seq_take_top_bit(sw) | (seq_take_top_bit(hw) << 1);
+    const SeqPt q{seq_pick(sel, zero, t1.x, t2.x, t3.x), seq_pick(sel, one, t1.y, t2.y, t3.y), seq_pick(sel, one, t1.z, t2.z, t3.z)};
+    acc = seq_add(k, acc, q);  // the identity included: the lanes of a wavefront seldom all skip a step
+  }
+  // (X : Y : Z) == (R8x, R8y)
+  const bool same = !acc.z.is_zero() && acc.x == mul(r8x, acc.z) && acc.y == mul(r8y, acc.z);
+  verdicts[t] = same ? 1 : 0;
+}
+
+// ------------------------------------------------------------------------------------------------ c, d. leaves and levels
+// val0[u] = multiHash(record u) (hashBalanceTreeLeaf, operator/src/utils/helpers.ts:80-82); standard form in and out
+static __global__ __launch_bounds__(64) void seq_leaf_kernel(const Fr *recs, size_t U, Fr *val0) {
+  const size_t u = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (u >= U) return;
+  Fr r = Fr::zero(), c = Fr::zero();
+  for (int i = 0; i < 4; i++) {
+    r = add(r, load_std_as_mont(recs + 4 * u + i));
+    mimc_feistel(r, c);
+  }
+  val0[u] = from_mont(r);
+}
+// The node above update u's node of level l, as it stands after update u: the hash of that node (val_l[u]) and its sibling, which
+// is what the latest earlier update under the sibling left there (val_l[prev_l[u]]) or, without one, the ledger's stored node.
+__device__ __forceinline__ Fr seq_sibling(const Fr *val_l, int32_t p, const Fr *tree_l, size_t node) { return p >= 0 ? val_l[p] : tree_l[node ^ 1]; }
+static __global__ __launch_bounds__(64) void seq_level_kernel(const Fr *val_l, Fr *val_next, const uint32_t *idx, const int32_t *prev_l, const Fr *tree_l, uint32_t l, size_t U) {
+  const size_t u = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (u >= U) return;
+  const size_t node = (size_t)idx[u] >> l;
+  const Fr cur = val_l[u], sib = seq_sibling(val_l, prev_l[u], tree_l, node);
+  const bool right = node & 1;
+  Fr r = to_mont(right ? sib : cur), c = Fr::zero();  // hashLeftRight (crypto.ts:36-38)
+  mimc_feistel(r, c);
+  r = add(r, to_mont(right ? cur : sib));
+  mimc_feistel(r, c);
+  val_next[u] = from_mont(r);
+}
+
+// ------------------------------------------------------------------------------------------------ e. assembly
+__host__ __device__ static inline size_t seq_level_offset(uint32_t depth, uint32_t l) {  // leaves first, root last (zkr_balance_tree_build's order)
+  return ((size_t)2 << depth) - ((size_t)2 << (depth - l));
+}
+struct SeqView {  // what one call left in device memory; U = 2T updates
+  const Fr *txs;        // T x 8, the applied transactions
+  const Fr *old_rec;    // U x 4
+  const Fr *val;        // (depth + 1) x U
+  const uint32_t *idx;  // U
+  const int32_t *prev;  // 3 x depth x U (sequencer_plan.hpp seq_tables)
+  const Fr *tree;       // the ledger's stored tree, before this call
+  size_t U;
+  uint32_t depth, batch;
+};
+// One thread per input signal of every batch, in circom's order (rollup_witness.hpp tx_layout: every input array flattened over
+// the batch, batchprocesstx.circom:13-36).
+static __global__ __launch_bounds__(256) void seq_assemble_kernel(SeqView v, size_t n_batches, Fr *inputs) {
+  const uint32_t depth = v.depth, batch = v.batch;
+  const size_t per = (size_t)batch * (18 + 3 * depth);
+  const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= per * n_batches) return;
+  const size_t bi = g / per;
+  uint32_t rem = (uint32_t)(g % per), f = 0, cnt = 1;
+  for (;; f++) {  // the field this signal belongs to: widths 1 8 2 1 1 depth 2 1 1 depth 1 depth
+    cnt = f == 1 ? 8 : (f == 2 || f == 6) ? 2 : (f == 5 || f == 9 || f == 11) ? depth : 1;
+    if (rem < batch * cnt) break;
+    rem -= batch * cnt;
+  }
+  const uint32_t j = rem % cnt;
+  const size_t k = bi * batch + rem / cnt, U = v.U, us = 2 * k, ur = 2 * k + 1;
+  const Fr *root_vals = v.val + (size_t)depth * U;
+  Fr out;
+  if (f == 0) out = k == 0 ? v.tree[seq_level_offset(depth, depth)] : root_vals[us - 1];  // balanceTreeRoot
+  else if (f == 1) out = v.txs[8 * k + j];                                                  // txData
+  else if (f == 2) out = v.old_rec[4 * us + j];                                             // txSenderPublicKey
+  else if (f == 3) out = v.old_rec[4 * us + 2];                                             // txSenderBalance
+  else if (f == 4) out = v.old_rec[4 * us + 3];                                             // txSenderNonce
+  else if (f == 6) out = v.old_rec[4 * ur + j];                                             // txRecipientPublicKey
+  else if (f == 7) out = v.old_rec[4 * ur + 2];                                             // txRecipientBalance
+  else if (f == 8) out = v.old_rec[4 * ur + 3];                                             // txRecipientNonce
+  else if (f == 10) out = root_vals[us];                                                    // intermediateBalanceTreeRoot
+  else {
+    // a path element of level j: the sender's before the transaction (5), the recipient's before it (9: table 1) and after the
+    // sender's update (11)
+    const size_t u = f == 11 ? ur : us;
+    const int32_t p = v.prev[((size_t)(f == 9 ? 1 : 0) * depth + j) * U + u];
+    const size_t node = (size_t)v.idx[f == 5 ? us : ur] >> j;
+    out = seq_sibling(v.val + (size_t)j * U, p, v.tree + seq_level_offset(depth, j), node);
+  }
+  inputs[g] = out;
+}
+// The last version of every touched node goes into the stored tree (table 2 names it; the root's is the last update's).
+static __global__ __launch_bounds__(256) void seq_store_kernel(SeqView v, Fr *tree) {
+  const size_t U = v.U, g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= ((size_t)v.depth + 1) * U) return;
+  const uint32_t l = (uint32_t)(g / U);
+  const size_t u = g % U;
+  const bool last = l == v.depth ? u == U - 1 : v.prev[((size_t)2 * v.depth + l) * U + u] != 0;
+  if (last) tree[seq_level_offset(v.depth, l) + ((size_t)v.idx[u] >> l)] = v.val[g];
+}
+static __global__ __launch_bounds__(256) void seq_fill_kernel(Fr *dst, size_t n, Fr value) {
+  const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g < n) dst[g] = value;
+}
+
+// ------------------------------------------------------------------------------------------------ host side
+static SigConsts sig_consts() {
+  static const SigConsts k = [] {
+    SigConsts c;
+    std::vector<Fr> tab(2 * 253);
+    rollup_device_constants(&c.a, &c.d, c.suborder, tab.data(), tab.data() + 253);
+    c.suborder[0] += 1;  // the constant is even (rollup.cpp Bj)
+    c.b8x = tab[0], c.b8y = tab[253];
+    return c;
+  }();
+  return k;
+}
+static inline unsigned blocks(size_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
+
+struct DevArena {  // one allocation per ledger, only ever grown; cut into aligned pieces per call
+  char *p = nullptr;
+  size_t cap = 0, at = 0;
+  int reserve(size_t bytes) {
+    at = 0;
+    if (bytes <= cap) return ZKR_OK;
+    if (p) hipFree(p);
+    p = nullptr, cap = 0;
+    ZKR_HIP_CHECK(hipMalloc((void **)&p, bytes + bytes / 2));
+    cap = bytes + bytes / 2;
+    return ZKR_OK;
+  }
+  static size_t padded(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+  template <class T> T *take(size_t count) {
+    T *r = reinterpret_cast<T *>(p + at);
+    at += padded(count * sizeof(T));
+    return r;
+  }
+};
+}  // namespace zkr
+
+using namespace zkr;
+
+struct zkr_ledger {
+  unsigned depth = 0;
+  int device = 0;
+  size_t accounts = 0;
+  uint64_t applied = 0, batches = 0;
+  std::vector<uint8_t> records;  // accounts x 128 B
+  Fr *d_tree = nullptr;          // (2^(depth + 1) - 1) nodes, standard form, leaves first
+  DevArena arena;
+  double stage_ms[5] = {0, 0, 0, 0, 0};
+  mutable std::mutex mu;
+};
+
+namespace {
+struct StageClock {  // wall time per stage, only when ZKR_SEQUENCER_STAGES is set: every mark waits for the stream
+  bool on;
+  hipStream_t s;
+  std::chrono::steady_clock::time_point t0;
+  StageClock(hipStream_t stream) : on(getenv("ZKR_SEQUENCER_STAGES") != nullptr), s(stream), t0(std::chrono::steady_clock::now()) {}
+  void mark(double &slot) {
+    if (!on) return;
+    hipStreamSynchronize(s);
+    const auto t1 = std::chrono::steady_clock::now();
+    slot = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    t0 = t1;
+  }
+};
+
+// Steps c and d for U leaf updates whose records, leaf indices and tables are already in the arena: val[0] from the records, then
+// level by level.  Every index the kernels follow was bounded on the host: idx[u] < accounts <= 2^depth, -1 <= prev[l][u] < u.
+int hash_updates(const zkr_ledger *L, size_t U, const Fr *d_new, const uint32_t *d_idx, const int32_t *d_prev, Fr *d_val, hipStream_t s, StageClock &clk, double *ms) {
+  seq_leaf_kernel<<<blocks(U, 64), 64, 0, s>>>(d_new, U, d_val);
+  ZKR_HIP_CHECK(hipGetLastError());
+  clk.mark(ms[2]);
+  for (unsigned l = 0; l < L->depth; l++) {
+    seq_level_kernel<<<blocks(U, 64), 64, 0, s>>>(d_val + (size_t)l * U, d_val + (size_t)(l + 1) * U, d_idx, d_prev + (size_t)l * U, L->d_tree + seq_level_offset(L->depth, l), l, U);
+    ZKR_HIP_CHECK(hipGetLastError());
+  }
+  clk.mark(ms[3]);
+  return ZKR_OK;
+}
+int need_device(int device, const char *what) {
+  if (zkr_device_count() <= device || device < 0) { set_error("no HIP device %d; %s runs on the GPU and has no CPU fallback", device, what); return ZKR_ERR_NO_DEVICE; }
+  return ZKR_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int zkr_ledger_new(unsigned depth, int device, zkr_ledger **out) {
+  if (!out) { set_error("null argument"); return ZKR_ERR_ARG; }
+  *out = nullptr;
+  if (depth < 1 || depth > 24) { set_error("ledger depth %u out of range (1..24)", depth); return ZKR_ERR_ARG; }
+  int rc = need_device(device, "the ledger");
+  if (rc) return rc;
+  ZKR_HIP_CHECK(hipSetDevice(device));
+  if ((rc = upload_mimc_constants(device))) return rc;
+  zkr_ledger *L = new zkr_ledger;
+  L->depth = depth, L->device = device;
+  const size_t total = ((size_t)2 << depth) - 1;
+  if (hipMalloc((void **)&L->d_tree, total * 32) != hipSuccess) { delete L; set_error("out of device memory for a tree of depth %u", depth); return ZKR_ERR_HIP; }
+  uint8_t z[64] = {0};  // the empty tree: every node of a level is the hash of two empty nodes below (merkletree.ts:44-60)
+  hipError_t e = hipSuccess;
+  for (unsigned l = 0; l <= depth && e == hipSuccess; l++) {
+    Fr v;
+    memcpy(v.v, z, 32);
+    const size_t width = (size_t)1 << (depth - l);
+    seq_fill_kernel<<<blocks(width, 256), 256>>>(L->d_tree + seq_level_offset(depth, l), width, v);
+    e = hipGetLastError();
+    memcpy(z + 32, z, 32);
+    zkr_mimcsponge_multihash(z, 2, z);
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) { hipFree(L->d_tree); delete L; set_error("ledger tree fill failed: %s", hipGetErrorString(e)); return ZKR_ERR_HIP; }
+  *out = L;
+  return ZKR_OK;
+}
+
+void zkr_ledger_free(zkr_ledger *l) {
+  if (!l) return;
+  if (hipSetDevice(l->device) == hipSuccess) {
+    if (l->d_tree) hipFree(l->d_tree);
+    if (l->arena.p) hipFree(l->arena.p);
+  }
+  delete l;
+}
+
+int zkr_ledger_info(const zkr_ledger *l, uint64_t out[4]) {
+  if (!l || !out) { set_error("null argument"); return ZKR_ERR_ARG; }
+  std::lock_guard<std::mutex> lk(l->mu);
+  out[0] = l->depth, out[1] = l->accounts, out[2] = l->applied, out[3] = l->batches;
+  return ZKR_OK;
+}
+
+int zkr_ledger_stage_times(const zkr_ledger *l, double ms[5]) {
+  if (!l || !ms) { set_error("null argument"); return ZKR_ERR_ARG; }
+  std::lock_guard<std::mutex> lk(l->mu);
+  for (int i = 0; i < 5; i++) ms[i] = l->stage_ms[i];
+  return ZKR_OK;
+}
+
+int zkr_ledger_root(const zkr_ledger *l, uint8_t root[32]) {
+  if (!l || !root) { set_error("null argument"); return ZKR_ERR_ARG; }
+  std::lock_guard<std::mutex> lk(l->mu);
+  ZKR_HIP_CHECK(hipSetDevice(l->device));
+  ZKR_HIP_CHECK(hipMemcpy(root, l->d_tree + seq_level_offset(l->depth, l->depth), 32, hipMemcpyDeviceToHost));
+  return ZKR_OK;
+}
+
+int zkr_ledger_account(const zkr_ledger *l, uint32_t index, uint8_t record[128], uint8_t *path) {
+  if (!l || !record) { set_error("null argument"); return ZKR_ERR_ARG; }
+  std::lock_guard<std::mutex> lk(l->mu);
+  if (index >= l->accounts) { set_error("account %u of %zu", index, l->accounts); return ZKR_ERR_ARG; }
+  memcpy(record, l->records.data() + (size_t)index * 128, 128);
+  if (!path) return ZKR_OK;
+  ZKR_HIP_CHECK(hipSetDevice(l->device));
+  for (unsigned lv = 0; lv < l->depth; lv++)  // getUpdatePath(index).pathElements: the sibling per level, leaf level first
+    ZKR_HIP_CHECK(hipMemcpy(path + 32 * lv, l->d_tree + seq_level_offset(l->depth, lv) + (((size_t)index >> lv) ^ 1), 32, hipMemcpyDeviceToHost));
+  return ZKR_OK;
+}
+
+int zkr_ledger_deposit(zkr_ledger *l, const uint32_t *indices, const uint8_t *records, size_t n) {
+  if (!l || (n && (!indices || !records))) { set_error("null argument"); return ZKR_ERR_ARG; }
+  if (n == 0) return ZKR_OK;
+  if (n > ((size_t)1 << 24)) { set_error("more than 2^24 records in one deposit"); return ZKR_ERR_ARG; }
+  std::lock_guard<std::mutex> lk(l->mu);
+  size_t accounts = l->accounts;
+  for (size_t i = 0; i < n; i++) {
+    if (indices[i] > accounts) { set_error("deposit %zu: index %u is out of sync with the ledger's %zu accounts (pubsub.ts:37-41)", i, indices[i], accounts); return ZKR_ERR_ARG; }
+    if (indices[i] == accounts) {
+      if (accounts == ((size_t)1 << l->depth)) { set_error("deposit %zu: the tree of depth %u is full", i, l->depth); return ZKR_ERR_ARG; }
+      accounts++;
+    }
+    for (int j = 0; j < 4; j++) {
+      const Int256 v = int256_load(records + i * 128 + 32 * j);
+      if (!int256_below_r(v) || (j >= 2 && !int256_below_2_250(v))) {
+        set_error("deposit %zu: element %d is not below r, or a balance / nonce does not fit the circuit's 250 bits", i, j);
+        return ZKR_ERR_ARG;
+      }
+    }
+  }
+  ZKR_HIP_CHECK(hipSetDevice(l->device));
+  const unsigned depth = l->depth;
+  const size_t U = n;
+  std::vector<uint32_t> idx(indices, indices + n);
+  std::vector<int32_t> prev(3 * (size_t)depth * U);
+  seq_tables(depth, idx, nullptr, accounts, prev.data());
+  int rc = l->arena.reserve(DevArena::padded(U * 128) + DevArena::padded(U * 4) + DevArena::padded(prev.size() * 4) + DevArena::padded(((size_t)depth + 1) * U * 32));
+  if (rc) return rc;
+  Fr *d_new = l->arena.take<Fr>(4 * U), *d_val = l->arena.take<Fr>(((size_t)depth + 1) * U);
+  uint32_t *d_idx = l->arena.take<uint32_t>(U);
+  int32_t *d_prev = l->arena.take<int32_t>(prev.size());
+  hipStream_t s = nullptr;
+  ZKR_HIP_CHECK(hipMemcpyAsync(d_new, records, U * 128, hipMemcpyHostToDevice, s));
+  ZKR_HIP_CHECK(hipMemcpyAsync(d_idx, idx.data(), U * 4, hipMemcpyHostToDevice, s));
+  ZKR_HIP_CHECK(hipMemcpyAsync(d_prev, prev.data(), prev.size() * 4, hipMemcpyHostToDevice, s));
+  StageClock clk(s);
+  clk.on = false;
+  double unused[5];
+  if ((rc = hash_updates(l, U, d_new, d_idx, d_prev, d_val, s, clk, unused))) return rc;
+  ZKR_HIP_CHECK(hipStreamSynchronize(s));  // the tree is untouched up to here: a failure above leaves the ledger as it was
+  SeqView v{nullptr, nullptr, d_val, d_idx, d_prev, l->d_tree, U, depth, 1};
+  seq_store_kernel<<<blocks(((size_t)depth + 1) * U, 256), 256, 0, s>>>(v, l->d_tree);
+  ZKR_HIP_CHECK(hipGetLastError());
+  ZKR_HIP_CHECK(hipStreamSynchronize(s));
+  l->records.resize(accounts * 128);
+  for (size_t i = 0; i < n; i++) memcpy(l->records.data() + (size_t)indices[i] * 128, records + i * 128, 128);
+  l->accounts = accounts;
+  return ZKR_OK;
+}
+
+int zkr_eddsa_verify_batch(const uint8_t *msgs, unsigned arity, const uint8_t *sigs, const uint8_t *pubs, size_t n, uint8_t *verdicts, int device) {
+  if (n && (!msgs || !sigs || !pubs || !verdicts)) { set_error("null argument"); return ZKR_ERR_ARG; }
+  if (arity < 1 || arity > 64) { set_error("message arity %u out of range (1..64)", arity); return ZKR_ERR_ARG; }
+  if (n > ((size_t)1 << 24)) { set_error("more than 2^24 signatures in one call"); return ZKR_ERR_ARG; }
+  int rc = need_device(device, "the batch signature check (zkr_eddsa_verify is the host call)");
+  if (rc) return rc;
+  if (n == 0) return ZKR_OK;
+  ZKR_HIP_CHECK(hipSetDevice(device));
+  if ((rc = upload_mimc_constants(device))) return rc;
+  const size_t mb = DevArena::padded(n * arity * 32), sb = DevArena::padded(n * 96), pb = DevArena::padded(n * 64);
+  char *d = nullptr;
+  ZKR_HIP_CHECK(hipMalloc((void **)&d, mb + sb + pb + n));
+  Fr *d_msgs = (Fr *)d, *d_sigs = (Fr *)(d + mb), *d_pubs = (Fr *)(d + mb + sb);
+  uint8_t *d_v = (uint8_t *)(d + mb + sb + pb);
+  hipError_t e = hipMemcpy(d_msgs, msgs, n * arity * 32, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_sigs, sigs, n * 96, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_pubs, pubs, n * 64, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    seq_verify_kernel<<<blocks(n, 64), 64>>>(d_msgs, arity, arity, d_sigs, 3, d_pubs, n, sig_consts(), 0, d_v);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(verdicts, d_v, n, hipMemcpyDeviceToHost);
+  hipFree(d);
+  if (e != hipSuccess) { set_error("batch signature check failed: %s", hipGetErrorString(e)); return ZKR_ERR_HIP; }
+  return ZKR_OK;
+}
+
+int zkr_ledger_sequence(zkr_ledger *l, const uint8_t *txs, size_t n_txs, uint32_t batch, uint8_t *status, void *d_inputs, size_t *n_batches, size_t *consumed, void *stream) {
+  if (!l || !d_inputs || !n_batches || !consumed || (n_txs && (!txs || !status))) { set_error("null argument"); return ZKR_ERR_ARG; }
+  *n_batches = 0, *consumed = 0;
+  std::lock_guard<std::mutex> lk(l->mu);
+  const unsigned depth = l->depth;
+  int rc = rollup_check_geometry(batch, depth);
+  if (rc) return rc;
+  if (n_txs > ((size_t)1 << 22)) { set_error("more than 2^22 transactions in one queue"); return ZKR_ERR_ARG; }
+  if (n_txs == 0) return ZKR_OK;
+  ZKR_HIP_CHECK(hipSetDevice(l->device));
+  hipStream_t s = (hipStream_t)stream;
+  double ms[5] = {0, 0, 0, 0, 0};
+  StageClock clk(s);
+
+  // a. the senders' stored keys beside their transactions; a sender that is no account gets a key that is on no curve
+  std::vector<uint8_t> keys(n_txs * 64, 0), verdicts(n_txs);
+  for (size_t t = 0; t < n_txs; t++) {
+    const Int256 from = int256_load(txs + t * 256);
+    if (!(from.w[1] | from.w[2] | from.w[3]) && from.w[0] < l->accounts) memcpy(&keys[t * 64], l->records.data() + (size_t)from.w[0] * 128, 64);
+  }
+  const size_t U_max = 2 * n_txs, tables_max = 3 * (size_t)depth * U_max;
+  rc = l->arena.reserve(2 * DevArena::padded(n_txs * 256) + DevArena::padded(n_txs * 64) + DevArena::padded(n_txs) + 2 * DevArena::padded(U_max * 128) +
+                        DevArena::padded(U_max * 4) + DevArena::padded(tables_max * 4) + DevArena::padded(((size_t)depth + 1) * U_max * 32));
+  if (rc) return rc;
+  Fr *d_queue = l->arena.take<Fr>(n_txs * 8), *d_keys = l->arena.take<Fr>(n_txs * 2);
+  uint8_t *d_verdicts = l->arena.take<uint8_t>(n_txs);
+  ZKR_HIP_CHECK(hipMemcpyAsync(d_queue, txs, n_txs * 256, hipMemcpyHostToDevice, s));
+  ZKR_HIP_CHECK(hipMemcpyAsync(d_keys, keys.data(), n_txs * 64, hipMemcpyHostToDevice, s));
+  seq_verify_kernel<<<blocks(n_txs, 64), 64, 0, s>>>(d_queue, 8, 5, d_queue + 5, 8, d_keys, n_txs, sig_consts(), 1, d_verdicts);
+  ZKR_HIP_CHECK(hipGetLastError());
+  ZKR_HIP_CHECK(hipMemcpyAsync(verdicts.data(), d_verdicts, n_txs, hipMemcpyDeviceToHost, s));
+  ZKR_HIP_CHECK(hipStreamSynchronize(s));
+  clk.mark(ms[0]);
+
+  // b. the pass
+  SeqPlan plan;
+  const char *why = "";
+  if (seq_plan(depth, l->records.data(), l->accounts, txs, n_txs, verdicts.data(), batch, plan, &why)) { set_error("%s", why); return ZKR_ERR_ARG; }
+  clk.mark(ms[1]);
+  const size_t T = plan.applied, U = 2 * T;
+  if (T) {
+    std::vector<uint8_t> h_txs(T * 256), h_old(U * 128), h_new(U * 128);
+    for (size_t k = 0; k < T; k++) memcpy(&h_txs[k * 256], txs + (size_t)plan.pos[k] * 256, 256);
+    for (size_t u = 0; u < U; u++)
+      for (int j = 0; j < 4; j++) int256_store(&h_old[u * 128 + 32 * j], plan.old_rec[u].f[j]), int256_store(&h_new[u * 128 + 32 * j], plan.new_rec[u].f[j]);
+    for (size_t u = 0; u < U; u++)  // every index the kernels follow, once more in one place
+      if (plan.idx[u] >= l->accounts) { set_error("internal: update %zu names leaf %u of %zu", u, plan.idx[u], l->accounts); return ZKR_ERR_ARG; }
+    for (size_t i = 0; i < 2 * (size_t)depth * U; i++)
+      if (plan.prev[i] < -1 || plan.prev[i] >= (int32_t)(i % U)) { set_error("internal: look-up table entry %zu out of range", i); return ZKR_ERR_ARG; }
+    Fr *d_txs = l->arena.take<Fr>(T * 8), *d_old = l->arena.take<Fr>(U * 4), *d_new = l->arena.take<Fr>(U * 4), *d_val = l->arena.take<Fr>(((size_t)depth + 1) * U);
+    uint32_t *d_idx = l->arena.take<uint32_t>(U);
+    int32_t *d_prev = l->arena.take<int32_t>(plan.prev.size());
+    ZKR_HIP_CHECK(hipMemcpyAsync(d_txs, h_txs.data(), h_txs.size(), hipMemcpyHostToDevice, s));
+    ZKR_HIP_CHECK(hipMemcpyAsync(d_old, h_old.data(), h_old.size(), hipMemcpyHostToDevice, s));
+    ZKR_HIP_CHECK(hipMemcpyAsync(d_new, h_new.data(), h_new.size(), hipMemcpyHostToDevice, s));
+    ZKR_HIP_CHECK(hipMemcpyAsync(d_idx, plan.idx.data(), U * 4, hipMemcpyHostToDevice, s));
+    ZKR_HIP_CHECK(hipMemcpyAsync(d_prev, plan.prev.data(), plan.prev.size() * 4, hipMemcpyHostToDevice, s));
+    if ((rc = hash_updates(l, U, d_new, d_idx, d_prev, d_val, s, clk, ms))) return rc;
+    const size_t nb = T / batch;
+    SeqView v{d_txs, d_old, d_val, d_idx, d_prev, l->d_tree, U, depth, batch};
+    seq_assemble_kernel<<<blocks(nb * batch * (18 + 3 * (size_t)depth), 256), 256, 0, s>>>(v, nb, (Fr *)d_inputs);
+    ZKR_HIP_CHECK(hipGetLastError());
+    ZKR_HIP_CHECK(hipStreamSynchronize(s));  // the tree is untouched up to here: a failure above leaves the ledger as it was
+    seq_store_kernel<<<blocks(((size_t)depth + 1) * U, 256), 256, 0, s>>>(v, l->d_tree);
+    ZKR_HIP_CHECK(hipGetLastError());
+    ZKR_HIP_CHECK(hipStreamSynchronize(s));
+    clk.mark(ms[4]);
+    for (size_t u = 0; u < U; u++) memcpy(l->records.data() + (size_t)plan.idx[u] * 128, &h_new[u * 128], 128);
+    l->applied += T, l->batches += nb;
+    *n_batches = nb;
+  }
+  memcpy(status, plan.status.data(), n_txs);
+  *consumed = plan.consumed;
+  if (clk.on) memcpy(l->stage_ms, ms, sizeof ms);
+  return ZKR_OK;
+}
+
+}  // extern "C"

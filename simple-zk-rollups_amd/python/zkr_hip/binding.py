@@ -143,6 +143,18 @@ def lib():
     L.zkr_rollup_witness_program_host.argtypes = [c.c_uint32, c.c_uint32, u8p, sz, vp, c.POINTER(c.c_uint32), c.POINTER(c.c_uint32)]
     L.zkr_rollup_statement_text.argtypes = [c.c_uint32]
     L.zkr_rollup_statement_text.restype = c.c_char_p
+    L.zkr_rollup_witness_batch_from_device.argtypes = [c.c_uint32, c.c_uint32, vp, sz, sz, vp, c.c_int, vp]
+    L.zkr_ledger_new.argtypes = [c.c_uint, i, c.POINTER(vp)]
+    L.zkr_ledger_free.argtypes = [vp]
+    L.zkr_ledger_free.restype = None
+    L.zkr_ledger_deposit.argtypes = [vp, c.POINTER(c.c_uint32), u8p, sz]
+    L.zkr_ledger_info.argtypes = [vp, c.POINTER(c.c_uint64)]
+    L.zkr_ledger_root.argtypes = [vp, u8p]
+    L.zkr_ledger_account.argtypes = [vp, c.c_uint32, u8p, u8p]
+    L.zkr_ledger_sequence.argtypes = [vp, u8p, sz, c.c_uint32, u8p, vp, c.POINTER(sz), c.POINTER(sz), vp]
+    L.zkr_ledger_stage_times.argtypes = [vp, c.POINTER(c.c_double)]
+    L.zkr_eddsa_verify_batch.argtypes = [u8p, c.c_uint, u8p, u8p, sz, u8p, i]
+    L.zkr_sequence_plan_host.argtypes = [c.c_uint, u8p, sz, u8p, sz, u8p, c.c_uint32, u8p, c.POINTER(sz), c.POINTER(c.c_int32)]
     _lib = L
     return L
 

@@ -83,6 +83,116 @@ def verify(msg, sig, pub) -> bool:
     return bool(ok.value)
 
 
+def verify_batch(msgs, sigs, pubs, device=0):
+    """verify(msg, sig, pubKey) (crypto.ts:170-177) for many signatures on the GPU, one thread each (zkr_eddsa_verify_batch):
+    msgs = equally long lists of message elements (taken mod r, as multi_hash takes them), sigs = {"R8": (x, y), "S": s},
+    pubs = (x, y); elements up to 2^256 - 1.  Returns a list of bools, the answers of `verify` one by one."""
+    msgs = [list(m) for m in msgs]
+    n = len(msgs)
+    assert len(sigs) == n and len(pubs) == n
+    if n == 0:
+        return []
+    arity = len(msgs[0])
+    assert all(len(m) == arity for m in msgs)
+    mb = b"".join(_le(v) for m in msgs for v in m)
+    sb = b"".join(_le(s["R8"][0]) + _le(s["R8"][1]) + _le(s["S"]) for s in sigs)
+    pb = b"".join(_le(p[0]) + _le(p[1]) for p in pubs)
+    out = ctypes.create_string_buffer(n)
+    _check(lib().zkr_eddsa_verify_batch(mb, arity, sb, pb, n, out, device))
+    return [b != 0 for b in out.raw]
+
+
+def tx_row(frm, to, amount, fee, nonce, sig):
+    """The txData row of batchprocesstx.circom for one signed transaction: from to amount fee nonce R8x R8y S."""
+    return [frm, to, amount, fee, nonce, sig["R8"][0], sig["R8"][1], sig["S"]]
+
+
+def sequence_plan_host(depth, records, txs, sig_verdicts, batch):
+    """The host pass of Ledger.sequence without a device (test hook, zkr_sequence_plan_host): records = [pubX, pubY, balance,
+    nonce] per account, txs = tx_row lists, sig_verdicts = one truth value per transaction standing in for rule 10.
+    Returns (status list, consumed, prev) with prev[table][level][update] as include/zkr.h describes the three tables."""
+    n = len(txs)
+    rb = b"".join(_le(v) for r in records for v in r)
+    tb = b"".join(_le(v) for t in txs for v in t)
+    vb = bytes(1 if v else 0 for v in sig_verdicts)
+    status = ctypes.create_string_buffer(max(n, 1))
+    consumed = ctypes.c_size_t()
+    prev = (ctypes.c_int32 * max(1, 3 * depth * 2 * n))()
+    _check(lib().zkr_sequence_plan_host(depth, rb, len(records), tb, n, vb, batch, status, ctypes.byref(consumed), prev))
+    st = list(status.raw[:n])
+    U = 2 * sum(1 for x in st if x == 0)
+    tables = [[[prev[(t * depth + l) * U + u] for u in range(U)] for l in range(depth)] for t in range(3)]
+    return st, consumed.value, tables
+
+
+class Ledger:
+    """The operator's state on the GPU (zkr_ledger_*): account records and the whole balance tree of `depth` levels.
+    `sequence` turns a queue of signed transactions into a status each (0 accepted, 1..10 the first broken rule of
+    include/zkr.h's list, 255 not reached) and the circuit inputs of every whole batch, left in device memory for
+    RollupCircuit.calculate_witness_batch_from_device -- the loop of operator/src/routes/send.ts:72-135 and the tree
+    updates of operator/src/routes/pubsub.ts:19-66 for a whole queue at once."""
+
+    def __init__(self, depth, device=0):
+        h = ctypes.c_void_p()
+        _check(lib().zkr_ledger_new(depth, device, ctypes.byref(h)))
+        self._h, self.depth, self.device = h, depth, device
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().zkr_ledger_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def deposit(self, index, pub=None, balance=None, nonce=0):
+        """onEventUpdateMerkleTree (pubsub.ts:19-66): one record, or `deposit([(index, pub, balance, nonce), ...])`."""
+        rows = index if pub is None else [(index, pub, balance, nonce)]
+        rows = [(int(r[0]), r[1], r[2], r[3] if len(r) > 3 else 0) for r in rows]
+        idx = (ctypes.c_uint32 * max(1, len(rows)))(*[r[0] for r in rows])
+        buf = b"".join(_le(r[1][0]) + _le(r[1][1]) + _le(r[2]) + _le(r[3]) for r in rows)
+        _check(lib().zkr_ledger_deposit(self._h, idx, buf, len(rows)))
+
+    def info(self):
+        out = (ctypes.c_uint64 * 4)()
+        _check(lib().zkr_ledger_info(self._h, out))
+        return {"depth": out[0], "accounts": out[1], "applied": out[2], "batches": out[3]}
+
+    @property
+    def root(self):
+        out = ctypes.create_string_buffer(32)
+        _check(lib().zkr_ledger_root(self._h, out))
+        return int.from_bytes(out.raw, "little")
+
+    def account(self, index):
+        """-> ([pubX, pubY, balance, nonce], getUpdatePath(index).pathElements)."""
+        rec, path = ctypes.create_string_buffer(128), ctypes.create_string_buffer(32 * self.depth)
+        _check(lib().zkr_ledger_account(self._h, index, rec, path))
+        return _ints(rec.raw), _ints(path.raw)
+
+    def sequence(self, txs, batch, stream=None):
+        """txs = tx_row lists.  -> (status list, torch.uint8 tensor [n_batches, (n_public - 1) * 32] on the device, consumed):
+        row b = the inputs of batch b as RollupCircuit.flatten_inputs orders them.  The caller resubmits txs[consumed:]."""
+        import torch
+        n = len(txs)
+        per = batch * (18 + 3 * self.depth) * 32
+        buf = b"".join(_le(v) for t in txs for v in t)
+        out = torch.empty((max(1, n // batch), per), dtype=torch.uint8, device=torch.device("cuda", self.device))
+        status = ctypes.create_string_buffer(max(n, 1))
+        nb, consumed = ctypes.c_size_t(), ctypes.c_size_t()
+        _check(lib().zkr_ledger_sequence(self._h, buf, n, batch, status, out.data_ptr(), ctypes.byref(nb), ctypes.byref(consumed), stream))
+        return list(status.raw[:n]), out[:nb.value], consumed.value
+
+    def stage_times(self):
+        """Milliseconds of the last sequence call's stages (recorded only with ZKR_SEQUENCER_STAGES set in the environment)."""
+        out = (ctypes.c_double * 5)()
+        _check(lib().zkr_ledger_stage_times(self._h, out))
+        return dict(zip(("signatures", "host_pass", "leaf_hashes", "levels", "assembly"), out))
+
+
 class RollupCircuit:
     """BatchProcessTx(batch, depth): what `new Circuit(await compiler("tx.circom"))` is to the reference
     (common.ts:12-15).  `r1cs()` feeds ProvingKey.setup_r1cs; `calculate_witness(inputs)` returns the witness as
@@ -150,6 +260,18 @@ class RollupCircuit:
         buf = b"".join(_le(v) for f in flats for v in f)
         out = torch.empty((len(flats), self.n_vars * 32), dtype=torch.uint8, device=torch.device("cuda", device))   # an allocation: nothing to wait for
         _check(lib().zkr_rollup_witness_batch_device(self.batch, self.depth, buf, self.n_public - 1, len(flats), out.data_ptr(), device))
+        return out
+
+    def calculate_witness_batch_from_device(self, inputs, stream=None):
+        """calculate_witness_batch_device for inputs that are already in device memory (zkr_rollup_witness_batch_from_device):
+        `inputs` = the uint8 tensor [n_batches, (n_public - 1) * 32] of Ledger.sequence.  Same kernels, same errors, same bytes."""
+        import torch
+        if inputs.dtype != torch.uint8 or inputs.dim() != 2 or inputs.shape[1] != (self.n_public - 1) * 32 or not inputs.is_cuda:
+            raise ZkrError(-5, "circuit inputs must be a uint8 device tensor [n_batches, %d]" % ((self.n_public - 1) * 32))
+        inputs = inputs.contiguous()
+        device = inputs.device.index or 0
+        out = torch.empty((inputs.shape[0], self.n_vars * 32), dtype=torch.uint8, device=inputs.device)
+        _check(lib().zkr_rollup_witness_batch_from_device(self.batch, self.depth, inputs.data_ptr(), self.n_public - 1, inputs.shape[0], out.data_ptr(), device, stream))
         return out
 
 
