@@ -674,10 +674,60 @@ int zkr_eddsa_verify_batch(const uint8_t *msgs, unsigned arity, const uint8_t *s
  * stream); the call returns when the statuses are final and d_inputs is complete.  On any error return the ledger is unchanged. */
 int zkr_ledger_sequence(zkr_ledger *l, const uint8_t *txs, size_t n_txs, uint32_t batch, uint8_t *status, void *d_inputs,
                         size_t *n_batches, size_t *consumed, void *stream);
-/* Wall milliseconds of the last zkr_ledger_sequence call's stages -- signatures, host pass, leaf hashes, tree levels, assembly --
- * recorded only while the environment variable ZKR_SEQUENCER_STAGES is set (the call then waits for the stream after each stage). */
+/* Wall milliseconds of the last zkr_ledger_sequence (or zkr_ledger_replay*) call's stages -- signatures, host pass, leaf hashes,
+ * tree levels, assembly -- recorded only while the environment variable ZKR_SEQUENCER_STAGES is set (the call then waits for the
+ * stream after each stage).  For a replay the first slot also holds the signals' way to the device or back from it, the last one
+ * the comparison and the store. */
 int zkr_ledger_stage_times(const zkr_ledger *l, double ms[5]);
+
+/* ---- following the chain: RollUp.sol:81-161 for a run of consecutive published batches, against the ledger's state (DESIGN.md
+ * 9g).  Every input of BatchProcessTx is public (batchprocesstx.circom:12-34), so the public signals of a batch are its complete
+ * state transition: a restarted operator rebuilds its ledger from them, and a second party follows the state and checks that each
+ * batch starts from the current root and ends in the root it claims.  zkr_ledger_sequence WRITES the signals the ledger derives;
+ * a replay COMPARES published signals with them and says, per batch, where they first differ.
+ * publics_std: n_batches x nPublic x 32 B in host memory, standard form, circom's order (newBalanceTreeRoot, then the inputs as
+ *   zkr_ledger_sequence writes them); nPublic = 1 + batch * (18 + 3 * depth).
+ * proof_verdicts: NULL, or n_batches bytes as zkr_verify_each returns them (non-zero = the contract would revert, RollUp.sol:96).
+ *   Proofs are not verified inside the call: the caller composes zkr_verify_each.
+ * flags: ZKR_REPLAY_SIGNATURES = also check every transaction's signature under the sender's stored key (rule 10 of
+ *   zkr_ledger_sequence, the same kernel).
+ * verdicts: n_batches bytes.  where: n_batches words.  *applied: batches applied = index of the first refused batch, or n_batches.
+ *
+ * Batches are judged in order, each against the state all earlier ones leave.  The first batch with a non-zero verdict keeps it
+ * and every later one is 255; the ledger ends as it stands after the last batch with verdict 0 (records, tree, root and the
+ * counters of zkr_ledger_info).  A batch gets the first of these codes that holds:
+ *    1  it cannot be applied: a signal not below r; `from` / `to` no account; amount, fee or nonce not below 2^250; a sender
+ *       balance below amount + fee; a recipient balance that would reach 2^250.  where = the offending signal (the lowest one not
+ *       below r, else the first transaction's; for the balances the transaction's amount signal, 1 + batch + 8k + 2)
+ *    2  balanceTreeRoot[0] is not the ledger's root before the batch (RollUp.sol:92).  where = 1
+ *    3  proof_verdicts[b] != 0 (RollUp.sol:96).  where = 0
+ *    5  only with ZKR_REPLAY_SIGNATURES: a signature fails under the sender's stored key.  where = the transaction within the batch
+ *    4  some signal differs from what the ledger derives from txData and its own state.  where = the lowest differing signal
+ *       (0 = newBalanceTreeRoot)
+ *    0  applied.  where = 0
+ * The arithmetic is the contract's (RollUp.sol:118-158) and processtx.circom's, from == to included: the sender's leaf moves first
+ * (balance - amount - fee, nonce := the transaction's), then the recipient's (balance + amount).  Rules 4-8 of zkr_ledger_sequence
+ * (positive amount and fee, the strict balance, the fee floor, nonce + 1) are NOT applied: they are operator policy or the
+ * circuit's matter (code 3); the contract applies whatever was proved, and a follower has to track the contract.  Fees are not
+ * accounted (accuredFees), events and calldata are not decoded.
+ * An argument error (null, batch 0, a geometry zkr_rollup_info refuses, more than 2^22 transactions, a null witness pointer) is
+ * ZKR_ERR_ARG and leaves the ledger, verdicts and where untouched and *applied = 0.  No CPU fallback (ZKR_ERR_NO_DEVICE). ---- */
+#define ZKR_REPLAY_SIGNATURES 1u
+int zkr_ledger_replay(zkr_ledger *l, const void *publics_std, size_t n_batches, uint32_t batch, const uint8_t *proof_verdicts,
+                      uint32_t flags, uint8_t *verdicts, uint32_t *where, size_t *applied, void *stream);
+/* The same with the signals read in place: d_witnesses_std is a host array of n_batches device pointers on the ledger's device,
+ * batch b's signals are words 1..nPublic of witness b (the convention of zkr_verify_each_device); no other word is read. */
+int zkr_ledger_replay_device(zkr_ledger *l, const void *const *d_witnesses_std, size_t n_batches, uint32_t batch,
+                             const uint8_t *proof_verdicts, uint32_t flags, uint8_t *verdicts, uint32_t *where, size_t *applied,
+                             void *stream);
 /* host only */
+/* Test hook: the host pass of zkr_ledger_replay alone (verdict 1 and the arithmetic), as zkr_sequence_plan_host is for the
+ * sequencer.  verdicts[b] = 0 planned, 1 the first batch that cannot be applied (where[b] = its signal), 255 behind it; *planned =
+ * that batch's index or n_batches.  With T = *planned x batch: idx (may be NULL) 2T leaf indices, old_rec / new_rec (may be NULL)
+ * 2T x 128 B, prev (may be NULL) the three tables [3][depth][2T]; room for 2 x batch x n_batches updates each. */
+int zkr_replay_plan_host(unsigned depth, const uint8_t *records, size_t n_accounts, const void *publics_std, size_t n_batches,
+                         uint32_t batch, uint8_t *verdicts, uint32_t *where, size_t *planned, uint32_t *idx, uint8_t *old_rec,
+                         uint8_t *new_rec, int32_t *prev);
 /* Test hook: the host pass of zkr_ledger_sequence (rules 1-9 and the arithmetic; rule 10 from sig_verdicts, one byte per
  * transaction) over records = n_accounts x 128 B.  prev (may be NULL): int32 [3][depth][2T], T = the number of status-0
  * transactions, room for 3 x depth x 2 x n_txs: table 0 [l][u] = the latest update u' < u under the sibling of update u's node

@@ -1,5 +1,5 @@
-// sequencer_plan.cpp -- the host pass of the transaction sequencer (sequencer_plan.hpp) and its test hook
-// zkr_sequence_plan_host.  Reference: /root/reference/operator/src/routes/send.ts:72-135 (the operator's checks),
+// sequencer_plan.cpp -- the host passes of the transaction sequencer and of a replay (sequencer_plan.hpp) and their test hooks
+// zkr_sequence_plan_host and zkr_replay_plan_host.  Reference: /root/reference/operator/src/routes/send.ts:72-135 (the operator's checks),
 // prover/circuits/processtx.circom:70-193 (what the circuit then enforces; rule 6 follows the circuit).
 #include "sequencer_plan.hpp"
 
@@ -124,6 +124,82 @@ int seq_plan(unsigned depth, const uint8_t *records, size_t n_accounts, const ui
   }
   return 0;
 }
+
+int replay_plan(unsigned depth, const uint8_t *records, size_t n_accounts, const uint8_t *publics, size_t n_batches, uint32_t batch,
+                SeqPlan &out, size_t *planned, uint32_t *where, const char **why) {
+  static const char *dummy;
+  if (!why) why = &dummy;
+  if (depth < 1 || depth > 24) { *why = "depth out of range (1..24)"; return -1; }
+  if (batch < 1) { *why = "batch must be at least 1"; return -1; }
+  if (n_accounts > ((size_t)1 << depth)) { *why = "more accounts than the tree has leaves"; return -1; }
+  if (batch > ((size_t)1 << 22) || n_batches > ((size_t)1 << 22) / batch) { *why = "more than 2^22 transactions in one run of batches"; return -1; }
+  if (!planned || !where || (n_accounts && !records) || (n_batches && !publics)) { *why = "null argument"; return -1; }
+  out = SeqPlan();
+  *planned = n_batches, *where = 0;
+  const size_t n_public = 1 + (size_t)batch * (18 + 3 * (size_t)depth);
+  std::unordered_map<uint32_t, SeqRecord> touched;  // the records the batches have changed so far
+  auto record = [&](uint32_t i) {
+    auto it = touched.find(i);
+    if (it != touched.end()) return it->second;
+    SeqRecord r;
+    for (int j = 0; j < 4; j++) r.f[j] = int256_load(records + (size_t)i * 128 + 32 * j);
+    return r;
+  };
+  auto account_of = [&](const Int256 &v, uint32_t &i) {
+    if (v.w[1] | v.w[2] | v.w[3] || v.w[0] >= n_accounts) return false;
+    i = (uint32_t)v.w[0];
+    return true;
+  };
+  for (size_t b = 0; b < n_batches && *planned == n_batches; b++) {
+    const uint8_t *row = publics + b * n_public * 32;
+    auto refuse = [&](size_t signal) { *planned = b, *where = (uint32_t)signal; };
+    for (size_t i = 0; i < n_public && *planned == n_batches; i++)
+      if (!int256_below_r(int256_load(row + 32 * i))) refuse(i);
+    for (uint32_t k = 0; k < batch && *planned == n_batches; k++) {
+      const size_t base = 1 + (size_t)batch + 8 * (size_t)k;  // this transaction's txData row
+      Int256 e[5];
+      for (int j = 0; j < 5; j++) e[j] = int256_load(row + 32 * (base + j));
+      const Int256 &amount = e[2], &fee = e[3], &nonce = e[4];
+      uint32_t from = 0, to = 0;
+      if (!account_of(e[0], from)) { refuse(base); break; }
+      if (!account_of(e[1], to)) { refuse(base + 1); break; }
+      if (!int256_below_2_250(amount)) { refuse(base + 2); break; }
+      if (!int256_below_2_250(fee)) { refuse(base + 3); break; }
+      if (!int256_below_2_250(nonce)) { refuse(base + 4); break; }
+      const SeqRecord s = record(from), r = record(to);
+      for (int j = 0; j < 4; j++)
+        if (!int256_below_r(s.f[j]) || !int256_below_r(r.f[j]) || (j >= 2 && (!int256_below_2_250(s.f[j]) || !int256_below_2_250(r.f[j])))) {
+          *why = "an account record is not a field element, or its balance or nonce does not fit 250 bits";
+          return -1;
+        }
+      const Int256 spend = int256_add(amount, fee);  // below 2^251
+      if (int256_cmp(s.f[2], spend) < 0) { refuse(base + 2); break; }
+      SeqRecord ns = s;
+      ns.f[2] = int256_sub(s.f[2], spend);
+      ns.f[3] = nonce;
+      SeqRecord nr = from == to ? ns : r;  // the same record when from == to (processtx.circom:141-159)
+      nr.f[2] = int256_add(nr.f[2], amount);
+      if (!int256_below_2_250(nr.f[2])) { refuse(base + 2); break; }
+      out.pos.push_back((uint32_t)(b * batch + k));
+      out.idx.push_back(from), out.idx.push_back(to);
+      out.old_rec.push_back(s), out.old_rec.push_back(r);
+      out.new_rec.push_back(ns), out.new_rec.push_back(nr);
+      touched[from] = ns;
+      touched[to] = nr;
+    }
+  }
+  // a refused batch takes its first transactions with it: nothing reads `touched` after it
+  const size_t T = *planned * batch;
+  out.applied = out.consumed = T;
+  out.pos.resize(T), out.idx.resize(2 * T), out.old_rec.resize(2 * T), out.new_rec.resize(2 * T);
+  out.prev.assign(3 * (size_t)depth * 2 * T, -1);
+  if (T) {
+    std::vector<uint32_t> to(T);
+    for (size_t k = 0; k < T; k++) to[k] = out.idx[2 * k + 1];
+    seq_tables(depth, out.idx, to.data(), n_accounts, out.prev.data());
+  }
+  return 0;
+}
 }  // namespace zkr
 
 using namespace zkr;
@@ -136,6 +212,29 @@ extern "C" int zkr_sequence_plan_host(unsigned depth, const uint8_t *records, si
   if (seq_plan(depth, records, n_accounts, txs, n_txs, sig_verdicts, batch, plan, &why)) { set_error("%s", why); return ZKR_ERR_ARG; }
   if (n_txs) memcpy(status, plan.status.data(), n_txs);
   *consumed = plan.consumed;
+  if (prev && !plan.prev.empty()) memcpy(prev, plan.prev.data(), plan.prev.size() * sizeof(int32_t));
+  return ZKR_OK;
+}
+
+extern "C" int zkr_replay_plan_host(unsigned depth, const uint8_t *records, size_t n_accounts, const void *publics_std, size_t n_batches,
+                                    uint32_t batch, uint8_t *verdicts, uint32_t *where, size_t *planned, uint32_t *idx, uint8_t *old_rec,
+                                    uint8_t *new_rec, int32_t *prev) {
+  if ((n_batches && (!verdicts || !where)) || !planned) { set_error("null argument"); return ZKR_ERR_ARG; }
+  SeqPlan plan;
+  const char *why = "";
+  uint32_t at = 0;
+  if (replay_plan(depth, records, n_accounts, (const uint8_t *)publics_std, n_batches, batch, plan, planned, &at, &why)) { set_error("%s", why); return ZKR_ERR_ARG; }
+  for (size_t b = 0; b < n_batches; b++) {
+    verdicts[b] = b < *planned ? 0 : b == *planned ? 1 : SEQ_NOT_REACHED;
+    where[b] = b == *planned ? at : 0;
+  }
+  const size_t U = plan.idx.size();
+  if (idx && U) memcpy(idx, plan.idx.data(), U * sizeof(uint32_t));
+  for (size_t u = 0; u < U; u++)
+    for (int j = 0; j < 4; j++) {
+      if (old_rec) int256_store(old_rec + u * 128 + 32 * j, plan.old_rec[u].f[j]);
+      if (new_rec) int256_store(new_rec + u * 128 + 32 * j, plan.new_rec[u].f[j]);
+    }
   if (prev && !plan.prev.empty()) memcpy(prev, plan.prev.data(), plan.prev.size() * sizeof(int32_t));
   return ZKR_OK;
 }

@@ -97,4 +97,20 @@ void seq_tables(unsigned depth, const std::vector<uint32_t> &idx, const uint32_t
 int seq_plan(unsigned depth, const uint8_t *records, size_t n_accounts, const uint8_t *txs, size_t n_txs, const uint8_t *sig_verdicts,
              uint32_t batch, SeqPlan &out, const char **why);
 
+// The pass of a REPLAY (zkr_ledger_replay): the state update of RollUp.sol:118-158 for a run of published batches,
+// from their txData alone.  This is the contract's arithmetic, not the operator's policy: of the sequencer's rules only 1, 2, 3
+// and 9 remain, and a sender needs balance >= amount + fee.  Positive amount and fee, the strict balance, the fee floor and
+// nonce + 1 (rules 4-8) are NOT applied -- the contract applies whatever was proved, and what the circuit enforces is the proof's
+// matter; a follower has to track the contract.  The sender's leaf moves first (balance - amount - fee, nonce := the
+// transaction's), then the recipient's (balance + amount), from == to included (processtx.circom:141-159).
+// publics: n_batches x n_public x 32 B, n_public = 1 + batch * (18 + 3 * depth), circom's order; only the < r check reads
+// anything but the txData rows (signal 1 + batch + 8k + j of a batch).
+// Batches are planned in order until one cannot be applied; *planned is its index (n_batches: none), *where the offending
+// signal: the lowest signal not below r, else for the first transaction it holds for: `from` / `to` no account; amount, fee or
+// nonce not below 2^250; and, at the transaction's amount signal, a sender balance below amount + fee or a recipient balance
+// that would reach 2^250.  out holds the planned batches' updates as seq_plan leaves them (pos[k] = k, consumed = applied =
+// *planned * batch, status empty), which is exactly what keeps the arithmetic and the kernels' indices in range without a proof.
+int replay_plan(unsigned depth, const uint8_t *records, size_t n_accounts, const uint8_t *publics, size_t n_batches, uint32_t batch,
+                SeqPlan &out, size_t *planned, uint32_t *where, const char **why);
+
 }  // namespace zkr

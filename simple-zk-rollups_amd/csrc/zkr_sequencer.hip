@@ -12,6 +12,11 @@
 //   d  tree levels    one launch per level, 2T independent hashes each: val[l+1][u] = H(ordered(val[l][u], sib[l][u]))
 //   e  assembly       one kernel writes the input signals, a second one the touched nodes' last versions into the ledger's tree
 // The field is field.hpp's 8 x 32 limbs throughout, as in the other cold-side kernels.
+//
+// And the opposite direction: zkr_ledger_replay applies the public signals of published batches to the ledger as
+// RollUp.sol:81-161 applies them -- steps a (when asked), b (replay_plan: the contract's arithmetic, none of the operator's
+// policy), c, d as above, then replay_compare_kernel, the twin of the assembly, which derives every signal the same way and
+// compares it with the claimed one, and the store of the batches in front of the first refused one.
 #include <chrono>
 #include <mutex>
 #include <vector>
@@ -74,21 +79,25 @@ __device__ __forceinline__ Fr seq_pick(uint32_t sel, const Fr &e0, const Fr &e1,
 // S * BASE8 == R8 + h * (8A) with h = multiHash(R8x, R8y, Ax, Ay, multiHash(message)) -- circomlib's verifyMiMCSponge
 // (crypto.ts:170-177), the answer of zkr_eddsa_verify.  strict: also refuse a key whose order divides 8 (4A has x = 0), which
 // the circuit refuses (eddsa.circom's patched verifier, ST_SMALL_ORDER in rollup_witness.hpp).
-// msgs / sigs / pubs: standard form, element t at t * stride; message elements of any size are taken mod r.
+// msgs / sigs / pubs: standard form; message elements of any size are taken mod r.  Message and signature t stand at
+// (t / group) * group_stride + (t % group) * stride; group 0 is a plain array, t * stride.  The txData rows of
+// published batches lie `batch` to a group, one group per batch's signals (zkr_ledger_replay).
 static __global__ __launch_bounds__(64) void seq_verify_kernel(const Fr *msgs, size_t msg_stride, uint32_t arity, const Fr *sigs, size_t sig_stride, const Fr *pubs,
-                                                               size_t n, SigConsts k, uint32_t strict, uint8_t *verdicts) {
+                                                               size_t n, uint32_t group, size_t group_stride, SigConsts k, uint32_t strict, uint8_t *verdicts) {
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= n) return;
   verdicts[t] = 0;
+  if (group) msgs += (t / group) * group_stride + (t % group) * msg_stride, sigs += (t / group) * group_stride + (t % group) * sig_stride;
+  else msgs += t * msg_stride, sigs += t * sig_stride;
   Fr r8x, r8y, S, ax, ay;
-  bool ok = seq_read(sigs + t * sig_stride, r8x);
-  ok = seq_read(sigs + t * sig_stride + 1, r8y) && ok;
-  ok = seq_read(sigs + t * sig_stride + 2, S) && ok;
+  bool ok = seq_read(sigs, r8x);
+  ok = seq_read(sigs + 1, r8y) && ok;
+  ok = seq_read(sigs + 2, S) && ok;
   ok = seq_read(pubs + 2 * t, ax) && ok;
   ok = seq_read(pubs + 2 * t + 1, ay) && ok;
   uint32_t sw[8], hw[8];
   {
-    const Fr s = sigs[t * sig_stride + 2];
+    const Fr s = sigs[2];
 #pragma unroll
     for (int i = 0; i < 8; i++) sw[i] = s.v[i];
   }
@@ -98,7 +107,7 @@ static __global__ __launch_bounds__(64) void seq_verify_kernel(const Fr *msgs, s
   {  // h = multiHash(R8x, R8y, Ax, Ay, multiHash(message))
     Fr r = Fr::zero(), c = Fr::zero();
     for (uint32_t i = 0; i < arity; i++) {
-      r = add(r, load_std_as_mont(msgs + t * msg_stride + i));
+      r = add(r, load_std_as_mont(msgs + i));
       mimc_feistel(r, c);
     }
     const Fr m = r;
@@ -180,58 +189,92 @@ __host__ __device__ static inline size_t seq_level_offset(uint32_t depth, uint32
 struct SeqView {  // what one call left in device memory; U = 2T updates
   const Fr *txs;        // T x 8, the applied transactions
   const Fr *old_rec;    // U x 4
-  const Fr *val;        // (depth + 1) x U
+  const Fr *val;        // (depth + 1) rows of `stride`, the first U of each in use
   const uint32_t *idx;  // U
   const int32_t *prev;  // 3 x depth x U (sequencer_plan.hpp seq_tables)
   const Fr *tree;       // the ledger's stored tree, before this call
-  size_t U;
+  size_t U, stride;     // stride > U: a prefix of the updates that were hashed (a replay that stops at a refused batch)
   uint32_t depth, batch;
 };
-// One thread per input signal of every batch, in circom's order (rollup_witness.hpp tx_layout: every input array flattened over
-// the batch, batchprocesstx.circom:13-36).
-static __global__ __launch_bounds__(256) void seq_assemble_kernel(SeqView v, size_t n_batches, Fr *inputs) {
-  const uint32_t depth = v.depth, batch = v.batch;
-  const size_t per = (size_t)batch * (18 + 3 * depth);
-  const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= per * n_batches) return;
-  const size_t bi = g / per;
-  uint32_t rem = (uint32_t)(g % per), f = 0, cnt = 1;
-  for (;; f++) {  // the field this signal belongs to: widths 1 8 2 1 1 depth 2 1 1 depth 1 depth
+// Input signal `rem` of a batch (0 .. batch * (18 + 3 * depth) - 1, circom's order: every input array flattened over the batch,
+// rollup_witness.hpp tx_layout, batchprocesstx.circom:13-36) -> its field, the element within the field and the transaction
+// within the batch.  The one copy of the width table: 1 8 2 1 1 depth 2 1 1 depth 1 depth.
+struct SeqSignal { uint32_t f, j, k; };
+__device__ __forceinline__ SeqSignal seq_signal_of(uint32_t rem, uint32_t batch, uint32_t depth) {
+  uint32_t f = 0, cnt = 1;
+  for (;; f++) {
     cnt = f == 1 ? 8 : (f == 2 || f == 6) ? 2 : (f == 5 || f == 9 || f == 11) ? depth : 1;
     if (rem < batch * cnt) break;
     rem -= batch * cnt;
   }
-  const uint32_t j = rem % cnt;
-  const size_t k = bi * batch + rem / cnt, U = v.U, us = 2 * k, ur = 2 * k + 1;
-  const Fr *root_vals = v.val + (size_t)depth * U;
-  Fr out;
-  if (f == 0) out = k == 0 ? v.tree[seq_level_offset(depth, depth)] : root_vals[us - 1];  // balanceTreeRoot
-  else if (f == 1) out = v.txs[8 * k + j];                                                  // txData
-  else if (f == 2) out = v.old_rec[4 * us + j];                                             // txSenderPublicKey
-  else if (f == 3) out = v.old_rec[4 * us + 2];                                             // txSenderBalance
-  else if (f == 4) out = v.old_rec[4 * us + 3];                                             // txSenderNonce
-  else if (f == 6) out = v.old_rec[4 * ur + j];                                             // txRecipientPublicKey
-  else if (f == 7) out = v.old_rec[4 * ur + 2];                                             // txRecipientBalance
-  else if (f == 8) out = v.old_rec[4 * ur + 3];                                             // txRecipientNonce
-  else if (f == 10) out = root_vals[us];                                                    // intermediateBalanceTreeRoot
-  else {
-    // a path element of level j: the sender's before the transaction (5), the recipient's before it (9: table 1) and after the
-    // sender's update (11)
-    const size_t u = f == 11 ? ur : us;
-    const int32_t p = v.prev[((size_t)(f == 9 ? 1 : 0) * depth + j) * U + u];
-    const size_t node = (size_t)v.idx[f == 5 ? us : ur] >> j;
-    out = seq_sibling(v.val + (size_t)j * U, p, v.tree + seq_level_offset(depth, j), node);
-  }
-  inputs[g] = out;
+  return SeqSignal{f, rem % cnt, rem / cnt};
 }
-// The last version of every touched node goes into the stored tree (table 2 names it; the root's is the last update's).
+// What the ledger derives for element j of field f (any but 1, txData) of applied transaction k.
+__device__ __forceinline__ Fr seq_derive(const SeqView &v, uint32_t f, uint32_t j, size_t k) {
+  const uint32_t depth = v.depth;
+  const size_t us = 2 * k, ur = 2 * k + 1;
+  const Fr *root_vals = v.val + (size_t)depth * v.stride;
+  if (f == 0) return k == 0 ? v.tree[seq_level_offset(depth, depth)] : root_vals[us - 1];  // balanceTreeRoot
+  if (f == 2) return v.old_rec[4 * us + j];                                                 // txSenderPublicKey
+  if (f == 3) return v.old_rec[4 * us + 2];                                                 // txSenderBalance
+  if (f == 4) return v.old_rec[4 * us + 3];                                                 // txSenderNonce
+  if (f == 6) return v.old_rec[4 * ur + j];                                                 // txRecipientPublicKey
+  if (f == 7) return v.old_rec[4 * ur + 2];                                                 // txRecipientBalance
+  if (f == 8) return v.old_rec[4 * ur + 3];                                                 // txRecipientNonce
+  if (f == 10) return root_vals[us];                                                        // intermediateBalanceTreeRoot
+  // a path element of level j: the sender's before the transaction (5), the recipient's before it (9: table 1) and after the
+  // sender's update (11)
+  const size_t u = f == 11 ? ur : us;
+  const int32_t p = v.prev[((size_t)(f == 9 ? 1 : 0) * depth + j) * v.U + u];
+  const size_t node = (size_t)v.idx[f == 5 ? us : ur] >> j;
+  return seq_sibling(v.val + (size_t)j * v.stride, p, v.tree + seq_level_offset(depth, j), node);
+}
+// One thread per input signal of every batch, in circom's order.
+static __global__ __launch_bounds__(256) void seq_assemble_kernel(SeqView v, size_t n_batches, Fr *inputs) {
+  const size_t per = (size_t)v.batch * (18 + 3 * v.depth);
+  const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= per * n_batches) return;
+  const SeqSignal s = seq_signal_of((uint32_t)(g % per), v.batch, v.depth);
+  const size_t k = (g / per) * v.batch + s.k;
+  inputs[g] = s.f == 1 ? v.txs[8 * k + s.j] : seq_derive(v, s.f, s.j, k);
+}
+// The twin of seq_assemble_kernel (zkr_ledger_replay): one thread per PUBLIC signal of every batch -- signal 0 is the batch's
+// newBalanceTreeRoot, the root after its last update, then the inputs -- derives it the same way and compares it with the claimed
+// one.  first_diff[b] (initialised to 0xFFFFFFFF) ends as the lowest differing signal of batch b; signal 1, the root the batch
+// starts from, has a flag of its own (initialised to 0) because its refusal comes first whatever else differs (RollUp.sol:92).
+// txData is what everything is derived from and compares equal by construction.
+static __global__ __launch_bounds__(256) void replay_compare_kernel(SeqView v, size_t n_batches, const Fr *claimed, uint32_t *first_diff, uint32_t *root_diff) {
+  const size_t n_public = 1 + (size_t)v.batch * (18 + 3 * v.depth);
+  const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= n_public * n_batches) return;
+  const size_t bi = g / n_public;
+  const uint32_t i = (uint32_t)(g % n_public);
+  Fr want;
+  if (i == 0) want = v.val[(size_t)v.depth * v.stride + 2 * (bi * v.batch + v.batch - 1) + 1];
+  else {
+    const SeqSignal s = seq_signal_of(i - 1, v.batch, v.depth);
+    if (s.f == 1) return;
+    want = seq_derive(v, s.f, s.j, bi * v.batch + s.k);
+  }
+  if (want == claimed[g]) return;
+  if (i == 1) root_diff[bi] = 1;
+  else atomicMin(&first_diff[bi], i);
+}
+// Word 1 + i of witness b -> signal i of batch b, one thread each: the public signals where zkr_verify_each_device reads them.
+static __global__ __launch_bounds__(256) void replay_gather_kernel(const Fr *const *witnesses, size_t n_batches, uint32_t n_public, Fr *out) {
+  const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= (size_t)n_public * n_batches) return;
+  out[g] = witnesses[g / n_public][1 + g % n_public];
+}
+// The last version of every touched node goes into the stored tree (table 2 names it; the root's is the last update's).  Both are
+// facts about the list of U updates that is stored, not about a longer one that was hashed.
 static __global__ __launch_bounds__(256) void seq_store_kernel(SeqView v, Fr *tree) {
   const size_t U = v.U, g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= ((size_t)v.depth + 1) * U) return;
   const uint32_t l = (uint32_t)(g / U);
   const size_t u = g % U;
   const bool last = l == v.depth ? u == U - 1 : v.prev[((size_t)2 * v.depth + l) * U + u] != 0;
-  if (last) tree[seq_level_offset(v.depth, l) + ((size_t)v.idx[u] >> l)] = v.val[g];
+  if (last) tree[seq_level_offset(v.depth, l) + ((size_t)v.idx[u] >> l)] = v.val[(size_t)l * v.stride + u];
 }
 static __global__ __launch_bounds__(256) void seq_fill_kernel(Fr *dst, size_t n, Fr value) {
   const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -317,6 +360,154 @@ int hash_updates(const zkr_ledger *L, size_t U, const Fr *d_new, const uint32_t 
 }
 int need_device(int device, const char *what) {
   if (zkr_device_count() <= device || device < 0) { set_error("no HIP device %d; %s runs on the GPU and has no CPU fallback", device, what); return ZKR_ERR_NO_DEVICE; }
+  return ZKR_OK;
+}
+
+// zkr_ledger_replay and zkr_ledger_replay_device: exactly one of publics (host) and d_witnesses (a host array of device pointers)
+// is set.  Stage times, when asked for: 0 the signals' way to both sides and the signatures, 1 the host pass, 2 leaf hashes,
+// 3 tree levels, 4 comparison and store.
+int replay(zkr_ledger *l, const uint8_t *publics, const void *const *d_witnesses, size_t n_batches, uint32_t batch, const uint8_t *proof_verdicts,
+           uint32_t flags, uint8_t *verdicts, uint32_t *where, size_t *applied, void *stream) {
+  if (applied) *applied = 0;
+  if (!l || !applied || (n_batches && ((!publics && !d_witnesses) || !verdicts || !where))) { set_error("null argument"); return ZKR_ERR_ARG; }
+  if (flags & ~ZKR_REPLAY_SIGNATURES) { set_error("unknown replay flags %#x", flags); return ZKR_ERR_ARG; }
+  std::lock_guard<std::mutex> lk(l->mu);
+  const unsigned depth = l->depth;
+  int rc = rollup_check_geometry(batch, depth);
+  if (rc) return rc;
+  if (n_batches > ((size_t)1 << 22) / batch) { set_error("more than 2^22 transactions in one run of batches"); return ZKR_ERR_ARG; }
+  for (size_t b = 0; d_witnesses && b < n_batches; b++)
+    if (!d_witnesses[b]) { set_error("witness %zu is a null pointer", b); return ZKR_ERR_ARG; }
+  if (n_batches == 0) return ZKR_OK;
+  ZKR_HIP_CHECK(hipSetDevice(l->device));
+  hipStream_t s = (hipStream_t)stream;
+  double ms[5] = {0, 0, 0, 0, 0};
+  StageClock clk(s);
+  const bool with_sigs = flags & ZKR_REPLAY_SIGNATURES;
+  const size_t n_public = 1 + (size_t)batch * (18 + 3 * (size_t)depth), n_txs = n_batches * batch, U_max = 2 * n_txs;
+  const size_t tables_max = 3 * (size_t)depth * U_max;
+  rc = l->arena.reserve(DevArena::padded(n_batches * n_public * 32) + DevArena::padded(n_batches * sizeof(void *)) + DevArena::padded(n_txs * 64) +
+                        DevArena::padded(n_txs) + 2 * DevArena::padded(U_max * 128) + DevArena::padded(U_max * 4) + DevArena::padded(tables_max * 4) +
+                        DevArena::padded(((size_t)depth + 1) * U_max * 32) + DevArena::padded(2 * n_batches * 4));
+  if (rc) return rc;
+  Fr *d_claimed = l->arena.take<Fr>(n_batches * n_public);
+  const Fr **d_ptrs = l->arena.take<const Fr *>(n_batches);
+  Fr *d_keys = l->arena.take<Fr>(n_txs * 2);
+  uint8_t *d_sig = l->arena.take<uint8_t>(n_txs);
+  uint32_t *d_diff = l->arena.take<uint32_t>(2 * n_batches);
+
+  // the claimed signals on both sides
+  std::vector<uint8_t> gathered;
+  if (publics) ZKR_HIP_CHECK(hipMemcpyAsync(d_claimed, publics, n_batches * n_public * 32, hipMemcpyHostToDevice, s));
+  else {
+    gathered.resize(n_batches * n_public * 32);
+    ZKR_HIP_CHECK(hipMemcpyAsync(d_ptrs, d_witnesses, n_batches * sizeof(void *), hipMemcpyHostToDevice, s));
+    replay_gather_kernel<<<blocks(n_batches * n_public, 256), 256, 0, s>>>(d_ptrs, n_batches, (uint32_t)n_public, d_claimed);
+    ZKR_HIP_CHECK(hipGetLastError());
+    ZKR_HIP_CHECK(hipMemcpyAsync(gathered.data(), d_claimed, gathered.size(), hipMemcpyDeviceToHost, s));
+    ZKR_HIP_CHECK(hipStreamSynchronize(s));
+    publics = gathered.data();
+  }
+
+  // a. signatures over the txData rows where they lie, under the senders' stored keys; a sender that is no account gets a key
+  // that is on no curve (its batch is refused with code 1 before the signature is looked at)
+  std::vector<uint8_t> sig_ok(n_txs, 1);
+  if (with_sigs) {
+    std::vector<uint8_t> keys(n_txs * 64, 0);
+    for (size_t t = 0; t < n_txs; t++) {
+      const Int256 from = int256_load(publics + ((t / batch) * n_public + 1 + batch + 8 * (t % batch)) * 32);
+      if (!(from.w[1] | from.w[2] | from.w[3]) && from.w[0] < l->accounts) memcpy(&keys[t * 64], l->records.data() + (size_t)from.w[0] * 128, 64);
+    }
+    ZKR_HIP_CHECK(hipMemcpyAsync(d_keys, keys.data(), n_txs * 64, hipMemcpyHostToDevice, s));
+    const Fr *rows = d_claimed + 1 + batch;
+    seq_verify_kernel<<<blocks(n_txs, 64), 64, 0, s>>>(rows, 8, 5, rows + 5, 8, d_keys, n_txs, batch, n_public, sig_consts(), 1, d_sig);
+    ZKR_HIP_CHECK(hipGetLastError());
+    ZKR_HIP_CHECK(hipMemcpyAsync(sig_ok.data(), d_sig, n_txs, hipMemcpyDeviceToHost, s));
+    ZKR_HIP_CHECK(hipStreamSynchronize(s));
+  }
+  clk.mark(ms[0]);
+
+  // b. the pass: every batch up to the first that cannot be applied
+  SeqPlan plan;
+  const char *why = "";
+  size_t planned = 0;
+  uint32_t where1 = 0;
+  if (replay_plan(depth, l->records.data(), l->accounts, publics, n_batches, batch, plan, &planned, &where1, &why)) { set_error("%s", why); return ZKR_ERR_ARG; }
+  clk.mark(ms[1]);
+  const size_t U = 2 * planned * batch;
+  std::vector<uint8_t> h_new(U * 128);
+  std::vector<uint32_t> diff(2 * n_batches, 0);
+  Fr *d_val = nullptr;
+  uint32_t *d_idx = nullptr;
+  int32_t *d_prev = nullptr;
+  if (U) {
+    std::vector<uint8_t> h_old(U * 128);
+    for (size_t u = 0; u < U; u++)
+      for (int j = 0; j < 4; j++) int256_store(&h_old[u * 128 + 32 * j], plan.old_rec[u].f[j]), int256_store(&h_new[u * 128 + 32 * j], plan.new_rec[u].f[j]);
+    for (size_t u = 0; u < U; u++)  // every index the kernels follow, once more in one place
+      if (plan.idx[u] >= l->accounts) { set_error("internal: update %zu names leaf %u of %zu", u, plan.idx[u], l->accounts); return ZKR_ERR_ARG; }
+    for (size_t i = 0; i < 2 * (size_t)depth * U; i++)
+      if (plan.prev[i] < -1 || plan.prev[i] >= (int32_t)(i % U)) { set_error("internal: look-up table entry %zu out of range", i); return ZKR_ERR_ARG; }
+    Fr *d_old = l->arena.take<Fr>(U * 4), *d_new = l->arena.take<Fr>(U * 4);
+    d_val = l->arena.take<Fr>(((size_t)depth + 1) * U);
+    d_idx = l->arena.take<uint32_t>(U);
+    d_prev = l->arena.take<int32_t>(plan.prev.size());
+    ZKR_HIP_CHECK(hipMemcpyAsync(d_old, h_old.data(), h_old.size(), hipMemcpyHostToDevice, s));
+    ZKR_HIP_CHECK(hipMemcpyAsync(d_new, h_new.data(), h_new.size(), hipMemcpyHostToDevice, s));
+    ZKR_HIP_CHECK(hipMemcpyAsync(d_idx, plan.idx.data(), U * 4, hipMemcpyHostToDevice, s));
+    ZKR_HIP_CHECK(hipMemcpyAsync(d_prev, plan.prev.data(), plan.prev.size() * 4, hipMemcpyHostToDevice, s));
+    ZKR_HIP_CHECK(hipMemsetAsync(d_diff, 0xFF, planned * 4, s));
+    ZKR_HIP_CHECK(hipMemsetAsync(d_diff + n_batches, 0, planned * 4, s));
+    if ((rc = hash_updates(l, U, d_new, d_idx, d_prev, d_val, s, clk, ms))) return rc;
+    SeqView v{nullptr, d_old, d_val, d_idx, d_prev, l->d_tree, U, U, depth, batch};
+    replay_compare_kernel<<<blocks(planned * n_public, 256), 256, 0, s>>>(v, planned, d_claimed, d_diff, d_diff + n_batches);
+    ZKR_HIP_CHECK(hipGetLastError());
+    ZKR_HIP_CHECK(hipMemcpyAsync(diff.data(), d_diff, planned * 4, hipMemcpyDeviceToHost, s));
+    ZKR_HIP_CHECK(hipMemcpyAsync(diff.data() + n_batches, d_diff + n_batches, planned * 4, hipMemcpyDeviceToHost, s));
+    ZKR_HIP_CHECK(hipStreamSynchronize(s));  // the tree is untouched up to here: a failure above leaves the ledger as it was
+  }
+
+  // the first refused batch B, by the precedence of include/zkr.h
+  size_t B = planned;
+  uint8_t code = planned < n_batches ? 1 : 0;
+  uint32_t at = where1;
+  for (size_t b = 0; b < planned; b++) {
+    uint8_t c = 0;
+    uint32_t w = 0;
+    if (diff[n_batches + b]) c = 2, w = 1;
+    else if (proof_verdicts && proof_verdicts[b]) c = 3;
+    else {
+      for (uint32_t k = 0; k < batch && !c; k++)
+        if (!sig_ok[b * batch + k]) c = 5, w = k;
+      if (!c && diff[b] != 0xFFFFFFFFu) c = 4, w = diff[b];
+    }
+    if (c) { B = b, code = c, at = w; break; }
+  }
+
+  // e. only the updates of batches 0 .. B - 1 go into the tree; the records move last
+  const size_t Ub = 2 * B * batch;
+  if (Ub) {
+    if (Ub < U) {  // "holds the last version of its node" is a fact about the stored list: the tables of the prefix
+      std::vector<uint32_t> idx(plan.idx.begin(), plan.idx.begin() + Ub);
+      std::vector<int32_t> prev(3 * (size_t)depth * Ub);
+      seq_tables(depth, idx, nullptr, l->accounts, prev.data());
+      ZKR_HIP_CHECK(hipMemcpyAsync(d_prev, prev.data(), prev.size() * 4, hipMemcpyHostToDevice, s));
+      ZKR_HIP_CHECK(hipStreamSynchronize(s));  // prev leaves scope
+    }
+    SeqView v{nullptr, nullptr, d_val, d_idx, d_prev, l->d_tree, Ub, U, depth, batch};  // val keeps the rows of the hashed list
+    seq_store_kernel<<<blocks(((size_t)depth + 1) * Ub, 256), 256, 0, s>>>(v, l->d_tree);
+    ZKR_HIP_CHECK(hipGetLastError());
+    ZKR_HIP_CHECK(hipStreamSynchronize(s));
+    for (size_t u = 0; u < Ub; u++) memcpy(l->records.data() + (size_t)plan.idx[u] * 128, &h_new[u * 128], 128);
+    l->applied += B * batch, l->batches += B;
+  }
+  clk.mark(ms[4]);
+  for (size_t b = 0; b < n_batches; b++) {
+    verdicts[b] = b < B ? 0 : b == B ? code : SEQ_NOT_REACHED;
+    where[b] = b == B ? at : 0;
+  }
+  *applied = B;
+  if (clk.on) memcpy(l->stage_ms, ms, sizeof ms);
   return ZKR_OK;
 }
 }  // namespace
@@ -435,7 +626,7 @@ int zkr_ledger_deposit(zkr_ledger *l, const uint32_t *indices, const uint8_t *re
   double unused[5];
   if ((rc = hash_updates(l, U, d_new, d_idx, d_prev, d_val, s, clk, unused))) return rc;
   ZKR_HIP_CHECK(hipStreamSynchronize(s));  // the tree is untouched up to here: a failure above leaves the ledger as it was
-  SeqView v{nullptr, nullptr, d_val, d_idx, d_prev, l->d_tree, U, depth, 1};
+  SeqView v{nullptr, nullptr, d_val, d_idx, d_prev, l->d_tree, U, U, depth, 1};
   seq_store_kernel<<<blocks(((size_t)depth + 1) * U, 256), 256, 0, s>>>(v, l->d_tree);
   ZKR_HIP_CHECK(hipGetLastError());
   ZKR_HIP_CHECK(hipStreamSynchronize(s));
@@ -463,7 +654,7 @@ int zkr_eddsa_verify_batch(const uint8_t *msgs, unsigned arity, const uint8_t *s
   if (e == hipSuccess) e = hipMemcpy(d_sigs, sigs, n * 96, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(d_pubs, pubs, n * 64, hipMemcpyHostToDevice);
   if (e == hipSuccess) {
-    seq_verify_kernel<<<blocks(n, 64), 64>>>(d_msgs, arity, arity, d_sigs, 3, d_pubs, n, sig_consts(), 0, d_v);
+    seq_verify_kernel<<<blocks(n, 64), 64>>>(d_msgs, arity, arity, d_sigs, 3, d_pubs, n, 0, 0, sig_consts(), 0, d_v);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpy(verdicts, d_v, n, hipMemcpyDeviceToHost);
@@ -500,7 +691,7 @@ int zkr_ledger_sequence(zkr_ledger *l, const uint8_t *txs, size_t n_txs, uint32_
   uint8_t *d_verdicts = l->arena.take<uint8_t>(n_txs);
   ZKR_HIP_CHECK(hipMemcpyAsync(d_queue, txs, n_txs * 256, hipMemcpyHostToDevice, s));
   ZKR_HIP_CHECK(hipMemcpyAsync(d_keys, keys.data(), n_txs * 64, hipMemcpyHostToDevice, s));
-  seq_verify_kernel<<<blocks(n_txs, 64), 64, 0, s>>>(d_queue, 8, 5, d_queue + 5, 8, d_keys, n_txs, sig_consts(), 1, d_verdicts);
+  seq_verify_kernel<<<blocks(n_txs, 64), 64, 0, s>>>(d_queue, 8, 5, d_queue + 5, 8, d_keys, n_txs, 0, 0, sig_consts(), 1, d_verdicts);
   ZKR_HIP_CHECK(hipGetLastError());
   ZKR_HIP_CHECK(hipMemcpyAsync(verdicts.data(), d_verdicts, n_txs, hipMemcpyDeviceToHost, s));
   ZKR_HIP_CHECK(hipStreamSynchronize(s));
@@ -531,7 +722,7 @@ int zkr_ledger_sequence(zkr_ledger *l, const uint8_t *txs, size_t n_txs, uint32_
     ZKR_HIP_CHECK(hipMemcpyAsync(d_prev, plan.prev.data(), plan.prev.size() * 4, hipMemcpyHostToDevice, s));
     if ((rc = hash_updates(l, U, d_new, d_idx, d_prev, d_val, s, clk, ms))) return rc;
     const size_t nb = T / batch;
-    SeqView v{d_txs, d_old, d_val, d_idx, d_prev, l->d_tree, U, depth, batch};
+    SeqView v{d_txs, d_old, d_val, d_idx, d_prev, l->d_tree, U, U, depth, batch};
     seq_assemble_kernel<<<blocks(nb * batch * (18 + 3 * (size_t)depth), 256), 256, 0, s>>>(v, nb, (Fr *)d_inputs);
     ZKR_HIP_CHECK(hipGetLastError());
     ZKR_HIP_CHECK(hipStreamSynchronize(s));  // the tree is untouched up to here: a failure above leaves the ledger as it was
@@ -547,6 +738,20 @@ int zkr_ledger_sequence(zkr_ledger *l, const uint8_t *txs, size_t n_txs, uint32_
   *consumed = plan.consumed;
   if (clk.on) memcpy(l->stage_ms, ms, sizeof ms);
   return ZKR_OK;
+}
+
+int zkr_ledger_replay(zkr_ledger *l, const void *publics_std, size_t n_batches, uint32_t batch, const uint8_t *proof_verdicts, uint32_t flags,
+                      uint8_t *verdicts, uint32_t *where, size_t *applied, void *stream) {
+  if (applied) *applied = 0;
+  if (n_batches && !publics_std) { set_error("null argument"); return ZKR_ERR_ARG; }
+  return replay(l, (const uint8_t *)publics_std, nullptr, n_batches, batch, proof_verdicts, flags, verdicts, where, applied, stream);
+}
+
+int zkr_ledger_replay_device(zkr_ledger *l, const void *const *d_witnesses_std, size_t n_batches, uint32_t batch, const uint8_t *proof_verdicts,
+                             uint32_t flags, uint8_t *verdicts, uint32_t *where, size_t *applied, void *stream) {
+  if (applied) *applied = 0;
+  if (n_batches && !d_witnesses_std) { set_error("null argument"); return ZKR_ERR_ARG; }
+  return replay(l, nullptr, d_witnesses_std, n_batches, batch, proof_verdicts, flags, verdicts, where, applied, stream);
 }
 
 }  // extern "C"

@@ -155,6 +155,10 @@ def lib():
     L.zkr_ledger_stage_times.argtypes = [vp, c.POINTER(c.c_double)]
     L.zkr_eddsa_verify_batch.argtypes = [u8p, c.c_uint, u8p, u8p, sz, u8p, i]
     L.zkr_sequence_plan_host.argtypes = [c.c_uint, u8p, sz, u8p, sz, u8p, c.c_uint32, u8p, c.POINTER(sz), c.POINTER(c.c_int32)]
+    L.zkr_ledger_replay.argtypes = [vp, u8p, sz, c.c_uint32, u8p, c.c_uint32, u8p, c.POINTER(c.c_uint32), c.POINTER(sz), vp]
+    L.zkr_ledger_replay_device.argtypes = [vp, c.POINTER(vp), sz, c.c_uint32, u8p, c.c_uint32, u8p, c.POINTER(c.c_uint32), c.POINTER(sz), vp]
+    L.zkr_replay_plan_host.argtypes = [c.c_uint, u8p, sz, u8p, sz, c.c_uint32, u8p, c.POINTER(c.c_uint32), c.POINTER(sz), c.POINTER(c.c_uint32), u8p, u8p,
+                                       c.POINTER(c.c_int32)]
     _lib = L
     return L
 

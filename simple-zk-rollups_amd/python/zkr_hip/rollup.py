@@ -13,6 +13,7 @@ SNARK_FIELD_SIZE = 2188824287183927522224640574525727508854836440041603434369820
 TX_INPUT_FIELDS = ("balanceTreeRoot", "txData", "txSenderPublicKey", "txSenderBalance", "txSenderNonce", "txSenderPathElements",
                    "txRecipientPublicKey", "txRecipientBalance", "txRecipientNonce", "txRecipientPathElements",
                    "intermediateBalanceTreeRoot", "intermediateBalanceTreePathElements")   # batchprocesstx.circom:13-36
+REPLAY_SIGNATURES = 1   # ZKR_REPLAY_SIGNATURES
 
 
 def _le(v):
@@ -125,6 +126,38 @@ def sequence_plan_host(depth, records, txs, sig_verdicts, batch):
     return st, consumed.value, tables
 
 
+def _publics_bytes(publics, n_public):
+    """A list of signal lists or of bytes (or one bytes object) -> (n_batches, the signals back to back)."""
+    if isinstance(publics, (bytes, bytearray)):
+        buf = bytes(publics)
+    else:
+        buf = b"".join(bytes(p) if isinstance(p, (bytes, bytearray)) else b"".join(_le(v) for v in p) for p in publics)
+    if len(buf) % (32 * n_public):
+        raise ValueError("public signals: %d bytes is no multiple of %d signals of 32 bytes" % (len(buf), n_public))
+    return len(buf) // (32 * n_public), buf
+
+
+def replay_plan_host(depth, records, publics, batch):
+    """The host pass of Ledger.replay without a device (test hook, zkr_replay_plan_host): records = [pubX, pubY, balance, nonce]
+    per account, publics = the signal list (or bytes) of every batch.  Returns a dict: verdicts (0 planned, 1 the first batch
+    that cannot be applied, 255 behind it), where, planned, and for the planned batches' updates idx, old / new (records as
+    lists of four) and tables[table][level][update] as include/zkr.h describes them."""
+    n_public = 1 + batch * (18 + 3 * depth) if batch > 0 and depth > 0 else 1
+    nb, pb = _publics_bytes(publics, n_public)
+    rb = b"".join(_le(v) for r in records for v in r)
+    room = max(1, 2 * batch * nb)
+    verdicts, where = ctypes.create_string_buffer(max(nb, 1)), (ctypes.c_uint32 * max(nb, 1))()
+    planned = ctypes.c_size_t()
+    idx, prev = (ctypes.c_uint32 * room)(), (ctypes.c_int32 * (3 * max(depth, 1) * room))()
+    old, new = ctypes.create_string_buffer(128 * room), ctypes.create_string_buffer(128 * room)
+    _check(lib().zkr_replay_plan_host(depth, rb, len(records), pb, nb, batch, verdicts, where, ctypes.byref(planned), idx, old, new, prev))
+    U = 2 * batch * planned.value
+    recs = lambda raw: [_ints(raw[128 * u:128 * u + 128]) for u in range(U)]
+    tables = [[[prev[(t * depth + l) * U + u] for u in range(U)] for l in range(depth)] for t in range(3)]
+    return {"verdicts": list(verdicts.raw[:nb]), "where": list(where[:nb]), "planned": planned.value, "idx": list(idx[:U]),
+            "old": recs(old.raw), "new": recs(new.raw), "tables": tables}
+
+
 class Ledger:
     """The operator's state on the GPU (zkr_ledger_*): account records and the whole balance tree of `depth` levels.
     `sequence` turns a queue of signed transactions into a status each (0 accepted, 1..10 the first broken rule of
@@ -186,8 +219,38 @@ class Ledger:
         _check(lib().zkr_ledger_sequence(self._h, buf, n, batch, status, out.data_ptr(), ctypes.byref(nb), ctypes.byref(consumed), stream))
         return list(status.raw[:n]), out[:nb.value], consumed.value
 
+    def _replay(self, call, first, n, batch, proof_verdicts, signatures, stream):
+        if proof_verdicts is not None:
+            if len(proof_verdicts) != n:
+                raise ValueError("%d proof verdicts for %d batches" % (len(proof_verdicts), n))
+            proof_verdicts = bytes(min(int(v), 255) for v in proof_verdicts)
+        verdicts, where = ctypes.create_string_buffer(max(n, 1)), (ctypes.c_uint32 * max(n, 1))()
+        applied = ctypes.c_size_t()
+        _check(call(self._h, first, n, batch, proof_verdicts, REPLAY_SIGNATURES if signatures else 0, verdicts, where, ctypes.byref(applied), stream))
+        return list(verdicts.raw[:n]), list(where[:n]), applied.value
+
+    def replay(self, publics, batch, proof_verdicts=None, signatures=False, stream=None):
+        """RollUp.sol:81-161 for a run of consecutive published batches against this ledger (zkr_ledger_replay): publics = the
+        public signals of every batch as a list of signal lists or of bytes (circom's order, newBalanceTreeRoot first),
+        proof_verdicts = what VerifyingKey.verify_each returned for them, or None; signatures=True also checks every
+        transaction's signature under the sender's stored key.  -> (verdicts, where, applied): 0 applied, 1 cannot be applied,
+        2 not the current root, 3 the proof is refused, 5 a signature fails, 4 a signal differs from what the ledger derives,
+        255 behind the first refused batch; include/zkr.h says what `where` names for each.  The ledger ends as it stands
+        after the last batch with verdict 0."""
+        n, buf = _publics_bytes(publics, 1 + batch * (18 + 3 * self.depth))
+        return self._replay(lib().zkr_ledger_replay, buf, n, batch, proof_verdicts, signatures, stream)
+
+    def replay_device(self, witness_ptrs, batch, proof_verdicts=None, signatures=False, stream=None):
+        """The same with the signals read in place (zkr_ledger_replay_device): witness_ptrs = one device pointer per batch, the
+        batch's signals are words 1..n_public of that witness -- the convention of VerifyingKey.verify_each_device."""
+        n = len(witness_ptrs)
+        ptrs = (ctypes.c_void_p * max(n, 1))(*[int(p) for p in witness_ptrs])
+        return self._replay(lib().zkr_ledger_replay_device, ptrs, n, batch, proof_verdicts, signatures, stream)
+
     def stage_times(self):
-        """Milliseconds of the last sequence call's stages (recorded only with ZKR_SEQUENCER_STAGES set in the environment)."""
+        """Milliseconds of the last sequence or replay call's stages (recorded only with ZKR_SEQUENCER_STAGES set in the
+        environment).  For a replay "signatures" includes the signals' way to the device (or back from it) and "assembly" is
+        the comparison and the store."""
         out = (ctypes.c_double * 5)()
         _check(lib().zkr_ledger_stage_times(self._h, out))
         return dict(zip(("signatures", "host_pass", "leaf_hashes", "levels", "assembly"), out))
