@@ -737,6 +737,61 @@ int zkr_replay_plan_host(unsigned depth, const uint8_t *records, size_t n_accoun
 int zkr_sequence_plan_host(unsigned depth, const uint8_t *records, size_t n_accounts, const uint8_t *txs, size_t n_txs,
                            const uint8_t *sig_verdicts, uint32_t batch, uint8_t *status, size_t *consumed, int32_t *prev);
 
+/* ---- keeping the ledger: read-out, snapshots with a checked restore, checkpoints with rollback, and an audit of the stored tree
+ * (DESIGN.md 9h).  Stands in for the load / save of operator/src/utils/merkletree.ts:274-403 around every event (pubsub.ts:35,65),
+ * which trusts the root it stored.  All device work runs under the ledger's lock on the default stream and every call returns
+ * synchronised.  None of these calls changes what an earlier call returns; with no checkpoint open zkr_ledger_deposit,
+ * zkr_ledger_sequence and the replays launch what they launched before.
+ *
+ * Read-out.  zkr_ledger_records copies `count` records of 128 B (pubX pubY balance nonce) from `first` on; a range past the
+ * accounts is ZKR_ERR_ARG.  zkr_ledger_tree gives the device address and byte length of the stored tree, (2^(depth+1) - 1) x 32 B,
+ * leaves first, root last (the layout of zkr_balance_tree_build), as zkr_key_arena gives a key's arena: a read-only view, valid
+ * until zkr_ledger_free; its contents move with every state-changing call.
+ *
+ * Snapshot "ZKRLEDG1", 128 + 128 x accounts bytes, integers little-endian, field elements 32 B standard form:
+ *     0  "ZKRLEDG1"      8  u32 depth     12  u32 0      16  u64 accounts     24  u64 applied     32  u64 batches     40  24 B zero
+ *    64  root           96  tag = zkr_mimcsponge_multihash(depth, accounts, applied, batches, root)          128  the records
+ * The tag covers the header, the root covers the records once they are rebuilt: no byte is unprotected.  Checkpoints are not part
+ * of a snapshot; it is the current state.
+ * zkr_ledger_snapshot returns a malloc'ed blob (zkr_free).  zkr_ledger_save writes it to `path`.tmp and renames that to `path`: a
+ * crash leaves the old file or the new one.
+ * zkr_ledger_snapshot_check (host only) checks magic, reserved words, length, depth 1..24, accounts <= 2^depth, the tag, and that
+ * every element is below r and every balance and nonce below 2^250 (what zkr_ledger_deposit requires).  *valid = 0 comes with
+ * ZKR_OK and a zkr_last_error line naming the first failure; info = depth, accounts, applied, batches of a valid blob.
+ * zkr_ledger_restore / zkr_ledger_load_file: that check first -- a failure is ZKR_ERR_ARG, reported before the device is looked
+ * at; then the device (ZKR_ERR_NO_DEVICE, no CPU fallback); then a new ledger whose tree is built in bulk from the records: leaf
+ * hashes straight into the tree, one launch per level over the nodes whose subtree holds an account, fewer than 2 x accounts +
+ * depth hashes and no tables (records go up in pieces of at most 2^20).  The rebuilt root is read back and compared with the
+ * blob's: a mismatch is ZKR_ERR_BAD_KEY with both roots in zkr_last_error, and no ledger is returned.  The counters are the blob's.
+ *
+ * Checkpoints.  zkr_ledger_checkpoint opens one and returns its id; they nest.  While at least one is open every storing call
+ * (zkr_ledger_deposit, zkr_ledger_sequence, both replays) first copies (node, old value) of every tree node it is about to
+ * overwrite into a journal the ledger owns, and the old records and counters beside it.  zkr_ledger_rollback(id) puts the ledger
+ * back exactly as it stood at zkr_ledger_checkpoint(id) -- records, account count (accounts inserted since disappear), every byte
+ * of the stored tree, applied and batches -- discards every checkpoint taken after `id`, and leaves `id` open: it can be rolled
+ * back to again.  zkr_ledger_release(id) forgets the marker and changes no state; with the last marker the journal is emptied
+ * and nothing more is recorded.  An unknown, released or discarded id is ZKR_ERR_ARG.  A journal that cannot grow is ZKR_ERR_HIP,
+ * raised before anything is stored: "on any error return the ledger is unchanged" covers the journal too.
+ * zkr_ledger_journal_info: out = open checkpoints, journalled nodes.
+ *
+ * zkr_ledger_audit is the ledger's zkr_key_check: one launch over all nodes, each check from stored values alone.  Leaf i <
+ * accounts must be the leaf hash of record i; a node whose whole subtree lies past the last account must be its level's
+ * empty-subtree constant (compared, not hashed); every other inner node must be the hash of its two stored children; a stored
+ * word not below r is a difference.  A bad tree is ZKR_OK with *sound = 0 and report = (level, index) of the first bad node,
+ * lowest level first, then lowest index; a sound one *sound = 1 and report = (0, 0). ---- */
+int zkr_ledger_records(const zkr_ledger *l, size_t first, size_t count, uint8_t *out);
+int zkr_ledger_tree(const zkr_ledger *l, const void **dev_ptr, size_t *len);
+int zkr_ledger_snapshot(const zkr_ledger *l, void **blob, size_t *len);
+int zkr_ledger_save(const zkr_ledger *l, const char *path);
+int zkr_ledger_snapshot_check(const void *blob, size_t len, uint64_t info[4], int *valid);
+int zkr_ledger_restore(const void *blob, size_t len, int device, zkr_ledger **out);
+int zkr_ledger_load_file(const char *path, int device, zkr_ledger **out);
+int zkr_ledger_checkpoint(zkr_ledger *l, uint64_t *id);
+int zkr_ledger_rollback(zkr_ledger *l, uint64_t id);
+int zkr_ledger_release(zkr_ledger *l, uint64_t id);
+int zkr_ledger_journal_info(const zkr_ledger *l, uint64_t out[2]);
+int zkr_ledger_audit(zkr_ledger *l, uint64_t report[2], int *sound);
+
 /* Integer-ALU microbenchmark: sustained Fq Montgomery multiplications per second on `device` with the multiplier of the
  * hot path (9 x 29-bit limbs, 162 multiply-adds without carry words, csrc/field29.hpp); used for the secondary (VALU)
  * roofline.  _legacy: the 8 x 32-bit multiplier of csrc/field.hpp (136 multiply-adds + 136 carry additions), kept for

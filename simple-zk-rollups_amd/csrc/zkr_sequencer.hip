@@ -17,6 +17,11 @@
 // RollUp.sol:81-161 applies them -- steps a (when asked), b (replay_plan: the contract's arithmetic, none of the operator's
 // policy), c, d as above, then replay_compare_kernel, the twin of the assembly, which derives every signal the same way and
 // compares it with the claimed one, and the store of the batches in front of the first refused one.
+//
+// And keeping that state (the host side is ledger_state.cpp / .hpp): read-out of the records and of the stored tree,
+// the ZKRLEDG1 snapshot whose restore rebuilds the tree in bulk and compares the root, checkpoints -- a journal of every node a
+// storing call is about to overwrite, undone call by call -- and the audit of the stored tree against the records.
+#include <stdio.h>
 #include <chrono>
 #include <mutex>
 #include <vector>
@@ -24,6 +29,7 @@
 #include "rollup_witness.hpp"
 #include "mimc_device.hpp"
 #include "sequencer_plan.hpp"
+#include "ledger_state.hpp"
 
 namespace zkr {
 void rollup_device_constants(Fr *a, Fr *d, uint32_t suborder_m1[8], Fr *b8x253, Fr *b8y253);  // rollup.cpp
@@ -281,6 +287,75 @@ static __global__ __launch_bounds__(256) void seq_fill_kernel(Fr *dst, size_t n,
   if (g < n) dst[g] = value;
 }
 
+// ------------------------------------------------------------------------------------------------ keeping the ledger
+__device__ __forceinline__ Fr state_hash_pair(const Fr &left, const Fr &right) {  // hashLeftRight, as seq_level_kernel computes it
+  Fr r = to_mont(left), c = Fr::zero();
+  mimc_feistel(r, c);
+  r = add(r, to_mont(right));
+  mimc_feistel(r, c);
+  return from_mont(r);
+}
+// The bulk build of a restore: level l (1 .. depth) of the stored tree from level l - 1, for the n = ceil(accounts / 2^l) nodes
+// whose subtree holds an account.  A right child past the populated prefix still holds its level's empty-subtree constant.
+static __global__ __launch_bounds__(64) void state_build_level_kernel(Fr *tree, uint32_t depth, uint32_t l, size_t n) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const Fr *below = tree + seq_level_offset(depth, l - 1);
+  tree[seq_level_offset(depth, l) + i] = state_hash_pair(below[2 * i], below[2 * i + 1]);
+}
+// The journal of a storing call made under a checkpoint: seq_store_kernel's domain and predicate, but instead of writing the new
+// value it appends (node offset, the value the tree holds now).  Within one call every node has one last writer, so the entries
+// are distinct nodes and their order does not matter; *count starts at 0 and ends as the number of entries, room bounds it.
+static __global__ __launch_bounds__(256) void state_journal_kernel(SeqView v, uint32_t *off, Fr *old, uint32_t room, uint32_t *count) {
+  const size_t U = v.U, g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= ((size_t)v.depth + 1) * U) return;
+  const uint32_t l = (uint32_t)(g / U);
+  const size_t u = g % U;
+  const bool last = l == v.depth ? u == U - 1 : v.prev[((size_t)2 * v.depth + l) * U + u] != 0;
+  if (!last) return;
+  const size_t node = seq_level_offset(v.depth, l) + ((size_t)v.idx[u] >> l);
+  const uint32_t at = atomicAdd(count, 1u);
+  if (at < room) off[at] = (uint32_t)node, old[at] = v.tree[node];
+}
+// The undo of one journalled call: its old values back where they came from.  n_nodes bounds every offset once more.
+static __global__ __launch_bounds__(256) void state_undo_kernel(Fr *tree, size_t n_nodes, const uint32_t *off, const Fr *old, size_t n) {
+  const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= n) return;
+  const size_t node = off[g];
+  if (node < n_nodes) tree[node] = old[g];
+}
+// The audit: one thread per node of [node_begin, node_begin + node_count) of the stored tree, every check from stored values
+// alone.  Leaf i < accounts equals the leaf hash of record i (only for the records present: recs holds records rec_first ..
+// rec_first + rec_count - 1); a node whose subtree lies past the last account equals its level's empty-subtree constant; any
+// other inner node equals the hash of its two stored children; and a stored word is below r.  *first_bad (initialised to all
+// ones) ends as the lowest (level << 32 | index) that fails.
+static __global__ __launch_bounds__(64) void state_audit_kernel(const Fr *tree, uint32_t depth, size_t accounts, const Fr *empty, const Fr *recs, size_t rec_first,
+                                                                size_t rec_count, size_t node_begin, size_t node_count, unsigned long long *first_bad) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= node_count) return;
+  const size_t g = node_begin + t;
+  uint32_t l = 0;
+  size_t i = g, width = (size_t)1 << depth;
+  while (i >= width) i -= width, width >>= 1, l++;  // g < 2^(depth + 1) - 1: ends with l <= depth
+  const Fr have = tree[g];
+  bool ok = words_below(have.v, FrParams::P);
+  const size_t populated = (accounts + (((size_t)1 << l) - 1)) >> l;
+  if (i >= populated) ok = ok && have == empty[l];
+  else if (l == 0) {
+    if (i < rec_first || i - rec_first >= rec_count) return;  // this launch does not hold the record
+    Fr r = Fr::zero(), c = Fr::zero();
+    for (int j = 0; j < 4; j++) {
+      r = add(r, load_std_as_mont(recs + 4 * (i - rec_first) + j));
+      mimc_feistel(r, c);
+    }
+    ok = ok && have == from_mont(r);
+  } else {
+    const Fr *below = tree + seq_level_offset(depth, l - 1);
+    ok = ok && have == state_hash_pair(below[2 * i], below[2 * i + 1]);
+  }
+  if (!ok) atomicMin(first_bad, ((unsigned long long)l << 32) | (unsigned long long)i);
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 static SigConsts sig_consts() {
   static const SigConsts k = [] {
@@ -328,6 +403,13 @@ struct zkr_ledger {
   DevArena arena;
   double stage_ms[5] = {0, 0, 0, 0, 0};
   mutable std::mutex mu;
+  // keeping the ledger
+  std::vector<uint8_t> empty;  // (depth + 1) x 32 B: the value of an empty subtree per level
+  LedgerJournal journal;       // checkpoints and what every storing call under them overwrote, host part
+  uint32_t *d_joff = nullptr;  // the journal's device part: node offsets ...
+  Fr *d_jold = nullptr;        // ... and old values, jcap entries each, the first journal.nodes() in use
+  uint32_t *d_jcount = nullptr;
+  size_t jcap = 0;
 };
 
 namespace {
@@ -361,6 +443,76 @@ int hash_updates(const zkr_ledger *L, size_t U, const Fr *d_new, const uint32_t 
 int need_device(int device, const char *what) {
   if (zkr_device_count() <= device || device < 0) { set_error("no HIP device %d; %s runs on the GPU and has no CPU fallback", device, what); return ZKR_ERR_NO_DEVICE; }
   return ZKR_OK;
+}
+
+// ---- keeping the ledger
+enum : size_t { STATE_PIECE = (size_t)1 << 20 };  // records go to the device in pieces of at most 2^20: 128 MB of staging
+
+// The journal step of a storing call, run only while a checkpoint is open: between the point where the call's hashes are
+// complete (the tree still untouched) and its seq_store_kernel.  v is the view the store will run over, last = its table 2 on
+// the host ([depth][v.U]), idx its leaf indices.  The entries land behind the ones in use; *out is the call's host part, which
+// the caller appends to the journal once its store has succeeded -- until then nothing of the journal has moved.  A journal
+// that cannot grow is ZKR_ERR_HIP, raised here, before anything is stored.
+int journal_before_store(zkr_ledger *l, const SeqView &v, const int32_t *last, const uint32_t *idx, hipStream_t s, JournalCall *out) {
+  const size_t U = v.U, base = l->journal.nodes();
+  size_t count = 1;  // the root
+  for (size_t i = 0; i < (size_t)v.depth * U; i++) count += last[i] != 0;
+  if (base + count > l->jcap) {
+    const size_t cap = (base + count) + (base + count) / 2;
+    uint32_t *off = nullptr;
+    Fr *old = nullptr;
+    if (hipMalloc((void **)&off, cap * 4) != hipSuccess || hipMalloc((void **)&old, cap * 32) != hipSuccess) {
+      if (off) hipFree(off);
+      set_error("out of device memory for a checkpoint journal of %zu nodes", cap);
+      return ZKR_ERR_HIP;
+    }
+    hipError_t e = base ? hipMemcpy(off, l->d_joff, base * 4, hipMemcpyDeviceToDevice) : hipSuccess;
+    if (e == hipSuccess && base) e = hipMemcpy(old, l->d_jold, base * 32, hipMemcpyDeviceToDevice);
+    if (e != hipSuccess) { hipFree(off), hipFree(old); set_error("moving the checkpoint journal failed: %s", hipGetErrorString(e)); return ZKR_ERR_HIP; }
+    if (l->d_joff) hipFree(l->d_joff);
+    if (l->d_jold) hipFree(l->d_jold);
+    l->d_joff = off, l->d_jold = old, l->jcap = cap;
+  }
+  if (!l->d_jcount) ZKR_HIP_CHECK(hipMalloc((void **)&l->d_jcount, 4));
+  uint32_t written = 0;
+  ZKR_HIP_CHECK(hipMemsetAsync(l->d_jcount, 0, 4, s));
+  state_journal_kernel<<<blocks(((size_t)v.depth + 1) * U, 256), 256, 0, s>>>(v, l->d_joff + base, l->d_jold + base, (uint32_t)count, l->d_jcount);
+  ZKR_HIP_CHECK(hipGetLastError());
+  ZKR_HIP_CHECK(hipMemcpyAsync(&written, l->d_jcount, 4, hipMemcpyDeviceToHost, s));
+  ZKR_HIP_CHECK(hipStreamSynchronize(s));
+  if (written != count) { set_error("internal: the journal holds %u nodes of a call whose tables name %zu", written, count); return ZKR_ERR_HIP; }
+  *out = l->journal.record_call(idx, U, l->records, l->accounts, l->applied, l->batches, count);
+  return ZKR_OK;
+}
+
+// The bulk build of a restore: L->records and L->accounts are set and checked, the tree is the empty one of zkr_ledger_new.
+// Leaf hashes straight into level 0, then one launch per level over the nodes whose subtree holds an account: no tables, no
+// value buffer, fewer than 2 * accounts + depth hashes.  Default stream; returns synchronised.
+int bulk_build(zkr_ledger *L) {
+  const size_t accounts = L->accounts;
+  if (!accounts) return ZKR_OK;
+  const size_t piece = accounts < STATE_PIECE ? accounts : (size_t)STATE_PIECE;
+  int rc = L->arena.reserve(DevArena::padded(piece * 128));
+  if (rc) return rc;
+  Fr *d_stage = L->arena.take<Fr>(piece * 4);
+  for (size_t first = 0; first < accounts; first += piece) {
+    const size_t n = accounts - first < piece ? accounts - first : piece;
+    ZKR_HIP_CHECK(hipMemcpy(d_stage, L->records.data() + first * 128, n * 128, hipMemcpyHostToDevice));
+    seq_leaf_kernel<<<blocks(n, 64), 64>>>(d_stage, n, L->d_tree + first);
+    ZKR_HIP_CHECK(hipGetLastError());
+  }
+  for (unsigned lv = 1; lv <= L->depth; lv++) {
+    const size_t n = (accounts + (((size_t)1 << lv) - 1)) >> lv;  // <= 2^(depth - lv), the level's width
+    state_build_level_kernel<<<blocks(n, 64), 64>>>(L->d_tree, L->depth, lv, n);
+    ZKR_HIP_CHECK(hipGetLastError());
+  }
+  ZKR_HIP_CHECK(hipDeviceSynchronize());
+  return ZKR_OK;
+}
+
+void hex_be(const uint8_t le[32], char out[67]) {
+  out[0] = '0', out[1] = 'x';
+  for (int i = 0; i < 32; i++) snprintf(out + 2 + 2 * i, 3, "%02x", le[31 - i]);
 }
 
 // zkr_ledger_replay and zkr_ledger_replay_device: exactly one of publics (host) and d_witnesses (a host array of device pointers)
@@ -487,17 +639,22 @@ int replay(zkr_ledger *l, const uint8_t *publics, const void *const *d_witnesses
   // e. only the updates of batches 0 .. B - 1 go into the tree; the records move last
   const size_t Ub = 2 * B * batch;
   if (Ub) {
+    std::vector<int32_t> prev;
     if (Ub < U) {  // "holds the last version of its node" is a fact about the stored list: the tables of the prefix
       std::vector<uint32_t> idx(plan.idx.begin(), plan.idx.begin() + Ub);
-      std::vector<int32_t> prev(3 * (size_t)depth * Ub);
+      prev.resize(3 * (size_t)depth * Ub);
       seq_tables(depth, idx, nullptr, l->accounts, prev.data());
       ZKR_HIP_CHECK(hipMemcpyAsync(d_prev, prev.data(), prev.size() * 4, hipMemcpyHostToDevice, s));
-      ZKR_HIP_CHECK(hipStreamSynchronize(s));  // prev leaves scope
+      ZKR_HIP_CHECK(hipStreamSynchronize(s));
     }
     SeqView v{nullptr, nullptr, d_val, d_idx, d_prev, l->d_tree, Ub, U, depth, batch};  // val keeps the rows of the hashed list
+    JournalCall jc;
+    const bool journalled = l->journal.open();  // the journal follows the list that is stored, as the store does
+    if (journalled && (rc = journal_before_store(l, v, (Ub < U ? prev.data() : plan.prev.data()) + 2 * (size_t)depth * Ub, plan.idx.data(), s, &jc))) return rc;
     seq_store_kernel<<<blocks(((size_t)depth + 1) * Ub, 256), 256, 0, s>>>(v, l->d_tree);
     ZKR_HIP_CHECK(hipGetLastError());
     ZKR_HIP_CHECK(hipStreamSynchronize(s));
+    if (journalled) l->journal.calls.push_back(std::move(jc));
     for (size_t u = 0; u < Ub; u++) memcpy(l->records.data() + (size_t)plan.idx[u] * 128, &h_new[u * 128], 128);
     l->applied += B * batch, l->batches += B;
   }
@@ -531,6 +688,7 @@ int zkr_ledger_new(unsigned depth, int device, zkr_ledger **out) {
   for (unsigned l = 0; l <= depth && e == hipSuccess; l++) {
     Fr v;
     memcpy(v.v, z, 32);
+    L->empty.insert(L->empty.end(), z, z + 32);
     const size_t width = (size_t)1 << (depth - l);
     seq_fill_kernel<<<blocks(width, 256), 256>>>(L->d_tree + seq_level_offset(depth, l), width, v);
     e = hipGetLastError();
@@ -548,6 +706,9 @@ void zkr_ledger_free(zkr_ledger *l) {
   if (hipSetDevice(l->device) == hipSuccess) {
     if (l->d_tree) hipFree(l->d_tree);
     if (l->arena.p) hipFree(l->arena.p);
+    if (l->d_joff) hipFree(l->d_joff);
+    if (l->d_jold) hipFree(l->d_jold);
+    if (l->d_jcount) hipFree(l->d_jcount);
   }
   delete l;
 }
@@ -627,9 +788,13 @@ int zkr_ledger_deposit(zkr_ledger *l, const uint32_t *indices, const uint8_t *re
   if ((rc = hash_updates(l, U, d_new, d_idx, d_prev, d_val, s, clk, unused))) return rc;
   ZKR_HIP_CHECK(hipStreamSynchronize(s));  // the tree is untouched up to here: a failure above leaves the ledger as it was
   SeqView v{nullptr, nullptr, d_val, d_idx, d_prev, l->d_tree, U, U, depth, 1};
+  JournalCall jc;
+  const bool journalled = l->journal.open();
+  if (journalled && (rc = journal_before_store(l, v, prev.data() + 2 * (size_t)depth * U, indices, s, &jc))) return rc;
   seq_store_kernel<<<blocks(((size_t)depth + 1) * U, 256), 256, 0, s>>>(v, l->d_tree);
   ZKR_HIP_CHECK(hipGetLastError());
   ZKR_HIP_CHECK(hipStreamSynchronize(s));
+  if (journalled) l->journal.calls.push_back(std::move(jc));
   l->records.resize(accounts * 128);
   for (size_t i = 0; i < n; i++) memcpy(l->records.data() + (size_t)indices[i] * 128, records + i * 128, 128);
   l->accounts = accounts;
@@ -726,9 +891,13 @@ int zkr_ledger_sequence(zkr_ledger *l, const uint8_t *txs, size_t n_txs, uint32_
     seq_assemble_kernel<<<blocks(nb * batch * (18 + 3 * (size_t)depth), 256), 256, 0, s>>>(v, nb, (Fr *)d_inputs);
     ZKR_HIP_CHECK(hipGetLastError());
     ZKR_HIP_CHECK(hipStreamSynchronize(s));  // the tree is untouched up to here: a failure above leaves the ledger as it was
+    JournalCall jc;
+    const bool journalled = l->journal.open();
+    if (journalled && (rc = journal_before_store(l, v, plan.prev.data() + 2 * (size_t)depth * U, plan.idx.data(), s, &jc))) return rc;
     seq_store_kernel<<<blocks(((size_t)depth + 1) * U, 256), 256, 0, s>>>(v, l->d_tree);
     ZKR_HIP_CHECK(hipGetLastError());
     ZKR_HIP_CHECK(hipStreamSynchronize(s));
+    if (journalled) l->journal.calls.push_back(std::move(jc));
     clk.mark(ms[4]);
     for (size_t u = 0; u < U; u++) memcpy(l->records.data() + (size_t)plan.idx[u] * 128, &h_new[u * 128], 128);
     l->applied += T, l->batches += nb;
@@ -752,6 +921,179 @@ int zkr_ledger_replay_device(zkr_ledger *l, const void *const *d_witnesses_std, 
   if (applied) *applied = 0;
   if (n_batches && !d_witnesses_std) { set_error("null argument"); return ZKR_ERR_ARG; }
   return replay(l, nullptr, d_witnesses_std, n_batches, batch, proof_verdicts, flags, verdicts, where, applied, stream);
+}
+
+// ------------------------------------------------------------------------------------------------ keeping the ledger
+int zkr_ledger_records(const zkr_ledger *l, size_t first, size_t count, uint8_t *out) {
+  if (!l || (count && !out)) { set_error("null argument"); return ZKR_ERR_ARG; }
+  std::lock_guard<std::mutex> lk(l->mu);
+  if (first > l->accounts || count > l->accounts - first) { set_error("records %zu .. %zu + %zu of %zu accounts", first, first, count, l->accounts); return ZKR_ERR_ARG; }
+  if (count) memcpy(out, l->records.data() + first * 128, count * 128);
+  return ZKR_OK;
+}
+
+int zkr_ledger_tree(const zkr_ledger *l, const void **dev_ptr, size_t *len) {
+  if (!l || !dev_ptr || !len) { set_error("null argument"); return ZKR_ERR_ARG; }
+  std::lock_guard<std::mutex> lk(l->mu);
+  *dev_ptr = l->d_tree, *len = (((size_t)2 << l->depth) - 1) * 32;
+  return ZKR_OK;
+}
+
+int zkr_ledger_snapshot(const zkr_ledger *l, void **blob, size_t *len) {
+  if (blob) *blob = nullptr;
+  if (!l || !blob || !len) { set_error("null argument"); return ZKR_ERR_ARG; }
+  std::lock_guard<std::mutex> lk(l->mu);
+  LedgerHeader h;
+  h.depth = l->depth, h.accounts = l->accounts, h.applied = l->applied, h.batches = l->batches;
+  ZKR_HIP_CHECK(hipSetDevice(l->device));
+  ZKR_HIP_CHECK(hipMemcpy(h.root, l->d_tree + seq_level_offset(l->depth, l->depth), 32, hipMemcpyDeviceToHost));
+  const size_t n = LEDGER_HEADER_BYTES + l->accounts * 128;
+  uint8_t *out = (uint8_t *)malloc(n);
+  if (!out) { set_error("out of memory for a snapshot of %zu bytes", n); return ZKR_ERR_ARG; }
+  if (ledger_header_write(h, out)) { free(out); set_error("the snapshot's tag could not be computed"); return ZKR_ERR_ARG; }
+  if (l->accounts) memcpy(out + LEDGER_HEADER_BYTES, l->records.data(), l->accounts * 128);
+  *blob = out, *len = n;
+  return ZKR_OK;
+}
+
+int zkr_ledger_save(const zkr_ledger *l, const char *path) {
+  if (!l || !path) { set_error("null argument"); return ZKR_ERR_ARG; }
+  void *blob = nullptr;
+  size_t len = 0;
+  int rc = zkr_ledger_snapshot(l, &blob, &len);
+  if (rc) return rc;
+  const std::string tmp = std::string(path) + ".tmp";  // either the old file or the new one, never a part of one
+  FILE *f = fopen(tmp.c_str(), "wb");
+  bool ok = f != nullptr;
+  if (f) {
+    ok = fwrite(blob, 1, len, f) == len;
+    ok = fflush(f) == 0 && ok;
+    ok = fclose(f) == 0 && ok;
+  }
+  free(blob);
+  if (ok) ok = rename(tmp.c_str(), path) == 0;
+  if (!ok) { remove(tmp.c_str()); set_error("cannot write the ledger snapshot to %s", path); return ZKR_ERR_ARG; }
+  return ZKR_OK;
+}
+
+int zkr_ledger_restore(const void *blob, size_t len, int device, zkr_ledger **out) {
+  if (out) *out = nullptr;
+  if (!blob || !out) { set_error("null argument"); return ZKR_ERR_ARG; }
+  LedgerHeader h;
+  char why[200];
+  if (ledger_snapshot_parse((const uint8_t *)blob, len, &h, why, sizeof why)) { set_error("%s", why); return ZKR_ERR_ARG; }  // before the device is looked at
+  int rc = need_device(device, "restoring a ledger");
+  if (rc) return rc;
+  zkr_ledger *L = nullptr;
+  if ((rc = zkr_ledger_new(h.depth, device, &L))) return rc;
+  L->accounts = (size_t)h.accounts;
+  L->records.assign((const uint8_t *)blob + LEDGER_HEADER_BYTES, (const uint8_t *)blob + len);
+  uint8_t root[32];
+  rc = bulk_build(L);
+  if (!rc && hipMemcpy(root, L->d_tree + seq_level_offset(L->depth, L->depth), 32, hipMemcpyDeviceToHost) != hipSuccess) {
+    set_error("reading the rebuilt root failed");
+    rc = ZKR_ERR_HIP;
+  }
+  if (!rc && memcmp(root, h.root, 32)) {  // the root pins the records: the stored one is not trusted, it is compared
+    char want[67], got[67];
+    hex_be(h.root, want), hex_be(root, got);
+    set_error("ledger snapshot: the records rebuild to root %s, the snapshot says %s", got, want);
+    rc = ZKR_ERR_BAD_KEY;
+  }
+  if (rc) { zkr_ledger_free(L); return rc; }
+  L->applied = h.applied, L->batches = h.batches;
+  *out = L;
+  return ZKR_OK;
+}
+
+int zkr_ledger_load_file(const char *path, int device, zkr_ledger **out) {
+  if (out) *out = nullptr;
+  if (!path || !out) { set_error("null argument"); return ZKR_ERR_ARG; }
+  FILE *f = fopen(path, "rb");
+  if (!f) { set_error("cannot open %s", path); return ZKR_ERR_ARG; }
+  std::vector<uint8_t> buf;
+  uint8_t chunk[1 << 16];
+  size_t n;
+  while ((n = fread(chunk, 1, sizeof chunk, f)) > 0) buf.insert(buf.end(), chunk, chunk + n);
+  const bool bad = ferror(f);
+  fclose(f);
+  if (bad) { set_error("cannot read %s", path); return ZKR_ERR_ARG; }
+  return zkr_ledger_restore(buf.data(), buf.size(), device, out);
+}
+
+int zkr_ledger_checkpoint(zkr_ledger *l, uint64_t *id) {
+  if (!l || !id) { set_error("null argument"); return ZKR_ERR_ARG; }
+  std::lock_guard<std::mutex> lk(l->mu);
+  *id = l->journal.checkpoint();
+  return ZKR_OK;
+}
+
+int zkr_ledger_release(zkr_ledger *l, uint64_t id) {
+  if (!l) { set_error("null argument"); return ZKR_ERR_ARG; }
+  std::lock_guard<std::mutex> lk(l->mu);
+  if (!l->journal.release(id)) { set_error("checkpoint %llu is not open (unknown, released or discarded by a rollback)", (unsigned long long)id); return ZKR_ERR_ARG; }
+  return ZKR_OK;
+}
+
+int zkr_ledger_rollback(zkr_ledger *l, uint64_t id) {
+  if (!l) { set_error("null argument"); return ZKR_ERR_ARG; }
+  std::lock_guard<std::mutex> lk(l->mu);
+  const long keep = l->journal.rollback_keep(id);
+  if (keep < 0) { set_error("checkpoint %llu is not open (unknown, released or discarded by a rollback)", (unsigned long long)id); return ZKR_ERR_ARG; }
+  const std::vector<JournalCall> &calls = l->journal.calls;
+  if (calls.size() > (size_t)keep) {
+    ZKR_HIP_CHECK(hipSetDevice(l->device));
+    const size_t n_nodes = ((size_t)2 << l->depth) - 1;
+    for (size_t c = calls.size(); c-- > (size_t)keep;) {  // call by call, the latest first: two calls may hold the same node
+      state_undo_kernel<<<blocks(calls[c].node_count, 256), 256>>>(l->d_tree, n_nodes, l->d_joff + calls[c].node_begin, l->d_jold + calls[c].node_begin, calls[c].node_count);
+      ZKR_HIP_CHECK(hipGetLastError());
+    }
+    ZKR_HIP_CHECK(hipDeviceSynchronize());
+    for (size_t c = calls.size(); c-- > (size_t)keep;) LedgerJournal::undo_host(calls[c], l->records, l->accounts, l->applied, l->batches);
+  }
+  l->journal.rollback_done(id);
+  return ZKR_OK;
+}
+
+int zkr_ledger_journal_info(const zkr_ledger *l, uint64_t out[2]) {
+  if (!l || !out) { set_error("null argument"); return ZKR_ERR_ARG; }
+  std::lock_guard<std::mutex> lk(l->mu);
+  out[0] = l->journal.markers.size(), out[1] = l->journal.nodes();
+  return ZKR_OK;
+}
+
+int zkr_ledger_audit(zkr_ledger *l, uint64_t report[2], int *sound) {
+  if (sound) *sound = 0;
+  if (!l || !report || !sound) { set_error("null argument"); return ZKR_ERR_ARG; }
+  std::lock_guard<std::mutex> lk(l->mu);
+  ZKR_HIP_CHECK(hipSetDevice(l->device));
+  const unsigned depth = l->depth;
+  const size_t accounts = l->accounts, n_nodes = ((size_t)2 << depth) - 1;
+  const size_t piece = accounts < STATE_PIECE ? accounts : (size_t)STATE_PIECE;
+  int rc = l->arena.reserve(DevArena::padded(piece * 128 + 128) + DevArena::padded(((size_t)depth + 1) * 32) + DevArena::padded(8));
+  if (rc) return rc;
+  Fr *d_stage = l->arena.take<Fr>(piece * 4 + 4), *d_empty = l->arena.take<Fr>(depth + 1);
+  unsigned long long *d_bad = l->arena.take<unsigned long long>(1), bad = ~0ull;
+  ZKR_HIP_CHECK(hipMemcpy(d_empty, l->empty.data(), ((size_t)depth + 1) * 32, hipMemcpyHostToDevice));
+  ZKR_HIP_CHECK(hipMemset(d_bad, 0xFF, 8));
+  if (piece) ZKR_HIP_CHECK(hipMemcpy(d_stage, l->records.data(), piece * 128, hipMemcpyHostToDevice));
+  // one launch over every node, with the first piece of records; a ledger of more than 2^20 accounts then has its remaining
+  // leaves looked at piece by piece
+  state_audit_kernel<<<blocks(n_nodes, 64), 64>>>(l->d_tree, depth, accounts, d_empty, d_stage, 0, piece, 0, n_nodes, d_bad);
+  ZKR_HIP_CHECK(hipGetLastError());
+  for (size_t first = piece; first < accounts; first += piece) {
+    const size_t n = accounts - first < piece ? accounts - first : piece;
+    ZKR_HIP_CHECK(hipMemcpy(d_stage, l->records.data() + first * 128, n * 128, hipMemcpyHostToDevice));
+    state_audit_kernel<<<blocks(n, 64), 64>>>(l->d_tree, depth, accounts, d_empty, d_stage, first, n, first, n, d_bad);
+    ZKR_HIP_CHECK(hipGetLastError());
+  }
+  ZKR_HIP_CHECK(hipMemcpy(&bad, d_bad, 8, hipMemcpyDeviceToHost));
+  ZKR_HIP_CHECK(hipDeviceSynchronize());
+  report[0] = report[1] = 0;
+  if (bad == ~0ull) { *sound = 1; return ZKR_OK; }
+  report[0] = bad >> 32, report[1] = bad & 0xFFFFFFFFull;
+  set_error("ledger audit: node %llu of level %llu is not what the records and the nodes below it make it", (unsigned long long)report[1], (unsigned long long)report[0]);
+  return ZKR_OK;
 }
 
 }  // extern "C"

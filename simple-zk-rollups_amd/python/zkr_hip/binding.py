@@ -159,6 +159,19 @@ def lib():
     L.zkr_ledger_replay_device.argtypes = [vp, c.POINTER(vp), sz, c.c_uint32, u8p, c.c_uint32, u8p, c.POINTER(c.c_uint32), c.POINTER(sz), vp]
     L.zkr_replay_plan_host.argtypes = [c.c_uint, u8p, sz, u8p, sz, c.c_uint32, u8p, c.POINTER(c.c_uint32), c.POINTER(sz), c.POINTER(c.c_uint32), u8p, u8p,
                                        c.POINTER(c.c_int32)]
+    u64p = c.POINTER(c.c_uint64)
+    L.zkr_ledger_records.argtypes = [vp, sz, sz, u8p]
+    L.zkr_ledger_tree.argtypes = [vp, c.POINTER(vp), c.POINTER(sz)]
+    L.zkr_ledger_snapshot.argtypes = [vp, c.POINTER(vp), c.POINTER(sz)]
+    L.zkr_ledger_save.argtypes = [vp, c.c_char_p]
+    L.zkr_ledger_snapshot_check.argtypes = [u8p, sz, u64p, c.POINTER(c.c_int)]
+    L.zkr_ledger_restore.argtypes = [u8p, sz, i, c.POINTER(vp)]
+    L.zkr_ledger_load_file.argtypes = [c.c_char_p, i, c.POINTER(vp)]
+    L.zkr_ledger_checkpoint.argtypes = [vp, u64p]
+    L.zkr_ledger_rollback.argtypes = [vp, c.c_uint64]
+    L.zkr_ledger_release.argtypes = [vp, c.c_uint64]
+    L.zkr_ledger_journal_info.argtypes = [vp, u64p]
+    L.zkr_ledger_audit.argtypes = [vp, u64p, c.POINTER(c.c_int)]
     _lib = L
     return L
 

@@ -6,6 +6,7 @@ operator/src/snarks/common.ts:12-21 for `BatchProcessTx(batch, depth)`
 (prover/circuits/batchprocesstx.circom:3-75).  All arithmetic is native (csrc/rollup.cpp).
 """
 import ctypes
+import os
 
 from .binding import ZkrError, _check, _take, lib
 
@@ -254,6 +255,107 @@ class Ledger:
         out = (ctypes.c_double * 5)()
         _check(lib().zkr_ledger_stage_times(self._h, out))
         return dict(zip(("signatures", "host_pass", "leaf_hashes", "levels", "assembly"), out))
+
+    # ---- keeping the ledger (include/zkr.h, DESIGN.md 9h)
+    @classmethod
+    def _adopt(cls, handle, device):
+        self = cls.__new__(cls)
+        self._h, self.device = handle, device
+        try:
+            self.depth = self.info()["depth"]
+        except Exception:
+            self.close()
+            raise
+        return self
+
+    def records(self, first=0, count=None):
+        """[pubX, pubY, balance, nonce] of `count` accounts from `first` on (default: all), from the host copy."""
+        if count is None:
+            count = self.info()["accounts"] - first
+        out = ctypes.create_string_buffer(max(1, 128 * count))
+        _check(lib().zkr_ledger_records(self._h, first, count, out))
+        return [_ints(out.raw[128 * i:128 * i + 128]) for i in range(count)]
+
+    def tree(self):
+        """The stored tree as a zero-copy torch uint8 view of device memory, [2^(depth+1) - 1, 32]: leaves first, root last,
+        standard form.  Read-only by contract; valid while the ledger lives; its contents move with every state-changing call."""
+        from .batch import _tensor_from_ptr
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        _check(lib().zkr_ledger_tree(self._h, ctypes.byref(p), ctypes.byref(n)))
+        return _tensor_from_ptr(p.value, n.value, self.device).view(-1, 32)
+
+    def paths(self, indices):
+        """getUpdatePath(i).pathElements for every i of `indices`, gathered from the tree view in one go."""
+        import torch
+        indices = [int(i) for i in indices]
+        if any(i < 0 or i >> self.depth for i in indices):
+            raise ValueError("a leaf index outside the tree of depth %d" % self.depth)
+        if not indices:
+            return []
+        rows = [((2 << self.depth) - (2 << (self.depth - l))) + ((i >> l) ^ 1) for i in indices for l in range(self.depth)]
+        view = self.tree()
+        got = view[torch.tensor(rows, dtype=torch.int64, device=view.device)].cpu().numpy().tobytes()
+        vals = _ints(got)
+        return [vals[k * self.depth:(k + 1) * self.depth] for k in range(len(indices))]
+
+    def snapshot(self) -> bytes:
+        """The ZKRLEDG1 blob of the current state: a header pinned by its tag, the records pinned by the root."""
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        _check(lib().zkr_ledger_snapshot(self._h, ctypes.byref(p), ctypes.byref(n)))
+        return _take(p, n.value)
+
+    def save(self, path):
+        _check(lib().zkr_ledger_save(self._h, os.fsencode(path)))
+
+    @staticmethod
+    def snapshot_check(blob):
+        """Host only: (info dict, None) of a well-formed blob, or (None, the line naming the first failure)."""
+        blob = bytes(blob)
+        info, valid = (ctypes.c_uint64 * 4)(), ctypes.c_int()
+        _check(lib().zkr_ledger_snapshot_check(blob, len(blob), info, ctypes.byref(valid)))
+        if not valid.value:
+            return None, lib().zkr_last_error().decode()
+        return {"depth": info[0], "accounts": info[1], "applied": info[2], "batches": info[3]}, None
+
+    @classmethod
+    def restore(cls, blob, device=0):
+        """A new ledger from a snapshot: checked on the host (ZkrError -5), rebuilt in bulk on the device, and refused
+        (ZkrError -2, both roots in the message) when the records do not rebuild to the snapshot's root."""
+        blob = bytes(blob)
+        h = ctypes.c_void_p()
+        _check(lib().zkr_ledger_restore(blob, len(blob), device, ctypes.byref(h)))
+        return cls._adopt(h, device)
+
+    @classmethod
+    def load(cls, path, device=0):
+        h = ctypes.c_void_p()
+        _check(lib().zkr_ledger_load_file(os.fsencode(path), device, ctypes.byref(h)))
+        return cls._adopt(h, device)
+
+    def checkpoint(self) -> int:
+        """Opens a checkpoint and returns its id.  Until every checkpoint is released, each storing call journals what it
+        overwrites, so that `rollback(cp)` puts records, tree and counters back exactly as they stand now."""
+        cp = ctypes.c_uint64()
+        _check(lib().zkr_ledger_checkpoint(self._h, ctypes.byref(cp)))
+        return cp.value
+
+    def rollback(self, cp):
+        _check(lib().zkr_ledger_rollback(self._h, cp))
+
+    def release(self, cp):
+        _check(lib().zkr_ledger_release(self._h, cp))
+
+    def journal_info(self):
+        """(open checkpoints, journalled nodes)."""
+        out = (ctypes.c_uint64 * 2)()
+        _check(lib().zkr_ledger_journal_info(self._h, out))
+        return out[0], out[1]
+
+    def audit(self):
+        """None when the stored tree is the tree of the records, else (level, index) of the first node that is not."""
+        report, sound = (ctypes.c_uint64 * 2)(), ctypes.c_int()
+        _check(lib().zkr_ledger_audit(self._h, report, ctypes.byref(sound)))
+        return None if sound.value else (report[0], report[1])
 
 
 class RollupCircuit:
