@@ -637,6 +637,35 @@ const char *zkr_rollup_statement_text(uint32_t stmt);
 int zkr_rollup_witness_batch_from_device(uint32_t batch, uint32_t depth, const void *d_inputs, size_t n_inputs, size_t n_batches,
                                          void *d_witnesses, int device, void *stream);
 
+/* ---- the user's side of crypto.ts and the withdraw circuit in bulk ON THE GPU, one thread per item (csrc/zkr_wallet.hip over
+ * csrc/wallet_program.hpp): formatPrivKeyForBabyJub (crypto.ts:58-76), genPublicKey (:78-84) and sign (:143-168)
+ * for n keys, each item equal to zkr_babyjub_format_privkey / zkr_babyjub_pubkey / zkr_eddsa_sign bit for bit.  privs: n x 32 B,
+ * msgs: n x arity x 32 B, arity 1..64; out: n x 32 B, pubs: n x 64 B, sigs: n x 96 B (R8x R8y S); all standard form.
+ * Arguments are checked first, without a device: a null pointer or an arity out of range is ZKR_ERR_ARG, and so is a key or a
+ * message element not below r, with the first such item's index in zkr_last_error (what the host calls refuse).  Then the
+ * device: no CPU fallback (ZKR_ERR_NO_DEVICE).  n = 0 is ZKR_OK with nothing launched.  On an error return the outputs are
+ * untouched.  Any n: more than 2^20 items go to the device in pieces.  Every device buffer that held a key or a formatted
+ * scalar is zeroed before it is freed.  The kernels are NOT constant time. */
+int zkr_babyjub_format_privkey_batch(const uint8_t *privs, size_t n, uint8_t *out, int device);
+int zkr_babyjub_pubkey_batch(const uint8_t *privs, size_t n, uint8_t *pubs, int device);
+int zkr_eddsa_sign_batch(const uint8_t *privs, const uint8_t *msgs, unsigned arity, size_t n, uint8_t *sigs, int device);
+/* `Circuit.calculateWitness` for withdraw.circom (operator/src/snarks/withdraw.ts:6-10) for n withdrawals at once: private_keys
+ * (FORMATTED keys) and nullifiers are n x 32 B in host memory, d_witnesses = device memory for n x nVars x 32 B, each witness
+ * laid out as zkr_withdraw_witness returns it (byte for byte) and ready for zkr_prove_batch_device, zkr_r1cs_check_device and
+ * zkr_verify_each_device.  The kernels run on `stream` (NULL: the default stream); the call returns when the witnesses are
+ * complete.  An input not below r is ZKR_ERR_ARG (checked before the device); a key past 253 bits is ZKR_ERR_UNSATISFIED naming
+ * the first failing witness and the statement, found before anything is launched.  No CPU fallback (ZKR_ERR_NO_DEVICE). */
+int zkr_withdraw_witness_batch_device(const uint8_t *private_keys, const uint8_t *nullifiers, size_t n, void *d_witnesses, int device, void *stream);
+/* Test hooks: the programs one GPU thread runs per item (csrc/wallet_program.hpp), run on the HOST for one item.  pubkey:
+ * formatted = the scalar of zkr_babyjub_format_privkey, pub = zkr_babyjub_pubkey's; sign: sig = zkr_eddsa_sign's; withdraw:
+ * *stmt = code of the first violated statement (zkr_withdraw_statement_text gives its wording) with witness_out untouched, or
+ * 0 with witness_out = nVars x 32 B as zkr_withdraw_witness lays it out (zkr_withdraw_n_vars: nVars). */
+int zkr_wallet_pubkey_program_host(const uint8_t priv[32], uint8_t formatted[32], uint8_t pub[64]);
+int zkr_wallet_sign_program_host(const uint8_t priv[32], const uint8_t *msg, unsigned arity, uint8_t sig[96]);
+int zkr_withdraw_witness_program_host(const uint8_t private_key[32], const uint8_t nullifier[32], uint8_t *witness_out, uint32_t *stmt);
+const char *zkr_withdraw_statement_text(uint32_t stmt);
+uint32_t zkr_withdraw_n_vars(void);
+
 /* ---- the operator's ledger on the GPU: a queue of signed transactions -> a status each and the circuit inputs of every whole
  * batch, in device memory (csrc/zkr_sequencer.hip).  Stands in for the per-transaction loop of
  * operator/src/routes/send.ts:72-135 and the tree updates of operator/src/routes/pubsub.ts:19-66.  The ledger holds the account

@@ -101,6 +101,26 @@ struct DevView {  // a typed look at device memory owned elsewhere
   void *p;
   template <class T> T *as() const { return static_cast<T *>(p); }
 };
+// Curve constants, the fixed-base table 2^i BASE8 and the round constants in device memory, uploaded once per device and shared
+// by everything that runs the programs of rollup_witness.hpp / wallet_program.hpp there (this file, zkr_wallet.hip).  The
+// caller has made `device` current.
+int rollup_device_tables(int device, TxConsts *k) {
+  static std::mutex mu;
+  static Fr *d_tab[64] = {nullptr};
+  std::lock_guard<std::mutex> lk(mu);
+  if (device < 0 || device >= 64) { set_error("device index out of range"); return ZKR_ERR_ARG; }
+  std::vector<Fr> tab(2 * 253 + MIMC_ROUNDS);
+  rollup_device_constants(&k->a, &k->d, k->suborder_m1, tab.data(), tab.data() + 253);
+  memcpy(tab.data() + 506, mimc_round_constants(), MIMC_ROUNDS * 32);
+  if (!d_tab[device]) {
+    Fr *d = nullptr;
+    ZKR_HIP_CHECK(hipMalloc(&d, tab.size() * 32));
+    if (hipMemcpy(d, tab.data(), tab.size() * 32, hipMemcpyHostToDevice) != hipSuccess) { hipFree(d); set_error("upload of the witness builder's tables failed"); return ZKR_ERR_HIP; }
+    d_tab[device] = d;
+  }
+  k->b8x = d_tab[device], k->b8y = d_tab[device] + 253, k->mimc = d_tab[device] + 506;
+  return ZKR_OK;
+}
 }  // namespace zkr
 
 // Host fast path of zkr_rollup_witness (rollup.cpp batch_witness): the value program on host threads, one task per
@@ -219,24 +239,8 @@ static int witness_batch(uint32_t batch, uint32_t depth, const uint8_t *inputs, 
   if (n_batches * (size_t)batch > (1u << 22)) { set_error("too many transactions in one call (%zu batches of %u)", n_batches, batch); return ZKR_ERR_ARG; }
   ZKR_HIP_CHECK(hipSetDevice(device));
   if ((rc = upload_constants(device))) return rc;
-  // curve constants, the fixed-base table and the round constants, once per device
-  static std::mutex mu;
-  static Fr *d_tab[64] = {nullptr};
   TxConsts k;
-  {
-    std::lock_guard<std::mutex> lk(mu);
-    if (device >= 64) { set_error("device index out of range"); return ZKR_ERR_ARG; }
-    std::vector<Fr> tab(2 * 253 + MIMC_ROUNDS);
-    rollup_device_constants(&k.a, &k.d, k.suborder_m1, tab.data(), tab.data() + 253);
-    memcpy(tab.data() + 506, mimc_round_constants(), MIMC_ROUNDS * 32);
-    if (!d_tab[device]) {
-      Fr *d = nullptr;
-      ZKR_HIP_CHECK(hipMalloc(&d, tab.size() * 32));
-      if (hipMemcpy(d, tab.data(), tab.size() * 32, hipMemcpyHostToDevice) != hipSuccess) { hipFree(d); set_error("upload of the witness builder's tables failed"); return ZKR_ERR_HIP; }
-      d_tab[device] = d;
-    }
-  }
-  k.b8x = d_tab[device], k.b8y = d_tab[device] + 253, k.mimc = d_tab[device] + 506;
+  if ((rc = rollup_device_tables(device, &k))) return rc;
   const size_t n_tx = n_batches * batch, nv = (size_t)p + 1 + (size_t)batch * K;
   // Scratch kept per device and only ever grown: hipMalloc / hipFree synchronise the whole device, i.e. every call would wait
   // for the proofs in flight on the key's streams (measured: the builder's 30 ms became the 63 ms of the prove call beside it).

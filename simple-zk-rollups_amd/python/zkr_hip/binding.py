@@ -144,6 +144,17 @@ def lib():
     L.zkr_rollup_statement_text.argtypes = [c.c_uint32]
     L.zkr_rollup_statement_text.restype = c.c_char_p
     L.zkr_rollup_witness_batch_from_device.argtypes = [c.c_uint32, c.c_uint32, vp, sz, sz, vp, c.c_int, vp]
+    L.zkr_babyjub_format_privkey_batch.argtypes = [u8p, sz, u8p, i]
+    L.zkr_babyjub_pubkey_batch.argtypes = [u8p, sz, u8p, i]
+    L.zkr_eddsa_sign_batch.argtypes = [u8p, u8p, c.c_uint, sz, u8p, i]
+    L.zkr_withdraw_witness_batch_device.argtypes = [u8p, u8p, sz, vp, i, vp]
+    L.zkr_wallet_pubkey_program_host.argtypes = [u8p, u8p, u8p]
+    L.zkr_wallet_sign_program_host.argtypes = [u8p, u8p, c.c_uint, u8p]
+    L.zkr_withdraw_witness_program_host.argtypes = [u8p, u8p, vp, c.POINTER(c.c_uint32)]
+    L.zkr_withdraw_statement_text.argtypes = [c.c_uint32]
+    L.zkr_withdraw_statement_text.restype = c.c_char_p
+    L.zkr_withdraw_n_vars.argtypes = []
+    L.zkr_withdraw_n_vars.restype = c.c_uint32
     L.zkr_ledger_new.argtypes = [c.c_uint, i, c.POINTER(vp)]
     L.zkr_ledger_free.argtypes = [vp]
     L.zkr_ledger_free.restype = None

@@ -104,6 +104,71 @@ def verify_batch(msgs, sigs, pubs, device=0):
     return [b != 0 for b in out.raw]
 
 
+def _keys_bytes(privs):
+    privs = [int(p) for p in privs]
+    if any(p < 0 or p >> 256 for p in privs):
+        raise ValueError("a private key outside 0 .. 2^256 - 1")
+    return privs, b"".join(_le(p) for p in privs)
+
+
+def format_priv_key_batch(privs, device=0):
+    """formatPrivKeyForBabyJub (crypto.ts:58-76) for many keys on the GPU, one thread each (zkr_babyjub_format_privkey_batch):
+    a list of scalars, each what `format_priv_key` returns.  A key not below r is ZkrError(-5) naming its index."""
+    privs, buf = _keys_bytes(privs)
+    if not privs:
+        return []
+    out = ctypes.create_string_buffer(32 * len(privs))
+    _check(lib().zkr_babyjub_format_privkey_batch(buf, len(privs), out, device))
+    return _ints(out.raw)
+
+
+def gen_public_key_batch(privs, device=0):
+    """genPublicKey (crypto.ts:78-84) for many keys on the GPU (zkr_babyjub_pubkey_batch): a list of (x, y), each what
+    `gen_public_key` returns."""
+    privs, buf = _keys_bytes(privs)
+    if not privs:
+        return []
+    out = ctypes.create_string_buffer(64 * len(privs))
+    _check(lib().zkr_babyjub_pubkey_batch(buf, len(privs), out, device))
+    v = _ints(out.raw)
+    return [(v[2 * k], v[2 * k + 1]) for k in range(len(privs))]
+
+
+def sign_batch(privs, msgs, device=0):
+    """sign(prv, msg) (crypto.ts:143-168) for many keys and messages on the GPU (zkr_eddsa_sign_batch): msgs = equally long lists
+    of message elements below r, one per key.  A list of {"R8": (x, y), "S": s}, each what `sign` returns."""
+    privs, buf = _keys_bytes(privs)
+    msgs = [[int(v) for v in m] for m in msgs]
+    if len(msgs) != len(privs):
+        raise ValueError("%d messages for %d keys" % (len(msgs), len(privs)))
+    if not privs:
+        return []
+    arity = len(msgs[0])
+    if any(len(m) != arity for m in msgs):
+        raise ValueError("messages of different lengths in one batch")
+    mb = b"".join(_le(v) for m in msgs for v in m)
+    out = ctypes.create_string_buffer(96 * len(privs))
+    _check(lib().zkr_eddsa_sign_batch(buf, mb, arity, len(privs), out, device))
+    v = _ints(out.raw)
+    return [{"R8": (v[3 * k], v[3 * k + 1]), "S": v[3 * k + 2]} for k in range(len(privs))]
+
+
+def wallet_pubkey_program_host(priv):
+    """The GPU threads' format_privkey and pubkey programs (csrc/wallet_program.hpp) on the host for one key (test hook):
+    (formatted scalar, (x, y))."""
+    f, p = ctypes.create_string_buffer(32), ctypes.create_string_buffer(64)
+    _check(lib().zkr_wallet_pubkey_program_host(_le(priv), f, p))
+    return int.from_bytes(f.raw, "little"), tuple(_ints(p.raw))
+
+
+def wallet_sign_program_host(priv, msg):
+    """The GPU threads' sign program on the host for one key and message (test hook): the dict `sign` returns."""
+    out = ctypes.create_string_buffer(96)
+    _check(lib().zkr_wallet_sign_program_host(_le(priv), b"".join(_le(v) for v in msg), len(msg), out))
+    v = _ints(out.raw)
+    return {"R8": (v[0], v[1]), "S": v[2]}
+
+
 def tx_row(frm, to, amount, fee, nonce, sig):
     """The txData row of batchprocesstx.circom for one signed transaction: from to amount fee nonce R8x R8y S."""
     return [frm, to, amount, fee, nonce, sig["R8"][0], sig["R8"][1], sig["S"]]
@@ -457,6 +522,33 @@ class WithdrawCircuit:
 
     def public_signals(self, witness_bin: bytes):
         return _ints(witness_bin[32:128])
+
+    @property
+    def n_vars(self):
+        return lib().zkr_withdraw_n_vars()
+
+    def witness_program_host(self, inputs):
+        """The GPU builder's per-witness program (csrc/wallet_program.hpp) run on the host (test hook): (witness bytes, None), or
+        (None, the text of the first violated statement)."""
+        out = ctypes.create_string_buffer(self.n_vars * 32)
+        stmt = ctypes.c_uint32()
+        _check(lib().zkr_withdraw_witness_program_host(_le(int(inputs["privateKey"])), _le(int(inputs["nullifier"])), out, ctypes.byref(stmt)))
+        if stmt.value:
+            return None, lib().zkr_withdraw_statement_text(stmt.value).decode()
+        return out.raw, None
+
+    def calculate_witness_batch_device(self, cases, device=0, stream=None):
+        """calculateWitness for MANY withdrawals on the GPU (zkr_withdraw_witness_batch_device: one thread per witness): cases = a
+        list of {"privateKey": formatted key, "nullifier": ...}.  A uint8 torch tensor [len(cases), nVars * 32] in HBM, row i =
+        the bytes calculate_witness(cases[i]) returns, ready for ProvingKey.prove_batch_device([t[i].data_ptr() ...]).  The
+        kernels run on `stream` (a raw stream handle; None: the default stream).  An input not below r is ZkrError(-5) -- the
+        nullifier is NOT taken mod r here; a key past 253 bits ZkrError(-7) naming the first such witness and the statement."""
+        import torch
+        keys = b"".join(_le(int(x["privateKey"])) for x in cases)
+        nuls = b"".join(_le(int(x["nullifier"])) for x in cases)
+        out = torch.empty((len(cases), self.n_vars * 32), dtype=torch.uint8, device=torch.device("cuda", device))
+        _check(lib().zkr_withdraw_witness_batch_device(keys, nuls, len(cases), out.data_ptr(), device, stream))
+        return out
 
 
 class BalanceTree:
