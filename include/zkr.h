@@ -840,6 +840,16 @@ int zkr_selftest_f29_forms(int device, int field, int form, const uint32_t *reco
  * packed coordinates of 8 / 16 words, then the 4 read back as limbs); inf: n bytes, 1 = the point at infinity.  The host build
  * of the same header (libzkr_hostarith.so zkt29_curve_raw) must give the same limbs: tests/test_gpu_group_law.py. */
 int zkr_selftest_curve29(int device, int g2, int op, const uint32_t *records, size_t n, uint32_t *out, uint8_t *inf);
+/* And one layer down, off the hot path: the 8 x 32-bit-limb field of csrc/field.hpp (radix 2^256) as the device compiles it -- the
+ * product scanning in a 96-bit column accumulator, the fused sums of csrc/field_fused.hpp, the schoolbook Fq2 product and both
+ * mul_sub, none of which the host build shares -- on raw limbs, one thread per record.  records: n x 8 operands x 8 words, least
+ * significant word first, nothing converted on the way in or out; an operation ignores the operands it does not read.  field 0 =
+ * Fq, 1 = Fr.  op (csrc/field_raw_ops.def): 0 mul(a,b), 1 sqr(a), 2 add(a,b), 3 sub(a,b), 4 neg(a), 5 reduce_once(a),
+ * 6 mul_sum2(a,b,c,d), 7 mul_sum4(a..h), 8 mul_sub(a,b,c,d), 9 to_mont(a), 10 from_mont(a), 11 inv(a); out: n x 8 words.  Over Fq2
+ * (field 0 only; an element = two operands, re then im): 12 mul(x,y), 13 sqr(x), 14 mul_sub(x,y,z,w), 15 inv(x); out: n x 16
+ * words.  Every result is canonical, so the host build of the same function (libzkr_hostarith.so zkt_fp_raw) and integer
+ * arithmetic must give the same words bit for bit: tests/test_gpu_field_raw.py. */
+int zkr_selftest_fp(int device, int field, int op, const uint32_t *records, size_t n, uint32_t *out);
 int zkr_bench_fq_mul(int device, double *gmuls_per_s);
 int zkr_bench_fq_mul_legacy(int device, double *gmuls_per_s);
 

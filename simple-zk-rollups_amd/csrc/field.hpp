@@ -3,8 +3,10 @@
 // Written for the CDNA4 VALU: every product is a 32x32+64 multiply-add (v_mad_u64_u32); loops are
 // fully unrolled so an element lives in 8 VGPRs.  No MFMA: this is integer work.
 // Moduli as in /root/reference/operator/src/utils/binarify.ts:79-81 (q) and :86-88 (r); Montgomery
-// radix 2^256 as in binarify.ts:78-90.  The same code compiles for the host (clang) so that the
-// arithmetic can be unit-tested on CPU against the oracle (tests/test_host_arith.py).
+// radix 2^256 as in binarify.ts:78-90.  The header compiles for the host (clang) too, but NOT to the same
+// products: there mul is mul_host64, the fused sums are separate products and the Fq2 product is Karatsuba,
+// so tests/test_host_arith.py tests the host's side only.  field_raw.hpp runs every operation of this file in
+// both builds on raw limbs; tests/test_field_raw_cpu.py and tests/test_gpu_field_raw.py compare them with integers.
 #pragma once
 #include <stdint.h>
 
@@ -85,7 +87,8 @@ struct Fp {
   }
 };
 
-// r = a - p if a >= p else a   (a < 2p)
+// r = a - p if a >= p else a: the canonical residue for a < 2p, which is what every caller in this file has.  The ingest kernels
+// (kernels_ntt.hpp, zkr_r1cs.hip) apply it five times to ARBITRARY 256-bit words: for any a it is this one conditional subtraction
 template <class PM>
 ZKR_HD Fp<PM> reduce_once(const Fp<PM> &a) {
   Fp<PM> d;
@@ -98,6 +101,7 @@ ZKR_HD Fp<PM> reduce_once(const Fp<PM> &a) {
   return r;
 }
 
+// add, sub: canonical operands (a, b < p), canonical result
 template <class PM>
 ZKR_HD Fp<PM> add(const Fp<PM> &a, const Fp<PM> &b) {
   Fp<PM> s;
@@ -119,6 +123,7 @@ ZKR_HD Fp<PM> sub(const Fp<PM> &a, const Fp<PM> &b) {
   return d;
 }
 
+// a <= p: mul_sub hands it an operand of a product, which may be p itself (neg(p) = neg(0) = 0); canonical result
 template <class PM>
 ZKR_HD Fp<PM> neg(const Fp<PM> &a) {
   if (a.is_zero()) return a;
@@ -260,6 +265,9 @@ inline Fp<PM> mul_host64(const Fp<PM> &a, const Fp<PM> &b) {
 }
 #endif
 
+// a * b / 2^256 mod p, canonical.  Operands <= p, as for the fused sums of field_fused.hpp (whose host build is this product):
+// a b <= p^2 < p 2^256, so the value before the last subtraction is below 2p in both builds.  sqr, to_mont and from_mont inherit
+// the bound; inv takes a canonical operand
 template <class PM>
 ZKR_HD Fp<PM> mul(const Fp<PM> &a, const Fp<PM> &b) {
 #if !defined(__HIP_DEVICE_COMPILE__)
@@ -364,7 +372,7 @@ ZKR_HD_COLD Fp<PM> inv(const Fp<PM> &a) { return inv_inline(a); }  // out of lin
 
 #include "field_fused.hpp"  // mul_sum2 / mul_sum4 (generated by tools/gen_mul_sum.py)
 
-// a*b - c*d with one reduction
+// a*b - c*d with one reduction; operands <= p as for mul_sum2
 template <class PM>
 ZKR_HD Fp<PM> mul_sub(const Fp<PM> &a, const Fp<PM> &b, const Fp<PM> &c, const Fp<PM> &d) {
   return mul_sum2(a, b, neg(c), d);
@@ -374,6 +382,7 @@ using Fq = Fp<FqParams>;
 using Fr = Fp<FrParams>;
 
 // ---------------------------------------------------------------- Fq2 = Fq[u]/(u^2+1)
+// components canonical (< q) in and out, for every operation below
 struct Fq2 {
   Fq a, b;  // a + b*u
   static ZKR_HD Fq2 zero() { return Fq2{Fq::zero(), Fq::zero()}; }

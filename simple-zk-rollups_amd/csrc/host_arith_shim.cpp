@@ -1,10 +1,17 @@
-// host_arith_shim.cpp -- exposes the device field/curve templates, compiled for the HOST, through a
+// host_arith_shim.cpp -- exposes the field/curve templates, compiled for the HOST, through a
 // tiny C ABI so tests/test_host_arith.py can check them against the oracle without a GPU.
 // Not part of the product path (the product is libzkr_hip.so).
+// What the host build does NOT share with the device (field.hpp chooses by __HIP_DEVICE_COMPILE__): mul -- and so sqr, to_mont,
+// from_mont, inv -- is mul_host64 here and the 96-bit column scan of the mac96* asm statements there; mul_sum2 / mul_sum4 add
+// separate products here and are one fused scan there (field_fused.hpp); the Fq2 product is Karatsuba here and schoolbook through
+// mul_sum2 there; both mul_sub go through those.  A pass of the tests of this shim says nothing about the device's side of these:
+// zkt_fp_raw below and zkr_selftest_fp (zkr_selftest.hip) run ONE function, field_raw_op, in the two builds on raw edge limbs, and
+// tests/test_field_raw_cpu.py / tests/test_gpu_field_raw.py compare each with integers and the two with each other.
 #include "hostops.hpp"
 #include "pairing.hpp"
 #include "curve29.hpp"
 #include "curve29_raw.hpp"
+#include "field_raw.hpp"
 #include "msm_plan.hpp"
 #include "eval_h.hpp"
 using namespace zkr;
@@ -349,6 +356,20 @@ int zkt29_chain_from_head(int g2, const uint8_t *pts, const uint8_t *signs, size
 int zkt29_g1_chain(const uint8_t *pts, const uint8_t *signs, size_t n, int twice, uint8_t *out) { return chain29<Fq>(pts, signs, n, twice, out); }
 int zkt29_g2_chain(const uint8_t *pts, const uint8_t *signs, size_t n, int twice, uint8_t *out) { return chain29<Fq2>(pts, signs, n, twice, out); }
 
+// the 8 x 32-bit-limb field on raw limbs, nothing converted on the way in or out: records (n x 64 words), operations and results
+// (n x 8 words, the Fq2 ops 16) as field_raw.hpp lays them out and as zkr_selftest_fp runs them on the device.  field 0 = Fq,
+// 1 = Fr; a pair (field, op) that field_raw_valid refuses writes nothing
+void zkt_fp_raw(int field, int op, const uint32_t *records, size_t n, uint32_t *out) {
+  if (!field_raw_valid(field, op)) return;
+  const size_t ow = (size_t)field_raw_out_words(op);
+  auto run = [&](auto pm) {
+    using PM = decltype(pm);
+    field_raw_dispatch<PM>(op, [&](auto tag) {
+      for (size_t i = 0; i < n; i++) field_raw_op<PM, decltype(tag)::value>(records + i * FIELD_RAW_RECORD_WORDS, out + i * ow);
+    });
+  };
+  if (field) run(FrParams{}); else run(FqParams{});
+}
 // op: 0 mul, 1 add, 2 sub, 3 inv(a), 4 neg(a), 5 sqr(a); inputs/outputs standard form
 void zkt_fp(int field, int op, const uint8_t *a, const uint8_t *b, uint8_t *out) {
   if (field == 0) {

@@ -127,6 +127,7 @@ def lib():
     L.zkr_bench_fq_mul_legacy.argtypes = [i, c.POINTER(c.c_double)]
     L.zkr_selftest_f29_forms.argtypes = [i, i, i, c.POINTER(c.c_uint32), sz, c.POINTER(c.c_uint32)]
     L.zkr_selftest_curve29.argtypes = [i, i, i, c.POINTER(c.c_uint32), sz, c.POINTER(c.c_uint32), c.POINTER(c.c_uint8)]
+    L.zkr_selftest_fp.argtypes = [i, i, i, c.POINTER(c.c_uint32), sz, c.POINTER(c.c_uint32)]
     L.zkr_mimcsponge_multihash.argtypes = [u8p, sz, u8p]
     L.zkr_babyjub_pubkey.argtypes = [u8p, u8p]
     L.zkr_eddsa_sign.argtypes = [u8p, u8p, sz, u8p]
@@ -998,6 +999,45 @@ def selftest_curve29(g2, op, records, device=0):
     inf = (ctypes.c_uint8 * max(1, n))()
     _check(lib().zkr_selftest_curve29(device, int(bool(g2)), op, flat, n, out, inf))
     return list(out[:ow * n]), list(inf[:n])
+
+
+FIELD_RAW_OPS_FILE = os.path.normpath(os.path.join(_HERE, "..", "..", "csrc", "field_raw_ops.def"))
+FIELD_RAW_RECORD_WORDS = 64   # csrc/field_raw.hpp: 8 operands x 8 words
+_field_raw_ops = None
+
+
+def field_raw_ops():
+    """The operations of zkr_selftest_fp as csrc/field_raw_ops.def lists them -- the file the C++ header includes -- as a dict
+    name -> (number, operands read, result words)."""
+    global _field_raw_ops
+    if _field_raw_ops is None:
+        import re
+        rows = re.findall(r"^ZKR_FIELD_RAW_OP\((\d+),\s*(\w+),\s*(\d+),\s*(\d+)\)", open(FIELD_RAW_OPS_FILE).read(), flags=re.M)
+        if not rows or sorted(int(r[0]) for r in rows) != list(range(len(rows))):
+            raise ValueError("%s does not number its operations 0 .. n - 1" % FIELD_RAW_OPS_FILE)
+        _field_raw_ops = {name: (int(num), int(operands), int(out_words)) for num, name, operands, out_words in rows}
+    return _field_raw_ops
+
+
+def selftest_fp(field, op, records, device=0):
+    """zkr_selftest_fp: records = n x 256 bytes (or n x 64 uint32 words as a ctypes array or a sequence): 8 operands of 8 words,
+    least significant first; op = a number or a name of field_raw_ops().  Returns the result words of every record as bytes (32 per
+    record, 64 for the Fq2 ops) as the device computes csrc/field.hpp on these raw limbs."""
+    ops = field_raw_ops()
+    num, _, ow = ops[op] if isinstance(op, str) else next((v for v in ops.values() if v[0] == op), (op, 0, 8))
+    if isinstance(records, (bytes, bytearray, memoryview)):
+        if len(records) % (4 * FIELD_RAW_RECORD_WORDS):
+            raise ValueError("records are not a whole number of %d-byte records" % (4 * FIELD_RAW_RECORD_WORDS))
+        flat = (ctypes.c_uint32 * max(1, len(records) // 4)).from_buffer_copy(bytes(records) or bytes(4))
+        n = len(records) // (4 * FIELD_RAW_RECORD_WORDS)
+    else:
+        if len(records) % FIELD_RAW_RECORD_WORDS:
+            raise ValueError("records are not a whole number of %d-word records" % FIELD_RAW_RECORD_WORDS)
+        flat = records if isinstance(records, ctypes.Array) else (ctypes.c_uint32 * max(1, len(records)))(*records)
+        n = len(records) // FIELD_RAW_RECORD_WORDS
+    out = (ctypes.c_uint32 * max(1, ow * n))()
+    _check(lib().zkr_selftest_fp(device, field, num, flat, n, out))
+    return bytes(out)[:4 * ow * n]
 
 
 def bench_fq_mul(device=0, legacy=False) -> float:

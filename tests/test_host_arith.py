@@ -1,5 +1,12 @@
-"""CPU: the DEVICE field/curve templates (csrc/field.hpp, curve.hpp) compiled for the host agree with
-the oracle -- the same source the gfx950 kernels inline."""
+"""CPU: the field/curve templates (csrc/field.hpp, curve.hpp) compiled for the HOST agree with the oracle.
+
+Most of that source is what the gfx950 kernels inline, but not the products of the 8 x 32-bit-limb field: field.hpp chooses by
+__HIP_DEVICE_COMPILE__.  Here mul (and so sqr, to_mont, from_mont, inv) is mul_host64, mul_sum2 / mul_sum4 add separate products,
+the Fq2 product is Karatsuba and both mul_sub go through those; on the device mul scans product columns in a 96-bit accumulator
+(the mac96* asm statements), mul_sum2 / mul_sum4 are one fused scan (field_fused.hpp), the Fq2 product is schoolbook through
+mul_sum2 and both mul_sub run the fused sums with negated operands.  zkt_fp and zkt_fq2 below test the host's side of these
+only; tests/test_field_raw_cpu.py and tests/test_gpu_field_raw.py run one function (field_raw.hpp) in both builds on raw edge limbs
+against integers.  The 29-bit-limb arithmetic further down has its own device hooks (tests/test_gpu_stages.py, test_gpu_group_law.py)."""
 import ctypes
 import os
 import random
