@@ -821,6 +821,91 @@ int zkr_ledger_release(zkr_ledger *l, uint64_t id);
 int zkr_ledger_journal_info(const zkr_ledger *l, uint64_t out[2]);
 int zkr_ledger_audit(zkr_ledger *l, uint64_t report[2], int *sound);
 
+/* ---- the ledger's book: the contract's side of the ledger, by public key (csrc/zkr_book.hip).  RollUp.sol addresses
+ * accounts by hashPair(publicKey) and keeps what goes with that -- balanceTreeUsers / isPublicKeysRegistered (RollUp.sol:56-57),
+ * usedNullifiers (:58), accuredFees (:63).  zkr_ledger_deposit takes the EVENT the contract emits after that work; a book takes the
+ * CALLS.  A ledger without an open book behaves and launches exactly as before.  No CPU fallback (ZKR_ERR_NO_DEVICE); every
+ * by-key call on a ledger with no open book is ZKR_ERR_ARG; argument checks run before the device is looked at; n is at most
+ * 2^22 per call and n = 0 is an empty result.  All device work runs under the ledger's lock and every call returns synchronised.
+ * On any error return the ledger and the book are unchanged.
+ *
+ * State, all on the ledger's device.  Key table: hashPair(pubX, pubY) of every record (one MiMCSponge multiHash of two elements
+ * per account) and an open-addressing table of 2^(depth+1) slots over them (load factor at most 1/2), built from the ledger's
+ * RECORDS and nothing else; where two accounts hold one key (the contract cannot produce that, zkr_ledger_deposit can) the lowest
+ * index owns it.  zkr_ledger_deposit on a ledger with an open book marks the table stale when it writes a key that differs from
+ * the stored one or inserts an account, zkr_ledger_rollback marks both tables stale; a stale table is rebuilt at the next by-key
+ * call.  zkr_ledger_sequence and the replays never move keys.  Nullifier set: the nullifiers in acceptance order and a slot table
+ * of 2^nullifier_cap_log2 slots (default 10, at least 2) that doubles before count + inserts would pass half of it; a slot is
+ * chosen by a 64-bit mix of all eight words with `salt` (0: drawn from the OS CSPRNG), since users choose their nullifiers.
+ * Fees: a 256-bit counter of the `fee` signal of every transaction zkr_ledger_sequence and the replays apply while the book is
+ * open (RollUp.sol:139), modulo 2^256 as the contract's uint256.
+ *
+ * zkr_ledger_book_open: blob NULL = an empty set and zero fees, else a ZKRBOOK1 blob (below); zkr_book_blob_check's refusals are
+ * ZKR_ERR_ARG, before the device; a blob that holds one nullifier twice is ZKR_ERR_BAD_KEY.  A second open is ZKR_ERR_ARG.
+ * zkr_ledger_book_info: out = distinct keys, nullifiers, nullifier table slots, key-table builds so far (the open counts).
+ *
+ * zkr_ledger_deposit_calls = deposit(publicKeyX, publicKeyY) payable (RollUp.sol:255-297) for a list of calls, in order.  pubs:
+ * n x 64 B, values (msg.value): n x 32 B, standard form.  status[i] is the first of
+ *    1  a key element not below r, or a value not below 2^250       2  the key is new and the tree is full
+ *    3  the new balance would not stay below 2^250                   0  applied
+ * A refused call is a revert: the following calls go on.  A new key gets the index `accounts so far` (RollUp.sol:279) and nonce
+ * 0; a later call of the same list with that key adds to the new account.  indices[i] (may be NULL) = balanceTreeLeafIndex of an
+ * applied call, 0xFFFFFFFF of a refused one; events (may be NULL): n x 128 B, pubX pubY balance nonce of the Deposit event
+ * (:290-296), zeros for a refused call.
+ *
+ * zkr_ledger_withdraw_calls = withdraw (RollUp.sol:212-253), or withdrawAll (:193-210) for every call when amounts is NULL.
+ * publics: n x 96 B, the public signals publicKey[0] publicKey[1] nullifier; amounts: n x 32 B (any 256-bit number);
+ * proof_verdicts: NULL or n bytes as zkr_verify_each returns them.  verdicts[i] is the first of
+ *    1  an element of the public signals not below r (the verifier's require)
+ *    2  the nullifier is used: in the set, or carried by an EARLIER call of this list that was applied (:224)
+ *    3  proof_verdicts[i] != 0 (:229)                                4  the key is not registered
+ *    5  amount above the balance (:237)                              6  withdrawAll with a zero balance (:205)
+ *    0  applied: the balance goes down, the nullifier goes into the set, the Withdraw event (:246-252) is in events / indices
+ * A refused call spends nothing: its nullifier stays free for a later call of the same list.
+ * Deliberate differences from the contract: verdict 4 -- the contract would read a zero User and, with amount 0, emit an event
+ * for leaf 0 under a foreign key; the codes are tried in the order of this table, so withdrawAll's balance check (:205) comes
+ * after the others, which changes which refusal is named and never whether a call is applied; and the leaf IS updated, as the
+ * operator's pubsub.ts:19-66 does on the event -- the contract itself never updates its tree in withdraw.
+ * zkr_ledger_withdraw_calls_device: the signals are words 1..3 of n witnesses in device memory (d_witnesses_std: a host array of
+ * device pointers, the convention of zkr_verify_each_device); the kernels run on `stream`.
+ *
+ * zkr_ledger_lookup_keys: indices[i] = the account that owns key i (isPublicKeyRegistered / getUserData, RollUp.sol:164-191),
+ * 0xFFFFFFFF = not registered.  zkr_ledger_nullifiers_used: used[i] = usedNullifiers[nullifier i] (:58, :224).
+ * zkr_ledger_fees = getAccuredFees (:299-301); reset != 0 also zeroes the counter, as withdrawAccuredFees does (:303-309), and
+ * is ZKR_ERR_ARG while a checkpoint is open.  zkr_ledger_rollback restores the account count, the nullifier count and the fee
+ * counter as at the checkpoint.
+ *
+ * Blob "ZKRBOOK1", 128 + 32 x count bytes, integers little-endian:
+ *     0  "ZKRBOOK1"     8  u64 count     16  48 B zero     64  fees (32 B)
+ *    96  tag = zkr_mimcsponge_multihash(count, fees mod 2^128, fees div 2^128)      128  the nullifiers in acceptance order
+ * The ZKRLEDG1 snapshot does not change; a snapshot and a blob taken together resume a ledger with its book.
+ * zkr_book_blob_check (host only): magic, reserved bytes, length, tag, every nullifier below r; *valid = 0 comes with ZKR_OK and
+ * a zkr_last_error line naming the first failure; info = count, byte length.  The Node binding does not carry the book. ---- */
+typedef struct { uint32_t nullifier_cap_log2; uint32_t reserved; uint64_t salt; } zkr_book_opts; /* NULL or zeros = defaults */
+int zkr_ledger_book_open(zkr_ledger *l, const zkr_book_opts *opts, const void *blob, size_t blob_len);
+int zkr_ledger_book_info(const zkr_ledger *l, uint64_t out[4]);
+int zkr_ledger_deposit_calls(zkr_ledger *l, const uint8_t *pubs, const uint8_t *values, size_t n, uint8_t *status, uint32_t *indices,
+                             uint8_t *events);
+int zkr_ledger_withdraw_calls(zkr_ledger *l, const uint8_t *publics, const uint8_t *amounts, const uint8_t *proof_verdicts, size_t n,
+                              uint8_t *verdicts, uint32_t *indices, uint8_t *events);
+int zkr_ledger_withdraw_calls_device(zkr_ledger *l, const void *const *d_witnesses_std, const uint8_t *amounts,
+                                     const uint8_t *proof_verdicts, size_t n, uint8_t *verdicts, uint32_t *indices, uint8_t *events,
+                                     void *stream);
+int zkr_ledger_lookup_keys(zkr_ledger *l, const uint8_t *pubs, size_t n, uint32_t *indices);
+int zkr_ledger_nullifiers_used(zkr_ledger *l, const uint8_t *nullifiers, size_t n, uint8_t *used);
+int zkr_ledger_fees(const zkr_ledger *l, uint8_t fees[32], int reset);
+int zkr_ledger_book_blob(const zkr_ledger *l, void **blob, size_t *len); /* malloc'ed, free with zkr_free */
+int zkr_book_blob_check(const void *blob, size_t len, uint64_t info[2], int *valid);
+/* Test hooks, host only, as zkr_sequence_plan_host is: the host pass alone over records = n_accounts x 128 B.  resolved: n x 3
+ * words per call as the resolve kernel leaves them -- flags (1 pubX below r, 2 pubY below r, 4 nullifier below r, 8 nullifier in
+ * the set), the key's account or 0xFFFFFFFF, the call's leader: the lowest list position with the same key (deposits) or the
+ * same nullifier (withdrawals).  ZKR_ERR_ARG when `resolved` cannot be true of these records and this list. */
+int zkr_book_deposit_plan_host(unsigned depth, const uint8_t *records, size_t n_accounts, const uint8_t *pubs, const uint8_t *values,
+                               size_t n, const uint32_t *resolved, uint8_t *status, uint32_t *indices, uint8_t *events);
+int zkr_book_withdraw_plan_host(const uint8_t *records, size_t n_accounts, const uint8_t *publics, const uint8_t *amounts,
+                                const uint8_t *proof_verdicts, size_t n, const uint32_t *resolved, uint8_t *verdicts,
+                                uint32_t *indices, uint8_t *events);
+
 /* Integer-ALU microbenchmark: sustained Fq Montgomery multiplications per second on `device` with the multiplier of the
  * hot path (9 x 29-bit limbs, 162 multiply-adds without carry words, csrc/field29.hpp); used for the secondary (VALU)
  * roofline.  _legacy: the 8 x 32-bit multiplier of csrc/field.hpp (136 multiply-adds + 136 carry additions), kept for

@@ -1,0 +1,115 @@
+// ledger_internal.hpp -- what the ledger's two HIP units share: zkr_sequencer.hip (queue to batches, replay, keeping the state) and
+// zkr_book.hip (the contract's key-addressed side).  The ledger handle, its arena, the view a storing call leaves in
+// device memory, and the steps of the one storing path -- hashes, journal, store -- which stay where their kernels are, in
+// zkr_sequencer.hip (no relocatable device code in this build: a kernel is launched from the unit that holds it).
+#pragma once
+#include <stdlib.h>
+#include <chrono>
+#include <mutex>
+#include <vector>
+#include "zkr_internal.hpp"
+#include "sequencer_plan.hpp"
+#include "ledger_state.hpp"
+
+namespace zkr {
+
+__host__ __device__ static inline size_t seq_level_offset(uint32_t depth, uint32_t l) {  // leaves first, root last (zkr_balance_tree_build's order)
+  return ((size_t)2 << depth) - ((size_t)2 << (depth - l));
+}
+struct SeqView {  // what one call left in device memory; U = 2T updates
+  const Fr *txs;        // T x 8, the applied transactions
+  const Fr *old_rec;    // U x 4
+  const Fr *val;        // (depth + 1) rows of `stride`, the first U of each in use
+  const uint32_t *idx;  // U
+  const int32_t *prev;  // 3 x depth x U (sequencer_plan.hpp seq_tables)
+  const Fr *tree;       // the ledger's stored tree, before this call
+  size_t U, stride;     // stride > U: a prefix of the updates that were hashed (a replay that stops at a refused batch)
+  uint32_t depth, batch;
+};
+
+static inline unsigned blocks(size_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
+
+struct DevArena {  // one allocation per ledger, only ever grown; cut into aligned pieces per call
+  char *p = nullptr;
+  size_t cap = 0, at = 0;
+  int reserve(size_t bytes) {
+    at = 0;
+    if (bytes <= cap) return ZKR_OK;
+    if (p) hipFree(p);
+    p = nullptr, cap = 0;
+    ZKR_HIP_CHECK(hipMalloc((void **)&p, bytes + bytes / 2));
+    cap = bytes + bytes / 2;
+    return ZKR_OK;
+  }
+  static size_t padded(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+  template <class T> T *take(size_t count) {
+    T *r = reinterpret_cast<T *>(p + at);
+    at += padded(count * sizeof(T));
+    return r;
+  }
+};
+
+// The book of a ledger (zkr_book.hip): the contract's key-addressed state beside the tree.  Everything a d_ pointer
+// names lives on the ledger's device and goes with the ledger.
+struct LedgerBook {
+  // key table: d_keyhash[i] = hashPair(pubX, pubY) of record i; d_keytab holds index + 1 in 2^(depth + 1) slots, 0 = empty
+  Fr *d_keyhash = nullptr;
+  uint32_t *d_keytab = nullptr;
+  bool keys_stale = true;
+  uint64_t distinct = 0, rebuilds = 0;
+  // nullifier set: d_null[0 .. null_count) in acceptance order; d_nulltab holds position + 1 in null_cap slots
+  Fr *d_null = nullptr;
+  uint32_t *d_nulltab = nullptr;
+  size_t null_count = 0, null_room = 0, null_cap = 0;  // room: entries d_null has memory for
+  bool null_stale = false;
+  uint64_t salt = 0;
+  Int256 fees = {{0, 0, 0, 0}};  // accuredFees (RollUp.sol:139)
+};
+}  // namespace zkr
+
+struct zkr_ledger {
+  unsigned depth = 0;
+  int device = 0;
+  size_t accounts = 0;
+  uint64_t applied = 0, batches = 0;
+  std::vector<uint8_t> records;  // accounts x 128 B
+  zkr::Fr *d_tree = nullptr;     // (2^(depth + 1) - 1) nodes, standard form, leaves first
+  zkr::DevArena arena;
+  double stage_ms[5] = {0, 0, 0, 0, 0};
+  mutable std::mutex mu;
+  // keeping the ledger
+  std::vector<uint8_t> empty;    // (depth + 1) x 32 B: the value of an empty subtree per level
+  zkr::LedgerJournal journal;    // checkpoints and what every storing call under them overwrote, host part
+  uint32_t *d_joff = nullptr;    // the journal's device part: node offsets ...
+  zkr::Fr *d_jold = nullptr;     // ... and old values, jcap entries each, the first journal.nodes() in use
+  uint32_t *d_jcount = nullptr;
+  size_t jcap = 0;
+  // the contract's side: null until zkr_ledger_book_open
+  zkr::LedgerBook *book = nullptr;
+};
+
+namespace zkr {
+struct StageClock {  // wall time per stage, only when ZKR_SEQUENCER_STAGES is set: every mark waits for the stream
+  bool on;
+  hipStream_t s;
+  std::chrono::steady_clock::time_point t0;
+  StageClock(hipStream_t stream) : on(getenv("ZKR_SEQUENCER_STAGES") != nullptr), s(stream), t0(std::chrono::steady_clock::now()) {}
+  void mark(double &slot) {
+    if (!on) return;
+    hipStreamSynchronize(s);
+    const auto t1 = std::chrono::steady_clock::now();
+    slot = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    t0 = t1;
+  }
+};
+
+// zkr_sequencer.hip
+int hash_updates(const zkr_ledger *L, size_t U, const Fr *d_new, const uint32_t *d_idx, const int32_t *d_prev, Fr *d_val, hipStream_t s, StageClock &clk, double *ms);
+int journal_before_store(zkr_ledger *l, const SeqView &v, const int32_t *last, const uint32_t *idx, hipStream_t s, JournalCall *out);
+int need_device(int device, const char *what);
+// The storing path of zkr_ledger_deposit for a checked update list, under the ledger's lock: tables, hashes, journal, store,
+// records.  `accounts` is the account count the list leaves.  On an error return the ledger is unchanged.
+int ledger_apply_updates(zkr_ledger *l, const uint32_t *indices, const uint8_t *records, size_t n, size_t accounts);
+// zkr_book.hip
+void book_free(zkr_ledger *l);
+}  // namespace zkr

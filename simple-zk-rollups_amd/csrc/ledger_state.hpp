@@ -33,6 +33,10 @@ struct JournalCall {
   uint64_t applied_before = 0, batches_before = 0;
   std::vector<uint32_t> rec_idx;  // overwritten records that existed before the call ...
   std::vector<uint8_t> rec_old;   // ... and what they held, 128 B each
+  // with a book open: the nullifier count and the fee counter before the call
+  bool has_book = false;
+  size_t nullifiers_before = 0;
+  uint64_t fees_before[4] = {0, 0, 0, 0};
 };
 struct JournalMarker {
   uint64_t id;

@@ -1,5 +1,6 @@
 // mimc_device.hpp -- MiMCSponge-220 for one GPU thread per hash, shared by the translation units that hash on the device
-// (rollup_gpu.hip: the batch hash and the tree build; zkr_sequencer.hip: signatures, leaves and the versioned tree levels).
+// (rollup_gpu.hip: the batch hash and the tree build; zkr_sequencer.hip: signatures, leaves and the versioned tree levels;
+// zkr_book.hip: hashPair of public keys).
 // The permutation of /root/reference/operator/src/utils/crypto.ts:28-38 `multiHash` (prover/circuits/hasher.circom:3-30): 220
 // rounds of x -> x^5 in Fr Montgomery arithmetic, key 0.  The round constants live in __constant__ memory, one copy per
 // translation unit that includes this header (no relocatable device code in this build); upload_mimc_constants fills this

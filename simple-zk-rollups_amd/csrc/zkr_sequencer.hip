@@ -30,6 +30,7 @@
 #include "mimc_device.hpp"
 #include "sequencer_plan.hpp"
 #include "ledger_state.hpp"
+#include "ledger_internal.hpp"
 
 namespace zkr {
 void rollup_device_constants(Fr *a, Fr *d, uint32_t suborder_m1[8], Fr *b8x253, Fr *b8y253);  // rollup.cpp
@@ -189,19 +190,6 @@ static __global__ __launch_bounds__(64) void seq_level_kernel(const Fr *val_l, F
 }
 
 // ------------------------------------------------------------------------------------------------ e. assembly
-__host__ __device__ static inline size_t seq_level_offset(uint32_t depth, uint32_t l) {  // leaves first, root last (zkr_balance_tree_build's order)
-  return ((size_t)2 << depth) - ((size_t)2 << (depth - l));
-}
-struct SeqView {  // what one call left in device memory; U = 2T updates
-  const Fr *txs;        // T x 8, the applied transactions
-  const Fr *old_rec;    // U x 4
-  const Fr *val;        // (depth + 1) rows of `stride`, the first U of each in use
-  const uint32_t *idx;  // U
-  const int32_t *prev;  // 3 x depth x U (sequencer_plan.hpp seq_tables)
-  const Fr *tree;       // the ledger's stored tree, before this call
-  size_t U, stride;     // stride > U: a prefix of the updates that were hashed (a replay that stops at a refused batch)
-  uint32_t depth, batch;
-};
 // Input signal `rem` of a batch (0 .. batch * (18 + 3 * depth) - 1, circom's order: every input array flattened over the batch,
 // rollup_witness.hpp tx_layout, batchprocesstx.circom:13-36) -> its field, the element within the field and the transaction
 // within the batch.  The one copy of the width table: 1 8 2 1 1 depth 2 1 1 depth 1 depth.
@@ -368,64 +356,6 @@ static SigConsts sig_consts() {
   }();
   return k;
 }
-static inline unsigned blocks(size_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
-
-struct DevArena {  // one allocation per ledger, only ever grown; cut into aligned pieces per call
-  char *p = nullptr;
-  size_t cap = 0, at = 0;
-  int reserve(size_t bytes) {
-    at = 0;
-    if (bytes <= cap) return ZKR_OK;
-    if (p) hipFree(p);
-    p = nullptr, cap = 0;
-    ZKR_HIP_CHECK(hipMalloc((void **)&p, bytes + bytes / 2));
-    cap = bytes + bytes / 2;
-    return ZKR_OK;
-  }
-  static size_t padded(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-  template <class T> T *take(size_t count) {
-    T *r = reinterpret_cast<T *>(p + at);
-    at += padded(count * sizeof(T));
-    return r;
-  }
-};
-}  // namespace zkr
-
-using namespace zkr;
-
-struct zkr_ledger {
-  unsigned depth = 0;
-  int device = 0;
-  size_t accounts = 0;
-  uint64_t applied = 0, batches = 0;
-  std::vector<uint8_t> records;  // accounts x 128 B
-  Fr *d_tree = nullptr;          // (2^(depth + 1) - 1) nodes, standard form, leaves first
-  DevArena arena;
-  double stage_ms[5] = {0, 0, 0, 0, 0};
-  mutable std::mutex mu;
-  // keeping the ledger
-  std::vector<uint8_t> empty;  // (depth + 1) x 32 B: the value of an empty subtree per level
-  LedgerJournal journal;       // checkpoints and what every storing call under them overwrote, host part
-  uint32_t *d_joff = nullptr;  // the journal's device part: node offsets ...
-  Fr *d_jold = nullptr;        // ... and old values, jcap entries each, the first journal.nodes() in use
-  uint32_t *d_jcount = nullptr;
-  size_t jcap = 0;
-};
-
-namespace {
-struct StageClock {  // wall time per stage, only when ZKR_SEQUENCER_STAGES is set: every mark waits for the stream
-  bool on;
-  hipStream_t s;
-  std::chrono::steady_clock::time_point t0;
-  StageClock(hipStream_t stream) : on(getenv("ZKR_SEQUENCER_STAGES") != nullptr), s(stream), t0(std::chrono::steady_clock::now()) {}
-  void mark(double &slot) {
-    if (!on) return;
-    hipStreamSynchronize(s);
-    const auto t1 = std::chrono::steady_clock::now();
-    slot = std::chrono::duration<double, std::milli>(t1 - t0).count();
-    t0 = t1;
-  }
-};
 
 // Steps c and d for U leaf updates whose records, leaf indices and tables are already in the arena: val[0] from the records, then
 // level by level.  Every index the kernels follow was bounded on the host: idx[u] < accounts <= 2^depth, -1 <= prev[l][u] < u.
@@ -482,8 +412,17 @@ int journal_before_store(zkr_ledger *l, const SeqView &v, const int32_t *last, c
   ZKR_HIP_CHECK(hipStreamSynchronize(s));
   if (written != count) { set_error("internal: the journal holds %u nodes of a call whose tables name %zu", written, count); return ZKR_ERR_HIP; }
   *out = l->journal.record_call(idx, U, l->records, l->accounts, l->applied, l->batches, count);
+  if (l->book) {  // what a rollback puts back beside the tree
+    out->has_book = true, out->nullifiers_before = l->book->null_count;
+    memcpy(out->fees_before, l->book->fees.w, 32);
+  }
   return ZKR_OK;
 }
+}  // namespace zkr
+
+using namespace zkr;
+
+namespace {
 
 // The bulk build of a restore: L->records and L->accounts are set and checked, the tree is the empty one of zkr_ledger_new.
 // Leaf hashes straight into level 0, then one launch per level over the nodes whose subtree holds an account: no tables, no
@@ -657,6 +596,8 @@ int replay(zkr_ledger *l, const uint8_t *publics, const void *const *d_witnesses
     if (journalled) l->journal.calls.push_back(std::move(jc));
     for (size_t u = 0; u < Ub; u++) memcpy(l->records.data() + (size_t)plan.idx[u] * 128, &h_new[u * 128], 128);
     l->applied += B * batch, l->batches += B;
+    if (l->book)  // accuredFees += fee (RollUp.sol:139): signal 1 + batch + 8k + 3 of every applied batch
+      for (size_t t = 0; t < B * batch; t++) l->book->fees = int256_add(l->book->fees, int256_load(publics + ((t / batch) * n_public + 1 + batch + 8 * (t % batch) + 3) * 32));
   }
   clk.mark(ms[4]);
   for (size_t b = 0; b < n_batches; b++) {
@@ -668,6 +609,43 @@ int replay(zkr_ledger *l, const uint8_t *publics, const void *const *d_witnesses
   return ZKR_OK;
 }
 }  // namespace
+
+namespace zkr {
+int ledger_apply_updates(zkr_ledger *l, const uint32_t *indices, const uint8_t *records, size_t n, size_t accounts) {
+  ZKR_HIP_CHECK(hipSetDevice(l->device));
+  const unsigned depth = l->depth;
+  const size_t U = n;
+  std::vector<uint32_t> idx(indices, indices + n);
+  std::vector<int32_t> prev(3 * (size_t)depth * U);
+  seq_tables(depth, idx, nullptr, accounts, prev.data());
+  int rc = l->arena.reserve(DevArena::padded(U * 128) + DevArena::padded(U * 4) + DevArena::padded(prev.size() * 4) + DevArena::padded(((size_t)depth + 1) * U * 32));
+  if (rc) return rc;
+  Fr *d_new = l->arena.take<Fr>(4 * U), *d_val = l->arena.take<Fr>(((size_t)depth + 1) * U);
+  uint32_t *d_idx = l->arena.take<uint32_t>(U);
+  int32_t *d_prev = l->arena.take<int32_t>(prev.size());
+  hipStream_t s = nullptr;
+  ZKR_HIP_CHECK(hipMemcpyAsync(d_new, records, U * 128, hipMemcpyHostToDevice, s));
+  ZKR_HIP_CHECK(hipMemcpyAsync(d_idx, idx.data(), U * 4, hipMemcpyHostToDevice, s));
+  ZKR_HIP_CHECK(hipMemcpyAsync(d_prev, prev.data(), prev.size() * 4, hipMemcpyHostToDevice, s));
+  StageClock clk(s);
+  clk.on = false;
+  double unused[5];
+  if ((rc = hash_updates(l, U, d_new, d_idx, d_prev, d_val, s, clk, unused))) return rc;
+  ZKR_HIP_CHECK(hipStreamSynchronize(s));  // the tree is untouched up to here: a failure above leaves the ledger as it was
+  SeqView v{nullptr, nullptr, d_val, d_idx, d_prev, l->d_tree, U, U, depth, 1};
+  JournalCall jc;
+  const bool journalled = l->journal.open();
+  if (journalled && (rc = journal_before_store(l, v, prev.data() + 2 * (size_t)depth * U, indices, s, &jc))) return rc;
+  seq_store_kernel<<<blocks(((size_t)depth + 1) * U, 256), 256, 0, s>>>(v, l->d_tree);
+  ZKR_HIP_CHECK(hipGetLastError());
+  ZKR_HIP_CHECK(hipStreamSynchronize(s));
+  if (journalled) l->journal.calls.push_back(std::move(jc));
+  l->records.resize(accounts * 128);
+  for (size_t i = 0; i < n; i++) memcpy(l->records.data() + (size_t)indices[i] * 128, records + i * 128, 128);
+  l->accounts = accounts;
+  return ZKR_OK;
+}
+}  // namespace zkr
 
 extern "C" {
 
@@ -709,7 +687,9 @@ void zkr_ledger_free(zkr_ledger *l) {
     if (l->d_joff) hipFree(l->d_joff);
     if (l->d_jold) hipFree(l->d_jold);
     if (l->d_jcount) hipFree(l->d_jcount);
+    book_free(l);
   }
+  delete l->book;
   delete l;
 }
 
@@ -767,38 +747,10 @@ int zkr_ledger_deposit(zkr_ledger *l, const uint32_t *indices, const uint8_t *re
       }
     }
   }
-  ZKR_HIP_CHECK(hipSetDevice(l->device));
-  const unsigned depth = l->depth;
-  const size_t U = n;
-  std::vector<uint32_t> idx(indices, indices + n);
-  std::vector<int32_t> prev(3 * (size_t)depth * U);
-  seq_tables(depth, idx, nullptr, accounts, prev.data());
-  int rc = l->arena.reserve(DevArena::padded(U * 128) + DevArena::padded(U * 4) + DevArena::padded(prev.size() * 4) + DevArena::padded(((size_t)depth + 1) * U * 32));
-  if (rc) return rc;
-  Fr *d_new = l->arena.take<Fr>(4 * U), *d_val = l->arena.take<Fr>(((size_t)depth + 1) * U);
-  uint32_t *d_idx = l->arena.take<uint32_t>(U);
-  int32_t *d_prev = l->arena.take<int32_t>(prev.size());
-  hipStream_t s = nullptr;
-  ZKR_HIP_CHECK(hipMemcpyAsync(d_new, records, U * 128, hipMemcpyHostToDevice, s));
-  ZKR_HIP_CHECK(hipMemcpyAsync(d_idx, idx.data(), U * 4, hipMemcpyHostToDevice, s));
-  ZKR_HIP_CHECK(hipMemcpyAsync(d_prev, prev.data(), prev.size() * 4, hipMemcpyHostToDevice, s));
-  StageClock clk(s);
-  clk.on = false;
-  double unused[5];
-  if ((rc = hash_updates(l, U, d_new, d_idx, d_prev, d_val, s, clk, unused))) return rc;
-  ZKR_HIP_CHECK(hipStreamSynchronize(s));  // the tree is untouched up to here: a failure above leaves the ledger as it was
-  SeqView v{nullptr, nullptr, d_val, d_idx, d_prev, l->d_tree, U, U, depth, 1};
-  JournalCall jc;
-  const bool journalled = l->journal.open();
-  if (journalled && (rc = journal_before_store(l, v, prev.data() + 2 * (size_t)depth * U, indices, s, &jc))) return rc;
-  seq_store_kernel<<<blocks(((size_t)depth + 1) * U, 256), 256, 0, s>>>(v, l->d_tree);
-  ZKR_HIP_CHECK(hipGetLastError());
-  ZKR_HIP_CHECK(hipStreamSynchronize(s));
-  if (journalled) l->journal.calls.push_back(std::move(jc));
-  l->records.resize(accounts * 128);
-  for (size_t i = 0; i < n; i++) memcpy(l->records.data() + (size_t)indices[i] * 128, records + i * 128, 128);
-  l->accounts = accounts;
-  return ZKR_OK;
+  if (l->book)  // a key written where another one stood, or a new account: the key table no longer says what the records say
+    for (size_t i = 0; i < n && !l->book->keys_stale; i++)
+      if (indices[i] >= l->accounts || memcmp(l->records.data() + (size_t)indices[i] * 128, records + i * 128, 64)) l->book->keys_stale = true;
+  return ledger_apply_updates(l, indices, records, n, accounts);
 }
 
 int zkr_eddsa_verify_batch(const uint8_t *msgs, unsigned arity, const uint8_t *sigs, const uint8_t *pubs, size_t n, uint8_t *verdicts, int device) {
@@ -901,6 +853,8 @@ int zkr_ledger_sequence(zkr_ledger *l, const uint8_t *txs, size_t n_txs, uint32_
     clk.mark(ms[4]);
     for (size_t u = 0; u < U; u++) memcpy(l->records.data() + (size_t)plan.idx[u] * 128, &h_new[u * 128], 128);
     l->applied += T, l->batches += nb;
+    if (l->book)  // accuredFees += fee (RollUp.sol:139)
+      for (size_t k = 0; k < T; k++) l->book->fees = int256_add(l->book->fees, int256_load(&h_txs[k * 256 + 96]));
     *n_batches = nb;
   }
   memcpy(status, plan.status.data(), n_txs);
@@ -1049,7 +1003,11 @@ int zkr_ledger_rollback(zkr_ledger *l, uint64_t id) {
       ZKR_HIP_CHECK(hipGetLastError());
     }
     ZKR_HIP_CHECK(hipDeviceSynchronize());
-    for (size_t c = calls.size(); c-- > (size_t)keep;) LedgerJournal::undo_host(calls[c], l->records, l->accounts, l->applied, l->batches);
+    for (size_t c = calls.size(); c-- > (size_t)keep;) {
+      LedgerJournal::undo_host(calls[c], l->records, l->accounts, l->applied, l->batches);
+      if (l->book && calls[c].has_book) l->book->null_count = calls[c].nullifiers_before, memcpy(l->book->fees.w, calls[c].fees_before, 32);
+    }
+    if (l->book) l->book->keys_stale = l->book->null_stale = true;  // both tables may name what is gone: rebuilt at the next by-key call
   }
   l->journal.rollback_done(id);
   return ZKR_OK;

@@ -16,6 +16,10 @@ STAGES = ("ingest", "spmv", "ntt", "msm_sort", "msm_accum_g1", "msm_accum_g2", "
 _lib = None
 
 
+class BookOpts(ctypes.Structure):   # zkr.h zkr_book_opts
+    _fields_ = [("nullifier_cap_log2", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("salt", ctypes.c_uint64)]
+
+
 class ZkrError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("zkr error %d: %s" % (code, msg))
@@ -184,6 +188,19 @@ def lib():
     L.zkr_ledger_release.argtypes = [vp, c.c_uint64]
     L.zkr_ledger_journal_info.argtypes = [vp, u64p]
     L.zkr_ledger_audit.argtypes = [vp, u64p, c.POINTER(c.c_int)]
+    u32p = c.POINTER(c.c_uint32)
+    L.zkr_ledger_book_open.argtypes = [vp, c.POINTER(BookOpts), u8p, sz]
+    L.zkr_ledger_book_info.argtypes = [vp, u64p]
+    L.zkr_ledger_deposit_calls.argtypes = [vp, u8p, u8p, sz, u8p, u32p, u8p]
+    L.zkr_ledger_withdraw_calls.argtypes = [vp, u8p, u8p, u8p, sz, u8p, u32p, u8p]
+    L.zkr_ledger_withdraw_calls_device.argtypes = [vp, c.POINTER(vp), u8p, u8p, sz, u8p, u32p, u8p, vp]
+    L.zkr_ledger_lookup_keys.argtypes = [vp, u8p, sz, u32p]
+    L.zkr_ledger_nullifiers_used.argtypes = [vp, u8p, sz, u8p]
+    L.zkr_ledger_fees.argtypes = [vp, u8p, i]
+    L.zkr_ledger_book_blob.argtypes = [vp, c.POINTER(vp), c.POINTER(sz)]
+    L.zkr_book_blob_check.argtypes = [u8p, sz, u64p, c.POINTER(c.c_int)]
+    L.zkr_book_deposit_plan_host.argtypes = [c.c_uint, u8p, sz, u8p, u8p, sz, u32p, u8p, u32p, u8p]
+    L.zkr_book_withdraw_plan_host.argtypes = [u8p, sz, u8p, u8p, u8p, sz, u32p, u8p, u32p, u8p]
     _lib = L
     return L
 

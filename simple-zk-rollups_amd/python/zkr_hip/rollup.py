@@ -8,7 +8,7 @@ operator/src/snarks/common.ts:12-21 for `BatchProcessTx(batch, depth)`
 import ctypes
 import os
 
-from .binding import ZkrError, _check, _take, lib
+from .binding import BookOpts, ZkrError, _check, _take, lib
 
 SNARK_FIELD_SIZE = 21888242871839275222246405745257275088548364400416034343698204186575808495617  # crypto.ts:16-18
 TX_INPUT_FIELDS = ("balanceTreeRoot", "txData", "txSenderPublicKey", "txSenderBalance", "txSenderNonce", "txSenderPathElements",
@@ -421,6 +421,131 @@ class Ledger:
         report, sound = (ctypes.c_uint64 * 2)(), ctypes.c_int()
         _check(lib().zkr_ledger_audit(self._h, report, ctypes.byref(sound)))
         return None if sound.value else (report[0], report[1])
+
+
+    # ---- the book: the contract's side, by public key (include/zkr.h)
+    def open_book(self, blob=None, nullifier_cap_log2=None, salt=None):
+        """Opens the ledger's book (zkr_ledger_book_open): the key table over the records, the nullifier set (empty, or the one
+        of a ZKRBOOK1 `blob` from book_blob) and the fee counter.  nullifier_cap_log2: the set's first table size (default 10);
+        salt: the 64-bit value that places nullifiers in their table (default: drawn from the OS)."""
+        opts = BookOpts(int(nullifier_cap_log2 or 0), 0, int(salt or 0))
+        blob = None if blob is None else bytes(blob)
+        _check(lib().zkr_ledger_book_open(self._h, ctypes.byref(opts), blob, len(blob) if blob is not None else 0))
+
+    def book_info(self):
+        out = (ctypes.c_uint64 * 4)()
+        _check(lib().zkr_ledger_book_info(self._h, out))
+        return {"keys": out[0], "nullifiers": out[1], "nullifier_capacity": out[2], "key_table_builds": out[3]}
+
+    @staticmethod
+    def _events(n, codes, indices, events):
+        """One (index, pubX, pubY, balance, nonce) per applied call -- the contract's event -- and None per refused one."""
+        codes = list(codes.raw[:n])
+        return codes, [None if codes[i] else tuple([indices[i]] + _ints(events.raw[128 * i:128 * i + 128])) for i in range(n)]
+
+    def deposit_calls(self, pubs, values):
+        """deposit(publicKeyX, publicKeyY) payable (RollUp.sol:255-297) for a list of calls in order: pubs = (x, y) pairs,
+        values = msg.value each.  -> (status, events): status 0 applied, 1 out of range, 2 tree full, 3 balance past 2^250;
+        events[i] = the Deposit event (index, pubX, pubY, balance, nonce) of an applied call, None of a refused one."""
+        n = len(pubs)
+        if len(values) != n:
+            raise ValueError("%d values for %d deposit calls" % (len(values), n))
+        pb, vb = b"".join(_le(p[0]) + _le(p[1]) for p in pubs), b"".join(_le(v) for v in values)
+        status, idx, ev = ctypes.create_string_buffer(max(n, 1)), (ctypes.c_uint32 * max(n, 1))(), ctypes.create_string_buffer(128 * max(n, 1))
+        _check(lib().zkr_ledger_deposit_calls(self._h, pb, vb, n, status, idx, ev))
+        return self._events(n, status, idx, ev)
+
+    @staticmethod
+    def _withdraw_args(n, amounts, proof_verdicts):
+        if amounts is not None and len(amounts) != n:
+            raise ValueError("%d amounts for %d withdraw calls" % (len(amounts), n))
+        if proof_verdicts is not None and len(proof_verdicts) != n:
+            raise ValueError("%d proof verdicts for %d withdraw calls" % (len(proof_verdicts), n))
+        ab = None if amounts is None else b"".join(int(a).to_bytes(32, "little") for a in amounts)
+        vb = None if proof_verdicts is None else bytes(min(int(v), 255) for v in proof_verdicts)
+        return ab, vb, ctypes.create_string_buffer(max(n, 1)), (ctypes.c_uint32 * max(n, 1))(), ctypes.create_string_buffer(128 * max(n, 1))
+
+    def withdraw_calls(self, publics, amounts=None, proof_verdicts=None):
+        """withdraw (RollUp.sol:212-253) for a list of calls in order, or withdrawAll (:193-210) for every call when amounts is
+        None.  publics = [pubX, pubY, nullifier] per call, proof_verdicts = what VerifyingKey.verify_each returned, or None.
+        -> (verdicts, events): 0 applied, 1 a signal not below r, 2 nullifier used, 3 proof refused, 4 key not registered,
+        5 amount above the balance, 6 withdrawAll of a zero balance; events[i] = the Withdraw event or None."""
+        n = len(publics)
+        ab, vb, verdicts, idx, ev = self._withdraw_args(n, amounts, proof_verdicts)
+        pb = b"".join(_le(p[0]) + _le(p[1]) + _le(p[2]) for p in publics)
+        _check(lib().zkr_ledger_withdraw_calls(self._h, pb, ab, vb, n, verdicts, idx, ev))
+        return self._events(n, verdicts, idx, ev)
+
+    def withdraw_calls_device(self, witness_ptrs, amounts=None, proof_verdicts=None, stream=None):
+        """The same with the signals read in place (zkr_ledger_withdraw_calls_device): witness_ptrs = one device pointer per
+        call, its signals are words 1..3 of that witness -- the convention of VerifyingKey.verify_each_device."""
+        n = len(witness_ptrs)
+        ab, vb, verdicts, idx, ev = self._withdraw_args(n, amounts, proof_verdicts)
+        ptrs = (ctypes.c_void_p * max(n, 1))(*[int(p) for p in witness_ptrs])
+        _check(lib().zkr_ledger_withdraw_calls_device(self._h, ptrs, ab, vb, n, verdicts, idx, ev, stream))
+        return self._events(n, verdicts, idx, ev)
+
+    def index_of(self, pubs):
+        """The account that owns each (x, y) key, None where the key is not registered."""
+        n = len(pubs)
+        out = (ctypes.c_uint32 * max(n, 1))()
+        _check(lib().zkr_ledger_lookup_keys(self._h, b"".join(_le(p[0]) + _le(p[1]) for p in pubs), n, out))
+        return [None if out[i] == 0xFFFFFFFF else out[i] for i in range(n)]
+
+    def nullifiers_used(self, nullifiers):
+        n = len(nullifiers)
+        out = ctypes.create_string_buffer(max(n, 1))
+        _check(lib().zkr_ledger_nullifiers_used(self._h, b"".join(_le(v) for v in nullifiers), n, out))
+        return [bool(v) for v in out.raw[:n]]
+
+    def fees(self, reset=False):
+        """accuredFees (RollUp.sol:139, :299-309): the fees of every transaction applied while the book is open; reset=True
+        also zeroes the counter, as withdrawAccuredFees does."""
+        out = ctypes.create_string_buffer(32)
+        _check(lib().zkr_ledger_fees(self._h, out, 1 if reset else 0))
+        return int.from_bytes(out.raw, "little")
+
+    def book_blob(self) -> bytes:
+        """The ZKRBOOK1 blob of the book: nullifier count, fees, a tag over both, the nullifiers in acceptance order."""
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        _check(lib().zkr_ledger_book_blob(self._h, ctypes.byref(p), ctypes.byref(n)))
+        return _take(p, n.value)
+
+    @staticmethod
+    def book_blob_check(blob):
+        """Host only: ({"nullifiers", "fees"}, None) of a well-formed blob, or (None, the line naming the first failure)."""
+        blob = bytes(blob)
+        info, valid = (ctypes.c_uint64 * 2)(), ctypes.c_int()
+        _check(lib().zkr_book_blob_check(blob, len(blob), info, ctypes.byref(valid)))
+        if not valid.value:
+            return None, lib().zkr_last_error().decode()
+        return {"nullifiers": info[0], "fees": int.from_bytes(blob[64:96], "little")}, None
+
+
+def _resolved_words(resolved):
+    flat = [int(w) for r in resolved for w in r]
+    return (ctypes.c_uint32 * max(1, len(flat)))(*flat)
+
+
+def book_deposit_plan_host(depth, records, pubs, values, resolved):
+    """The host pass of Ledger.deposit_calls without a device (test hook, zkr_book_deposit_plan_host): resolved = (flags, account,
+    leader) per call as include/zkr.h describes them.  -> (status, events) as Ledger.deposit_calls returns them."""
+    n = len(pubs)
+    rb = b"".join(_le(v) for r in records for v in r)
+    status, idx, ev = ctypes.create_string_buffer(max(n, 1)), (ctypes.c_uint32 * max(n, 1))(), ctypes.create_string_buffer(128 * max(n, 1))
+    _check(lib().zkr_book_deposit_plan_host(depth, rb, len(records), b"".join(_le(p[0]) + _le(p[1]) for p in pubs), b"".join(_le(v) for v in values), n,
+                                            _resolved_words(resolved), status, idx, ev))
+    return Ledger._events(n, status, idx, ev)
+
+
+def book_withdraw_plan_host(records, publics, amounts, proof_verdicts, resolved):
+    """The host pass of Ledger.withdraw_calls without a device (test hook, zkr_book_withdraw_plan_host)."""
+    n = len(publics)
+    rb = b"".join(_le(v) for r in records for v in r)
+    ab, vb, verdicts, idx, ev = Ledger._withdraw_args(n, amounts, proof_verdicts)
+    _check(lib().zkr_book_withdraw_plan_host(rb, len(records), b"".join(_le(p[0]) + _le(p[1]) + _le(p[2]) for p in publics), ab, vb, n,
+                                             _resolved_words(resolved), verdicts, idx, ev))
+    return Ledger._events(n, verdicts, idx, ev)
 
 
 class RollupCircuit:
