@@ -1,7 +1,7 @@
 // ledger_internal.hpp -- what the ledger's two HIP units share: zkr_sequencer.hip (queue to batches, replay, keeping the state) and
 // zkr_book.hip (the contract's key-addressed side).  The ledger handle, its arena, the view a storing call leaves in
-// device memory, and the steps of the one storing path -- hashes, journal, store -- which stay where their kernels are, in
-// zkr_sequencer.hip (no relocatable device code in this build: a kernel is launched from the unit that holds it).
+// device memory, and the two steps of the one storing path -- stage_updates, store_updates -- which stay where their kernels are,
+// in zkr_sequencer.hip (no relocatable device code in this build: a kernel is launched from the unit that holds it).
 #pragma once
 #include <stdlib.h>
 #include <chrono>
@@ -103,13 +103,36 @@ struct StageClock {  // wall time per stage, only when ZKR_SEQUENCER_STAGES is s
   }
 };
 
-// zkr_sequencer.hip
-int hash_updates(const zkr_ledger *L, size_t U, const Fr *d_new, const uint32_t *d_idx, const int32_t *d_prev, Fr *d_val, hipStream_t s, StageClock &clk, double *ms);
-int journal_before_store(zkr_ledger *l, const SeqView &v, const int32_t *last, const uint32_t *idx, hipStream_t s, JournalCall *out);
-int need_device(int device, const char *what);
-// The storing path of zkr_ledger_deposit for a checked update list, under the ledger's lock: tables, hashes, journal, store,
-// records.  `accounts` is the account count the list leaves.  On an error return the ledger is unchanged.
+// ---- the storing path (zkr_sequencer.hip), under the ledger's lock: reserve the arena, stage_updates, what the caller derives from
+// the hashes, store_updates, the caller's counters.  "On an error return the ledger is unchanged" is argued in these two steps:
+// nothing before store_updates' first synchronise writes the tree, the journal moves after the store, the records move last.
+struct UpdateList {  // U leaf updates on the host
+  size_t U;
+  const uint32_t *idx;               // U leaf indices
+  const uint8_t *new_rec, *old_rec;  // U x 128 B each; old_rec is null where nothing is derived from it (a deposit)
+  const int32_t *prev;               // 3 x depth x U (seq_tables)
+};
+struct StagedUpdates {  // the same list in the arena, hashed: val[l][u] for l <= depth
+  Fr *d_old, *d_new, *d_val;
+  uint32_t *d_idx;
+  int32_t *d_prev;
+  size_t U;
+  // the view over the first `stored` updates (fewer than U only for a replay that stops early); val keeps the hashed list's rows
+  SeqView view(const zkr_ledger *l, const Fr *txs, uint32_t batch, size_t stored) const {
+    return SeqView{txs, d_old, d_val, d_idx, d_prev, l->d_tree, stored, U, l->depth, batch};
+  }
+};
+size_t update_arena_bytes(size_t U_max, unsigned depth, bool with_old);  // what stage_updates cuts; a caller's reserve adds its own
+// Bounds idx[u] < accounts and, with check_tables, -1 <= prev[l][u] < u (a plan's tables; ledger_apply_updates computes its own and
+// never scanned them: profiles/ledger_refactor.md), cuts the arena, uploads, hashes leaves and levels (stage slots 2, 3).
+int stage_updates(zkr_ledger *l, const UpdateList &in, size_t accounts, bool check_tables, hipStream_t s, StageClock &clk, double *ms, StagedUpdates *out);
+// Synchronises, journals when a checkpoint is open, stores the last versions under v, synchronises, appends the journal's call,
+// marks `slot` (stage slot 4) and copies the records into l->records, which has room for every index.  last = the stored list's
+// table 2 on the host, idx and new_rec its leaf indices and records.  Counters stay with the caller.
+int store_updates(zkr_ledger *l, const SeqView &v, const int32_t *last, const uint32_t *idx, const uint8_t *new_rec, hipStream_t s, StageClock &clk, double &slot);
+// zkr_ledger_deposit behind its argument checks, and how the book applies its update lists; `accounts` = the count the list leaves
 int ledger_apply_updates(zkr_ledger *l, const uint32_t *indices, const uint8_t *records, size_t n, size_t accounts);
+int need_device(int device, const char *what);
 // zkr_book.hip
 void book_free(zkr_ledger *l);
 }  // namespace zkr

@@ -22,12 +22,7 @@ int rollup_check_geometry(uint32_t batch, uint32_t depth);
 static __global__ __launch_bounds__(256) void mimc_multihash_kernel(const Fr *in, size_t count, uint32_t arity, Fr *out) {
   size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= count) return;
-  Fr r = Fr::zero(), c = Fr::zero();
-  for (uint32_t i = 0; i < arity; i++) {
-    r = add(r, load_std_as_mont(in + t * arity + i));
-    mimc_feistel(r, c);
-  }
-  out[t] = from_mont(r);
+  out[t] = from_mont(mimc_hash_std(in + t * arity, arity));
 }
 
 static int upload_constants(int device) { return upload_mimc_constants(device); }

@@ -54,14 +54,32 @@ struct TxB {
   ZKR_HD void fail(uint32_t code);
 };
 ZKR_HD void TxB::fail(uint32_t code) { if (!err) err = code; }
+// BabyJub's group law in projective coordinates, the one copy for device and shared code: the witness programs here and in
+// wallet_program.hpp and the signature kernel of zkr_sequencer.hip (rollup.cpp's pt_add stays apart: the host builder these are
+// tested against).  a, d: the curve's constants, Montgomery.
 struct PtD { Fr x, y, z; };
-ZKR_HDF PtD ptd_add(const TxB &b, const PtD &p, const PtD &q) {  // add-2008-bbjlp, complete on BabyJub (rollup.cpp pt_add)
-  Fr A = mul(p.z, q.z), B = sqr(A), C = mul(p.x, q.x), D = mul(p.y, q.y);
-  Fr E = mul(b.k.d, mul(C, D)), F = sub(B, E), G = add(B, E);
-  Fr x3 = mul(mul(A, F), sub(sub(mul(add(p.x, p.y), add(q.x, q.y)), C), D));
-  Fr y3 = mul(mul(A, G), sub(D, mul(b.k.a, C)));
+// add-2008-bbjlp, complete on BabyJub, for a second point (qx : qy : Z2) with the product A = Z1 Z2 given
+ZKR_HD PtD bj_add_zz(const Fr &a, const Fr &d, const PtD &p, const Fr &qx, const Fr &qy, const Fr &A) {
+  Fr B = sqr(A), C = mul(p.x, qx), D = mul(p.y, qy);
+  Fr E = mul(d, mul(C, D)), F = sub(B, E), G = add(B, E);
+  Fr x3 = mul(mul(A, F), sub(sub(mul(add(p.x, p.y), add(qx, qy)), C), D));
+  Fr y3 = mul(mul(A, G), sub(D, mul(a, C)));
   return PtD{x3, y3, mul(F, G)};
 }
+ZKR_HD PtD bj_add(const Fr &a, const Fr &d, const PtD &p, const PtD &q) { return bj_add_zz(a, d, p, q.x, q.y, mul(p.z, q.z)); }
+// (X : Y : Z) + (x, y): Z2 = 1, one product less
+ZKR_HD PtD bj_add_affine(const Fr &a, const Fr &d, const PtD &p, const Fr &qx, const Fr &qy) { return bj_add_zz(a, d, p, qx, qy, p.z); }
+ZKR_HD PtD bj_dbl(const Fr &a, const PtD &p) {  // dbl-2008-bbjlp
+  Fr B = sqr(add(p.x, p.y)), C = sqr(p.x), D = sqr(p.y), E = mul(a, C), F = add(E, D), H = sqr(p.z);
+  Fr J = sub(F, dbl(H));
+  return PtD{mul(sub(sub(B, C), D), J), mul(F, sub(E, D)), mul(F, J)};
+}
+ZKR_HD bool bj_on_curve(const Fr &a, const Fr &d, const Fr &x, const Fr &y) {  // a x^2 + y^2 = 1 + d x^2 y^2
+  Fr x2 = sqr(x), y2 = sqr(y);
+  return add(mul(a, x2), y2) == add(Fr::one(), mul(d, mul(x2, y2)));
+}
+// the witness program's chains: a real call where the compiler wants one (the chain is not the program's long part)
+ZKR_HDF PtD ptd_add(const TxB &b, const PtD &p, const PtD &q) { return bj_add(b.k.a, b.k.d, p, q); }
 // affine coordinates of the cnt points in the workspace, one field inversion (rollup.cpp affine_all / batch_inverse)
 ZKR_HDF void ws_affine(TxB &b, uint32_t cnt) {
   Fr acc = Fr::one();

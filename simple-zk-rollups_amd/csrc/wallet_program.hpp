@@ -148,14 +148,6 @@ ZKR_HD Fr wl_hash1(const Fr *mimc, const Fr &x) {  // multiHash([x])
   wl_feistel(mimc, r, c);
   return r;
 }
-// (X : Y : Z) + (x, y): add-2008-bbjlp with Z2 = 1, complete on BabyJub (ptd_add less one product)
-ZKR_HD PtD wl_add_affine(const TxConsts &k, const PtD &p, const Fr &qx, const Fr &qy) {
-  const Fr B = sqr(p.z), C = mul(p.x, qx), D = mul(p.y, qy);
-  const Fr E = mul(k.d, mul(C, D)), F = sub(B, E), G = add(B, E);
-  const Fr x3 = mul(mul(p.z, F), sub(sub(mul(add(p.x, p.y), add(qx, qy)), C), D));
-  const Fr y3 = mul(mul(p.z, G), sub(D, mul(k.a, C)));
-  return PtD{x3, y3, mul(F, G)};
-}
 // e * BASE8 for e < 2^253 as ONE projective chain over the table 2^i BASE8 (e is used up).  A step whose bit is clear adds the
 // identity: the lanes of a wavefront seldom all skip a step.
 ZKR_HD PtD wl_mul_base8(const TxConsts &k, uint32_t (&e)[8]) {
@@ -164,7 +156,7 @@ ZKR_HD PtD wl_mul_base8(const TxConsts &k, uint32_t (&e)[8]) {
 #pragma unroll 1
   for (int i = 0; i < 253; i++) {
     const uint32_t bit = wl_take_low_bit(e);
-    acc = wl_add_affine(k, acc, wl_pick(bit, k.b8x[i], zero), wl_pick(bit, k.b8y[i], one));
+    acc = bj_add_affine(k.a, k.d, acc, wl_pick(bit, k.b8x[i], zero), wl_pick(bit, k.b8y[i], one));
   }
   return acc;
 }
@@ -337,7 +329,7 @@ ZKR_HD uint32_t wd_witness(const TxConsts &k, const Fr *key, const Fr *nul, Fr *
 #pragma unroll 1
     for (int i = 1; i < 253; i++) {
       const uint32_t bit = wl_take_low_bit(sh);
-      acc = wl_add_affine(k, acc, wl_pick(bit, k.b8x[i], zero), wl_pick(bit, k.b8y[i], one));
+      acc = bj_add_affine(k.a, k.d, acc, wl_pick(bit, k.b8x[i], zero), wl_pick(bit, k.b8y[i], one));
       wx[i - 1] = acc.x, wy[i - 1] = acc.y, wz[i - 1] = acc.z;
     }
     Fr run = one;  // rollup.cpp affine_all / batch_inverse; a complete addition never gives Z = 0

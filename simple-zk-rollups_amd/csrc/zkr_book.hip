@@ -2,13 +2,14 @@
 // deposit(publicKeyX, publicKeyY) (contracts/contracts/RollUp.sol:255-297 of the reference), withdraw / withdrawAll (:193-253) and
 // accuredFees (:139, :299-309) for whole lists of calls:
 //
-//   a  key hashes     one thread per key: hashPair(pubX, pubY), of the ledger's records (the key table) or of a call list
+//   a  key hashes     one thread per key: hashPair(pubX, pubY) (mimc_device.hpp mimc_hash_pair), of the ledger's records (the key
+//                     table) or of a call list
 //   b  claim          "insert n keys into a slot table, the lowest position wins": the key table, the nullifier table, and a
 //                     scratch table per call list that gives every entry its leader -- the lowest list position with its key
 //   c  resolve        one thread per call entry, in a LATER launch: words below r, the key's account, nullifier spent, leader
 //   d  host pass      book_plan.cpp: the contract's checks and balance arithmetic in list order
 //   e  apply          the applied calls' events are an update list for the storing path of zkr_ledger_deposit
-//                     (ledger_apply_updates in zkr_sequencer.hip: tables, hashes, journal, store, records)
+//                     (ledger_apply_updates in zkr_sequencer.hip: tables, then stage_updates and store_updates)
 //
 // Every probe loop below is a `for` over at most the table's capacity, and the host establishes a load factor of at most 1/2
 // before a launch that inserts.  The claim writes slot words only (the keys are in place before the launch), with ordinary
@@ -36,13 +37,7 @@ static __global__ __launch_bounds__(64) void book_keyhash_kernel(const Fr *keys,
   if (!words_below(x.v, FrParams::P) || !words_below(y.v, FrParams::P)) {
 #pragma unroll
     for (int j = 0; j < 8; j++) h.v[j] = 0xFFFFFFFFu;
-  } else {
-    Fr r = to_mont(x), c = Fr::zero();
-    mimc_feistel(r, c);
-    r = add(r, to_mont(y));
-    mimc_feistel(r, c);
-    h = from_mont(r);
-  }
+  } else h = mimc_hash_pair(x, y);
   out[i] = h;
 }
 

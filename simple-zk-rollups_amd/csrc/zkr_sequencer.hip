@@ -11,7 +11,10 @@
 //   c  leaf hashes    one launch, 2T hashes of four elements
 //   d  tree levels    one launch per level, 2T independent hashes each: val[l+1][u] = H(ordered(val[l][u], sib[l][u]))
 //   e  assembly       one kernel writes the input signals, a second one the touched nodes' last versions into the ledger's tree
-// The field is field.hpp's 8 x 32 limbs throughout, as in the other cold-side kernels.
+// The field is field.hpp's 8 x 32 limbs throughout, as in the other cold-side kernels; the group law is rollup_witness.hpp's
+// (bj_add, bj_dbl, bj_on_curve), the hashes are mimc_device.hpp's (mimc_hash_std, mimc_hash_pair).  Steps c, d and the store are
+// the ledger's ONE storing path, stage_updates and store_updates (ledger_internal.hpp): zkr_ledger_sequence, replay() and
+// ledger_apply_updates differ in what they derive between the two steps and in the counters they move afterwards.
 //
 // And the opposite direction: zkr_ledger_replay applies the public signals of published batches to the ledger as
 // RollUp.sol:81-161 applies them -- steps a (when asked), b (replay_plan: the contract's arithmetic, none of the operator's
@@ -37,28 +40,10 @@ void rollup_device_constants(Fr *a, Fr *d, uint32_t suborder_m1[8], Fr *b8x253, 
 int rollup_check_geometry(uint32_t batch, uint32_t depth);
 
 // ------------------------------------------------------------------------------------------------ a. signatures
-struct SigConsts {
+struct SigConsts {  // the group law itself is rollup_witness.hpp's (bj_add, bj_dbl, bj_on_curve)
   Fr a, d, b8x, b8y;     // Montgomery
   uint32_t suborder[8];  // eddsa.circom:32 (+ 1)
 };
-struct SeqPt { Fr x, y, z; };
-
-__device__ __forceinline__ SeqPt seq_add(const SigConsts &k, const SeqPt &p, const SeqPt &q) {  // add-2008-bbjlp, complete on BabyJub
-  Fr A = mul(p.z, q.z), B = sqr(A), C = mul(p.x, q.x), D = mul(p.y, q.y);
-  Fr E = mul(k.d, mul(C, D)), F = sub(B, E), G = add(B, E);
-  Fr x3 = mul(mul(A, F), sub(sub(mul(add(p.x, p.y), add(q.x, q.y)), C), D));
-  Fr y3 = mul(mul(A, G), sub(D, mul(k.a, C)));
-  return SeqPt{x3, y3, mul(F, G)};
-}
-__device__ __forceinline__ SeqPt seq_dbl(const SigConsts &k, const SeqPt &p) {  // dbl-2008-bbjlp
-  Fr B = sqr(add(p.x, p.y)), C = sqr(p.x), D = sqr(p.y), E = mul(k.a, C), F = add(E, D), H = sqr(p.z);
-  Fr J = sub(F, dbl(H));
-  return SeqPt{mul(sub(sub(B, C), D), J), mul(F, sub(E, D)), mul(F, J)};
-}
-__device__ __forceinline__ bool seq_on_curve(const SigConsts &k, const Fr &x, const Fr &y) {  // a x^2 + y^2 = 1 + d x^2 y^2
-  Fr x2 = sqr(x), y2 = sqr(y);
-  return add(mul(k.a, x2), y2) == add(Fr::one(), mul(k.d, mul(x2, y2)));
-}
 // standard form -> Montgomery; false when the words are not below r
 __device__ __forceinline__ bool seq_read(const Fr *p, Fr &out) {
   Fr a = *p;
@@ -109,52 +94,43 @@ static __global__ __launch_bounds__(64) void seq_verify_kernel(const Fr *msgs, s
     for (int i = 0; i < 8; i++) sw[i] = s.v[i];
   }
   ok = ok && words_below(sw, k.suborder);
-  ok = ok && seq_on_curve(k, r8x, r8y) && seq_on_curve(k, ax, ay);
+  ok = ok && bj_on_curve(k.a, k.d, r8x, r8y) && bj_on_curve(k.a, k.d, ax, ay);
   if (!ok) return;
-  {  // h = multiHash(R8x, R8y, Ax, Ay, multiHash(message))
+  {  // h = multiHash(R8x, R8y, Ax, Ay, multiHash(message)): the outer hash's elements are Montgomery already
+    const Fr m = mimc_hash_std(msgs, arity);
     Fr r = Fr::zero(), c = Fr::zero();
-    for (uint32_t i = 0; i < arity; i++) {
-      r = add(r, load_std_as_mont(msgs + i));
-      mimc_feistel(r, c);
-    }
-    const Fr m = r;
-    r = r8x, c = Fr::zero();
-    mimc_feistel(r, c);
-    r = add(r, r8y);
-    mimc_feistel(r, c);
-    r = add(r, ax);
-    mimc_feistel(r, c);
-    r = add(r, ay);
-    mimc_feistel(r, c);
-    r = add(r, m);
-    mimc_feistel(r, c);
+    mimc_absorb(r, c, r8x);
+    mimc_absorb(r, c, r8y);
+    mimc_absorb(r, c, ax);
+    mimc_absorb(r, c, ay);
+    mimc_absorb(r, c, m);
     const Fr h = from_mont(r);
 #pragma unroll
     for (int i = 0; i < 8; i++) hw[i] = h.v[i];
   }
   // the table: 0 the identity, 1 BASE8, 2 -(8A), 3 BASE8 - 8A
   const Fr one = Fr::one(), zero = Fr::zero();
-  SeqPt t2{ax, ay, one};
+  PtD t2{ax, ay, one};
   bool small_order = false;
 #pragma unroll 1
   for (int i = 0; i < 3; i++) {
-    t2 = seq_dbl(k, t2);
+    t2 = bj_dbl(k.a, t2);
     if (i == 1) small_order = t2.x.is_zero();
   }
   if (strict && small_order) return;
   t2.x = neg(t2.x);
-  const SeqPt t1{k.b8x, k.b8y, one};
-  const SeqPt t3 = seq_add(k, t1, t2);
+  const PtD t1{k.b8x, k.b8y, one};
+  const PtD t3 = bj_add(k.a, k.d, t1, t2);
   // S < 2^251 and h < 2^254: 254 steps from bit 253 down
   seq_take_top_bit(sw), seq_take_top_bit(sw);
   seq_take_top_bit(hw), seq_take_top_bit(hw);
-  SeqPt acc{zero, one, one};
+  PtD acc{zero, one, one};
 #pragma unroll 1
   for (int i = 0; i < 254; i++) {
-    acc = seq_dbl(k, acc);
+    acc = bj_dbl(k.a, acc);
     const uint32_t sel = seq_take_top_bit(sw) | (seq_take_top_bit(hw) << 1);
-    const SeqPt q{seq_pick(sel, zero, t1.x, t2.x, t3.x), seq_pick(sel, one, t1.y, t2.y, t3.y), seq_pick(sel, one, t1.z, t2.z, t3.z)};
-    acc = seq_add(k, acc, q);  // the identity included: the lanes of a wavefront seldom all skip a step
+    const PtD q{seq_pick(sel, zero, t1.x, t2.x, t3.x), seq_pick(sel, one, t1.y, t2.y, t3.y), seq_pick(sel, one, t1.z, t2.z, t3.z)};
+    acc = bj_add(k.a, k.d, acc, q);  // the identity included: the lanes of a wavefront seldom all skip a step
   }
   // (X : Y : Z) == (R8x, R8y)
   const bool same = !acc.z.is_zero() && acc.x == mul(r8x, acc.z) && acc.y == mul(r8y, acc.z);
@@ -166,12 +142,7 @@ static __global__ __launch_bounds__(64) void seq_verify_kernel(const Fr *msgs, s
 static __global__ __launch_bounds__(64) void seq_leaf_kernel(const Fr *recs, size_t U, Fr *val0) {
   const size_t u = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (u >= U) return;
-  Fr r = Fr::zero(), c = Fr::zero();
-  for (int i = 0; i < 4; i++) {
-    r = add(r, load_std_as_mont(recs + 4 * u + i));
-    mimc_feistel(r, c);
-  }
-  val0[u] = from_mont(r);
+  val0[u] = from_mont(mimc_hash_std(recs + 4 * u, 4));
 }
 // The node above update u's node of level l, as it stands after update u: the hash of that node (val_l[u]) and its sibling, which
 // is what the latest earlier update under the sibling left there (val_l[prev_l[u]]) or, without one, the ledger's stored node.
@@ -182,11 +153,7 @@ static __global__ __launch_bounds__(64) void seq_level_kernel(const Fr *val_l, F
   const size_t node = (size_t)idx[u] >> l;
   const Fr cur = val_l[u], sib = seq_sibling(val_l, prev_l[u], tree_l, node);
   const bool right = node & 1;
-  Fr r = to_mont(right ? sib : cur), c = Fr::zero();  // hashLeftRight (crypto.ts:36-38)
-  mimc_feistel(r, c);
-  r = add(r, to_mont(right ? cur : sib));
-  mimc_feistel(r, c);
-  val_next[u] = from_mont(r);
+  val_next[u] = mimc_hash_pair(right ? sib : cur, right ? cur : sib);  // both are hashes or stored nodes: below r
 }
 
 // ------------------------------------------------------------------------------------------------ e. assembly
@@ -260,15 +227,23 @@ static __global__ __launch_bounds__(256) void replay_gather_kernel(const Fr *con
   if (g >= (size_t)n_public * n_batches) return;
   out[g] = witnesses[g / n_public][1 + g % n_public];
 }
-// The last version of every touched node goes into the stored tree (table 2 names it; the root's is the last update's).  Both are
-// facts about the list of U updates that is stored, not about a longer one that was hashed.
+// Thread g of the (depth + 1) x U threads over a stored list -> level l, update u, and whether u holds the LAST version of its
+// node of level l (table 2 names it; the root's is the last update's), with that node's offset in the stored tree.  Both are
+// facts about the list of U updates that is stored, not about a longer one that was hashed.  The store and the journal decode g
+// here and nowhere else: the journal is right exactly when it names the nodes the store writes.
+struct SeqWriter { uint32_t l; size_t u, node; bool last; };
+__device__ __forceinline__ SeqWriter seq_writer_of(const SeqView &v, size_t g) {
+  const uint32_t l = (uint32_t)(g / v.U);
+  const size_t u = g % v.U;
+  const bool last = l == v.depth ? u == v.U - 1 : v.prev[((size_t)2 * v.depth + l) * v.U + u] != 0;
+  return SeqWriter{l, u, last ? seq_level_offset(v.depth, l) + ((size_t)v.idx[u] >> l) : 0, last};
+}
+// The last version of every touched node goes into the stored tree.
 static __global__ __launch_bounds__(256) void seq_store_kernel(SeqView v, Fr *tree) {
-  const size_t U = v.U, g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= ((size_t)v.depth + 1) * U) return;
-  const uint32_t l = (uint32_t)(g / U);
-  const size_t u = g % U;
-  const bool last = l == v.depth ? u == U - 1 : v.prev[((size_t)2 * v.depth + l) * U + u] != 0;
-  if (last) tree[seq_level_offset(v.depth, l) + ((size_t)v.idx[u] >> l)] = v.val[(size_t)l * v.stride + u];
+  const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= ((size_t)v.depth + 1) * v.U) return;
+  const SeqWriter w = seq_writer_of(v, g);
+  if (w.last) tree[w.node] = v.val[(size_t)w.l * v.stride + w.u];
 }
 static __global__ __launch_bounds__(256) void seq_fill_kernel(Fr *dst, size_t n, Fr value) {
   const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -276,34 +251,24 @@ static __global__ __launch_bounds__(256) void seq_fill_kernel(Fr *dst, size_t n,
 }
 
 // ------------------------------------------------------------------------------------------------ keeping the ledger
-__device__ __forceinline__ Fr state_hash_pair(const Fr &left, const Fr &right) {  // hashLeftRight, as seq_level_kernel computes it
-  Fr r = to_mont(left), c = Fr::zero();
-  mimc_feistel(r, c);
-  r = add(r, to_mont(right));
-  mimc_feistel(r, c);
-  return from_mont(r);
-}
 // The bulk build of a restore: level l (1 .. depth) of the stored tree from level l - 1, for the n = ceil(accounts / 2^l) nodes
 // whose subtree holds an account.  A right child past the populated prefix still holds its level's empty-subtree constant.
 static __global__ __launch_bounds__(64) void state_build_level_kernel(Fr *tree, uint32_t depth, uint32_t l, size_t n) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const Fr *below = tree + seq_level_offset(depth, l - 1);
-  tree[seq_level_offset(depth, l) + i] = state_hash_pair(below[2 * i], below[2 * i + 1]);
+  tree[seq_level_offset(depth, l) + i] = mimc_hash_pair(below[2 * i], below[2 * i + 1]);  // as seq_level_kernel computes it
 }
 // The journal of a storing call made under a checkpoint: seq_store_kernel's domain and predicate, but instead of writing the new
 // value it appends (node offset, the value the tree holds now).  Within one call every node has one last writer, so the entries
 // are distinct nodes and their order does not matter; *count starts at 0 and ends as the number of entries, room bounds it.
 static __global__ __launch_bounds__(256) void state_journal_kernel(SeqView v, uint32_t *off, Fr *old, uint32_t room, uint32_t *count) {
-  const size_t U = v.U, g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= ((size_t)v.depth + 1) * U) return;
-  const uint32_t l = (uint32_t)(g / U);
-  const size_t u = g % U;
-  const bool last = l == v.depth ? u == U - 1 : v.prev[((size_t)2 * v.depth + l) * U + u] != 0;
-  if (!last) return;
-  const size_t node = seq_level_offset(v.depth, l) + ((size_t)v.idx[u] >> l);
+  const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= ((size_t)v.depth + 1) * v.U) return;
+  const SeqWriter w = seq_writer_of(v, g);
+  if (!w.last) return;
   const uint32_t at = atomicAdd(count, 1u);
-  if (at < room) off[at] = (uint32_t)node, old[at] = v.tree[node];
+  if (at < room) off[at] = (uint32_t)w.node, old[at] = v.tree[w.node];
 }
 // The undo of one journalled call: its old values back where they came from.  n_nodes bounds every offset once more.
 static __global__ __launch_bounds__(256) void state_undo_kernel(Fr *tree, size_t n_nodes, const uint32_t *off, const Fr *old, size_t n) {
@@ -331,15 +296,10 @@ static __global__ __launch_bounds__(64) void state_audit_kernel(const Fr *tree, 
   if (i >= populated) ok = ok && have == empty[l];
   else if (l == 0) {
     if (i < rec_first || i - rec_first >= rec_count) return;  // this launch does not hold the record
-    Fr r = Fr::zero(), c = Fr::zero();
-    for (int j = 0; j < 4; j++) {
-      r = add(r, load_std_as_mont(recs + 4 * (i - rec_first) + j));
-      mimc_feistel(r, c);
-    }
-    ok = ok && have == from_mont(r);
+    ok = ok && have == from_mont(mimc_hash_std(recs + 4 * (i - rec_first), 4));
   } else {
     const Fr *below = tree + seq_level_offset(depth, l - 1);
-    ok = ok && have == state_hash_pair(below[2 * i], below[2 * i + 1]);
+    ok = ok && have == mimc_hash_pair(below[2 * i], below[2 * i + 1]);
   }
   if (!ok) atomicMin(first_bad, ((unsigned long long)l << 32) | (unsigned long long)i);
 }
@@ -359,7 +319,7 @@ static SigConsts sig_consts() {
 
 // Steps c and d for U leaf updates whose records, leaf indices and tables are already in the arena: val[0] from the records, then
 // level by level.  Every index the kernels follow was bounded on the host: idx[u] < accounts <= 2^depth, -1 <= prev[l][u] < u.
-int hash_updates(const zkr_ledger *L, size_t U, const Fr *d_new, const uint32_t *d_idx, const int32_t *d_prev, Fr *d_val, hipStream_t s, StageClock &clk, double *ms) {
+static int hash_updates(const zkr_ledger *L, size_t U, const Fr *d_new, const uint32_t *d_idx, const int32_t *d_prev, Fr *d_val, hipStream_t s, StageClock &clk, double *ms) {
   seq_leaf_kernel<<<blocks(U, 64), 64, 0, s>>>(d_new, U, d_val);
   ZKR_HIP_CHECK(hipGetLastError());
   clk.mark(ms[2]);
@@ -378,12 +338,12 @@ int need_device(int device, const char *what) {
 // ---- keeping the ledger
 enum : size_t { STATE_PIECE = (size_t)1 << 20 };  // records go to the device in pieces of at most 2^20: 128 MB of staging
 
-// The journal step of a storing call, run only while a checkpoint is open: between the point where the call's hashes are
+// The journal step of store_updates, run only while a checkpoint is open: between the point where the call's hashes are
 // complete (the tree still untouched) and its seq_store_kernel.  v is the view the store will run over, last = its table 2 on
 // the host ([depth][v.U]), idx its leaf indices.  The entries land behind the ones in use; *out is the call's host part, which
-// the caller appends to the journal once its store has succeeded -- until then nothing of the journal has moved.  A journal
+// store_updates appends to the journal once the store has succeeded -- until then nothing of the journal has moved.  A journal
 // that cannot grow is ZKR_ERR_HIP, raised here, before anything is stored.
-int journal_before_store(zkr_ledger *l, const SeqView &v, const int32_t *last, const uint32_t *idx, hipStream_t s, JournalCall *out) {
+static int journal_before_store(zkr_ledger *l, const SeqView &v, const int32_t *last, const uint32_t *idx, hipStream_t s, JournalCall *out) {
   const size_t U = v.U, base = l->journal.nodes();
   size_t count = 1;  // the root
   for (size_t i = 0; i < (size_t)v.depth * U; i++) count += last[i] != 0;
@@ -417,6 +377,97 @@ int journal_before_store(zkr_ledger *l, const SeqView &v, const int32_t *last, c
     memcpy(out->fees_before, l->book->fees.w, 32);
   }
   return ZKR_OK;
+}
+
+// ---- the one storing path: stage_updates, whatever the caller derives from the hashes, store_updates, the caller's counters
+size_t update_arena_bytes(size_t U_max, unsigned depth, bool with_old) {  // what stage_updates takes, piece by piece
+  return (with_old ? 2 : 1) * DevArena::padded(U_max * 128) + DevArena::padded(((size_t)depth + 1) * U_max * 32) + DevArena::padded(U_max * 4) +
+         DevArena::padded(3 * (size_t)depth * U_max * 4);
+}
+int stage_updates(zkr_ledger *l, const UpdateList &in, size_t accounts, bool check_tables, hipStream_t s, StageClock &clk, double *ms, StagedUpdates *out) {
+  const size_t U = in.U, depth = l->depth;
+  // every index the kernels follow, once more in one place: a scan without a branch, then the first offender for the message
+  size_t bad = 0, u = 0;
+  for (size_t i = 0; i < U; i++) bad |= in.idx[i] >= accounts;
+  if (bad) {
+    while (in.idx[u] < accounts) u++;
+    set_error("internal: update %zu names leaf %u of %zu", u, in.idx[u], accounts);
+    return ZKR_ERR_ARG;
+  }
+  for (size_t row = 0; check_tables && row < 2 * depth; row++) {
+    const int32_t *p = in.prev + row * U;
+    for (size_t i = 0; i < U; i++) bad |= (p[i] < -1) | (p[i] >= (int32_t)i);
+    if (!bad) continue;
+    while (p[u] >= -1 && p[u] < (int32_t)u) u++;
+    set_error("internal: look-up table entry %zu out of range", row * U + u);
+    return ZKR_ERR_ARG;
+  }
+  StagedUpdates d;
+  d.U = U;
+  d.d_old = in.old_rec ? l->arena.take<Fr>(U * 4) : nullptr, d.d_new = l->arena.take<Fr>(U * 4);
+  d.d_val = l->arena.take<Fr>((depth + 1) * U);
+  d.d_idx = l->arena.take<uint32_t>(U);
+  d.d_prev = l->arena.take<int32_t>(3 * depth * U);
+  if (in.old_rec) ZKR_HIP_CHECK(hipMemcpyAsync(d.d_old, in.old_rec, U * 128, hipMemcpyHostToDevice, s));
+  ZKR_HIP_CHECK(hipMemcpyAsync(d.d_new, in.new_rec, U * 128, hipMemcpyHostToDevice, s));
+  ZKR_HIP_CHECK(hipMemcpyAsync(d.d_idx, in.idx, U * 4, hipMemcpyHostToDevice, s));
+  ZKR_HIP_CHECK(hipMemcpyAsync(d.d_prev, in.prev, 3 * depth * U * 4, hipMemcpyHostToDevice, s));
+  *out = d;
+  return hash_updates(l, U, d.d_new, d.d_idx, d.d_prev, d.d_val, s, clk, ms);
+}
+int store_updates(zkr_ledger *l, const SeqView &v, const int32_t *last, const uint32_t *idx, const uint8_t *new_rec, hipStream_t s, StageClock &clk, double &slot) {
+  ZKR_HIP_CHECK(hipStreamSynchronize(s));  // the tree is untouched up to here: a failure above leaves the ledger as it was
+  JournalCall jc;
+  const bool journalled = l->journal.open();  // the journal follows the list that is stored, as the store does
+  int rc;
+  if (journalled && (rc = journal_before_store(l, v, last, idx, s, &jc))) return rc;
+  seq_store_kernel<<<blocks(((size_t)v.depth + 1) * v.U, 256), 256, 0, s>>>(v, l->d_tree);
+  ZKR_HIP_CHECK(hipGetLastError());
+  ZKR_HIP_CHECK(hipStreamSynchronize(s));
+  if (journalled) l->journal.calls.push_back(std::move(jc));
+  clk.mark(slot);
+  for (size_t u = 0; u < v.U; u++) memcpy(l->records.data() + (size_t)idx[u] * 128, new_rec + u * 128, 128);  // the records move last
+  return ZKR_OK;
+}
+int ledger_apply_updates(zkr_ledger *l, const uint32_t *indices, const uint8_t *records, size_t n, size_t accounts) {
+  ZKR_HIP_CHECK(hipSetDevice(l->device));
+  const unsigned depth = l->depth;
+  std::vector<uint32_t> idx(indices, indices + n);
+  std::vector<int32_t> prev(3 * (size_t)depth * n);
+  seq_tables(depth, idx, nullptr, accounts, prev.data());
+  int rc = l->arena.reserve(update_arena_bytes(n, depth, false));
+  if (rc) return rc;
+  hipStream_t s = nullptr;
+  StageClock clk(s);
+  clk.on = false;
+  double unused[5];
+  StagedUpdates st;
+  if ((rc = stage_updates(l, UpdateList{n, indices, records, nullptr, prev.data()}, accounts, false, s, clk, unused, &st))) return rc;
+  l->records.resize(accounts * 128);  // room for the accounts the list adds; they count once l->accounts moves
+  if ((rc = store_updates(l, st.view(l, nullptr, 1, n), prev.data() + 2 * (size_t)depth * n, indices, records, s, clk, unused[4]))) {
+    l->records.resize(l->accounts * 128);
+    return rc;
+  }
+  l->accounts = accounts;
+  return ZKR_OK;
+}
+
+// Step a's keys: the senders' stored keys beside their transactions.  Row t (eight words, `from` first) stands where
+// seq_verify_kernel finds it: group 0 is a plain array, else (t / group) * group_stride + (t % group) * 8 words behind `rows`.
+// A sender that is no account gets the all-zero key, which is on no curve.
+static std::vector<uint8_t> sender_keys(const zkr_ledger *l, const uint8_t *rows, size_t n_txs, uint32_t group, size_t group_stride) {
+  std::vector<uint8_t> keys(n_txs * 64, 0);
+  for (size_t t = 0; t < n_txs; t++) {
+    const Int256 from = int256_load(rows + (group ? (t / group) * group_stride + (t % group) * 8 : t * 8) * 32);
+    if (!(from.w[1] | from.w[2] | from.w[3]) && from.w[0] < l->accounts) memcpy(&keys[t * 64], l->records.data() + (size_t)from.w[0] * 128, 64);
+  }
+  return keys;
+}
+// The old and new records of a plan's first U updates as the device takes them: 128 B each, standard form.
+static void pack_records(const SeqPlan &plan, size_t U, std::vector<uint8_t> &h_old, std::vector<uint8_t> &h_new) {
+  h_new.resize(U * 128), h_old.resize(U * 128);
+  for (size_t u = 0; u < U; u++)
+    for (int j = 0; j < 4; j++) int256_store(&h_old[u * 128 + 32 * j], plan.old_rec[u].f[j]), int256_store(&h_new[u * 128 + 32 * j], plan.new_rec[u].f[j]);
 }
 }  // namespace zkr
 
@@ -476,10 +527,8 @@ int replay(zkr_ledger *l, const uint8_t *publics, const void *const *d_witnesses
   StageClock clk(s);
   const bool with_sigs = flags & ZKR_REPLAY_SIGNATURES;
   const size_t n_public = 1 + (size_t)batch * (18 + 3 * (size_t)depth), n_txs = n_batches * batch, U_max = 2 * n_txs;
-  const size_t tables_max = 3 * (size_t)depth * U_max;
   rc = l->arena.reserve(DevArena::padded(n_batches * n_public * 32) + DevArena::padded(n_batches * sizeof(void *)) + DevArena::padded(n_txs * 64) +
-                        DevArena::padded(n_txs) + 2 * DevArena::padded(U_max * 128) + DevArena::padded(U_max * 4) + DevArena::padded(tables_max * 4) +
-                        DevArena::padded(((size_t)depth + 1) * U_max * 32) + DevArena::padded(2 * n_batches * 4));
+                        DevArena::padded(n_txs) + DevArena::padded(2 * n_batches * 4) + update_arena_bytes(U_max, depth, true));
   if (rc) return rc;
   Fr *d_claimed = l->arena.take<Fr>(n_batches * n_public);
   const Fr **d_ptrs = l->arena.take<const Fr *>(n_batches);
@@ -504,11 +553,7 @@ int replay(zkr_ledger *l, const uint8_t *publics, const void *const *d_witnesses
   // that is on no curve (its batch is refused with code 1 before the signature is looked at)
   std::vector<uint8_t> sig_ok(n_txs, 1);
   if (with_sigs) {
-    std::vector<uint8_t> keys(n_txs * 64, 0);
-    for (size_t t = 0; t < n_txs; t++) {
-      const Int256 from = int256_load(publics + ((t / batch) * n_public + 1 + batch + 8 * (t % batch)) * 32);
-      if (!(from.w[1] | from.w[2] | from.w[3]) && from.w[0] < l->accounts) memcpy(&keys[t * 64], l->records.data() + (size_t)from.w[0] * 128, 64);
-    }
+    const std::vector<uint8_t> keys = sender_keys(l, publics + (1 + (size_t)batch) * 32, n_txs, batch, n_public);
     ZKR_HIP_CHECK(hipMemcpyAsync(d_keys, keys.data(), n_txs * 64, hipMemcpyHostToDevice, s));
     const Fr *rows = d_claimed + 1 + batch;
     seq_verify_kernel<<<blocks(n_txs, 64), 64, 0, s>>>(rows, 8, 5, rows + 5, 8, d_keys, n_txs, batch, n_public, sig_consts(), 1, d_sig);
@@ -526,32 +571,16 @@ int replay(zkr_ledger *l, const uint8_t *publics, const void *const *d_witnesses
   if (replay_plan(depth, l->records.data(), l->accounts, publics, n_batches, batch, plan, &planned, &where1, &why)) { set_error("%s", why); return ZKR_ERR_ARG; }
   clk.mark(ms[1]);
   const size_t U = 2 * planned * batch;
-  std::vector<uint8_t> h_new(U * 128);
+  std::vector<uint8_t> h_new;
   std::vector<uint32_t> diff(2 * n_batches, 0);
-  Fr *d_val = nullptr;
-  uint32_t *d_idx = nullptr;
-  int32_t *d_prev = nullptr;
+  StagedUpdates st;
   if (U) {
-    std::vector<uint8_t> h_old(U * 128);
-    for (size_t u = 0; u < U; u++)
-      for (int j = 0; j < 4; j++) int256_store(&h_old[u * 128 + 32 * j], plan.old_rec[u].f[j]), int256_store(&h_new[u * 128 + 32 * j], plan.new_rec[u].f[j]);
-    for (size_t u = 0; u < U; u++)  // every index the kernels follow, once more in one place
-      if (plan.idx[u] >= l->accounts) { set_error("internal: update %zu names leaf %u of %zu", u, plan.idx[u], l->accounts); return ZKR_ERR_ARG; }
-    for (size_t i = 0; i < 2 * (size_t)depth * U; i++)
-      if (plan.prev[i] < -1 || plan.prev[i] >= (int32_t)(i % U)) { set_error("internal: look-up table entry %zu out of range", i); return ZKR_ERR_ARG; }
-    Fr *d_old = l->arena.take<Fr>(U * 4), *d_new = l->arena.take<Fr>(U * 4);
-    d_val = l->arena.take<Fr>(((size_t)depth + 1) * U);
-    d_idx = l->arena.take<uint32_t>(U);
-    d_prev = l->arena.take<int32_t>(plan.prev.size());
-    ZKR_HIP_CHECK(hipMemcpyAsync(d_old, h_old.data(), h_old.size(), hipMemcpyHostToDevice, s));
-    ZKR_HIP_CHECK(hipMemcpyAsync(d_new, h_new.data(), h_new.size(), hipMemcpyHostToDevice, s));
-    ZKR_HIP_CHECK(hipMemcpyAsync(d_idx, plan.idx.data(), U * 4, hipMemcpyHostToDevice, s));
-    ZKR_HIP_CHECK(hipMemcpyAsync(d_prev, plan.prev.data(), plan.prev.size() * 4, hipMemcpyHostToDevice, s));
+    std::vector<uint8_t> h_old;  // only the comparison reads them
+    pack_records(plan, U, h_old, h_new);
     ZKR_HIP_CHECK(hipMemsetAsync(d_diff, 0xFF, planned * 4, s));
     ZKR_HIP_CHECK(hipMemsetAsync(d_diff + n_batches, 0, planned * 4, s));
-    if ((rc = hash_updates(l, U, d_new, d_idx, d_prev, d_val, s, clk, ms))) return rc;
-    SeqView v{nullptr, d_old, d_val, d_idx, d_prev, l->d_tree, U, U, depth, batch};
-    replay_compare_kernel<<<blocks(planned * n_public, 256), 256, 0, s>>>(v, planned, d_claimed, d_diff, d_diff + n_batches);
+    if ((rc = stage_updates(l, UpdateList{U, plan.idx.data(), h_new.data(), h_old.data(), plan.prev.data()}, l->accounts, true, s, clk, ms, &st))) return rc;
+    replay_compare_kernel<<<blocks(planned * n_public, 256), 256, 0, s>>>(st.view(l, nullptr, batch, U), planned, d_claimed, d_diff, d_diff + n_batches);
     ZKR_HIP_CHECK(hipGetLastError());
     ZKR_HIP_CHECK(hipMemcpyAsync(diff.data(), d_diff, planned * 4, hipMemcpyDeviceToHost, s));
     ZKR_HIP_CHECK(hipMemcpyAsync(diff.data() + n_batches, d_diff + n_batches, planned * 4, hipMemcpyDeviceToHost, s));
@@ -583,23 +612,17 @@ int replay(zkr_ledger *l, const uint8_t *publics, const void *const *d_witnesses
       std::vector<uint32_t> idx(plan.idx.begin(), plan.idx.begin() + Ub);
       prev.resize(3 * (size_t)depth * Ub);
       seq_tables(depth, idx, nullptr, l->accounts, prev.data());
-      ZKR_HIP_CHECK(hipMemcpyAsync(d_prev, prev.data(), prev.size() * 4, hipMemcpyHostToDevice, s));
-      ZKR_HIP_CHECK(hipStreamSynchronize(s));
+      ZKR_HIP_CHECK(hipMemcpyAsync(st.d_prev, prev.data(), prev.size() * 4, hipMemcpyHostToDevice, s));  // the step below waits for it
     }
-    SeqView v{nullptr, nullptr, d_val, d_idx, d_prev, l->d_tree, Ub, U, depth, batch};  // val keeps the rows of the hashed list
-    JournalCall jc;
-    const bool journalled = l->journal.open();  // the journal follows the list that is stored, as the store does
-    if (journalled && (rc = journal_before_store(l, v, (Ub < U ? prev.data() : plan.prev.data()) + 2 * (size_t)depth * Ub, plan.idx.data(), s, &jc))) return rc;
-    seq_store_kernel<<<blocks(((size_t)depth + 1) * Ub, 256), 256, 0, s>>>(v, l->d_tree);
-    ZKR_HIP_CHECK(hipGetLastError());
-    ZKR_HIP_CHECK(hipStreamSynchronize(s));
-    if (journalled) l->journal.calls.push_back(std::move(jc));
-    for (size_t u = 0; u < Ub; u++) memcpy(l->records.data() + (size_t)plan.idx[u] * 128, &h_new[u * 128], 128);
+    // val keeps the rows of the hashed list: the view's stride stays U
+    if ((rc = store_updates(l, st.view(l, nullptr, batch, Ub), (Ub < U ? prev.data() : plan.prev.data()) + 2 * (size_t)depth * Ub, plan.idx.data(), h_new.data(), s, clk, ms[4]))) return rc;
     l->applied += B * batch, l->batches += B;
     if (l->book)  // accuredFees += fee (RollUp.sol:139): signal 1 + batch + 8k + 3 of every applied batch
       for (size_t t = 0; t < B * batch; t++) l->book->fees = int256_add(l->book->fees, int256_load(publics + ((t / batch) * n_public + 1 + batch + 8 * (t % batch) + 3) * 32));
   }
-  clk.mark(ms[4]);
+  double tail = 0;  // a replay's slot 4 runs to here, as it always did: the records' copy and the fees are in it
+  clk.mark(tail);
+  ms[4] += tail;
   for (size_t b = 0; b < n_batches; b++) {
     verdicts[b] = b < B ? 0 : b == B ? code : SEQ_NOT_REACHED;
     where[b] = b == B ? at : 0;
@@ -609,43 +632,6 @@ int replay(zkr_ledger *l, const uint8_t *publics, const void *const *d_witnesses
   return ZKR_OK;
 }
 }  // namespace
-
-namespace zkr {
-int ledger_apply_updates(zkr_ledger *l, const uint32_t *indices, const uint8_t *records, size_t n, size_t accounts) {
-  ZKR_HIP_CHECK(hipSetDevice(l->device));
-  const unsigned depth = l->depth;
-  const size_t U = n;
-  std::vector<uint32_t> idx(indices, indices + n);
-  std::vector<int32_t> prev(3 * (size_t)depth * U);
-  seq_tables(depth, idx, nullptr, accounts, prev.data());
-  int rc = l->arena.reserve(DevArena::padded(U * 128) + DevArena::padded(U * 4) + DevArena::padded(prev.size() * 4) + DevArena::padded(((size_t)depth + 1) * U * 32));
-  if (rc) return rc;
-  Fr *d_new = l->arena.take<Fr>(4 * U), *d_val = l->arena.take<Fr>(((size_t)depth + 1) * U);
-  uint32_t *d_idx = l->arena.take<uint32_t>(U);
-  int32_t *d_prev = l->arena.take<int32_t>(prev.size());
-  hipStream_t s = nullptr;
-  ZKR_HIP_CHECK(hipMemcpyAsync(d_new, records, U * 128, hipMemcpyHostToDevice, s));
-  ZKR_HIP_CHECK(hipMemcpyAsync(d_idx, idx.data(), U * 4, hipMemcpyHostToDevice, s));
-  ZKR_HIP_CHECK(hipMemcpyAsync(d_prev, prev.data(), prev.size() * 4, hipMemcpyHostToDevice, s));
-  StageClock clk(s);
-  clk.on = false;
-  double unused[5];
-  if ((rc = hash_updates(l, U, d_new, d_idx, d_prev, d_val, s, clk, unused))) return rc;
-  ZKR_HIP_CHECK(hipStreamSynchronize(s));  // the tree is untouched up to here: a failure above leaves the ledger as it was
-  SeqView v{nullptr, nullptr, d_val, d_idx, d_prev, l->d_tree, U, U, depth, 1};
-  JournalCall jc;
-  const bool journalled = l->journal.open();
-  if (journalled && (rc = journal_before_store(l, v, prev.data() + 2 * (size_t)depth * U, indices, s, &jc))) return rc;
-  seq_store_kernel<<<blocks(((size_t)depth + 1) * U, 256), 256, 0, s>>>(v, l->d_tree);
-  ZKR_HIP_CHECK(hipGetLastError());
-  ZKR_HIP_CHECK(hipStreamSynchronize(s));
-  if (journalled) l->journal.calls.push_back(std::move(jc));
-  l->records.resize(accounts * 128);
-  for (size_t i = 0; i < n; i++) memcpy(l->records.data() + (size_t)indices[i] * 128, records + i * 128, 128);
-  l->accounts = accounts;
-  return ZKR_OK;
-}
-}  // namespace zkr
 
 extern "C" {
 
@@ -795,14 +781,9 @@ int zkr_ledger_sequence(zkr_ledger *l, const uint8_t *txs, size_t n_txs, uint32_
   StageClock clk(s);
 
   // a. the senders' stored keys beside their transactions; a sender that is no account gets a key that is on no curve
-  std::vector<uint8_t> keys(n_txs * 64, 0), verdicts(n_txs);
-  for (size_t t = 0; t < n_txs; t++) {
-    const Int256 from = int256_load(txs + t * 256);
-    if (!(from.w[1] | from.w[2] | from.w[3]) && from.w[0] < l->accounts) memcpy(&keys[t * 64], l->records.data() + (size_t)from.w[0] * 128, 64);
-  }
-  const size_t U_max = 2 * n_txs, tables_max = 3 * (size_t)depth * U_max;
-  rc = l->arena.reserve(2 * DevArena::padded(n_txs * 256) + DevArena::padded(n_txs * 64) + DevArena::padded(n_txs) + 2 * DevArena::padded(U_max * 128) +
-                        DevArena::padded(U_max * 4) + DevArena::padded(tables_max * 4) + DevArena::padded(((size_t)depth + 1) * U_max * 32));
+  const std::vector<uint8_t> keys = sender_keys(l, txs, n_txs, 0, 0);
+  std::vector<uint8_t> verdicts(n_txs);
+  rc = l->arena.reserve(2 * DevArena::padded(n_txs * 256) + DevArena::padded(n_txs * 64) + DevArena::padded(n_txs) + update_arena_bytes(2 * n_txs, depth, true));
   if (rc) return rc;
   Fr *d_queue = l->arena.take<Fr>(n_txs * 8), *d_keys = l->arena.take<Fr>(n_txs * 2);
   uint8_t *d_verdicts = l->arena.take<uint8_t>(n_txs);
@@ -821,37 +802,18 @@ int zkr_ledger_sequence(zkr_ledger *l, const uint8_t *txs, size_t n_txs, uint32_
   clk.mark(ms[1]);
   const size_t T = plan.applied, U = 2 * T;
   if (T) {
-    std::vector<uint8_t> h_txs(T * 256), h_old(U * 128), h_new(U * 128);
+    std::vector<uint8_t> h_txs(T * 256), h_old, h_new;
     for (size_t k = 0; k < T; k++) memcpy(&h_txs[k * 256], txs + (size_t)plan.pos[k] * 256, 256);
-    for (size_t u = 0; u < U; u++)
-      for (int j = 0; j < 4; j++) int256_store(&h_old[u * 128 + 32 * j], plan.old_rec[u].f[j]), int256_store(&h_new[u * 128 + 32 * j], plan.new_rec[u].f[j]);
-    for (size_t u = 0; u < U; u++)  // every index the kernels follow, once more in one place
-      if (plan.idx[u] >= l->accounts) { set_error("internal: update %zu names leaf %u of %zu", u, plan.idx[u], l->accounts); return ZKR_ERR_ARG; }
-    for (size_t i = 0; i < 2 * (size_t)depth * U; i++)
-      if (plan.prev[i] < -1 || plan.prev[i] >= (int32_t)(i % U)) { set_error("internal: look-up table entry %zu out of range", i); return ZKR_ERR_ARG; }
-    Fr *d_txs = l->arena.take<Fr>(T * 8), *d_old = l->arena.take<Fr>(U * 4), *d_new = l->arena.take<Fr>(U * 4), *d_val = l->arena.take<Fr>(((size_t)depth + 1) * U);
-    uint32_t *d_idx = l->arena.take<uint32_t>(U);
-    int32_t *d_prev = l->arena.take<int32_t>(plan.prev.size());
+    pack_records(plan, U, h_old, h_new);
+    Fr *d_txs = l->arena.take<Fr>(T * 8);
     ZKR_HIP_CHECK(hipMemcpyAsync(d_txs, h_txs.data(), h_txs.size(), hipMemcpyHostToDevice, s));
-    ZKR_HIP_CHECK(hipMemcpyAsync(d_old, h_old.data(), h_old.size(), hipMemcpyHostToDevice, s));
-    ZKR_HIP_CHECK(hipMemcpyAsync(d_new, h_new.data(), h_new.size(), hipMemcpyHostToDevice, s));
-    ZKR_HIP_CHECK(hipMemcpyAsync(d_idx, plan.idx.data(), U * 4, hipMemcpyHostToDevice, s));
-    ZKR_HIP_CHECK(hipMemcpyAsync(d_prev, plan.prev.data(), plan.prev.size() * 4, hipMemcpyHostToDevice, s));
-    if ((rc = hash_updates(l, U, d_new, d_idx, d_prev, d_val, s, clk, ms))) return rc;
+    StagedUpdates st;
+    if ((rc = stage_updates(l, UpdateList{U, plan.idx.data(), h_new.data(), h_old.data(), plan.prev.data()}, l->accounts, true, s, clk, ms, &st))) return rc;
     const size_t nb = T / batch;
-    SeqView v{d_txs, d_old, d_val, d_idx, d_prev, l->d_tree, U, U, depth, batch};
+    const SeqView v = st.view(l, d_txs, batch, U);
     seq_assemble_kernel<<<blocks(nb * batch * (18 + 3 * (size_t)depth), 256), 256, 0, s>>>(v, nb, (Fr *)d_inputs);
     ZKR_HIP_CHECK(hipGetLastError());
-    ZKR_HIP_CHECK(hipStreamSynchronize(s));  // the tree is untouched up to here: a failure above leaves the ledger as it was
-    JournalCall jc;
-    const bool journalled = l->journal.open();
-    if (journalled && (rc = journal_before_store(l, v, plan.prev.data() + 2 * (size_t)depth * U, plan.idx.data(), s, &jc))) return rc;
-    seq_store_kernel<<<blocks(((size_t)depth + 1) * U, 256), 256, 0, s>>>(v, l->d_tree);
-    ZKR_HIP_CHECK(hipGetLastError());
-    ZKR_HIP_CHECK(hipStreamSynchronize(s));
-    if (journalled) l->journal.calls.push_back(std::move(jc));
-    clk.mark(ms[4]);
-    for (size_t u = 0; u < U; u++) memcpy(l->records.data() + (size_t)plan.idx[u] * 128, &h_new[u * 128], 128);
+    if ((rc = store_updates(l, v, plan.prev.data() + 2 * (size_t)depth * U, plan.idx.data(), h_new.data(), s, clk, ms[4]))) return rc;
     l->applied += T, l->batches += nb;
     if (l->book)  // accuredFees += fee (RollUp.sol:139)
       for (size_t k = 0; k < T; k++) l->book->fees = int256_add(l->book->fees, int256_load(&h_txs[k * 256 + 96]));
