@@ -935,6 +935,31 @@ int zkr_selftest_curve29(int device, int g2, int op, const uint32_t *records, si
  * words.  Every result is canonical, so the host build of the same function (libzkr_hostarith.so zkt_fp_raw) and integer
  * arithmetic must give the same words bit for bit: tests/test_gpu_field_raw.py. */
 int zkr_selftest_fp(int device, int field, int op, const uint32_t *records, size_t n, uint32_t *out);
+/* The NTT pass kernel (csrc/kernels_ntt.hpp) in every mode its two host drivers launch it in, alone: exactly ONE run_ntt
+ * (cross = 0) or ONE run_ntt_cross (cross = 1) of csrc/zkr_prove.hip -- the code objects the proofs launch -- on host-supplied
+ * vectors, the raw result back: no bit-reversal copy, no 1/n.  Twiddle tables are built for 2^tlog as zkr_ntt builds them for
+ * 2^logn.  Every field is checked before any launch (ZKR_ERR_ARG and a message):
+ *   logn 1..22; tlog logn + coset_shift .. 24; dif, inverse, pair, in_place, canon, cross 0 / 1; pre 0 none, 1 coset (position gi
+ *   times g^(((bitrev(gi) << coset_shift) | coset_add) << (tlog - logn - coset_shift)), g = w_{2^(tlog+1)}; coset_add below
+ *   2^coset_shift, both 0 without it), 2 product with in1 (x y / 2^256); nbat >= 1 vectors end to end (nbat 2^logn <= 2^24);
+ *   want_lo / want_n: run_ntt's output range (0, 0 = all; run_ntt itself refuses a range of a DIT transform or one outside it).
+ *   cross: klog 1..3 below logn, columns [col_lo, col_lo + col_n) of the 2^klog row blocks of 2^(logn - klog) elements, col_lo and
+ *   col_n multiples of the tile width run_ntt_cross picks; in_sub / out_sub 0 or col_lo; pre 0 or 2; tlog >= logn; nbat 1, no pair,
+ *   no range, no coset fields; canon as given (cross = 0: run_ntt decides).
+ * Vectors are host buffers of 32-byte little-endian standard-form words, all IN and OUT: each is copied to the device (in0, in1
+ * and their _b twins through the ingest kernel, as zkr_ntt does; out as it is), and copied back after the run, so a caller sees
+ * that an out-of-place transform left its inputs alone and what it left of `out` outside the range or the columns it was asked for.
+ * cross = 0: every vector nbat 2^logn words.  cross = 1: the 2^klog row blocks end to end, 2^(logn - klog) words each -- col_n
+ * words each for in0 / in1 when in_sub != 0 and for out when out_sub != 0 (a local buffer of this shard's columns) -- and every
+ * block in a device allocation of its own.  in1 (in1_b): pre == 2 only; out (out_b): in_place == 0 only -- in place the result
+ * comes back in in0 (cross: in_sub == out_sub); the _b vectors: pair == 1 only.  Unused ones may be NULL.
+ * Every device vector lies between two guard regions of a fixed pattern, read back after the run: a changed guard is ZKR_ERR_HIP
+ * with a message naming the vector (the vectors are still copied back).  tests/test_gpu_ntt_modes.py, tests/ntt_cases.py. */
+typedef struct {
+  uint32_t logn, tlog, dif, inverse, pre, nbat, pair, in_place, want_lo, want_n, coset_shift, coset_add;
+  uint32_t cross, klog, col_lo, col_n, in_sub, out_sub, canon, reserved;
+} zkr_ntt_selftest_desc;
+int zkr_selftest_ntt(int device, const zkr_ntt_selftest_desc *desc, void *in0, void *in1, void *out, void *in0_b, void *in1_b, void *out_b);
 int zkr_bench_fq_mul(int device, double *gmuls_per_s);
 int zkr_bench_fq_mul_legacy(int device, double *gmuls_per_s);
 

@@ -11,6 +11,7 @@
 #include <string.h>
 #include <time.h>
 #include <algorithm>
+#include <memory>
 #include "kernels_msm.hpp"
 #include "kernels_ntt.hpp"
 #include "zkr_internal.hpp"
@@ -291,13 +292,18 @@ thread_local bool shard_turn_held = false;
 // The top klog stages of a transform of 2^L points whose 2^klog blocks live in different buffers (kernels_ntt.hpp CROSS): this
 // shard's columns [col_lo, col_lo + col_n) of every block.  rows_*[r]: where block r starts (x_sub = 0) or where this shard's
 // columns of block r start in a local buffer (x_sub = col_lo).
+// log2 of the columns per tile: a full tile's, or as many as the shard has (col_lo and col_n must be multiples of it)
+static int ntt_cross_wlog(int klog, uint32_t col_n) {
+  int wlog = NTT_TILE_LOG - klog;
+  while ((1u << wlog) > col_n) wlog--;
+  return wlog;
+}
 static int run_ntt_cross(hipStream_t s, const NttTables &tb, int L, int klog, bool dif, bool inverse, int pre, bool canon, const Fr *const *rows_in0,
                          const Fr *const *rows_in1, Fr *const *rows_out, uint32_t in_sub, uint32_t out_sub, uint32_t col_lo, uint32_t col_n, Prof pf) {
   NttPassArgs a = {};
   a.tw = tb.tw; a.tw29 = tb.tw29; a.twl29 = tb.twl29; a.tlog = tb.tlog; a.L = L;
   a.lo = L - klog; a.hi = L;
-  int wlog = NTT_TILE_LOG - klog;
-  while ((1u << wlog) > col_n) wlog--;
+  const int wlog = ntt_cross_wlog(klog, col_n);
   a.wlog = wlog;
   a.pre = pre;
   a.canon = canon ? 1 : 0;
@@ -1345,6 +1351,140 @@ int zkr_ntt(void *data_std, unsigned logn, int inverse, int device) {
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------ zkr_selftest_ntt: one run_ntt / run_ntt_cross on host vectors
+// A device vector of the NTT self test: its own allocation, a guard region of one full tile's bytes on either side of the data,
+// filled with a fixed pattern and compared after the run.
+constexpr size_t NTT_GUARD_BYTES = (size_t)32 << NTT_TILE_LOG;
+constexpr int NTT_GUARD_FILL = 0xC3;
+struct NttTestVec {
+  DevBuf buf;
+  size_t bytes = 0;
+  void *host = nullptr;  // where the data came from, and where they go back to
+  const char *name = "";
+  unsigned row = 0;
+  Fr *data() const { return reinterpret_cast<Fr *>(buf.as<unsigned char>() + NTT_GUARD_BYTES); }
+  int upload(const char *nm, unsigned r, void *h, size_t n, bool ingest) {
+    name = nm; row = r; host = h; bytes = n * 32;
+    if (int rc = buf.alloc(bytes + 2 * NTT_GUARD_BYTES)) return rc;
+    ZKR_HIP_CHECK(hipMemset(buf.p, NTT_GUARD_FILL, NTT_GUARD_BYTES));
+    ZKR_HIP_CHECK(hipMemset(buf.as<unsigned char>() + NTT_GUARD_BYTES + bytes, NTT_GUARD_FILL, NTT_GUARD_BYTES));
+    ZKR_HIP_CHECK(hipMemcpy(data(), h, bytes, hipMemcpyHostToDevice));
+    if (ingest) ingest_kernel<<<(unsigned)((n + 255) / 256), 256>>>(data(), data(), n);  // below r, as zkr_ntt does: the passes state bounds on what they load
+    return 0;
+  }
+  // the data back to the host; *guard_bad = 1 (and the message) when a guard byte is not the pattern any more
+  int download(int *guard_bad) {
+    ZKR_HIP_CHECK(hipMemcpy(host, data(), bytes, hipMemcpyDeviceToHost));
+    std::vector<unsigned char> g(2 * NTT_GUARD_BYTES);
+    ZKR_HIP_CHECK(hipMemcpy(g.data(), buf.p, NTT_GUARD_BYTES, hipMemcpyDeviceToHost));
+    ZKR_HIP_CHECK(hipMemcpy(g.data() + NTT_GUARD_BYTES, buf.as<unsigned char>() + NTT_GUARD_BYTES + bytes, NTT_GUARD_BYTES, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < g.size() && !*guard_bad; i++)
+      if (g[i] != NTT_GUARD_FILL) {
+        const bool before = i < NTT_GUARD_BYTES;
+        set_error("zkr_selftest_ntt: the guard %s vector %s (row block %u) changed: a launch wrote %zu bytes %s it", before ? "in front of" : "behind", name,
+                  row, before ? NTT_GUARD_BYTES - i : i - NTT_GUARD_BYTES + 1, before ? "before" : "past");
+        *guard_bad = 1;
+      }
+    return 0;
+  }
+};
+
+extern "C" int zkr_selftest_ntt(int device, const zkr_ntt_selftest_desc *desc, void *in0, void *in1, void *out, void *in0_b, void *in1_b, void *out_b) {
+  if (!desc) { set_error("zkr_selftest_ntt: null descriptor"); return ZKR_ERR_ARG; }
+  const zkr_ntt_selftest_desc d = *desc;
+  auto bad = [](const char *what) { set_error("zkr_selftest_ntt: %s", what); return ZKR_ERR_ARG; };
+  if (d.logn < 1 || d.logn > 22) return bad("logn must be 1 .. 22");
+  if (d.dif > 1 || d.inverse > 1 || d.pair > 1 || d.in_place > 1 || d.canon > 1 || d.cross > 1) return bad("dif, inverse, pair, in_place, canon and cross are 0 or 1");
+  if (d.pre > 2) return bad("pre must be 0 (none), 1 (coset) or 2 (product)");
+  if (d.reserved) return bad("the reserved word must be 0");
+  if (d.pre != PRE_COSET && (d.coset_shift || d.coset_add)) return bad("coset_shift / coset_add need pre = 1");
+  if (d.tlog > 24 || d.coset_shift > 24 || d.tlog < d.logn + d.coset_shift) return bad("tlog must be logn + coset_shift .. 24");
+  if (d.coset_add >> d.coset_shift) return bad("coset_add must be below 2^coset_shift");
+  if (d.nbat < 1 || ((uint64_t)d.nbat << d.logn) > (1ull << 24)) return bad("nbat must be at least 1, with nbat 2^logn at most 2^24 elements");
+  const uint32_t Bk = d.cross && d.klog <= 3 ? (1u << d.logn) >> d.klog : 0;  // elements of a row block
+  if (d.cross) {
+    if (d.klog < 1 || d.klog > 3 || d.klog >= d.logn) return bad("klog must be 1 .. 3 and below logn");
+    if (d.nbat != 1 || d.pair || d.want_lo || d.want_n || d.pre == PRE_COSET) return bad("a cross pass takes one transform, no pair, no range and no coset factors");
+    if (!d.col_n || (uint64_t)d.col_lo + d.col_n > Bk) return bad("the columns must lie inside a row block of 2^(logn - klog) elements");
+    const uint32_t wmask = (1u << ntt_cross_wlog((int)d.klog, d.col_n)) - 1;
+    if ((d.col_lo & wmask) || (d.col_n & wmask)) return bad("col_lo and col_n must be multiples of the tile width (the largest power of two up to col_n and 2^(11 - klog))");
+    if ((d.in_sub && d.in_sub != d.col_lo) || (d.out_sub && d.out_sub != d.col_lo)) return bad("in_sub and out_sub are 0 (whole blocks) or col_lo (local columns)");
+    if (d.in_place && d.in_sub != d.out_sub) return bad("an in-place cross pass reads and writes the same buffers: in_sub = out_sub");
+  } else if (d.klog || d.col_lo || d.col_n || d.in_sub || d.out_sub || d.canon) {
+    return bad("klog, col_lo, col_n, in_sub, out_sub and canon need cross = 1");
+  }
+  const bool mul2 = d.pre == PRE_MUL;
+  if (!in0 || (mul2 && !in1) || (!d.in_place && !out)) return bad("null vector (in0; in1 with pre = 2; out unless in place)");
+  if (d.pair && (!in0_b || (mul2 && !in1_b) || (!d.in_place && !out_b))) return bad("null vector of the second transform (pair = 1)");
+  if (int rc = need_device(device)) return rc;
+  ZKR_HIP_CHECK(hipSetDevice(device));
+  if (int lrc = ntt_lds_check(device)) return lrc;
+
+  // the tables, as zkr_ntt builds them, for 2^tlog
+  const size_t nt = (size_t)1 << d.tlog;
+  DevBuf btw, btwl, btw29, btwl29;
+  int rc;
+  if ((rc = btw.alloc(nt * 32)) || (rc = btwl.alloc((size_t)(1u << TWL_LOG) * 32))) return rc;
+  Fr *tw = btw.as<Fr>(), *twl = btwl.as<Fr>();
+  twiddle_table_kernel<<<(unsigned)((nt + 255) / 256), 256>>>(tw, (uint32_t)nt, host_root_of_unity(d.tlog + 1));
+  twiddle_table_kernel<<<((1u << TWL_LOG) + 255) / 256, 256>>>(twl, 1u << TWL_LOG, host_root_of_unity(TWL_LOG + 1));
+  Tw29 *tw29 = nullptr, *twl29 = nullptr;
+  rc = ntt_tables29_build(tw, (uint32_t)nt, twl, 1u << TWL_LOG, nullptr, &tw29, &twl29);
+  btw29.p = tw29; btwl29.p = twl29;
+  if (rc) return rc;
+  const NttTables tb{tw, tw29, twl29, (int)d.tlog};
+
+  // the vectors: one allocation each (cross: one per row block), between guards
+  const unsigned rows = d.cross ? 1u << d.klog : 1;
+  const size_t n_in = d.cross ? (d.in_sub ? d.col_n : Bk) : (size_t)d.nbat << d.logn;
+  const size_t n_out = d.cross ? (d.out_sub ? d.col_n : Bk) : n_in;
+  std::vector<std::unique_ptr<NttTestVec>> all;
+  auto load = [&](const char *name, void *host, size_t n, bool ingest, NttTestVec **set) -> int {
+    for (unsigned r = 0; r < rows; r++) {
+      all.emplace_back(new NttTestVec);
+      set[r] = all.back().get();
+      if (int lrc = set[r]->upload(name, r, (unsigned char *)host + (size_t)r * n * 32, n, ingest)) return lrc;
+    }
+    return 0;
+  };
+  NttTestVec *v_in0[8] = {}, *v_in1[8] = {}, *v_out[8] = {}, *v_in0b[8] = {}, *v_in1b[8] = {}, *v_outb[8] = {};
+  if ((rc = load("in0", in0, n_in, true, v_in0))) return rc;
+  if (mul2 && (rc = load("in1", in1, n_in, true, v_in1))) return rc;
+  if (!d.in_place && (rc = load("out", out, n_out, false, v_out))) return rc;
+  if (d.pair) {
+    if ((rc = load("in0_b", in0_b, n_in, true, v_in0b))) return rc;
+    if (mul2 && (rc = load("in1_b", in1_b, n_in, true, v_in1b))) return rc;
+    if (!d.in_place && (rc = load("out_b", out_b, n_out, false, v_outb))) return rc;
+  }
+  ZKR_HIP_CHECK(hipGetLastError());
+
+  // THE launch under test
+  if (!d.cross) {
+    Fr *o = d.in_place ? v_in0[0]->data() : v_out[0]->data();
+    Fr *ob = !d.pair ? nullptr : d.in_place ? v_in0b[0]->data() : v_outb[0]->data();
+    rc = run_ntt(nullptr, v_in0[0]->data(), mul2 ? v_in1[0]->data() : nullptr, o, tb, (int)d.logn, d.dif != 0, d.inverse != 0, (int)d.pre, (int)d.nbat,
+                 Prof{nullptr, nullptr}, d.pair ? v_in0b[0]->data() : nullptr, d.pair && mul2 ? v_in1b[0]->data() : nullptr, ob, d.want_lo, d.want_n,
+                 d.coset_shift, d.coset_add);
+  } else {
+    const Fr *r_in0[8], *r_in1[8];
+    Fr *r_out[8];
+    for (unsigned r = 0; r < rows; r++) {
+      r_in0[r] = v_in0[r]->data();
+      r_in1[r] = mul2 ? v_in1[r]->data() : nullptr;
+      r_out[r] = d.in_place ? v_in0[r]->data() : v_out[r]->data();
+    }
+    rc = run_ntt_cross(nullptr, tb, (int)d.logn, (int)d.klog, d.dif != 0, d.inverse != 0, (int)d.pre, d.canon != 0, r_in0, mul2 ? r_in1 : nullptr, r_out, d.in_sub,
+                       d.out_sub, d.col_lo, d.col_n, Prof{nullptr, nullptr});
+  }
+  const hipError_t e = hipDeviceSynchronize();  // also after a refused run: the vectors go with this scope
+  if (rc) return rc;
+  if (e != hipSuccess) { set_error("zkr_selftest_ntt: the run failed: %s", hipGetErrorString(e)); return ZKR_ERR_HIP; }
+  int guard_bad = 0;
+  for (auto &v : all)
+    if ((rc = v->download(&guard_bad))) return rc;
+  return guard_bad ? ZKR_ERR_HIP : 0;
+}
 
 template <class F>
 static int msm_hook(const void *points_mont, const void *scalars_std, size_t n, uint8_t *out, int *is_inf, int device) {

@@ -20,6 +20,11 @@ class BookOpts(ctypes.Structure):   # zkr.h zkr_book_opts
     _fields_ = [("nullifier_cap_log2", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("salt", ctypes.c_uint64)]
 
 
+class NttSelftestDesc(ctypes.Structure):   # zkr.h zkr_ntt_selftest_desc
+    _fields_ = [(f, ctypes.c_uint32) for f in ("logn", "tlog", "dif", "inverse", "pre", "nbat", "pair", "in_place", "want_lo", "want_n", "coset_shift",
+                                               "coset_add", "cross", "klog", "col_lo", "col_n", "in_sub", "out_sub", "canon", "reserved")]
+
+
 class ZkrError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("zkr error %d: %s" % (code, msg))
@@ -132,6 +137,7 @@ def lib():
     L.zkr_selftest_f29_forms.argtypes = [i, i, i, c.POINTER(c.c_uint32), sz, c.POINTER(c.c_uint32)]
     L.zkr_selftest_curve29.argtypes = [i, i, i, c.POINTER(c.c_uint32), sz, c.POINTER(c.c_uint32), c.POINTER(c.c_uint8)]
     L.zkr_selftest_fp.argtypes = [i, i, i, c.POINTER(c.c_uint32), sz, c.POINTER(c.c_uint32)]
+    L.zkr_selftest_ntt.argtypes = [i, c.POINTER(NttSelftestDesc)] + [vp] * 6
     L.zkr_mimcsponge_multihash.argtypes = [u8p, sz, u8p]
     L.zkr_babyjub_pubkey.argtypes = [u8p, u8p]
     L.zkr_eddsa_sign.argtypes = [u8p, u8p, sz, u8p]
@@ -1055,6 +1061,56 @@ def selftest_fp(field, op, records, device=0):
     out = (ctypes.c_uint32 * max(1, ow * n))()
     _check(lib().zkr_selftest_fp(device, field, num, flat, n, out))
     return bytes(out)[:4 * ow * n]
+
+
+def _ntt_selftest_desc(desc):
+    d = NttSelftestDesc()
+    fields = dict(desc)
+    fields.setdefault("nbat", 1)
+    fields.setdefault("tlog", fields.get("logn", 0) + fields.get("coset_shift", 0))
+    for k, v in fields.items():
+        if k not in dict(NttSelftestDesc._fields_):
+            raise ValueError("zkr_ntt_selftest_desc has no field %r" % k)
+        setattr(d, k, int(v))
+    return d
+
+
+def ntt_selftest_words(desc):
+    """(words of an input vector, words of an output vector) that zkr_selftest_ntt reads for this descriptor: nbat 2^logn, or for a
+    cross pass the 2^klog row blocks end to end -- col_n words each where in_sub / out_sub say the buffers are local.  None for a
+    shape whose sizes mean nothing (the C side refuses it before it reads a vector)."""
+    d = _ntt_selftest_desc(desc)
+    if not (1 <= d.logn <= 22 and d.nbat >= 1 and d.nbat << d.logn <= 1 << 24):
+        return None
+    if d.cross != 1:
+        return d.nbat << d.logn, d.nbat << d.logn
+    if not (1 <= d.klog <= 3 and d.klog < d.logn):
+        return None
+    rows, block = 1 << d.klog, (1 << d.logn) >> d.klog
+    return rows * (d.col_n if d.in_sub else block), rows * (d.col_n if d.out_sub else block)
+
+
+def selftest_ntt(desc, in0, in1=None, out=None, in0_b=None, in1_b=None, out_b=None, device=0):
+    """zkr_selftest_ntt: ONE run_ntt (or, with cross=1, ONE run_ntt_cross) of csrc/zkr_prove.hip on these vectors.  desc: a dict of
+    the fields of zkr_ntt_selftest_desc (include/zkr.h; tlog defaults to logn + coset_shift, nbat to 1, the rest to 0); the
+    vectors: bytes of 32-byte little-endian standard-form words (cross: the row blocks end to end; ntt_selftest_words has the
+    lengths), None where the mode takes none.  Every vector is copied to the device and back: returns a dict name -> bytes of what
+    each holds after the run -- the raw result in "out" (in place: in "in0"), no bit reversal, no 1/n."""
+    d = _ntt_selftest_desc(desc)
+    bufs = {}
+    for name, v in (("in0", in0), ("in1", in1), ("out", out), ("in0_b", in0_b), ("in1_b", in1_b), ("out_b", out_b)):
+        if v is not None:
+            v = bytes(v)
+            bufs[name] = ctypes.create_string_buffer(v, max(1, len(v)))
+    words = ntt_selftest_words(desc)
+    if words is not None:   # the lengths the C side will read
+        for name, b in bufs.items():
+            need = 32 * words[1 if name.startswith("out") else 0]
+            if len(b) != need:
+                raise ValueError("vector %s has %d bytes, the descriptor asks for %d" % (name, len(b), need))
+    arg = lambda name: ctypes.cast(bufs[name], ctypes.c_void_p) if name in bufs else None
+    _check(lib().zkr_selftest_ntt(device, ctypes.byref(d), arg("in0"), arg("in1"), arg("out"), arg("in0_b"), arg("in1_b"), arg("out_b")))
+    return {name: b.raw for name, b in bufs.items()}
 
 
 def bench_fq_mul(device=0, legacy=False) -> float:

@@ -70,10 +70,12 @@ def test_ntt_matches_oracle(logn):
 
 @pytest.mark.parametrize("logn", [11, 13, 16])
 def test_ntt_extreme_inputs_match_oracle(logn):
-    """The butterflies keep lazily reduced values (kernels_ntt.hpp: sums grow by up to 4 half-moduli per stage of a DIT
-    pass, a DIF pair of stages quadruples one of its outputs before the quotient-estimate reduction): vectors whose
-    entries are all r - 1, only 0 and r - 1, and values whose 29-bit limbs are all ones drive every intermediate to the top
-    of its bound.  Sizes: one full-tile pass (2^11), a short strided pass in front of it (2^13), two long passes (2^16)."""
+    """The butterflies keep lazily reduced values (kernels_ntt.hpp: a DIF pair of stages quadruples one of its outputs before
+    the quotient-estimate reduction): vectors whose entries are all r - 1, only 0 and r - 1, and values whose 29-bit limbs are
+    all ones drive every intermediate to the top of its bound.  zkr_ntt launches DIF passes only, forward and inverse; the DIT
+    bounds (sums grow by up to 4 half-moduli per stage of a DIT pass) are driven by
+    tests/test_gpu_ntt_modes.py::test_structured_inputs_in_every_direction.
+    Sizes: one full-tile pass (2^11), a short strided pass in front of it (2^13), two long passes (2^16)."""
     import zkr_hip
     rnd = random.Random(1000 + logn)
     n = 1 << logn

@@ -30,6 +30,7 @@ def ntt_plan(L, tile_log, strided_log):
     lows = min(L, tile_log)
     rem = L - lows
     if rem > 0:
+        strided_log = min(strided_log, tile_log - 1)   # at least two columns per row of a strided pass
         nch = (rem + strided_log - 1) // strided_log
         hi = L
         for i in range(nch):
@@ -158,6 +159,19 @@ def test_device_plan_shapes():
         assert bits[0][0] == 0 and bits[-1][1] == L and all(a[1] == b[0] for a, b in zip(bits, bits[1:]))
         for lo, hi, wlog in plan[:-1]:
             assert hi - lo <= 9 and hi - lo + wlog <= 11 and wlog <= lo and lo >= 11
+    # the shapes the device tests name: one short strided pass, the even stage counts, two strided passes from 2^21 on
+    assert ntt_plan(13, 11, 9) == [(11, 13, 9), (0, 11, 0)] and ntt_plan(15, 11, 9) == [(11, 15, 7), (0, 11, 0)]
+    assert ntt_plan(20, 11, 9) == [(11, 20, 2), (0, 11, 0)] and ntt_plan(21, 11, 9) == [(16, 21, 6), (11, 16, 6), (0, 11, 0)]
+    # a tile no larger than the strided limit: a strided pass keeps at least two columns per row (tile_log - 1 stages at most)
+    for tile_log in (2, 3, 4, 9, 10):
+        for L in range(1, 28):
+            plan = ntt_plan(L, tile_log, 9)
+            assert plan[-1] == (0, min(L, tile_log), 0)
+            bits = sorted((lo, hi) for lo, hi, _ in plan)
+            assert bits[0][0] == 0 and bits[-1][1] == L and all(a[1] == b[0] for a, b in zip(bits, bits[1:]))
+            for lo, hi, wlog in plan[:-1]:
+                assert 1 <= hi - lo <= min(9, tile_log - 1) and 1 <= wlog and hi - lo + wlog <= tile_log and wlog <= lo
+    assert ntt_plan(9, 4, 9) == [(6, 9, 1), (4, 6, 2), (0, 4, 0)]
 
 
 def test_calc_h_pipeline_constants():
