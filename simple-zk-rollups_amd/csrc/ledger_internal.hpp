@@ -30,14 +30,13 @@ struct SeqView {  // what one call left in device memory; U = 2T updates
 static inline unsigned blocks(size_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
 
 struct DevArena {  // one allocation per ledger, only ever grown; cut into aligned pieces per call
-  char *p = nullptr;
+  Dev<char> p;
   size_t cap = 0, at = 0;
   int reserve(size_t bytes) {
     at = 0;
     if (bytes <= cap) return ZKR_OK;
-    if (p) hipFree(p);
-    p = nullptr, cap = 0;
-    ZKR_HIP_CHECK(hipMalloc((void **)&p, bytes + bytes / 2));
+    cap = 0;
+    if (int rc = p.alloc(bytes + bytes / 2)) return rc;  // the old block goes first: a call keeps nothing in the arena
     cap = bytes + bytes / 2;
     return ZKR_OK;
   }
@@ -50,16 +49,16 @@ struct DevArena {  // one allocation per ledger, only ever grown; cut into align
 };
 
 // The book of a ledger (zkr_book.hip): the contract's key-addressed state beside the tree.  Everything a d_ pointer
-// names lives on the ledger's device and goes with the ledger.
+// names lives on the ledger's device and goes with the book, which goes with the ledger.
 struct LedgerBook {
   // key table: d_keyhash[i] = hashPair(pubX, pubY) of record i; d_keytab holds index + 1 in 2^(depth + 1) slots, 0 = empty
-  Fr *d_keyhash = nullptr;
-  uint32_t *d_keytab = nullptr;
+  Dev<Fr> d_keyhash;
+  Dev<uint32_t> d_keytab;
   bool keys_stale = true;
   uint64_t distinct = 0, rebuilds = 0;
   // nullifier set: d_null[0 .. null_count) in acceptance order; d_nulltab holds position + 1 in null_cap slots
-  Fr *d_null = nullptr;
-  uint32_t *d_nulltab = nullptr;
+  Dev<Fr> d_null;
+  Dev<uint32_t> d_nulltab;
   size_t null_count = 0, null_room = 0, null_cap = 0;  // room: entries d_null has memory for
   bool null_stale = false;
   uint64_t salt = 0;
@@ -73,19 +72,20 @@ struct zkr_ledger {
   size_t accounts = 0;
   uint64_t applied = 0, batches = 0;
   std::vector<uint8_t> records;  // accounts x 128 B
-  zkr::Fr *d_tree = nullptr;     // (2^(depth + 1) - 1) nodes, standard form, leaves first
+  zkr::Dev<zkr::Fr> d_tree;      // (2^(depth + 1) - 1) nodes, standard form, leaves first
   zkr::DevArena arena;
   double stage_ms[5] = {0, 0, 0, 0, 0};
   mutable std::mutex mu;
   // keeping the ledger
   std::vector<uint8_t> empty;    // (depth + 1) x 32 B: the value of an empty subtree per level
   zkr::LedgerJournal journal;    // checkpoints and what every storing call under them overwrote, host part
-  uint32_t *d_joff = nullptr;    // the journal's device part: node offsets ...
-  zkr::Fr *d_jold = nullptr;     // ... and old values, jcap entries each, the first journal.nodes() in use
-  uint32_t *d_jcount = nullptr;
+  zkr::Dev<uint32_t> d_joff;     // the journal's device part: node offsets ...
+  zkr::Dev<zkr::Fr> d_jold;      // ... and old values, jcap entries each, the first journal.nodes() in use
+  zkr::Dev<uint32_t> d_jcount;
   size_t jcap = 0;
   // the contract's side: null until zkr_ledger_book_open
   zkr::LedgerBook *book = nullptr;
+  ~zkr_ledger() { delete book; }
 };
 
 namespace zkr {
@@ -132,7 +132,4 @@ int stage_updates(zkr_ledger *l, const UpdateList &in, size_t accounts, bool che
 int store_updates(zkr_ledger *l, const SeqView &v, const int32_t *last, const uint32_t *idx, const uint8_t *new_rec, hipStream_t s, StageClock &clk, double &slot);
 // zkr_ledger_deposit behind its argument checks, and how the book applies its update lists; `accounts` = the count the list leaves
 int ledger_apply_updates(zkr_ledger *l, const uint32_t *indices, const uint8_t *records, size_t n, size_t accounts);
-int need_device(int device, const char *what);
-// zkr_book.hip
-void book_free(zkr_ledger *l);
 }  // namespace zkr

@@ -101,17 +101,17 @@ struct DevView {  // a typed look at device memory owned elsewhere
 // caller has made `device` current.
 int rollup_device_tables(int device, TxConsts *k) {
   static std::mutex mu;
-  static Fr *d_tab[64] = {nullptr};
+  static Fr *d_tab[64] = {nullptr};  // raw and never freed: made once per device, read by every later call of the process
   std::lock_guard<std::mutex> lk(mu);
   if (device < 0 || device >= 64) { set_error("device index out of range"); return ZKR_ERR_ARG; }
   std::vector<Fr> tab(2 * 253 + MIMC_ROUNDS);
   rollup_device_constants(&k->a, &k->d, k->suborder_m1, tab.data(), tab.data() + 253);
   memcpy(tab.data() + 506, mimc_round_constants(), MIMC_ROUNDS * 32);
   if (!d_tab[device]) {
-    Fr *d = nullptr;
-    ZKR_HIP_CHECK(hipMalloc(&d, tab.size() * 32));
-    if (hipMemcpy(d, tab.data(), tab.size() * 32, hipMemcpyHostToDevice) != hipSuccess) { hipFree(d); set_error("upload of the witness builder's tables failed"); return ZKR_ERR_HIP; }
-    d_tab[device] = d;
+    Dev<Fr> d;
+    if (int rc = d.alloc(tab.size())) return rc;
+    if (hipMemcpy(d, tab.data(), tab.size() * 32, hipMemcpyHostToDevice) != hipSuccess) { set_error("upload of the witness builder's tables failed"); return ZKR_ERR_HIP; }
+    d_tab[device] = d.release();
   }
   k->b8x = d_tab[device], k->b8y = d_tab[device] + 253, k->mimc = d_tab[device] + 506;
   return ZKR_OK;
@@ -201,21 +201,18 @@ extern "C" {
 
 int zkr_mimcsponge_multihash_batch(const void *inputs_std, size_t count, unsigned arity, void *out_std, int device) {
   if (!inputs_std || !out_std || arity < 1 || arity > 64) { set_error("bad argument"); return ZKR_ERR_ARG; }
-  if (zkr_device_count() <= device || device < 0) { set_error("no HIP device %d; the batch hash runs on the GPU (zkr_mimcsponge_multihash is the host call)", device); return ZKR_ERR_NO_DEVICE; }
+  int rc = need_device(device, "the batch hash (zkr_mimcsponge_multihash is the host call)");
+  if (rc) return rc;
   if (count == 0) return ZKR_OK;
   ZKR_HIP_CHECK(hipSetDevice(device));
-  int rc = upload_constants(device);
-  if (rc) return rc;
-  Fr *d_in = nullptr, *d_out = nullptr;
-  ZKR_HIP_CHECK(hipMalloc(&d_in, count * arity * 32));
-  if (hipMalloc(&d_out, count * 32) != hipSuccess) { hipFree(d_in); set_error("out of device memory"); return ZKR_ERR_HIP; }
+  if ((rc = upload_constants(device))) return rc;
+  Dev<Fr> d_in, d_out;
+  if ((rc = d_in.alloc(count * arity)) || (rc = d_out.alloc(count))) return rc;
   hipError_t e = hipMemcpy(d_in, inputs_std, count * arity * 32, hipMemcpyHostToDevice);
   if (e == hipSuccess) {
     mimc_multihash_kernel<<<(unsigned)((count + 255) / 256), 256>>>(d_in, count, arity, d_out);
     e = hipMemcpy(out_std, d_out, count * 32, hipMemcpyDeviceToHost);
   }
-  hipFree(d_in);
-  hipFree(d_out);
   if (e != hipSuccess) { set_error("batch hash failed: %s", hipGetErrorString(e)); return ZKR_ERR_HIP; }
   return ZKR_OK;
 }
@@ -227,7 +224,7 @@ static int witness_batch(uint32_t batch, uint32_t depth, const uint8_t *inputs, 
   if ((!inputs && !d_inputs && n_batches) || !d_witnesses) { set_error("null argument"); return ZKR_ERR_ARG; }
   int rc = rollup_check_geometry(batch, depth);
   if (rc) return rc;
-  if (zkr_device_count() <= device || device < 0) { set_error("no HIP device %d; the batch witness builder runs on the GPU (zkr_rollup_witness is the host call)", device); return ZKR_ERR_NO_DEVICE; }
+  if ((rc = need_device(device, "the batch witness builder (zkr_rollup_witness is the host call)"))) return rc;
   const uint32_t p = rollup_n_public(batch, depth), K = rollup_tx_private_count(depth);
   if (n_inputs != p - 1) { set_error("rollup circuit (%u, %u) takes %u inputs, got %zu", batch, depth, p - 1, n_inputs); return ZKR_ERR_ARG; }
   if (n_batches == 0) return ZKR_OK;
@@ -240,8 +237,8 @@ static int witness_batch(uint32_t batch, uint32_t depth, const uint8_t *inputs, 
   // Scratch kept per device and only ever grown: hipMalloc / hipFree synchronise the whole device, i.e. every call would wait
   // for the proofs in flight on the key's streams (measured: the builder's 30 ms became the 63 ms of the prove call beside it).
   // One call per device at a time (the lock is held to the end of the call).
-  struct Scratch { void *p = nullptr; size_t cap = 0; };
-  static Scratch scratch[64][4];
+  struct Scratch { DevBuf mem; size_t cap = 0; };
+  static Scratch(*const scratch)[4] = new Scratch[64][4];  // never freed: the blocks live as long as the process
   static std::mutex scratch_mu[64];
   std::lock_guard<std::mutex> scratch_lock(scratch_mu[device]);
   const uint32_t ROWS = TX_PARTS + 1;  // a row of statement codes per part, one for tx_finish
@@ -249,18 +246,17 @@ static int witness_batch(uint32_t batch, uint32_t depth, const uint8_t *inputs, 
   for (int j = 0; j < 4; j++) {
     Scratch &sc = scratch[device][j];
     if (sc.cap >= want[j]) continue;
-    if (sc.p) hipFree(sc.p);
-    sc.p = nullptr, sc.cap = 0;
-    ZKR_HIP_CHECK(hipMalloc(&sc.p, want[j] + want[j] / 2));
+    sc.cap = 0;
+    if ((rc = sc.mem.alloc(want[j] + want[j] / 2))) return rc;  // the old block goes first: a call keeps nothing in it
     sc.cap = want[j] + want[j] / 2;
   }
-  const DevView b_in{d_inputs ? const_cast<void *>(d_inputs) : scratch[device][0].p}, b_ws{scratch[device][1].p}, b_roots{scratch[device][2].p}, b_errs{scratch[device][3].p};
+  const DevView b_in{d_inputs ? const_cast<void *>(d_inputs) : scratch[device][0].mem.p}, b_ws{scratch[device][1].mem}, b_roots{scratch[device][2].mem}, b_errs{scratch[device][3].mem};
   // Its own stream (non-blocking, highest priority): the builder is a handful of long-running wavefronts that must neither wait
   // for nor hold up the proofs in flight on the key's streams; nothing here synchronises the device.
   // Made once per device and kept (the scratch lock above serialises the calls): streams that come and go reshuffle the
   // runtime's hardware queues under the provers' streams (zkr_key.hip DeviceStreams).
   struct StreamRef { hipStream_t s = nullptr; };
-  static StreamRef kept[64];
+  static StreamRef kept[64];  // raw and never destroyed, on purpose (above)
   if (!d_inputs && !kept[device].s) {
     int prio_lo = 0, prio_hi = 0;
     ZKR_HIP_CHECK(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
@@ -353,13 +349,13 @@ const char *zkr_rollup_statement_text(uint32_t stmt) { return stmt < ST_COUNT ? 
 
 int zkr_balance_tree_build(const void *leaves_std, unsigned depth, void *levels_out, int device) {
   if (!leaves_std || !levels_out || depth < 1 || depth > 28) { set_error("bad argument"); return ZKR_ERR_ARG; }
-  if (zkr_device_count() <= device || device < 0) { set_error("no HIP device %d", device); return ZKR_ERR_NO_DEVICE; }
+  if (int drc = need_device(device)) return drc;
   ZKR_HIP_CHECK(hipSetDevice(device));
   int rc = upload_constants(device);
   if (rc) return rc;
   const size_t n = (size_t)1 << depth, total = 2 * n - 1;
-  Fr *d = nullptr;
-  ZKR_HIP_CHECK(hipMalloc(&d, total * 32));
+  Dev<Fr> d;
+  if ((rc = d.alloc(total))) return rc;
   hipError_t e = hipMemcpy(d, leaves_std, n * 32, hipMemcpyHostToDevice);
   size_t off = 0, width = n;
   while (e == hipSuccess && width > 1) {  // level l+1 = hashLeftRight of adjacent pairs of level l (merkletree.ts:70-82)
@@ -369,7 +365,6 @@ int zkr_balance_tree_build(const void *leaves_std, unsigned depth, void *levels_
     width >>= 1;
   }
   if (e == hipSuccess) e = hipMemcpy(levels_out, d, total * 32, hipMemcpyDeviceToHost);
-  hipFree(d);
   if (e != hipSuccess) { set_error("tree build failed: %s", hipGetErrorString(e)); return ZKR_ERR_HIP; }
   return ZKR_OK;
 }

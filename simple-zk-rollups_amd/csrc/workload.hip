@@ -207,11 +207,10 @@ struct Generated {
   Toxic tox;
   SetupScalars sc;
   bool secret = false;  // fresh toxic waste (zkr_setup_r1cs without injected scalars): everything derived from it is wiped
-  void *d_tbl[N_TABLES] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  DevBuf d_tbl[N_TABLES];
   uint8_t consts[448];
   std::vector<uint8_t> ic_std, gamma2_std;
   ~Generated() {
-    for (auto p : d_tbl) if (p) hipFree(p);
     if (secret) {  // t, alfa, beta, gamma, delta and the per-signal / per-power scalars (a_s, b_s, c_s, K_s/delta, K_s/gamma, t^i Z/delta):
                    // any of them lets its holder forge proofs for the generated key
       explicit_bzero((void *)&tox, sizeof(tox));
@@ -235,22 +234,20 @@ static int setup_from_circuit(int device, Generated &g) {
   for (int t = 0; t < N_TABLES; t++) {
     if (g.secret) wipe_vector(bytes);
     to_std_bytes(*src[t], bytes);
-    if ((rc = fixed_base_points(device, t == T_B2, bytes.data(), src[t]->size(), &g.d_tbl[t], g.secret))) return rc;
+    if ((rc = fixed_base_points(device, t == T_B2, bytes.data(), src[t]->size(), g.d_tbl[t], g.secret))) return rc;
   }
   // vk_alfa_1, vk_beta_1, vk_delta_1 | vk_beta_2, vk_delta_2  (header layout binarify.ts:163-167)
   std::vector<Fr> g1s = {g.tox.alfa, g.tox.beta, g.tox.delta}, g2s = {g.tox.beta, g.tox.delta, g.tox.gamma};
-  void *d = nullptr;
+  DevBuf d;
   if (g.secret) wipe_vector(bytes);
   to_std_bytes(g1s, bytes);
-  if ((rc = fixed_base_points(device, false, bytes.data(), 3, &d, g.secret))) return rc;
+  if ((rc = fixed_base_points(device, false, bytes.data(), 3, d, g.secret))) return rc;
   ZKR_HIP_CHECK(hipMemcpy(g.consts, d, 192, hipMemcpyDeviceToHost));
-  hipFree(d);
   to_std_bytes(g2s, bytes);
-  if ((rc = fixed_base_points(device, true, bytes.data(), 3, &d, g.secret))) return rc;
+  if ((rc = fixed_base_points(device, true, bytes.data(), 3, d, g.secret))) return rc;
   if (g.secret) { wipe_vector(g1s); wipe_vector(g2s); }
   uint8_t g2pts[384];
   ZKR_HIP_CHECK(hipMemcpy(g2pts, d, 384, hipMemcpyDeviceToHost));
-  hipFree(d);
   memcpy(g.consts + 192, g2pts, 256);
   G2Affine gm = load_g2(g2pts + 256);
   g.gamma2_std.resize(128);
@@ -258,10 +255,9 @@ static int setup_from_circuit(int device, Generated &g) {
   // IC points for the checker
   if (g.secret) wipe_vector(bytes);
   to_std_bytes(g.sc.ic, bytes);
-  if ((rc = fixed_base_points(device, false, bytes.data(), g.sc.ic.size(), &d, g.secret))) return rc;
+  if ((rc = fixed_base_points(device, false, bytes.data(), g.sc.ic.size(), d, g.secret))) return rc;
   std::vector<uint8_t> icm(g.sc.ic.size() * 64);
   ZKR_HIP_CHECK(hipMemcpy(icm.data(), d, icm.size(), hipMemcpyDeviceToHost));
-  hipFree(d);
   g.ic_std.resize(icm.size());
   for (size_t i = 0; i < g.sc.ic.size(); i++) store_g1_std(&g.ic_std[i * 64], load_g1(&icm[i * 64]));
   return 0;
@@ -288,7 +284,7 @@ struct KeptPoints {
 };
 // CSR rows of the QAP (A gets the nPublic+1 input-consistency rows), the kept points of every table, then the arena.
 // d_tbl: device tables; the C point of private signal s is entry s - nPublic - 1 + c_src_base of d_tbl[T_C].
-static int build_key_from_tables(const Circuit &c, const KeptPoints &keep, void *const d_tbl[N_TABLES], uint32_t c_src_base, const uint8_t *consts448, int device,
+static int build_key_from_tables(const Circuit &c, const KeptPoints &keep, const DevBuf d_tbl[N_TABLES], uint32_t c_src_base, const uint8_t *consts448, int device,
                                  zkr_key **key_out) {
   uint32_t n = c.n, p = c.p, m = c.m;
   // QAP rows in CSR (A gets the nPublic+1 input-consistency rows)
@@ -384,33 +380,29 @@ static int key_build_eval_tables(zkr_key *k, const Generated &g, bool refuse) {
   }
   EvalTables &ev = k->eval;
   auto give_up = [&](bool hip_failed) { if (hip_failed) (void)hipGetLastError(); key_eval_tables_free(k); return 0; };
-  // level 0 from the scalars, then the window levels in place (msm_precompute), in a buffer sized as arena_layout sizes a table's
-  auto table = [&](const std::vector<Fr> &scalars, const MsmPlan &pl, void **out) -> int {
+  // level 0 from the scalars, then the window levels in place (msm_precompute)
+  auto table = [&](const std::vector<Fr> &scalars, const MsmPlan &pl, void *out) -> int {
     const size_t np = scalars.size();
-    if (hipMalloc(out, np * pl.K * 64 + 64) != hipSuccess) { *out = nullptr; return 1; }
     to_std_bytes(scalars, sec.bytes);
-    void *lvl0 = nullptr;
-    if (int rc = fixed_base_points(k->device, false, sec.bytes.data(), np, &lvl0, g.secret)) return rc;
-    hipError_t e = hipMemcpy(*out, lvl0, np * 64, hipMemcpyDeviceToDevice);
-    hipFree(lvl0);
+    DevBuf lvl0;
+    if (int rc = fixed_base_points(k->device, false, sec.bytes.data(), np, lvl0, g.secret)) return rc;
+    hipError_t e = hipMemcpy(out, lvl0, np * 64, hipMemcpyDeviceToDevice);
     if (e != hipSuccess) { set_error("copy of a side table's base points failed: %s", hipGetErrorString(e)); return ZKR_ERR_HIP; }
-    return msm_precompute(k->device, false, *out, (uint32_t)np, pl);
+    return msm_precompute(k->device, false, out, (uint32_t)np, pl);
   };
   int rc;
-  if ((rc = table(sec.c_sc, k->plan[T_C], &ev.c_pts)) > 0) return give_up(true);
-  if (rc) { give_up(false); return rc; }
-  if ((rc = table(sec.es.eprime, k->plan[T_H], &ev.e_pts)) > 0) return give_up(true);
-  if (rc) { give_up(false); return rc; }
   if ((rc = key_eval_rows(k, c)) > 0) return give_up(true);
+  if (!rc) rc = table(sec.c_sc, k->plan[T_C], ev.c_pts);
+  if (!rc) rc = table(sec.es.eprime, k->plan[T_H], ev.e_pts);
   if (rc) { give_up(false); return rc; }
   ev.ready = true;
   return 0;
 }
 
-// What a key's side tables need beside their points, whoever made those (above; zkr_eval_tables.hip): C by row over the whole
-// domain (rows from nConstraints on are empty), STANDARD-form coefficients -- with the standard-form witness the row sums come out
-// as c_j / R, which is what one product of a_j and b_j leaves (kernels_ntt.hpp eval_unsatisfied_kernel) -- and, per proof
-// slot, a counter for each proof of a fused group (the slot's capacity).  Above zero: an allocation failed (the caller gives the tables up); below: a failed copy.
+// Room for a whole key's side tables (eval_tables_alloc; whoever fills the points: above, zkr_eval_tables.hip) and what they need
+// beside their points: C by row over the whole domain (rows from nConstraints on are empty), STANDARD-form coefficients -- with the
+// standard-form witness the row sums come out as c_j / R, which is what one product of a_j and b_j leaves (kernels_ntt.hpp
+// eval_unsatisfied_kernel).  Above zero: an allocation failed (the caller gives the tables up); below: a failed copy.
 int key_eval_rows(zkr_key *k, const Circuit &c) {
   const uint32_t m = k->h.m;
   EvalTables &ev = k->eval;
@@ -421,14 +413,7 @@ int key_eval_rows(zkr_key *k, const Circuit &c) {
   for (uint32_t r = 0; r <= m; r++) rowptr[r] = c.rowC[r < c.nC ? r : c.nC];
   for (uint32_t r = 0; r < c.nC; r++)
     if (rowptr[r + 1] - rowptr[r] > 8) wide.push_back(r);  // kernels_ntt.hpp SPMV_WIDE
-  ev.nnz = (uint32_t)sig.size();
-  ev.n_wide = (uint32_t)wide.size();
-  bool ok = hipMalloc(&ev.c_rowptr, rowptr.size() * 4) == hipSuccess && hipMalloc(&ev.c_col, sig.size() * 4 + 4) == hipSuccess &&
-            hipMalloc(&ev.c_coef, coef.size() * 32 + 32) == hipSuccess && hipMalloc(&ev.c_wide, wide.size() * 4 + 4) == hipSuccess;
-  for (ProofSlot &sl : k->slot)
-    ok = ok && hipMalloc(&sl.d_bad, (size_t)sl.cap * 4) == hipSuccess && hipHostMalloc(&sl.h_bad, (size_t)sl.cap * 4, hipHostMallocDefault) == hipSuccess;
-  if (!ok) return 1;
-  for (ProofSlot &sl : k->slot) memset(sl.h_bad, 0, (size_t)sl.cap * 4);
+  if (!eval_tables_alloc(k, k->h.npts[k->layout.sort_src[T_C]], m, (uint32_t)sig.size(), (uint32_t)wide.size())) return 1;
   hipError_t e = hipMemcpy(ev.c_rowptr, rowptr.data(), rowptr.size() * 4, hipMemcpyHostToDevice);
   if (e == hipSuccess && !sig.empty()) e = hipMemcpy(ev.c_col, sig.data(), sig.size() * 4, hipMemcpyHostToDevice);
   if (e == hipSuccess && !coef.empty()) e = hipMemcpy(ev.c_coef, coef.data(), coef.size() * 32, hipMemcpyHostToDevice);

@@ -208,10 +208,9 @@ int nulls_room(LedgerBook *b, size_t inserts) {
   while (b->null_count + inserts > cap / 2) cap *= 2;
   if (cap == b->null_cap) return ZKR_OK;
   if (cap > ((size_t)1 << 31)) { set_error("the nullifier set cannot hold %zu entries", b->null_count + inserts); return ZKR_ERR_ARG; }
-  Fr *arr = nullptr;
-  uint32_t *tab = nullptr;
-  if (hipMalloc((void **)&arr, cap / 2 * 32) != hipSuccess || hipMalloc((void **)&tab, cap * 4) != hipSuccess) {
-    if (arr) hipFree(arr);
+  Dev<Fr> arr;
+  Dev<uint32_t> tab;
+  if (arr.alloc(cap / 2) || tab.alloc(cap)) {
     set_error("out of device memory for a nullifier table of %zu slots", cap);
     return ZKR_ERR_HIP;
   }
@@ -220,14 +219,9 @@ int nulls_room(LedgerBook *b, size_t inserts) {
   int rc = ZKR_OK;
   if (e == hipSuccess) rc = launch_claim(tab, (uint32_t)cap, arr, 1, 0, b->null_count, b->salt, 1, nullptr, nullptr);
   if (e == hipSuccess && !rc) e = hipDeviceSynchronize();
-  if (e != hipSuccess || rc) {
-    hipFree(arr), hipFree(tab);
-    if (e != hipSuccess) { set_error("growing the nullifier table failed: %s", hipGetErrorString(e)); return ZKR_ERR_HIP; }
-    return rc;
-  }
-  if (b->d_null) hipFree(b->d_null);
-  if (b->d_nulltab) hipFree(b->d_nulltab);
-  b->d_null = arr, b->d_nulltab = tab, b->null_cap = cap, b->null_room = cap / 2, b->null_stale = false;
+  if (e != hipSuccess) { set_error("growing the nullifier table failed: %s", hipGetErrorString(e)); return ZKR_ERR_HIP; }
+  if (rc) return rc;
+  b->d_null = std::move(arr), b->d_nulltab = std::move(tab), b->null_cap = cap, b->null_room = cap / 2, b->null_stale = false;
   return ZKR_OK;
 }
 
@@ -334,15 +328,6 @@ int withdraw_calls(zkr_ledger *l, const uint8_t *publics, const void *const *d_w
 }
 }  // namespace
 
-void book_free(zkr_ledger *l) {  // the device side; the caller has selected the device and deletes the struct
-  LedgerBook *b = l->book;
-  if (!b) return;
-  if (b->d_keyhash) hipFree(b->d_keyhash);
-  if (b->d_keytab) hipFree(b->d_keytab);
-  if (b->d_null) hipFree(b->d_null);
-  if (b->d_nulltab) hipFree(b->d_nulltab);
-  b->d_keyhash = b->d_null = nullptr, b->d_keytab = b->d_nulltab = nullptr;
-}
 }  // namespace zkr
 
 using namespace zkr;
@@ -372,13 +357,11 @@ int zkr_ledger_book_open(zkr_ledger *l, const zkr_book_opts *opts, const void *b
   memcpy(b->fees.w, h.fees, 32);
   l->book = b;
   auto fail = [&](int code) {
-    book_free(l);
     delete b;
     l->book = nullptr;
     return code;
   };
-  if (hipMalloc((void **)&b->d_keyhash, ((size_t)1 << l->depth) * 32) != hipSuccess || hipMalloc((void **)&b->d_keytab, ((size_t)2 << l->depth) * 4) != hipSuccess ||
-      hipMalloc((void **)&b->d_null, b->null_room * 32) != hipSuccess || hipMalloc((void **)&b->d_nulltab, b->null_cap * 4) != hipSuccess) {
+  if (b->d_keyhash.alloc((size_t)1 << l->depth) || b->d_keytab.alloc((size_t)2 << l->depth) || b->d_null.alloc(b->null_room) || b->d_nulltab.alloc(b->null_cap)) {
     set_error("out of device memory for the book of a ledger of depth %u", l->depth);
     return fail(ZKR_ERR_HIP);
   }

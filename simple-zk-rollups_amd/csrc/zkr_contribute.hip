@@ -298,11 +298,9 @@ int zkr_key_contribution_verify(const zkr_key *before, const zkr_key *after, con
     void *base = nullptr;
     size_t base_len = 0;
     if (int rc = zkr_key_base_arena(const_cast<zkr_key *>(after), &base, &base_len)) return rc;
-    unsigned char *tmp = nullptr;
+    Dev<unsigned char> tmp;
     ArenaHeader ht;
-    if (int rc = arena_from_base(base, base_len, device, &tmp, &ht)) return rc;
-    DevBuf tmp_owner;
-    tmp_owner.p = tmp;
+    if (int rc = arena_from_base(base, base_len, device, tmp, &ht)) return rc;
     std::vector<CmpRange> rg;
     for (int t : {T_C, T_H}) rg.push_back(range_of(ha.off_pts[t], ht.off_pts[t], (uint64_t)ha.npts[t] * levels(t) * 64, ZKR_KEYSEC_POINTS, (uint32_t)t));
     uint32_t first = 0;

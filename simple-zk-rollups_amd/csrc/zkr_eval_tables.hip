@@ -52,7 +52,7 @@ int add_each_hook(void *points_mont, const void *addends_mont, size_t n) {
   return 0;
 }
 
-// The two point tables, on the key's device, under k->mu with no proof in flight.  0 with *why = null: both are in k->eval;
+// The two point tables, into the room key_eval_rows made, on the key's device, under k->mu with no proof in flight.  0 with *why = null: both are in k->eval;
 // 0 with a reason: the key keeps the coefficient form (nothing is left allocated); below zero: a kernel or a copy failed.
 int derive_points(zkr_key *k, const Circuit &c, const unsigned char *base, const char **why) {
   const ArenaHeader &h = k->h;
@@ -69,9 +69,8 @@ int derive_points(zkr_key *k, const Circuit &c, const unsigned char *base, const
 
   const size_t n_z = m > np_c ? m : np_c;
   DevBuf pw, tmp, tw, ztmp, sc;
-  if (hipMalloc(&pw.p, (size_t)m * sizeof(G1Affine)) != hipSuccess || hipMalloc(&tmp.p, (size_t)m * sizeof(G1Affine)) != hipSuccess ||
-      hipMalloc(&tw.p, ((size_t)m / 2 + 1) * sizeof(Fr)) != hipSuccess || hipMalloc(&ztmp.p, 2 * n_z * sizeof(Fq)) != hipSuccess || hipMalloc(&sc.p, (size_t)m * sizeof(Fr)) != hipSuccess ||
-      hipMalloc(&ev.e_pts, (size_t)m * k->plan[T_H].K * 64 + 64) != hipSuccess || hipMalloc(&ev.c_pts, (size_t)np_c * k->plan[T_C].K * 64 + 64) != hipSuccess)
+  if (pw.alloc((size_t)m * sizeof(G1Affine)) || tmp.alloc((size_t)m * sizeof(G1Affine)) || tw.alloc(((size_t)m / 2 + 1) * sizeof(Fr)) ||
+      ztmp.alloc(2 * n_z * sizeof(Fq)) || sc.alloc((size_t)m * sizeof(Fr)))
     return give_up(no_memory);
   G1Affine *P = pw.as<G1Affine>();
   const unsigned grid_m = (m + 255) / 256;
@@ -111,7 +110,7 @@ int derive_points(zkr_key *k, const Circuit &c, const unsigned char *base, const
     QapColumns cols;
     qap_columns(c, 2, cols);
     DevBuf comb;
-    if ((rc = g1_combine_columns(n, cols, P, &comb.p))) return rc;
+    if ((rc = g1_combine_columns(n, cols, P, comb))) return rc;
     ZKR_HIP_CHECK(hipMemcpy(ev.c_pts, base_c, (size_t)np_c * sizeof(G1Affine), hipMemcpyDeviceToDevice));
     const uint32_t *rank = h.rank_identity[lt] ? nullptr : (const uint32_t *)(k->arena + h.off_rank[lt]);
     FaultCounter unplaced;
@@ -158,8 +157,9 @@ int zkr_key_eval_tables(zkr_key *key, const void *r1cs_bin, size_t r1cs_len, uns
   if (const char *e = getenv("ZKR_H_FORM"); e && !strcmp(e, "coefficients")) { set_error("zkr_key_eval_tables: not built: ZKR_H_FORM=coefficients"); return 0; }
   if (!h.npts[T_C] || h.npts[T_H] != h.m) { set_error("zkr_key_eval_tables: not built: the key's H table dropped a point, or it has no C points"); return 0; }
   const char *why = nullptr;
-  int rc = derive_points(key, c, (const unsigned char *)base, &why);
-  if (!rc && !why && (rc = key_eval_rows(key, c)) > 0) { rc = 0; why = "the device has no memory for the side tables"; }
+  int rc = key_eval_rows(key, c);
+  if (rc > 0) { rc = 0; why = "the device has no memory for the side tables"; }
+  if (!rc && !why) rc = derive_points(key, c, (const unsigned char *)base, &why);
   if (rc || why) {
     (void)hipGetLastError();
     key_eval_tables_free(key);

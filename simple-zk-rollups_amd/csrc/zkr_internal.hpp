@@ -11,13 +11,13 @@
 #include <vector>
 #include "../../include/zkr.h"
 #include "hostops.hpp"
+#include "zkr_owners.hpp"
 #include "msm_plan.hpp"
 #include "shard_group.hpp"
 
 namespace zkr {
 
 struct Tw29;  // kernels_ntt.hpp: a butterfly twiddle as nine 29-bit limbs
-void set_error(const char *fmt, ...);
 int os_random(void *out, size_t bytes);  // `bytes` from the OS CSPRNG (zkr_key.hip, beside set_error); ZKR_ERR_ARG with a message when it cannot be read
 // every entry point that needs a GPU refuses the same way when there is none
 inline int need_device(int device) {
@@ -25,27 +25,12 @@ inline int need_device(int device) {
   if (found <= device || device < 0) { set_error("no HIP device %d (found %d); libzkr_hip has no CPU fallback", device, found); return ZKR_ERR_NO_DEVICE; }
   return 0;
 }
-#define ZKR_HIP_CHECK(expr)                                                                 \
-  do {                                                                                      \
-    hipError_t _e = (expr);                                                                 \
-    if (_e != hipSuccess) {                                                                 \
-      set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-      return ZKR_ERR_HIP;                                                                   \
-    }                                                                                       \
-  } while (0)
+// the same for a call that has a name of its own: `what`, with the host call that does the same job where there is one
+inline int need_device(int device, const char *what) {
+  if (zkr_device_count() <= device || device < 0) { set_error("no HIP device %d; %s runs on the GPU and has no CPU fallback", device, what); return ZKR_ERR_NO_DEVICE; }
+  return 0;
+}
 
-// a device allocation (or a HIP event) that goes when its scope ends: the test hooks and one-off entry points return early on
-// every failed HIP call, and none of those paths may leave device memory behind
-struct DevBuf {
-  void *p = nullptr;
-  DevBuf() = default;
-  DevBuf(const DevBuf &) = delete;
-  DevBuf &operator=(const DevBuf &) = delete;
-  ~DevBuf() { if (p) hipFree(p); }
-  int alloc(size_t bytes) { ZKR_HIP_CHECK(hipMalloc(&p, bytes ? bytes : 1)); return 0; }
-  template <class T> T *as() const { return static_cast<T *>(p); }
-  void *release() { void *q = p; p = nullptr; return q; }
-};
 // "How many are bad, and which comes first": the two words a checking kernel updates with group_note_bad (kernels_group.hpp).
 struct FaultCounter {
   DevBuf buf;
@@ -65,14 +50,6 @@ struct FaultCounter {
     count = res[0]; first = res[1];
     return 0;
   }
-};
-struct ScopedEvent {
-  hipEvent_t e = nullptr;
-  ScopedEvent() = default;
-  ScopedEvent(const ScopedEvent &) = delete;
-  ScopedEvent &operator=(const ScopedEvent &) = delete;
-  ~ScopedEvent() { if (e) hipEventDestroy(e); }
-  int create() { ZKR_HIP_CHECK(hipEventCreate(&e)); return 0; }
 };
 
 // The device key is ONE position-independent arena: header + sections addressed by byte offsets,
@@ -108,24 +85,24 @@ inline uint32_t rank_entries(const ArenaHeader &h, int t) { return h.sc_n[t == T
 
 // digit records of one scalar vector, split by bucket range (kernels_msm.hpp "digit sort", stage 1)
 struct DigitLists {
-  uint32_t *rng = nullptr;  // counts[range][XCD slot] | fill cursors[range][XCD slot] | range offsets[nR + 1]  (kernels_msm.hpp DIGIT_RNG_WORDS)
-  uint32_t *ent_s = nullptr, *ent_b = nullptr;
+  Dev<uint32_t> rng;  // counts[range][XCD slot] | fill cursors[range][XCD slot] | range offsets[nR + 1]  (kernels_msm.hpp DIGIT_RNG_WORDS)
+  Dev<uint32_t> ent_s, ent_b;
 };
 
 // The digit sort of one point set: bucket occupancies, offsets and the sorted entry list, read by the accumulation of every table over
 // that point set (B2 over B1's, C over A's: ProofLayout::sort_src) and by their oversized-bucket kernels.
 struct MsmSort {
-  uint32_t *counts = nullptr, *offsets = nullptr, *entries = nullptr;
-  uint32_t *size_hist = nullptr, *order = nullptr;  // [2][SIZE_BINS] size-class histogram + hand-out counters; bucket ids fullest first
-  uint32_t *chunk_cnt = nullptr;  // [K][J][nbw] per-chunk bucket occupancies, then per-bucket prefixes over chunks
-  uint32_t *big_list = nullptr, *big_count = nullptr, *block_sums = nullptr;
+  Dev<uint32_t> counts, offsets, entries;
+  Dev<uint32_t> size_hist, order;  // [2][SIZE_BINS] size-class histogram + hand-out counters; bucket ids fullest first
+  Dev<uint32_t> chunk_cnt;  // [K][J][nbw] per-chunk bucket occupancies, then per-bucket prefixes over chunks
+  Dev<uint32_t> big_list, big_count, block_sums;
   size_t max_nb = 0, max_entries = 0;
 };
 // One reduction chain: `sets` bucket sets per proof end to end (the fused proofs of each set together) with the buffers of the
 // launch set that reduces them (ChainLayout).  result / h_result: one point per set and proof, set-major.
 struct MsmChain {
-  void *buckets = nullptr, *group_out = nullptr, *task_out = nullptr, *result = nullptr;
-  void *h_result = nullptr;  // pinned host copy of the result points (XYZZ)
+  DevBuf buckets, group_out, task_out, result;
+  PinnedBuf h_result;  // pinned host copy of the result points (XYZZ)
   size_t sets = 1;
   bool g2 = false;
 };
@@ -134,12 +111,8 @@ struct MsmChain {
 struct MsmScratch {
   DigitLists dig;
   MsmSort sort;
-  void *big_partials = nullptr;
+  DevBuf big_partials;
   MsmChain chain;
-  MsmScratch() = default;
-  MsmScratch(const MsmScratch &) = delete;
-  MsmScratch &operator=(const MsmScratch &) = delete;
-  ~MsmScratch();
 };
 
 struct ProfStage {
@@ -166,21 +139,20 @@ constexpr int MAX_FUSE = 16;  // most proofs one launch set carries (zkr_key.hip
 // witnesses do.
 constexpr int STAGE_BUFS = PROOF_SLOTS + 1;
 struct WitnessStage {
-  Fr *d_w = nullptr;         // its device copy, read by ingest_kernel
-  hipEvent_t ev_up = nullptr;
+  Dev<Fr> d_w;         // its device copy, read by ingest_kernel
+  ScopedEvent ev_up;
   bool busy = false;
 };
 struct ProofSlot {
-  Fr *d_w = nullptr, *va = nullptr, *vb = nullptr, *ca = nullptr, *cb = nullptr, *d_h = nullptr;
+  Dev<Fr> d_w, va, vb, ca, cb, d_h;
   DigitLists dig_w, dig_h;  // digit records of w (shared by A, B1, B2, C) and of h
   MsmSort sort[N_TABLES];          // of the tables that own their sort (layout.sort_src[t] == t) and have points
-  void *big_partials[N_TABLES] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // oversized-bucket partial sums of every table that has points
+  DevBuf big_partials[N_TABLES];  // oversized-bucket partial sums of every table that has points
   MsmChain chain[N_TABLES];        // the first layout.n_chains of them
-  hipEvent_t ev_w = nullptr, ev_h = nullptr;
-  hipEvent_t ev_end[3] = {nullptr, nullptr, nullptr};  // end of the proof's work on the G2-chain, G1-chain and auxiliary streams
-  hipEvent_t ev_done[N_TABLES] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  hipEvent_t ev_sorted[N_TABLES] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  hipEvent_t ev_res[N_TABLES] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // by chain: its result points have landed in its pinned host buffer
+  ScopedEvent ev_w, ev_h;
+  ScopedEvent ev_end[3];  // end of the proof's work on the G2-chain, G1-chain and auxiliary streams
+  ScopedEvent ev_done[N_TABLES], ev_sorted[N_TABLES];
+  ScopedEvent ev_res[N_TABLES];  // by chain: its result points have landed in its pinned host buffer
   bool res_pending[N_TABLES] = {false, false, false, false, false};
   int cap = 1;    // proofs one submit can fuse into shared launches (small circuits; every buffer above is cap times one proof's)
   int nbat = 0;   // proofs of the group in flight
@@ -189,9 +161,10 @@ struct ProofSlot {
   // H in evaluation form (EvalTables): the proof in flight took that path; rows of its witness with a_j b_j != c_j, counted on the
   // device and copied to the pinned word before the sort of H (so it has landed when the proof's last chain has)
   bool eval = false;
-  uint32_t *d_bad = nullptr, *h_bad = nullptr;
+  Dev<uint32_t> d_bad;
+  Pinned<uint32_t> h_bad;
   std::vector<ProfSpan> spans;
-  std::vector<hipEvent_t> event_pool;
+  std::vector<ScopedEvent> event_pool;
   size_t event_next = 0;
 };
 }  // namespace zkr
@@ -207,21 +180,22 @@ namespace zkr {
 // where a scalar is zero; E': m points in natural order), so a proof uses the same sorts, bucket sets and chains either way.
 struct EvalTables {
   bool ready = false;
-  void *c_pts = nullptr, *e_pts = nullptr;
-  uint32_t *c_rowptr = nullptr, *c_col = nullptr, *c_wide = nullptr;  // C by QAP row, as the arena holds A and B, but with
-  Fr *c_coef = nullptr;                                               // STANDARD-form coefficients: the row sums come out as c_j / R
+  DevBuf c_pts, e_pts;
+  Dev<uint32_t> c_rowptr, c_col, c_wide;  // C by QAP row, as the arena holds A and B, but with
+  Dev<Fr> c_coef;                         // STANDARD-form coefficients: the row sums come out as c_j / R
   uint32_t n_wide = 0, nnz = 0;
   std::atomic<uint64_t> retries{0};  // proofs proved again through the coefficient form (their witness did not satisfy the R1CS)
 };
 int key_eval_tables_free(zkr_key *k);  // zkr_key.hip
+bool eval_tables_alloc(zkr_key *k, uint32_t np_c, uint32_t np_e, uint32_t nnz, uint32_t n_wide);  // zkr_key.hip: room for all of them and the slots' counters; false: no memory
 }  // namespace zkr
 
 struct zkr_key {
   int device = 0;
-  unsigned char *arena = nullptr;
+  unsigned char *arena = nullptr;  // what every launch reads: arena_mem's block, or the caller's (zkr_key_adopt_arena), which is never freed here
   size_t arena_len = 0;
-  bool owns_arena = true;
-  unsigned char *base_arena = nullptr;  // compact form for replication (zkr_key_base_arena), built on first request
+  zkr::Dev<unsigned char> arena_mem;
+  zkr::Dev<unsigned char> base_arena;  // compact form for replication (zkr_key_base_arena), built on first request
   size_t base_arena_len = 0;
   zkr::ArenaHeader h;
   hipStream_t stream = nullptr;                    // the bucket accumulations
@@ -249,7 +223,7 @@ struct zkr_key {
   zkr::ProofLayout layout;
   zkr::EvalTables eval;
   // proof assembly on the host: 4-bit window tables of delta_1 / delta_2 (built on first use)
-  zkr::Tw29 *tw29 = nullptr, *twl29 = nullptr;  // butterfly twiddles, derived from the arena's tables when the key is set up (not part of the arena)
+  zkr::Dev<zkr::Tw29> tw29, twl29;  // butterfly twiddles, derived from the arena's tables when the key is set up (not part of the arena)
   std::once_flag delta_once;
   std::vector<zkr::G1Affine> delta1_tab;
   std::vector<zkr::G2Affine> delta2_tab;
@@ -269,7 +243,8 @@ int key_build(int device, uint32_t n, uint32_t p, uint32_t m, const std::vector<
               const std::vector<uint32_t> tbl_srcidx[N_TABLES], const std::vector<uint32_t> tbl_sidx[N_TABLES], const uint8_t *consts448,
               zkr_key **out);
 int key_alloc_workspace(zkr_key *k);
-int fixed_base_points(int device, bool g2, const uint8_t *scalars_std, size_t n, void **d_out, bool wipe_scalars = false);  // device array of affine Montgomery points
+int fixed_base_points(int device, bool g2, const uint8_t *scalars_std, size_t n, DevBuf &out, bool wipe_scalars = false);  // out: device array of affine Montgomery points
+int key_from_arena(int device, Dev<unsigned char> &&arena, const ArenaHeader &h, zkr_key **out);  // the key that owns `arena` from here on, with its workspace
 // zkr_prove.hip
 struct Prof {  // where a launch helper records its timing spans (null key: stage hooks, no timing)
   zkr_key *k;
@@ -280,7 +255,7 @@ void prof_end(Prof pf, hipStream_t s, int span);
 int prof_collect(zkr_key *k, ProofSlot &sl);
 struct NttTables { const Fr *tw; const Tw29 *tw29, *twl29; int tlog; };  // x 2^256 powers of w_{2m} (coset factors); x 2^261 powers for the butterflies (kernels_ntt.hpp)
 int ntt_lds_check(int device);  // ZKR_ERR_NO_DEVICE with a clear message when the device cannot hold an NTT tile in LDS
-int ntt_tables29_build(const Fr *tw, uint32_t n_tw, const Fr *twl, uint32_t n_twl, hipStream_t s, Tw29 **tw29, Tw29 **twl29);
+int ntt_tables29_build(const Fr *tw, uint32_t n_tw, const Fr *twl, uint32_t n_twl, hipStream_t s, Dev<Tw29> &tw29, Dev<Tw29> &twl29);
 int run_ntt(hipStream_t s, const Fr *in0, const Fr *in1, Fr *out, const NttTables &tb, int L, bool dif, bool inverse, int pre, int nbat, Prof pf,
             const Fr *in0_b = nullptr, const Fr *in1_b = nullptr, Fr *out_b = nullptr,  // in0_b / in1_b / out_b: a second transform of the same shape in the same launches
             uint32_t want_lo = 0, uint32_t want_n = 0,   // DIF: only this range of the output is wanted (0, 0: all of it)
@@ -299,7 +274,7 @@ void arena_layout(ArenaHeader &h);  // section offsets and total_len from the si
 const char *arena_header_fault(const ArenaHeader &h, size_t len);  // null when a full arena's header is consistent with its sizes
 const char *window_fault(const ArenaHeader &h);  // null when the header's windows are ones the proof path can run with
 void base_layout(const ArenaHeader &full, ArenaHeader &b);  // the same for the compact form (zkr_key_base_arena)
-int arena_from_base(const void *dev_ptr, size_t len, int device, unsigned char **arena_out, ArenaHeader *h_out);  // the full arena a compact one stands for, rebuilt (caller hipFree's)
+int arena_from_base(const void *dev_ptr, size_t len, int device, Dev<unsigned char> &arena_out, ArenaHeader *h_out);  // the full arena a compact one stands for, rebuilt
 // zkr_prove.hip: sum_s scalars[s] * (table t of the key)[rank[s]] by the key's MSM path on a workspace of its own (zkr_key_contribution_verify);
 // d_scalars: the table's whole scalar vector on the key's device, standard form below r; *out as the proof assembly reads MSM results
 int key_table_msm(const zkr_key *k, int t, const Fr *d_scalars, XYZZ<Fq> *out);
@@ -312,15 +287,15 @@ struct QapColumns {
   std::vector<uint8_t> coef;
 };
 // cols: A (with the input-consistency rows), B, C over the domain m.  Steps 1-5 of zkr_ptau_verify run on the transcript first
-// (ZKR_ERR_BAD_KEY).  d_tbl (device, Montgomery affine, infinity where a signal's polynomial vanishes; the caller hipFree's them):
+// (ZKR_ERR_BAD_KEY).  d_tbl (device, Montgomery affine, infinity where a signal's polynomial vanishes):
 // [T_A], [T_B1], [T_B2]: n points; [T_C]: the n points K[s] = beta A_s + alfa B_s + C_s (IC for s <= nPublic, C above); [T_H]: m
-int ptau_key_tables(const void *ptau, size_t len, int device, uint32_t m, uint32_t n, const QapColumns cols[3], void *d_tbl[N_TABLES], uint8_t consts448[448]);
+int ptau_key_tables(const void *ptau, size_t len, int device, uint32_t m, uint32_t n, const QapColumns cols[3], DevBuf d_tbl[N_TABLES], uint8_t consts448[448]);
 // zkr_ptau.hip: its launches over vectors of G1 points, for the side tables derived from a key's own points (zkr_eval_tables.hip).
 // On the current device and its null stream; points Montgomery affine x 2^256, x == 0 = infinity; ztmp: 2 n coordinates.
 int g1_scale_each(G1Affine *pts, size_t n, const Fr *d_scalars, uint32_t sc_stride, void *ztmp);  // pts[i] <- s[i] pts[i]; scalars standard form, one per point (stride 1) or one for all (0)
 int g1_group_ntt(G1Affine *pts, G1Affine *tmp, unsigned logn, bool inverse, Fr *tw, void *ztmp);  // natural order in and out, the inverse with 1 / n; tmp: n points, tw: n / 2 + 1 scalars
-// *out (a fresh allocation the caller hipFree's): point s < n = sum over column s of coefficient x pts[row]; partial sums lie behind
-int g1_combine_columns(uint32_t n, const QapColumns &cols, const G1Affine *pts, void **out);
+// out: point s < n = sum over column s of coefficient x pts[row]; partial sums lie behind
+int g1_combine_columns(uint32_t n, const QapColumns &cols, const G1Affine *pts, DevBuf &out);
 // workload.hip: a rank-1 constraint system as the setups and zkr_r1cs.hip take it, rows in CSR
 struct Term { uint32_t sig; Fr coef; };  // coef Montgomery
 struct Circuit {
@@ -332,9 +307,8 @@ struct Circuit {
 int parse_r1cs(const void *r1cs_bin, size_t r1cs_len, Circuit &c);  // r1cs_bin (include/zkr.h) -> the circuit, with its domain; host only; ZKR_ERR_ARG with a message
 int device_bytes_equal(int device, const void *a, const void *b, size_t bytes, bool *same);  // zkr_contribute.hip: its compare kernel over one range; bytes a multiple of 16
 void qap_columns(const Circuit &c, int side, QapColumns &q);  // one side of the QAP (0 = A with its input-consistency rows, 1 = B, 2 = C) by signal
-int key_eval_rows(zkr_key *k, const Circuit &c);  // C by row and the slots' counters of a key's side tables; above zero: an allocation failed
+int key_eval_rows(zkr_key *k, const Circuit &c);  // room for a whole key's side tables (eval_tables_alloc), C by row filled in; above zero: an allocation failed
 int digit_lists_alloc(DigitLists &dl, size_t n_scalars, const MsmPlan &pl);
-void digit_lists_free(DigitLists &dl);
 int msm_scratch_alloc(MsmScratch &m, size_t n_scalars, size_t n_points, const MsmPlan &pl, bool g2);  // for one proof of one table
 int msm_precompute(int device, bool g2, void *d_table, uint32_t n, const MsmPlan &pl);  // fills levels 1..K-1 of a table whose level 0 is in place, then converts the table to the hot path's radix
 int radix_convert(int device, bool g2, void *d_points, size_t count, bool to261);

@@ -100,50 +100,37 @@ const char *arena_header_fault(const ArenaHeader &h, size_t len) {
 // msm_digits_count_kernel)
 static int msm_sort_alloc(MsmSort &so, size_t n, const MsmPlan &pl, size_t cap) {
   size_t nb = pl.nb * cap;
-  ZKR_HIP_CHECK(hipMalloc(&so.counts, (nb + 1) * 4));
-  ZKR_HIP_CHECK(hipMalloc(&so.offsets, (nb + 1) * 4));
-  ZKR_HIP_CHECK(hipMalloc(&so.size_hist, 2 * SIZE_BINS * 4));
-  ZKR_HIP_CHECK(hipMalloc(&so.order, (nb + 1) * 4));
-  ZKR_HIP_CHECK(hipMalloc(&so.chunk_cnt, (size_t)pl.J * nb * 4 + 4));
-  ZKR_HIP_CHECK(hipMalloc(&so.entries, (n * pl.K * cap + 1) * 4));
-  ZKR_HIP_CHECK(hipMalloc(&so.big_list, BIG_CAP * 4));
-  ZKR_HIP_CHECK(hipMalloc(&so.big_count, 16));  // [0] oversized buckets, [1] total entries, [2] tile ticket (kernels_msm.hpp SortScratch)
-  ZKR_HIP_CHECK(hipMalloc(&so.block_sums, (nb / SCAN_BLOCK + 2) * 8));  // the scan tiles' sums (msm_scan_sums_kernel, msm_scan_top_kernel)
+  int rc;
+  if ((rc = so.counts.alloc(nb + 1)) || (rc = so.offsets.alloc(nb + 1)) || (rc = so.size_hist.alloc(2 * SIZE_BINS)) || (rc = so.order.alloc(nb + 1)) ||
+      (rc = so.chunk_cnt.alloc((size_t)pl.J * nb + 1)) || (rc = so.entries.alloc(n * pl.K * cap + 1)) || (rc = so.big_list.alloc(BIG_CAP)) ||
+      (rc = so.big_count.alloc(4)) ||  // [0] oversized buckets, [1] total entries, [2] tile ticket (kernels_msm.hpp SortScratch)
+      (rc = so.block_sums.alloc((nb / SCAN_BLOCK + 2) * 2)))  // the scan tiles' sums, 8 bytes each (msm_scan_sums_kernel, msm_scan_top_kernel)
+    return rc;
   so.max_nb = nb;
   so.max_entries = n * pl.K * cap;
   return 0;
 }
-static void msm_sort_free(MsmSort &so) {
-  hipFree(so.counts); hipFree(so.offsets); hipFree(so.chunk_cnt); hipFree(so.size_hist); hipFree(so.order); hipFree(so.entries); hipFree(so.big_list); hipFree(so.big_count); hipFree(so.block_sums);
-  so = MsmSort();
-}
 static size_t xyzz_bytes(bool g2) { return g2 ? sizeof(G2XYZZ) : sizeof(G1XYZZ); }
-static int big_partials_alloc(void **p, bool g2) { ZKR_HIP_CHECK(hipMalloc(p, (size_t)BIG_CAP * BIG_SPLIT * xyzz_bytes(g2))); return 0; }
+static int big_partials_alloc(DevBuf &p, bool g2) { return p.alloc((size_t)BIG_CAP * BIG_SPLIT * xyzz_bytes(g2)); }
 // `sets` bucket sets per proof (2 in the chain that reduces A behind B1) of the plan's geometry, with their reduction buffers
 static int msm_chain_alloc(MsmChain &ch, const MsmPlan &pl, bool g2, size_t cap, size_t sets) {
   const size_t nb = pl.nb * cap, xb = xyzz_bytes(g2);
   ch.sets = sets;
   ch.g2 = g2;
-  ZKR_HIP_CHECK(hipMalloc(&ch.buckets, nb * sets * xb));
+  int rc;
+  if ((rc = ch.buckets.alloc(nb * sets * xb))) return rc;
   // sized for the plan's groups AND for the smaller groups of a latency-mode chain (zkr_prove.hip msm_reduce_enqueue: groups of
   // 2^LAT_GLOG buckets when nothing else is in flight), whose task sums take up to 16 splits
   const int g_min = pl.glog < LAT_GLOG ? pl.glog : LAT_GLOG;
-  ZKR_HIP_CHECK(hipMalloc(&ch.group_out, (size_t)(pl.nbw >> g_min) * cap * sets * 2 * xb));
-  ZKR_HIP_CHECK(hipMalloc(&ch.task_out, (size_t)(pl.c + 2) * (pl.S > 16 ? pl.S : 16) * cap * sets * xb));
-  ZKR_HIP_CHECK(hipMalloc(&ch.result, xb * cap * sets));
-  ZKR_HIP_CHECK(hipHostMalloc(&ch.h_result, xb * cap * sets, hipHostMallocDefault));
-  return 0;
-}
-static void msm_chain_free(MsmChain &ch) {
-  hipFree(ch.buckets); hipFree(ch.group_out); hipFree(ch.task_out); hipFree(ch.result);
-  if (ch.h_result) hipHostFree(ch.h_result);
-  ch = MsmChain();
+  if ((rc = ch.group_out.alloc((size_t)(pl.nbw >> g_min) * cap * sets * 2 * xb)) ||
+      (rc = ch.task_out.alloc((size_t)(pl.c + 2) * (pl.S > 16 ? pl.S : 16) * cap * sets * xb)) || (rc = ch.result.alloc(xb * cap * sets)))
+    return rc;
+  return ch.h_result.alloc(xb * cap * sets);
 }
 int digit_lists_alloc(DigitLists &dl, size_t n_scalars, const MsmPlan &pl) {  // n_scalars: of the whole (fused) vector
-  ZKR_HIP_CHECK(hipMalloc(&dl.rng, DIGIT_RNG_WORDS * 4));
-  ZKR_HIP_CHECK(hipMalloc(&dl.ent_s, (size_t)pl.K * n_scalars * 4 + 4));
-  ZKR_HIP_CHECK(hipMalloc(&dl.ent_b, (size_t)pl.K * n_scalars * 4 + 4));
-  return 0;
+  int rc;
+  if ((rc = dl.rng.alloc(DIGIT_RNG_WORDS)) || (rc = dl.ent_s.alloc((size_t)pl.K * n_scalars + 1))) return rc;
+  return dl.ent_b.alloc((size_t)pl.K * n_scalars + 1);
 }
 // How many proofs of this key one submit fuses into shared launches: circuits far below the size that fills the chip
 // (the reference's own tx circuit: 2^17) run every kernel over `cap` witnesses at once -- vectors end to end, `cap` bucket
@@ -160,20 +147,10 @@ int fused_capacity(const ArenaHeader &h, const MsmPlan plan[N_TABLES]) {
   if (cap > (uint32_t)MAX_FUSE) cap = MAX_FUSE;
   return cap < 1 ? 1 : (int)cap;
 }
-void digit_lists_free(DigitLists &dl) {
-  hipFree(dl.rng); hipFree(dl.ent_s); hipFree(dl.ent_b);
-  dl = DigitLists();
-}
 int msm_scratch_alloc(MsmScratch &m, size_t n_scalars, size_t n, const MsmPlan &pl, bool g2) {
   int rc;
-  if ((rc = digit_lists_alloc(m.dig, n_scalars, pl)) || (rc = msm_sort_alloc(m.sort, n, pl, 1)) || (rc = big_partials_alloc(&m.big_partials, g2))) return rc;
+  if ((rc = digit_lists_alloc(m.dig, n_scalars, pl)) || (rc = msm_sort_alloc(m.sort, n, pl, 1)) || (rc = big_partials_alloc(m.big_partials, g2))) return rc;
   return msm_chain_alloc(m.chain, pl, g2, 1, 1);
-}
-MsmScratch::~MsmScratch() {
-  digit_lists_free(dig);
-  msm_sort_free(sort);
-  hipFree(big_partials);
-  msm_chain_free(chain);
 }
 
 // The streams of a device, made ONCE per process and shared by every key on that device.  The HIP runtime multiplexes the streams
@@ -186,7 +163,7 @@ MsmScratch::~MsmScratch() {
 // and the shared streams cannot wait for each other in a circle.
 namespace {
 struct DeviceStreams {
-  hipStream_t accum = nullptr, prep = nullptr, g2 = nullptr, g1 = nullptr, aux = nullptr;  // zkr_internal.hpp zkr_key: the roles
+  hipStream_t accum = nullptr, prep = nullptr, g2 = nullptr, g1 = nullptr, aux = nullptr;  // zkr_internal.hpp zkr_key: the roles; raw and never destroyed, on purpose (above)
   std::mutex enqueue_mu;
 };
 std::mutex g_streams_mu;
@@ -248,7 +225,7 @@ int key_alloc_workspace(zkr_key *k) {
     k->aux_stream = ds->aux;
   }
   {
-    int rc = ntt_tables29_build((const Fr *)(k->arena + h.off_tw), 1u << h.tlog, (const Fr *)(k->arena + h.off_twl), 1u << TWL_LOG, nullptr, &k->tw29, &k->twl29);
+    int rc = ntt_tables29_build((const Fr *)(k->arena + h.off_tw), 1u << h.tlog, (const Fr *)(k->arena + h.off_twl), 1u << TWL_LOG, nullptr, k->tw29, k->twl29);
     if (rc) return rc;
   }
   const size_t cap = (size_t)fused_capacity(h, k->plan);
@@ -256,22 +233,18 @@ int key_alloc_workspace(zkr_key *k) {
     sl.cap = (int)cap;
     sl.rb.assign(32 * cap, 0);
     sl.sb.assign(32 * cap, 0);
-    for (int t = 0; t < N_TABLES; t++) {
-      ZKR_HIP_CHECK(hipEventCreateWithFlags(&sl.ev_done[t], hipEventDisableTiming));
-      ZKR_HIP_CHECK(hipEventCreateWithFlags(&sl.ev_sorted[t], hipEventDisableTiming));
-      ZKR_HIP_CHECK(hipEventCreateWithFlags(&sl.ev_res[t], hipEventDisableTiming));
-    }
-    ZKR_HIP_CHECK(hipEventCreateWithFlags(&sl.ev_w, hipEventDisableTiming));
-    ZKR_HIP_CHECK(hipEventCreateWithFlags(&sl.ev_h, hipEventDisableTiming));
-    for (hipEvent_t &e : sl.ev_end) ZKR_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    ZKR_HIP_CHECK(hipMalloc(&sl.d_w, (size_t)h.n * 32 * cap));
-    Fr **vecs[5] = {&sl.va, &sl.vb, &sl.ca, &sl.cb, &sl.d_h};
-    for (auto v : vecs) ZKR_HIP_CHECK(hipMalloc(v, (size_t)h.m * 32 * cap));
     int rc = 0;
+    for (ScopedEvent *e : {sl.ev_done, sl.ev_sorted, sl.ev_res})
+      for (int t = 0; t < N_TABLES && !rc; t++) rc = e[t].create(hipEventDisableTiming);
+    for (ScopedEvent *e : {&sl.ev_w, &sl.ev_h, &sl.ev_end[0], &sl.ev_end[1], &sl.ev_end[2]})
+      if (!rc) rc = e->create(hipEventDisableTiming);
+    if (!rc) rc = sl.d_w.alloc((size_t)h.n * cap);
+    for (Dev<Fr> *v : {&sl.va, &sl.vb, &sl.ca, &sl.cb, &sl.d_h})
+      if (!rc) rc = v->alloc((size_t)h.m * cap);
     for (int t = 0; t < N_TABLES && !rc; t++) {
       if (!h.npts[t]) continue;  // an empty table is sorted, accumulated and reduced nowhere (it is in no chain of the layout)
       if (lay.sort_src[t] == t) rc = msm_sort_alloc(sl.sort[t], h.npts[t], k->plan[t], cap);
-      if (!rc) rc = big_partials_alloc(&sl.big_partials[t], t == T_B2);
+      if (!rc) rc = big_partials_alloc(sl.big_partials[t], t == T_B2);
     }
     for (int c = 0; c < lay.n_chains && !rc; c++) rc = msm_chain_alloc(sl.chain[c], k->plan[lay.chains[c].geom], lay.chains[c].g2, cap, (size_t)lay.chains[c].sets);
     if (!rc) rc = digit_lists_alloc(sl.dig_w, (size_t)h.sc_n[0] * cap, k->plan[T_A]);
@@ -286,19 +259,29 @@ int key_alloc_workspace(zkr_key *k) {
   return 0;
 }
 
+// Room for the side tables of the evaluation form, whoever fills them: C' of np_c points and E' of np_e with the key's plans of C
+// and H (sized as arena_layout sizes a table), C by row (nnz terms, n_wide wide rows) over the whole domain, and per proof slot a
+// counter for each proof of a fused group, device and pinned, the pinned ones zero.  False: the device or the host has no memory
+// for them -- what is allocated stays until key_eval_tables_free, and what follows is the caller's policy.
+bool eval_tables_alloc(zkr_key *k, uint32_t np_c, uint32_t np_e, uint32_t nnz, uint32_t n_wide) {
+  EvalTables &ev = k->eval;
+  ev.nnz = nnz;
+  ev.n_wide = n_wide;
+  bool ok = !ev.c_pts.alloc((size_t)np_c * k->plan[T_C].K * 64 + 64) && !ev.e_pts.alloc((size_t)np_e * k->plan[T_H].K * 64 + 64) &&
+            !ev.c_rowptr.alloc((size_t)k->h.m + 1) && !ev.c_col.alloc((size_t)nnz + 1) && !ev.c_coef.alloc((size_t)nnz + 1) && !ev.c_wide.alloc((size_t)n_wide + 1);
+  for (ProofSlot &sl : k->slot) {
+    ok = ok && !sl.d_bad.alloc((size_t)sl.cap) && !sl.h_bad.alloc((size_t)sl.cap);
+    if (ok) memset(sl.h_bad, 0, (size_t)sl.cap * 4);
+  }
+  return ok;
+}
+
 // the side tables of the evaluation form and what the slots hold for them; the key's proofs must have been collected
 int key_eval_tables_free(zkr_key *k) {
   EvalTables &ev = k->eval;
   ev.ready = false;
-  hipFree(ev.c_pts); hipFree(ev.e_pts); hipFree(ev.c_rowptr); hipFree(ev.c_col); hipFree(ev.c_coef); hipFree(ev.c_wide);
-  ev.c_pts = ev.e_pts = nullptr;
-  ev.c_rowptr = ev.c_col = ev.c_wide = nullptr;
-  ev.c_coef = nullptr;
-  for (ProofSlot &sl : k->slot) {
-    hipFree(sl.d_bad);
-    if (sl.h_bad) hipHostFree(sl.h_bad);
-    sl.d_bad = sl.h_bad = nullptr;
-  }
+  ev.c_pts.reset(); ev.e_pts.reset(); ev.c_rowptr.reset(); ev.c_col.reset(); ev.c_coef.reset(); ev.c_wide.reset();
+  for (ProofSlot &sl : k->slot) { sl.d_bad.reset(); sl.h_bad.reset(); }
   return 0;
 }
 
@@ -349,6 +332,20 @@ int msm_precompute(int device, bool g2, void *d_table, uint32_t n, const MsmPlan
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipDeviceSynchronize();
   if (e != hipSuccess) { set_error("window-table build failed: %s", hipGetErrorString(e)); return ZKR_ERR_HIP; }
+  return 0;
+}
+
+// the key over an arena this library allocated: it owns the block from here on, whether or not its workspace can be made
+int key_from_arena(int device, Dev<unsigned char> &&arena, const ArenaHeader &h, zkr_key **out) {
+  zkr_key *k = new zkr_key();
+  k->device = device;
+  k->arena_mem = std::move(arena);
+  k->arena = k->arena_mem;
+  k->arena_len = h.total_len;
+  k->h = h;
+  int rc = key_alloc_workspace(k);
+  if (rc) { zkr_key_free(k); return rc; }
+  *out = k;
   return 0;
 }
 
@@ -413,8 +410,8 @@ int key_build(int device, uint32_t n, uint32_t p, uint32_t m, const std::vector<
   arena_layout(h);
   const size_t off = h.total_len;
 
-  unsigned char *arena = nullptr;
-  ZKR_HIP_CHECK(hipMalloc(&arena, off));
+  Dev<unsigned char> arena;
+  if (int arc = arena.alloc(off)) return arc;
   ZKR_HIP_CHECK(hipMemset(arena, 0, off));  // alignment gaps and slack bytes are part of the arena's bytes (replicas, packed key files): defined, not stale
   ZKR_HIP_CHECK(hipMemcpy(arena, &h, sizeof(h), hipMemcpyHostToDevice));
   for (int s = 0; s < 2; s++) {
@@ -437,8 +434,8 @@ int key_build(int device, uint32_t n, uint32_t p, uint32_t m, const std::vector<
       ZKR_HIP_CHECK(hipMemcpy(arena + h.off_rank[t], rank.data(), rank.size() * 4, hipMemcpyHostToDevice));
     }
     if (tbl_src_on_device[t]) {
-      uint32_t *d_idx = nullptr;
-      ZKR_HIP_CHECK(hipMalloc(&d_idx, np * 4));
+      Dev<uint32_t> d_idx;
+      if (int irc = d_idx.alloc(np)) return irc;
       ZKR_HIP_CHECK(hipMemcpy(d_idx, srcidx_eff[t]->data(), np * 4, hipMemcpyHostToDevice));
       unsigned grid = (unsigned)((np * (pb / 16) + 255) / 256);  // one 16-byte piece per thread
       if (t == T_B2)
@@ -447,7 +444,6 @@ int key_build(int device, uint32_t n, uint32_t p, uint32_t m, const std::vector<
         gather_kernel<G1Affine><<<grid, 256>>>((const G1Affine *)tbl_src[t], d_idx, np, (G1Affine *)(arena + h.off_pts[t]));
       ZKR_HIP_CHECK(hipGetLastError());
       ZKR_HIP_CHECK(hipDeviceSynchronize());
-      hipFree(d_idx);
     } else {
       std::vector<uint8_t> stage(np * pb);
       const uint8_t *src = (const uint8_t *)tbl_src[t];
@@ -457,8 +453,7 @@ int key_build(int device, uint32_t n, uint32_t p, uint32_t m, const std::vector<
       }
       ZKR_HIP_CHECK(hipMemcpy(arena + h.off_pts[t], stage.data(), np * pb, hipMemcpyHostToDevice));
     }
-    int rc = msm_precompute(device, t == T_B2, arena + h.off_pts[t], (uint32_t)np, plan[t]);
-    if (rc) { hipFree(arena); return rc; }
+    if (int rc = msm_precompute(device, t == T_B2, arena + h.off_pts[t], (uint32_t)np, plan[t])) return rc;
   }
   ZKR_HIP_CHECK(hipMemcpy(arena, &h, sizeof(h), hipMemcpyHostToDevice));  // again: rank_identity was filled in above
   // twiddles on device: T[k] = w_{2m}^k and w_2048^k
@@ -467,22 +462,13 @@ int key_build(int device, uint32_t n, uint32_t p, uint32_t m, const std::vector<
   ZKR_HIP_CHECK(hipGetLastError());
   ZKR_HIP_CHECK(hipDeviceSynchronize());
 
-  zkr_key *k = new zkr_key();
-  k->device = device;
-  k->arena = arena;
-  k->arena_len = off;
-  k->owns_arena = true;
-  k->h = h;
-  int rc = key_alloc_workspace(k);
-  if (rc) { zkr_key_free(k); return rc; }
-  *out = k;
-  return 0;
+  return key_from_arena(device, std::move(arena), h, out);
 }
 
-// scalars (host, std form) * generator -> device array of affine Montgomery points (caller hipFree's).  wipe: the
+// scalars (host, std form) * generator -> device array of affine Montgomery points in `out`.  wipe: the
 // scalars are secret (setup with fresh toxic waste): their device copy is zeroed before it is freed, on every path.
 template <class F>
-static int fixed_base_impl(int device, const Affine<F> &gen, const uint8_t *scalars_std, size_t n, void **d_out, bool wipe) {
+static int fixed_base_impl(int device, const Affine<F> &gen, const uint8_t *scalars_std, size_t n, DevBuf &out, bool wipe) {
   ZKR_HIP_CHECK(hipSetDevice(device));
   // T[j][d] = d * 2^(8j) * G on the host (8160 group operations, once per generator)
   std::vector<Affine<F>> table(32 * 256);
@@ -496,43 +482,36 @@ static int fixed_base_impl(int device, const Affine<F> &gen, const uint8_t *scal
     table[j * 256] = Affine<F>{F::zero(), F::one()};
     for (int b = 0; b < 8; b++) base = dbl_xyzz(base);
   }
-  struct DevBufs {  // freed (and the scalars cleared) however the function is left
-    Affine<F> *table = nullptr, *pts = nullptr;
-    Fr *sc = nullptr;
-    size_t sc_bytes = 0;
+  struct Scalars {  // their device copy, cleared before it is freed when they are secret, however the function is left
+    Dev<Fr> sc;
+    size_t bytes = 0;
     bool wipe = false;
-    ~DevBufs() {
-      if (sc) {
-        if (wipe) { hipMemset(sc, 0, sc_bytes); hipDeviceSynchronize(); }
-        hipFree(sc);
-      }
-      if (table) hipFree(table);
-      if (pts) hipFree(pts);
+    ~Scalars() {
+      if (sc && wipe) { hipMemset(sc, 0, bytes); hipDeviceSynchronize(); }
     }
   } d;
   d.wipe = wipe;
-  d.sc_bytes = (n + 1) * 32;
-  ZKR_HIP_CHECK(hipMalloc(&d.table, table.size() * sizeof(Affine<F>)));
-  ZKR_HIP_CHECK(hipMalloc(&d.pts, (n + 1) * sizeof(Affine<F>)));
-  ZKR_HIP_CHECK(hipMalloc(&d.sc, d.sc_bytes));
-  ZKR_HIP_CHECK(hipMemcpy(d.table, table.data(), table.size() * sizeof(Affine<F>), hipMemcpyHostToDevice));
+  d.bytes = (n + 1) * 32;
+  Dev<Affine<F>> d_table, pts;
+  int rc;
+  if ((rc = d_table.alloc(table.size())) || (rc = pts.alloc(n + 1)) || (rc = d.sc.alloc(n + 1))) return rc;
+  ZKR_HIP_CHECK(hipMemcpy(d_table, table.data(), table.size() * sizeof(Affine<F>), hipMemcpyHostToDevice));
   ZKR_HIP_CHECK(hipMemcpy(d.sc, scalars_std, n * 32, hipMemcpyHostToDevice));
   constexpr int MINW = sizeof(F) == 32 ? 2 : 1;
-  fixed_base_kernel<F, MINW><<<(unsigned)((n + 255) / 256), 256>>>(d.table, d.sc, n, d.pts);
+  fixed_base_kernel<F, MINW><<<(unsigned)((n + 255) / 256), 256>>>(d_table, d.sc, n, pts);
   ZKR_HIP_CHECK(hipGetLastError());
   ZKR_HIP_CHECK(hipDeviceSynchronize());
-  *d_out = d.pts;
-  d.pts = nullptr;  // handed to the caller
+  out = std::move(pts.buf);
   return 0;
 }
 
-int fixed_base_points(int device, bool g2, const uint8_t *scalars_std, size_t n, void **d_out, bool wipe_scalars) {
+int fixed_base_points(int device, bool g2, const uint8_t *scalars_std, size_t n, DevBuf &out, bool wipe_scalars) {
   if (!g2) {
     G1Affine g{Fq::one(), add(Fq::one(), Fq::one())};  // (1, 2), TxVerifier.sol:24-26
-    return fixed_base_impl<Fq>(device, g, scalars_std, n, d_out, wipe_scalars);
+    return fixed_base_impl<Fq>(device, g, scalars_std, n, out, wipe_scalars);
   }
   const G2Affine g = g2_generator();
-  return fixed_base_impl<Fq2>(device, g, scalars_std, n, d_out, wipe_scalars);
+  return fixed_base_impl<Fq2>(device, g, scalars_std, n, out, wipe_scalars);
 }
 
 }  // namespace zkr
@@ -552,7 +531,7 @@ int zkr_device_count(void) {
 
 int zkr_device_pci_bus_id(int device, char *out, size_t out_len) {
   if (!out || out_len < 16) { set_error("buffer too small"); return ZKR_ERR_ARG; }
-  if (zkr_device_count() <= device || device < 0) { set_error("no HIP device %d", device); return ZKR_ERR_NO_DEVICE; }
+  if (int rc = need_device(device)) return rc;
   ZKR_HIP_CHECK(hipDeviceGetPCIBusId(out, (int)out_len, device));
   return 0;
 }
@@ -645,40 +624,14 @@ void zkr_key_free(zkr_key *k) {
   // the streams are the device's (one set per device, shared by its keys): wait for THIS key's work only -- the last events of its
   // proof slots and staged uploads (an event that was never recorded is complete) -- not for the proofs other keys have in flight
   for (ProofSlot &sl : k->slot) {
-    for (auto e : sl.ev_end)
+    for (hipEvent_t e : sl.ev_end)
       if (e) hipEventSynchronize(e);
     for (int t = 0; t < N_TABLES; t++)
       if (sl.ev_res[t]) hipEventSynchronize(sl.ev_res[t]);
   }
   for (WitnessStage &ws : k->stage)
     if (ws.ev_up) hipEventSynchronize(ws.ev_up);
-  for (ProofSlot &sl : k->slot) {
-    for (int t = 0; t < N_TABLES; t++) {
-      if (sl.ev_done[t]) hipEventDestroy(sl.ev_done[t]);
-      if (sl.ev_sorted[t]) hipEventDestroy(sl.ev_sorted[t]);
-      if (sl.ev_res[t]) hipEventDestroy(sl.ev_res[t]);
-      msm_sort_free(sl.sort[t]);
-      hipFree(sl.big_partials[t]);
-      msm_chain_free(sl.chain[t]);
-    }
-    if (sl.ev_w) hipEventDestroy(sl.ev_w);
-    if (sl.ev_h) hipEventDestroy(sl.ev_h);
-    for (auto e : sl.ev_end)
-      if (e) hipEventDestroy(e);
-    digit_lists_free(sl.dig_w); digit_lists_free(sl.dig_h);
-    hipFree(sl.d_w); hipFree(sl.va); hipFree(sl.vb); hipFree(sl.ca); hipFree(sl.cb); hipFree(sl.d_h);
-    for (auto e : sl.event_pool) hipEventDestroy(e);
-  }
-  for (WitnessStage &ws : k->stage) {
-    if (ws.d_w) hipFree(ws.d_w);
-    if (ws.ev_up) hipEventDestroy(ws.ev_up);
-  }
-  key_eval_tables_free(k);
-  hipFree(k->tw29);
-  hipFree(k->twl29);
-  if (k->owns_arena) hipFree(k->arena);
-  if (k->base_arena) hipFree(k->base_arena);
-  delete k;
+  delete k;  // every buffer, event and table goes with its owner; a caller's arena (zkr_key_adopt_arena) is not among them
 }
 
 int zkr_key_info(const zkr_key *k, uint64_t out[10]) {
@@ -713,7 +666,7 @@ int zkr_key_arena(const zkr_key *k, void **dev_ptr, size_t *len) {
 
 int zkr_key_adopt_arena(void *dev_ptr, size_t len, int device, zkr_key **out) {
   if (!dev_ptr || !out) { set_error("null argument"); return ZKR_ERR_ARG; }
-  if (zkr_device_count() <= device || device < 0) { set_error("no HIP device %d", device); return ZKR_ERR_NO_DEVICE; }
+  if (int rc = need_device(device)) return rc;
   ZKR_HIP_CHECK(hipSetDevice(device));
   ArenaHeader h;
   if (len < ARENA_HEADER_BYTES) { set_error("arena too small"); return ZKR_ERR_BAD_KEY; }
@@ -722,9 +675,8 @@ int zkr_key_adopt_arena(void *dev_ptr, size_t len, int device, zkr_key **out) {
   if (int rc = key_arena_check(device, (const unsigned char *)dev_ptr, h, 0, nullptr)) return rc;
   zkr_key *k = new zkr_key();
   k->device = device;
-  k->arena = (unsigned char *)dev_ptr;
+  k->arena = (unsigned char *)dev_ptr;  // the caller's: arena_mem stays empty
   k->arena_len = len;
-  k->owns_arena = false;
   k->h = h;
   int rc = key_alloc_workspace(k);
   if (rc) { zkr_key_free(k); return rc; }
@@ -770,8 +722,8 @@ int zkr_key_base_arena(zkr_key *k, void **dev_ptr, size_t *len) {
   if (!k->base_arena) {
     ArenaHeader b;
     base_layout(k->h, b);
-    unsigned char *buf = nullptr;
-    ZKR_HIP_CHECK(hipMalloc(&buf, b.total_len));
+    Dev<unsigned char> buf;
+    if (int arc = buf.alloc(b.total_len)) return arc;
     auto cp = [&](uint64_t dst, uint64_t src, size_t bytes) { return bytes ? hipMemcpy(buf + dst, k->arena + src, bytes, hipMemcpyDeviceToDevice) : hipSuccess; };
     hipError_t e = hipMemset(buf, 0, b.total_len);
     if (e == hipSuccess) e = hipMemcpy(buf, &b, sizeof(b), hipMemcpyHostToDevice);
@@ -787,14 +739,13 @@ int zkr_key_base_arena(zkr_key *k, void **dev_ptr, size_t *len) {
       if (e == hipSuccess) e = cp(b.off_rank[t], k->h.off_rank[t], (size_t)rank_entries(k->h, t) * 4);
     }
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) { hipFree(buf); set_error("building the compact arena failed: %s", hipGetErrorString(e)); return ZKR_ERR_HIP; }
+    if (e != hipSuccess) { set_error("building the compact arena failed: %s", hipGetErrorString(e)); return ZKR_ERR_HIP; }
     // the compact form carries the base points in the key's own radix (2^256): the receiver rebuilds the window levels from
     // them with msm_precompute, exactly as a key load does
     for (int t = 0; t < N_TABLES; t++) {
-      int rc = radix_convert(k->device, t == T_B2, buf + b.off_pts[t], k->h.npts[t], false);
-      if (rc) { hipFree(buf); return rc; }
+      if (int rc = radix_convert(k->device, t == T_B2, buf + b.off_pts[t], k->h.npts[t], false)) return rc;
     }
-    k->base_arena = buf;
+    k->base_arena = std::move(buf);
     k->base_arena_len = b.total_len;
   }
   *dev_ptr = k->base_arena;
@@ -804,10 +755,10 @@ int zkr_key_base_arena(zkr_key *k, void **dev_ptr, size_t *len) {
 
 }  // extern "C"
 namespace zkr {
-// The full arena a compact one stands for, rebuilt on `device` (the caller hipFree's *arena_out): sections copied to their
+// The full arena a compact one stands for, rebuilt on `device` into `arena_out`: sections copied to their
 // places in THE layout, window levels and twiddles recomputed.  The receiver of a replica makes a key of it
 // (zkr_key_adopt_base_arena); zkr_key_contribution_verify compares it with the arena it was handed.
-int arena_from_base(const void *dev_ptr, size_t len, int device, unsigned char **arena_out, ArenaHeader *h_out) {
+int arena_from_base(const void *dev_ptr, size_t len, int device, Dev<unsigned char> &arena_out, ArenaHeader *h_out) {
   ZKR_HIP_CHECK(hipSetDevice(device));
   if (len < ARENA_HEADER_BYTES) { set_error("compact arena too small"); return ZKR_ERR_BAD_KEY; }
   ArenaHeader b;
@@ -838,9 +789,9 @@ int arena_from_base(const void *dev_ptr, size_t len, int device, unsigned char *
     }
     if (!ok) { set_error("compact arena: a section lies outside the %zu bytes handed over", len); return ZKR_ERR_BAD_KEY; }
   }
-  unsigned char *arena = nullptr;
-  ZKR_HIP_CHECK(hipMalloc(&arena, off));
-  if (hipMemset(arena, 0, off) != hipSuccess) { hipFree(arena); set_error("hipMemset failed"); return ZKR_ERR_HIP; }  // as key_build: gaps and slack are defined bytes
+  Dev<unsigned char> arena;
+  if (int arc = arena.alloc(off)) return arc;
+  if (hipMemset(arena, 0, off) != hipSuccess) { set_error("hipMemset failed"); return ZKR_ERR_HIP; }  // as key_build: gaps and slack are defined bytes
   const unsigned char *src = (const unsigned char *)dev_ptr;
   auto cp = [&](uint64_t dst, uint64_t from, size_t bytes) { return bytes ? hipMemcpy(arena + dst, src + from, bytes, hipMemcpyDeviceToDevice) : hipSuccess; };
   hipError_t e = hipMemcpy(arena, &h, sizeof(h), hipMemcpyHostToDevice);
@@ -855,19 +806,17 @@ int arena_from_base(const void *dev_ptr, size_t len, int device, unsigned char *
     e = cp(h.off_pts[t], b.off_pts[t], (size_t)h.npts[t] * (t == T_B2 ? 128 : 64));
     if (e == hipSuccess) e = cp(h.off_rank[t], b.off_rank[t], (size_t)rank_entries(h, t) * 4);
   }
-  if (e != hipSuccess) { hipFree(arena); set_error("unpacking the compact arena failed: %s", hipGetErrorString(e)); return ZKR_ERR_HIP; }
+  if (e != hipSuccess) { set_error("unpacking the compact arena failed: %s", hipGetErrorString(e)); return ZKR_ERR_HIP; }
   // the unpacked rows and rank maps before anything is built from them (the window levels and twiddles are rebuilt below)
-  if (int crc = key_arena_check(device, arena, h, 0, nullptr)) { hipFree(arena); return crc; }
-  for (int t = 0; t < N_TABLES; t++) {
-    int rc = msm_precompute(device, t == T_B2, arena + h.off_pts[t], h.npts[t], plan[t]);
-    if (rc) { hipFree(arena); return rc; }
-  }
+  if (int crc = key_arena_check(device, arena, h, 0, nullptr)) return crc;
+  for (int t = 0; t < N_TABLES; t++)
+    if (int rc = msm_precompute(device, t == T_B2, arena + h.off_pts[t], h.npts[t], plan[t])) return rc;
   twiddle_table_kernel<<<(h.m + 255) / 256, 256>>>((Fr *)(arena + h.off_tw), h.m, fr_root_of_unity(h.logm + 1));
   twiddle_table_kernel<<<((1u << TWL_LOG) + 255) / 256, 256>>>((Fr *)(arena + h.off_twl), 1u << TWL_LOG, fr_root_of_unity(TWL_LOG + 1));
   e = hipGetLastError();
   if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e != hipSuccess) { hipFree(arena); set_error("rebuilding the window tables failed: %s", hipGetErrorString(e)); return ZKR_ERR_HIP; }
-  *arena_out = arena;
+  if (e != hipSuccess) { set_error("rebuilding the window tables failed: %s", hipGetErrorString(e)); return ZKR_ERR_HIP; }
+  arena_out = std::move(arena);
   *h_out = h;
   return 0;
 }
@@ -876,20 +825,11 @@ extern "C" {
 
 int zkr_key_adopt_base_arena(const void *dev_ptr, size_t len, int device, zkr_key **out) {
   if (!dev_ptr || !out) { set_error("null argument"); return ZKR_ERR_ARG; }
-  if (zkr_device_count() <= device || device < 0) { set_error("no HIP device %d", device); return ZKR_ERR_NO_DEVICE; }
-  unsigned char *arena = nullptr;
+  if (int rc = need_device(device)) return rc;
+  Dev<unsigned char> arena;
   ArenaHeader h;
-  if (int brc = arena_from_base(dev_ptr, len, device, &arena, &h)) return brc;
-  zkr_key *k = new zkr_key();
-  k->device = device;
-  k->arena = arena;
-  k->arena_len = h.total_len;
-  k->owns_arena = true;
-  k->h = h;
-  int rc = key_alloc_workspace(k);
-  if (rc) { zkr_key_free(k); return rc; }
-  *out = k;
-  return 0;
+  if (int brc = arena_from_base(dev_ptr, len, device, arena, &h)) return brc;
+  return key_from_arena(device, std::move(arena), h, out);
 }
 
 int zkr_key_save(const zkr_key *k, const char *path) {
@@ -898,17 +838,14 @@ int zkr_key_save(const zkr_key *k, const char *path) {
   FILE *f = fopen(path, "wb");
   if (!f) { set_error("cannot open %s for writing", path); return ZKR_ERR_ARG; }
   const size_t CHUNK = (size_t)64 << 20;
-  void *stage = nullptr;
-  hipError_t e = hipHostMalloc(&stage, CHUNK, hipHostMallocDefault);
-  int rc = 0;
-  if (e != hipSuccess) { set_error("pinned staging buffer: %s", hipGetErrorString(e)); rc = ZKR_ERR_HIP; }
+  PinnedBuf stage;
+  int rc = stage.alloc(CHUNK);
   for (size_t off = 0; !rc && off < k->arena_len; off += CHUNK) {
     size_t nb = k->arena_len - off < CHUNK ? k->arena_len - off : CHUNK;
-    e = hipMemcpy(stage, k->arena + off, nb, hipMemcpyDeviceToHost);
+    hipError_t e = hipMemcpy(stage, k->arena + off, nb, hipMemcpyDeviceToHost);
     if (e != hipSuccess) { set_error("arena download failed: %s", hipGetErrorString(e)); rc = ZKR_ERR_HIP; }
     else if (fwrite(stage, 1, nb, f) != nb) { set_error("short write to %s", path); rc = ZKR_ERR_ARG; }
   }
-  if (stage) hipHostFree(stage);
   if (fclose(f) != 0 && !rc) { set_error("close failed on %s", path); rc = ZKR_ERR_ARG; }
   return rc;
 }
@@ -930,32 +867,22 @@ int zkr_key_load_file(const char *path, int device, zkr_key **out) {
   if (flen < 0 || (uint64_t)flen != h.total_len) { fclose(f); set_error("%s: length %ld != header total %llu", path, flen, (unsigned long long)h.total_len); return ZKR_ERR_BAD_KEY; }
   if (const char *fault = arena_header_fault(h, h.total_len)) { fclose(f); set_error("%s: %s", path, fault); return ZKR_ERR_BAD_KEY; }
   fseek(f, 0, SEEK_SET);
-  unsigned char *arena = nullptr;
+  Dev<unsigned char> arena;
   const size_t CHUNK = (size_t)64 << 20;
-  void *stage = nullptr;
-  int rc = 0;
-  hipError_t e = hipMalloc(&arena, h.total_len);
-  if (e == hipSuccess) e = hipHostMalloc(&stage, CHUNK, hipHostMallocDefault);
-  if (e != hipSuccess) { set_error("allocation failed: %s", hipGetErrorString(e)); rc = ZKR_ERR_HIP; }
+  PinnedBuf stage;
+  hipError_t e;
+  int rc = arena.alloc(h.total_len);
+  if (!rc) rc = stage.alloc(CHUNK);
   for (size_t off = 0; !rc && off < h.total_len; off += CHUNK) {
     size_t nb = h.total_len - off < CHUNK ? h.total_len - off : CHUNK;
     if (fread(stage, 1, nb, f) != nb) { set_error("short read from %s", path); rc = ZKR_ERR_BAD_KEY; }
     else if ((e = hipMemcpy(arena + off, stage, nb, hipMemcpyHostToDevice)) != hipSuccess) { set_error("arena upload failed: %s", hipGetErrorString(e)); rc = ZKR_ERR_HIP; }
   }
   fclose(f);
-  if (stage) hipHostFree(stage);
+  stage.reset();
   if (!rc) rc = key_arena_check(device, arena, h, 0, nullptr);
-  if (rc) { hipFree(arena); return rc; }
-  zkr_key *k = new zkr_key();
-  k->device = device;
-  k->arena = arena;
-  k->arena_len = h.total_len;
-  k->owns_arena = true;
-  k->h = h;
-  rc = key_alloc_workspace(k);
-  if (rc) { zkr_key_free(k); return rc; }
-  *out = k;
-  return 0;
+  if (rc) return rc;
+  return key_from_arena(device, std::move(arena), h, out);
 }
 
 void zkr_free(void *p) { free(p); }

@@ -13,6 +13,7 @@
 // which comes back to the host in one copy.  The check runs on a non-blocking stream of its own and waits for that stream only:
 // proofs other threads have in flight on the device are not waited for.
 #include <string.h>
+#include <memory>
 #include <map>
 #include <mutex>
 #include "kernels_msm.hpp"
@@ -233,16 +234,11 @@ bool canonical_fq(const Fq &x) { return words_below(x.v, FqParams::P); }
 // stream set, zkr_key.hip): a check frees nothing, and a free would wait for the whole device.  Checks on one device take turns.
 struct CheckCtx {
   std::mutex mu;
-  CheckRecord *d_rec = nullptr, *h_rec = nullptr;
+  Dev<CheckRecord> d_rec;
+  Pinned<CheckRecord> h_rec;
 };
 std::mutex g_ctx_mu;
-std::map<int, CheckCtx *> g_ctx;
-
-// the check's own non-blocking stream, destroyed when the check ends (it leaves the device's hardware queue hand-out as it was)
-struct OwnStream {
-  hipStream_t s = nullptr;
-  ~OwnStream() { if (s) hipStreamDestroy(s); }
-};
+std::map<int, CheckCtx *> g_ctx;  // never freed: a complete context lives as long as the process
 
 const char *const SEC_NAME[N_SEC] = {"none", "rowptr", "col", "wide", "rank", "header", "points", "twiddles", "coef", "shared rank", "consts"};
 const char *part_name(int sec, int part) {
@@ -269,25 +265,25 @@ int key_arena_check(int device, const unsigned char *arena, const ArenaHeader &h
     std::lock_guard<std::mutex> lk(g_ctx_mu);
     CheckCtx *&slot = g_ctx[device];
     if (!slot) {
-      CheckCtx *c = new CheckCtx();
-      if (hipMalloc(&c->d_rec, sizeof(CheckRecord)) != hipSuccess || hipHostMalloc(&c->h_rec, sizeof(CheckRecord), hipHostMallocDefault) != hipSuccess) {
+      std::unique_ptr<CheckCtx> c(new CheckCtx());
+      if (c->d_rec.alloc(1) || c->h_rec.alloc(1)) {
         set_error("key check: allocation of the result record failed");
-        return ZKR_ERR_HIP;  // (c stays unreachable: a few hundred bytes, on a device that cannot allocate them)
+        return ZKR_ERR_HIP;
       }
-      slot = c;
+      slot = c.release();
     }
     ctx = slot;
   }
   std::lock_guard<std::mutex> lk(ctx->mu);
-  OwnStream os;
-  ZKR_HIP_CHECK(hipStreamCreateWithFlags(&os.s, hipStreamNonBlocking));
-  const hipStream_t st = os.s;
+  OwnStream os;  // the check's own non-blocking stream, destroyed when the check ends (it leaves the device's hardware queue hand-out as it was)
+  if (int src = os.create()) return src;
+  const hipStream_t st = os;
   {  // the arena may just have been written through the null stream (the unpacking copies of zkr_key_adopt_base_arena): wait for
      // that stream's work -- the key's own streams are non-blocking, so no proof in flight is waited for
     ScopedEvent ev;
     if (int erc = ev.create()) return erc;
-    ZKR_HIP_CHECK(hipEventRecord(ev.e, nullptr));
-    ZKR_HIP_CHECK(hipStreamWaitEvent(st, ev.e, 0));
+    ZKR_HIP_CHECK(hipEventRecord(ev, nullptr));
+    ZKR_HIP_CHECK(hipStreamWaitEvent(st, ev, 0));
   }
   CheckRecord *rec = ctx->d_rec;
   ZKR_HIP_CHECK(hipMemsetAsync(rec->count, 0, sizeof(rec->count), st));

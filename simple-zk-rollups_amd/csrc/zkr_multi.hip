@@ -67,7 +67,7 @@ extern "C" {
 int zkr_key_replicate(const zkr_key *src, int dst_device, int mode, zkr_key **out) {
   if (!src || !out) { set_error("null argument"); return ZKR_ERR_ARG; }
   if (mode != ZKR_REPLICATE_AUTO && mode != ZKR_REPLICATE_FULL && mode != ZKR_REPLICATE_BASE) { set_error("unknown replication mode %d", mode); return ZKR_ERR_ARG; }
-  if (zkr_device_count() <= dst_device || dst_device < 0) { set_error("no HIP device %d (found %d)", dst_device, zkr_device_count()); return ZKR_ERR_NO_DEVICE; }
+  if (int rc = need_device(dst_device)) return rc;
   if (const char *e = getenv("ZKR_REPLICATE_MODE")) {  // experiments / tests: force a form whatever the caller asked for
     if (!strcmp(e, "full")) mode = ZKR_REPLICATE_FULL;
     else if (!strcmp(e, "base")) mode = ZKR_REPLICATE_BASE;
@@ -77,15 +77,14 @@ int zkr_key_replicate(const zkr_key *src, int dst_device, int mode, zkr_key **ou
   if (mode == ZKR_REPLICATE_FULL) {
     // the whole arena, window tables included: nothing is recomputed on the receiver (4.47 GB at 2^20: ~30 ms per xGMI link)
     ZKR_HIP_CHECK(hipSetDevice(dst_device));
-    DevBuf buf;
+    Dev<unsigned char> buf;
     if (int rc = buf.alloc(src->arena_len)) return rc;
-    if (int rc = copy_between_devices(buf.p, dst_device, src->arena, src->device, src->arena_len)) return rc;
+    if (int rc = copy_between_devices(buf, dst_device, src->arena, src->device, src->arena_len)) return rc;
     zkr_key *k = nullptr;
-    int rc = zkr_key_adopt_arena(buf.p, src->arena_len, dst_device, &k);
+    int rc = zkr_key_adopt_arena(buf, src->arena_len, dst_device, &k);
     if (rc) return rc;
-    k->owns_arena = true;  // unlike an adopted broadcast buffer, this copy belongs to the replica
+    k->arena_mem = std::move(buf);  // unlike an adopted broadcast buffer, this copy belongs to the replica
     k->replica_mode = ZKR_REPLICATE_FULL; k->replica_direct = direct;
-    buf.release();
     *out = k;
     return 0;
   }
@@ -239,14 +238,7 @@ int shard_eval_tables(zkr_key *k, const zkr_key *src, uint32_t c_lo, const char 
   const char *const no_memory = "the device has no memory for the side tables";
   const uint32_t np_c = h.npts[lt], np_e = h.npts[T_H];
   const size_t rows = ((size_t)sh.m + 1) * 4;
-  bool ok = hipMalloc(&ev.e_pts, (size_t)np_e * k->plan[T_H].K * 64 + 64) == hipSuccess && hipMalloc(&ev.c_pts, (size_t)np_c * k->plan[T_C].K * 64 + 64) == hipSuccess &&
-            hipMalloc(&ev.c_rowptr, rows) == hipSuccess && hipMalloc(&ev.c_col, (size_t)sv.nnz * 4 + 4) == hipSuccess &&
-            hipMalloc(&ev.c_coef, (size_t)sv.nnz * 32 + 32) == hipSuccess && hipMalloc(&ev.c_wide, (size_t)sv.n_wide * 4 + 4) == hipSuccess;
-  for (ProofSlot &sl : k->slot)
-    ok = ok && hipMalloc(&sl.d_bad, (size_t)sl.cap * 4) == hipSuccess && hipHostMalloc(&sl.h_bad, (size_t)sl.cap * 4, hipHostMallocDefault) == hipSuccess;
-  if (!ok) return give_up(no_memory);
-  for (ProofSlot &sl : k->slot) memset(sl.h_bad, 0, (size_t)sl.cap * 4);
-  ev.nnz = sv.nnz; ev.n_wide = sv.n_wide;
+  if (!eval_tables_alloc(k, np_c, np_e, sv.nnz, sv.n_wide)) return give_up(no_memory);
   int rc = cut_table(ev.e_pts, k->device, sv.e_pts, src->device, false, sh.npts[T_H], sh.win_c[T_H], h.sc_lo[1], np_e, k->plan[T_H]);
   if (!rc) rc = cut_table(ev.c_pts, k->device, sv.c_pts, src->device, false, sh.npts[lt], sh.win_c[T_C], c_lo, np_c, k->plan[T_C]);
   auto cp = [&](void *dst, const void *from, size_t bytes) { return bytes ? copy_between_devices(dst, k->device, from, src->device, bytes) : 0; };
@@ -270,7 +262,7 @@ int zkr_key_shard_opts(const zkr_key *src, unsigned part, unsigned parts, int de
   if (flags & ~ZKR_SHARD_SIDE_TABLES) { set_error("zkr_key_shard_opts: unknown flags %#x", flags); return ZKR_ERR_ARG; }
   if (parts < 1 || parts > 64 || part >= parts) { set_error("shard %u of %u: parts must be 1..64 and part below it", part, parts); return ZKR_ERR_ARG; }
   if (src->h.shard_parts != 1) { set_error("the key is itself a shard (%u of %u): shard the whole key", src->h.shard_part, src->h.shard_parts); return ZKR_ERR_ARG; }
-  if (zkr_device_count() <= device || device < 0) { set_error("no HIP device %d (found %d)", device, zkr_device_count()); return ZKR_ERR_NO_DEVICE; }
+  if (int rc = need_device(device)) return rc;
   const ArenaHeader &sh = src->h;
   ArenaHeader h = sh;
   h.shard_part = part; h.shard_parts = parts;
@@ -319,9 +311,9 @@ int zkr_key_shard_opts(const zkr_key *src, unsigned part, unsigned parts, int de
   for (int d = 0, nd = zkr_device_count(); d < nd; d++)
     if (d != device) { (void)peer_direct(device, d); (void)peer_direct(d, device); }
   ZKR_HIP_CHECK(hipSetDevice(device));
-  DevBuf buf;
+  Dev<unsigned char> buf;
   if (int rc = buf.alloc(h.total_len)) return rc;
-  unsigned char *arena = buf.as<unsigned char>();
+  unsigned char *arena = buf;
   ZKR_HIP_CHECK(hipMemset(arena, 0, h.total_len));
   ZKR_HIP_CHECK(hipMemcpy(arena, &h, sizeof(h), hipMemcpyHostToDevice));
   auto cp = [&](uint64_t dst, uint64_t from, size_t bytes) { return bytes ? copy_between_devices(arena + dst, device, src->arena + from, src->device, bytes) : 0; };
@@ -346,8 +338,7 @@ int zkr_key_shard_opts(const zkr_key *src, unsigned part, unsigned parts, int de
   zkr_key *k = nullptr;
   rc = zkr_key_adopt_arena(arena, h.total_len, device, &k);
   if (rc) return rc;
-  k->owns_arena = true;
-  buf.release();
+  k->arena_mem = std::move(buf);
   if (flags & ZKR_SHARD_SIDE_TABLES) {
     const char *why = nullptr;
     rc = shard_eval_tables(k, src, pt_lo[src->layout.sort_src[T_C]], &why);

@@ -29,9 +29,9 @@ static int stage_index(const char *name) {
 }
 static hipEvent_t next_event(ProofSlot &sl) {  // nullptr when the runtime cannot create another event
   if (sl.event_next == sl.event_pool.size()) {
-    hipEvent_t e = nullptr;
-    if (hipEventCreate(&e) != hipSuccess) return nullptr;
-    sl.event_pool.push_back(e);
+    ScopedEvent e;
+    if (e.create()) return nullptr;
+    sl.event_pool.push_back(std::move(e));
   }
   return sl.event_pool[sl.event_next++];
 }
@@ -92,17 +92,16 @@ static std::vector<PassSpec> ntt_plan(int L, int tile_log) {
 }
 
 // the butterflies' twiddle tables (x 2^261, one entry more than the x 2^256 tables they are made from; kernels_ntt.hpp)
-int ntt_tables29_build(const Fr *tw, uint32_t n_tw, const Fr *twl, uint32_t n_twl, hipStream_t s, Tw29 **tw29, Tw29 **twl29) {
-  *tw29 = *twl29 = nullptr;
-  DevBuf a, b;
+int ntt_tables29_build(const Fr *tw, uint32_t n_tw, const Fr *twl, uint32_t n_twl, hipStream_t s, Dev<Tw29> &tw29, Dev<Tw29> &twl29) {
+  Dev<Tw29> a, b;
   int rc;
-  if ((rc = a.alloc(((size_t)n_tw + 1) * sizeof(Tw29))) || (rc = b.alloc(((size_t)n_twl + 1) * sizeof(Tw29)))) return rc;
-  twiddle261_kernel<<<(n_tw + 256) / 256, 256, 0, s>>>(tw, n_tw, a.as<Tw29>());
-  twiddle261_kernel<<<(n_twl + 256) / 256, 256, 0, s>>>(twl, n_twl, b.as<Tw29>());
+  if ((rc = a.alloc((size_t)n_tw + 1)) || (rc = b.alloc((size_t)n_twl + 1))) return rc;
+  twiddle261_kernel<<<(n_tw + 256) / 256, 256, 0, s>>>(tw, n_tw, a);
+  twiddle261_kernel<<<(n_twl + 256) / 256, 256, 0, s>>>(twl, n_twl, b);
   ZKR_HIP_CHECK(hipGetLastError());
   ZKR_HIP_CHECK(hipStreamSynchronize(s));  // the proving streams are non-blocking: they do not order themselves after this one
-  *tw29 = (Tw29 *)a.release();
-  *twl29 = (Tw29 *)b.release();
+  tw29 = std::move(a);
+  twl29 = std::move(b);
   return 0;
 }
 
@@ -1013,9 +1012,10 @@ static int stage_acquire(zkr_key *k, int *idx, bool wait = true) {
       if (ws.busy) continue;
       if (!ws.d_w) {
         ZKR_HIP_CHECK(hipSetDevice(k->device));
-        const size_t bytes = (size_t)k->h.n * 32 * (size_t)k->slot[0].cap;  // one fused group of witnesses
-        if (!ws.ev_up) ZKR_HIP_CHECK(hipEventCreateWithFlags(&ws.ev_up, hipEventDisableTiming));
-        ZKR_HIP_CHECK(hipMalloc(&ws.d_w, bytes));  // last: a stage with d_w set is complete
+        const size_t count = (size_t)k->h.n * (size_t)k->slot[0].cap;  // one fused group of witnesses
+        if (!ws.ev_up)
+          if (int erc = ws.ev_up.create(hipEventDisableTiming)) return erc;
+        if (int arc = ws.d_w.alloc(count)) return arc;  // last: a stage with d_w set is complete
       }
       ws.busy = true;
       *idx = i;
@@ -1329,7 +1329,8 @@ int zkr_ntt(void *data_std, unsigned logn, int inverse, int device) {
   ZKR_HIP_CHECK(hipSetDevice(device));
   if (int lrc = ntt_lds_check(device)) return lrc;
   size_t n = (size_t)1 << logn;
-  DevBuf bd, bd2, btw, btwl, btw29, btwl29;
+  DevBuf bd, bd2, btw, btwl;
+  Dev<Tw29> tw29, twl29;
   int rc;
   if ((rc = bd.alloc(n * 32)) || (rc = bd2.alloc(n * 32)) || (rc = btw.alloc(n * 32)) || (rc = btwl.alloc((size_t)(1u << TWL_LOG) * 32))) return rc;
   Fr *d = bd.as<Fr>(), *d2 = bd2.as<Fr>(), *tw = btw.as<Fr>(), *twl = btwl.as<Fr>();
@@ -1337,9 +1338,7 @@ int zkr_ntt(void *data_std, unsigned logn, int inverse, int device) {
   ingest_kernel<<<(unsigned)((n + 255) / 256), 256>>>(d, d, n);  // any 256-bit word -> below r, as the proving path does with witnesses: the passes state bounds on what they load
   twiddle_table_kernel<<<(unsigned)((n + 255) / 256), 256>>>(tw, (uint32_t)n, host_root_of_unity(logn + 1));
   twiddle_table_kernel<<<((1u << TWL_LOG) + 255) / 256, 256>>>(twl, 1u << TWL_LOG, host_root_of_unity(TWL_LOG + 1));
-  Tw29 *tw29 = nullptr, *twl29 = nullptr;
-  rc = ntt_tables29_build(tw, (uint32_t)n, twl, 1u << TWL_LOG, nullptr, &tw29, &twl29);
-  btw29.p = tw29; btwl29.p = twl29;
+  rc = ntt_tables29_build(tw, (uint32_t)n, twl, 1u << TWL_LOG, nullptr, tw29, twl29);
   if (!rc) rc = run_ntt(nullptr, d, nullptr, d, NttTables{tw, tw29, twl29, (int)logn}, (int)logn, true, inverse != 0, PRE_NONE, 1, Prof{nullptr, nullptr});  // natural -> bit-reversed
   if (!rc) {
     bitrev_copy_kernel<<<(unsigned)((n + 255) / 256), 256>>>(d, d2, (int)logn);
@@ -1423,15 +1422,14 @@ extern "C" int zkr_selftest_ntt(int device, const zkr_ntt_selftest_desc *desc, v
 
   // the tables, as zkr_ntt builds them, for 2^tlog
   const size_t nt = (size_t)1 << d.tlog;
-  DevBuf btw, btwl, btw29, btwl29;
+  DevBuf btw, btwl;
+  Dev<Tw29> tw29, twl29;
   int rc;
   if ((rc = btw.alloc(nt * 32)) || (rc = btwl.alloc((size_t)(1u << TWL_LOG) * 32))) return rc;
   Fr *tw = btw.as<Fr>(), *twl = btwl.as<Fr>();
   twiddle_table_kernel<<<(unsigned)((nt + 255) / 256), 256>>>(tw, (uint32_t)nt, host_root_of_unity(d.tlog + 1));
   twiddle_table_kernel<<<((1u << TWL_LOG) + 255) / 256, 256>>>(twl, 1u << TWL_LOG, host_root_of_unity(TWL_LOG + 1));
-  Tw29 *tw29 = nullptr, *twl29 = nullptr;
-  rc = ntt_tables29_build(tw, (uint32_t)nt, twl, 1u << TWL_LOG, nullptr, &tw29, &twl29);
-  btw29.p = tw29; btwl29.p = twl29;
+  rc = ntt_tables29_build(tw, (uint32_t)nt, twl, 1u << TWL_LOG, nullptr, tw29, twl29);
   if (rc) return rc;
   const NttTables tb{tw, tw29, twl29, (int)d.tlog};
 
@@ -1588,7 +1586,7 @@ int zkr_prof_get(zkr_key *key, const char *stage, double *ms_total, uint64_t *la
 
 static int bench_fq_mul(int device, double *gmuls_per_s, int legacy) {
   if (!gmuls_per_s) { set_error("null argument"); return ZKR_ERR_ARG; }
-  if (zkr_device_count() <= device || device < 0) { set_error("no HIP device %d", device); return ZKR_ERR_NO_DEVICE; }
+  if (int rc = need_device(device)) return rc;
   ZKR_HIP_CHECK(hipSetDevice(device));
   const unsigned blocks = 256 * 8, iters = 2048;
   size_t nthreads = (size_t)blocks * MSM_THREADS;
@@ -1603,12 +1601,12 @@ static int bench_fq_mul(int device, double *gmuls_per_s, int legacy) {
   fq_mul_bench_kernel<<<blocks, MSM_THREADS>>>(d, 256, legacy);  // warm up: brings the clock up under this load
   float ms = 0;
   for (int rep = 0; rep < 3; rep++) {  // best of three ~30 ms launches: a single short launch scatters by +-4 % with the clock ramp
-    ZKR_HIP_CHECK(hipEventRecord(ev0.e, nullptr));
+    ZKR_HIP_CHECK(hipEventRecord(ev0, nullptr));
     fq_mul_bench_kernel<<<blocks, MSM_THREADS>>>(d, (int)iters, legacy);
-    ZKR_HIP_CHECK(hipEventRecord(ev1.e, nullptr));
-    ZKR_HIP_CHECK(hipEventSynchronize(ev1.e));
+    ZKR_HIP_CHECK(hipEventRecord(ev1, nullptr));
+    ZKR_HIP_CHECK(hipEventSynchronize(ev1));
     float t = 0;
-    ZKR_HIP_CHECK(hipEventElapsedTime(&t, ev0.e, ev1.e));
+    ZKR_HIP_CHECK(hipEventElapsedTime(&t, ev0, ev1));
     if (rep == 0 || t < ms) ms = t;
   }
   *gmuls_per_s = (double)nthreads * iters * 4 / (ms * 1e-3) / 1e9;
@@ -1616,13 +1614,12 @@ static int bench_fq_mul(int device, double *gmuls_per_s, int legacy) {
 }
 int zkr_selftest_f29_forms(int device, int field, int form, const uint32_t *records, size_t n, uint32_t *out) {
   if (!records || !out || form < 0 || form > 3 || (field != 0 && field != 1)) { set_error("bad argument"); return ZKR_ERR_ARG; }
-  if (zkr_device_count() <= device || device < 0) { set_error("no HIP device %d", device); return ZKR_ERR_NO_DEVICE; }
+  if (int rc = need_device(device)) return rc;
   if (n == 0) return 0;
   ZKR_HIP_CHECK(hipSetDevice(device));
-  uint32_t *d_in = nullptr, *d_out = nullptr;
-  ZKR_HIP_CHECK(hipMalloc(&d_in, n * 72 * 4));
-  if (hipMalloc(&d_out, n * 9 * 4) != hipSuccess) { hipFree(d_in); set_error("hipMalloc failed"); return ZKR_ERR_HIP; }
-  int rc = 0;
+  Dev<uint32_t> d_in, d_out;
+  int rc;
+  if ((rc = d_in.alloc(n * 72)) || (rc = d_out.alloc(n * 9))) return rc;
   if (hipMemcpy(d_in, records, n * 72 * 4, hipMemcpyHostToDevice) != hipSuccess) rc = ZKR_ERR_HIP;
   if (!rc) {
     const unsigned grid = (unsigned)((n + 127) / 128);
@@ -1630,8 +1627,6 @@ int zkr_selftest_f29_forms(int device, int field, int form, const uint32_t *reco
     else f29_forms_kernel<Fr29><<<grid, 128>>>(d_in, n, form, d_out);
     if (hipGetLastError() != hipSuccess || hipMemcpy(out, d_out, n * 9 * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = ZKR_ERR_HIP;
   }
-  hipFree(d_in);
-  hipFree(d_out);
   if (rc) set_error("HIP failure in the product-form self test");
   return rc;
 }

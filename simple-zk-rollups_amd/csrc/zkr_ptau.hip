@@ -527,9 +527,9 @@ struct DeviceCombinePlan {
     return 0;
   }
 };
-// out (n_out points, a fresh allocation the caller owns) = the plan's combinations of `pts`
+// out (n_out points, a fresh allocation) = the plan's combinations of `pts`
 template <class C>
-int combine_run(const DeviceCombinePlan &dp, const Affine<typename C::W> *pts, void *ztmp, void **out) {
+int combine_run(const DeviceCombinePlan &dp, const Affine<typename C::W> *pts, void *ztmp, DevBuf &out) {
   using W = typename C::W;
   DevBuf o;
   if (int rc = o.alloc(dp.n_out * sizeof(Affine<W>))) return rc;
@@ -541,7 +541,7 @@ int combine_run(const DeviceCombinePlan &dp, const Affine<typename C::W> *pts, v
                                                                                           k == 0 ? pts : o.as<Affine<W>>());
     ZKR_HIP_CHECK(hipGetLastError());
   }
-  *out = o.release();
+  out = std::move(o);
   return 0;
 }
 
@@ -563,7 +563,7 @@ struct PtauSecrets {
 
 }  // namespace
 
-int ptau_key_tables(const void *ptau, size_t len, int device, uint32_t m, uint32_t n, const QapColumns cols[3], void *d_tbl[N_TABLES], uint8_t consts448[448]) {
+int ptau_key_tables(const void *ptau, size_t len, int device, uint32_t m, uint32_t n, const QapColumns cols[3], DevBuf d_tbl[N_TABLES], uint8_t consts448[448]) {
   PtauLayout l;
   if (const char *f = ptau_header_fault(ptau, len, l)) { set_error("zkr_setup_r1cs_ptau: %s", f); return ZKR_ERR_ARG; }
   if (m > l.M) { set_error("zkr_setup_r1cs_ptau: the circuit's domain is %u; a transcript of power %u serves domains up to 2^%u", m, l.power, l.power); return ZKR_ERR_ARG; }
@@ -604,23 +604,20 @@ int ptau_key_tables(const void *ptau, size_t len, int device, uint32_t m, uint32
   ZKR_HIP_CHECK(hipMemcpy(lag2.p, d.vec<G2Affine>(V_TAU2), (size_t)m * sizeof(G2Affine), hipMemcpyDeviceToDevice));
   if ((rc = group_ntt_launch<G2C>(lag2.as<G2Affine>(), tmp.as<G2Affine>(), logm, true, tw.as<Fr>(), ztmp.p))) return rc;
 
-  struct Tables {  // freed unless handed over
-    void *t[N_TABLES] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    ~Tables() { for (void *p : t) if (p) hipFree(p); }
-  } out;
+  DevBuf out[N_TABLES];  // handed over when all five are complete
   {
     DeviceCombinePlan dp;
-    if ((rc = dp.upload(pa)) || (rc = combine_run<G1C>(dp, lag1.as<G1Affine>(), ztmp.p, &out.t[T_A])) || (rc = sync_or_fail("the A points"))) return rc;
+    if ((rc = dp.upload(pa)) || (rc = combine_run<G1C>(dp, lag1.as<G1Affine>(), ztmp.p, out[T_A])) || (rc = sync_or_fail("the A points"))) return rc;
   }
   {
     DeviceCombinePlan dp;
-    if ((rc = dp.upload(pb)) || (rc = combine_run<G1C>(dp, lag1.as<G1Affine>(), ztmp.p, &out.t[T_B1])) || (rc = combine_run<G2C>(dp, lag2.as<G2Affine>(), ztmp.p, &out.t[T_B2])) ||
+    if ((rc = dp.upload(pb)) || (rc = combine_run<G1C>(dp, lag1.as<G1Affine>(), ztmp.p, out[T_B1])) || (rc = combine_run<G2C>(dp, lag2.as<G2Affine>(), ztmp.p, out[T_B2])) ||
         (rc = sync_or_fail("the B points")))
       return rc;
   }
   {
     DeviceCombinePlan dp;
-    if ((rc = dp.upload(pk)) || (rc = combine_run<G1C>(dp, lag1.as<G1Affine>(), ztmp.p, &out.t[T_C])) || (rc = sync_or_fail("the C and IC points"))) return rc;
+    if ((rc = dp.upload(pk)) || (rc = combine_run<G1C>(dp, lag1.as<G1Affine>(), ztmp.p, out[T_C])) || (rc = sync_or_fail("the C and IC points"))) return rc;
   }
   // hExps[i] = (tau^(i + m) - tau^i) G1 = tau^i Z(tau) G1
   {
@@ -629,7 +626,7 @@ int ptau_key_tables(const void *ptau, size_t len, int device, uint32_t m, uint32
     group_diff_kernel<G1C><<<(m + GROUP_THREADS - 1) / GROUP_THREADS, GROUP_THREADS>>>(hx.as<G1Affine>(), d.vec<G1Affine>(V_TAU1) + m, d.vec<G1Affine>(V_TAU1), m, ztmp.as<Fq>());
     ZKR_HIP_CHECK(hipGetLastError());
     if ((rc = sync_or_fail("the H points"))) return rc;
-    out.t[T_H] = hx.release();
+    out[T_H] = std::move(hx);
   }
   // vk_alfa_1, vk_beta_1, vk_delta_1 | vk_beta_2, vk_delta_2 with delta = 1
   ZKR_HIP_CHECK(hipMemcpy(consts448, d.vec<unsigned char>(V_ALFA1), 64, hipMemcpyDeviceToHost));
@@ -637,14 +634,14 @@ int ptau_key_tables(const void *ptau, size_t len, int device, uint32_t m, uint32
   ZKR_HIP_CHECK(hipMemcpy(consts448 + 192, d.vec<unsigned char>(V_BETA2), 128, hipMemcpyDeviceToHost));
   store_g1_mont(consts448 + 128, g1_generator());
   store_g2_mont(consts448 + 320, g2_generator());
-  for (int t = 0; t < N_TABLES; t++) { d_tbl[t] = out.t[t]; out.t[t] = nullptr; }
+  for (int t = 0; t < N_TABLES; t++) d_tbl[t] = std::move(out[t]);
   return 0;
 }
 
 // the same launches for the side tables a key derives from its own points (zkr_internal.hpp)
 int g1_scale_each(G1Affine *pts, size_t n, const Fr *d_scalars, uint32_t sc_stride, void *ztmp) { return scale_each_launch<G1C>(pts, n, d_scalars, sc_stride, ztmp); }
 int g1_group_ntt(G1Affine *pts, G1Affine *tmp, unsigned logn, bool inverse, Fr *tw, void *ztmp) { return group_ntt_launch<G1C>(pts, tmp, logn, inverse, tw, ztmp); }
-int g1_combine_columns(uint32_t n, const QapColumns &cols, const G1Affine *pts, void **out) {
+int g1_combine_columns(uint32_t n, const QapColumns &cols, const G1Affine *pts, DevBuf &out) {
   CombinePlan pl;
   const QapColumns *src[1] = {&cols};
   const uint32_t zero[1] = {0};
@@ -653,7 +650,7 @@ int g1_combine_columns(uint32_t n, const QapColumns &cols, const G1Affine *pts, 
   DevBuf ztmp;
   int rc;
   if ((rc = dp.upload(pl)) || (rc = ztmp.alloc(2 * pl.n_out * sizeof(Fq))) || (rc = combine_run<G1C>(dp, pts, ztmp.p, out))) return rc;
-  if ((rc = sync_or_fail("combining the points"))) { hipFree(*out); *out = nullptr; }
+  if ((rc = sync_or_fail("combining the points"))) out.reset();
   return rc;
 }
 

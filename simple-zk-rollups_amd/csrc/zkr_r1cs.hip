@@ -176,16 +176,10 @@ struct zkr_r1cs {
   uint64_t nnz[3] = {0, 0, 0};
   DevBuf rowptr[3], col[3], coef[3], wide;
   DevBuf d_ptrs, d_rep;                 // one chunk's witness pointers and reports
-  void *h_ptrs = nullptr;               // pinned: the pointers on their way up
-  unsigned long long *h_rep = nullptr;  // pinned: the reports on their way down
-  hipStream_t stream = nullptr;         // non-blocking, the system's own
-  hipEvent_t ev = nullptr;              // "the caller's stream has come this far"
-  ~zkr_r1cs() {
-    if (ev) hipEventDestroy(ev);
-    if (stream) hipStreamDestroy(stream);
-    if (h_ptrs) hipHostFree(h_ptrs);
-    if (h_rep) hipHostFree(h_rep);
-  }
+  PinnedBuf h_ptrs;                   // the pointers on their way up
+  Pinned<unsigned long long> h_rep;   // the reports on their way down
+  OwnStream stream;                   // non-blocking, the system's own
+  ScopedEvent ev;                     // "the caller's stream has come this far"
   R1csSide side(int s) const { return R1csSide{rowptr[s].as<uint32_t>(), col[s].as<uint32_t>(), coef[s].as<Fr>()}; }
 };
 
@@ -217,12 +211,10 @@ static int r1cs_upload(zkr_r1cs *cs, const Circuit &c) {
   cs->n_wide = (uint32_t)wide.size();
   if (int rc = upload(cs->wide, wide.data(), wide.size() * 4)) return rc;
   int rc;
-  if ((rc = cs->d_ptrs.alloc(R1CS_CHUNK * sizeof(void *))) || (rc = cs->d_rep.alloc(R1CS_CHUNK * 3 * 8))) return rc;
-  ZKR_HIP_CHECK(hipHostMalloc(&cs->h_ptrs, R1CS_CHUNK * sizeof(void *), hipHostMallocDefault));
-  ZKR_HIP_CHECK(hipHostMalloc((void **)&cs->h_rep, R1CS_CHUNK * 3 * 8, hipHostMallocDefault));
-  ZKR_HIP_CHECK(hipStreamCreateWithFlags(&cs->stream, hipStreamNonBlocking));
-  ZKR_HIP_CHECK(hipEventCreateWithFlags(&cs->ev, hipEventDisableTiming));
-  return 0;
+  if ((rc = cs->d_ptrs.alloc(R1CS_CHUNK * sizeof(void *))) || (rc = cs->d_rep.alloc(R1CS_CHUNK * 3 * 8)) || (rc = cs->h_ptrs.alloc(R1CS_CHUNK * sizeof(void *))) ||
+      (rc = cs->h_rep.alloc(R1CS_CHUNK * 3)) || (rc = cs->stream.create()))
+    return rc;
+  return cs->ev.create(hipEventDisableTiming);
 }
 
 extern "C" {

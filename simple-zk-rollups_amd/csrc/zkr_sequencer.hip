@@ -26,6 +26,7 @@
 // storing call is about to overwrite, undone call by call -- and the audit of the stored tree against the records.
 #include <stdio.h>
 #include <chrono>
+#include <memory>
 #include <mutex>
 #include <vector>
 #include "zkr_internal.hpp"
@@ -330,10 +331,6 @@ static int hash_updates(const zkr_ledger *L, size_t U, const Fr *d_new, const ui
   clk.mark(ms[3]);
   return ZKR_OK;
 }
-int need_device(int device, const char *what) {
-  if (zkr_device_count() <= device || device < 0) { set_error("no HIP device %d; %s runs on the GPU and has no CPU fallback", device, what); return ZKR_ERR_NO_DEVICE; }
-  return ZKR_OK;
-}
 
 // ---- keeping the ledger
 enum : size_t { STATE_PIECE = (size_t)1 << 20 };  // records go to the device in pieces of at most 2^20: 128 MB of staging
@@ -349,21 +346,19 @@ static int journal_before_store(zkr_ledger *l, const SeqView &v, const int32_t *
   for (size_t i = 0; i < (size_t)v.depth * U; i++) count += last[i] != 0;
   if (base + count > l->jcap) {
     const size_t cap = (base + count) + (base + count) / 2;
-    uint32_t *off = nullptr;
-    Fr *old = nullptr;
-    if (hipMalloc((void **)&off, cap * 4) != hipSuccess || hipMalloc((void **)&old, cap * 32) != hipSuccess) {
-      if (off) hipFree(off);
+    Dev<uint32_t> off;
+    Dev<Fr> old;
+    if (off.alloc(cap) || old.alloc(cap)) {
       set_error("out of device memory for a checkpoint journal of %zu nodes", cap);
       return ZKR_ERR_HIP;
     }
     hipError_t e = base ? hipMemcpy(off, l->d_joff, base * 4, hipMemcpyDeviceToDevice) : hipSuccess;
     if (e == hipSuccess && base) e = hipMemcpy(old, l->d_jold, base * 32, hipMemcpyDeviceToDevice);
-    if (e != hipSuccess) { hipFree(off), hipFree(old); set_error("moving the checkpoint journal failed: %s", hipGetErrorString(e)); return ZKR_ERR_HIP; }
-    if (l->d_joff) hipFree(l->d_joff);
-    if (l->d_jold) hipFree(l->d_jold);
-    l->d_joff = off, l->d_jold = old, l->jcap = cap;
+    if (e != hipSuccess) { set_error("moving the checkpoint journal failed: %s", hipGetErrorString(e)); return ZKR_ERR_HIP; }
+    l->d_joff = std::move(off), l->d_jold = std::move(old), l->jcap = cap;
   }
-  if (!l->d_jcount) ZKR_HIP_CHECK(hipMalloc((void **)&l->d_jcount, 4));
+  if (!l->d_jcount)
+    if (int rc = l->d_jcount.alloc(1)) return rc;
   uint32_t written = 0;
   ZKR_HIP_CHECK(hipMemsetAsync(l->d_jcount, 0, 4, s));
   state_journal_kernel<<<blocks(((size_t)v.depth + 1) * U, 256), 256, 0, s>>>(v, l->d_joff + base, l->d_jold + base, (uint32_t)count, l->d_jcount);
@@ -643,10 +638,10 @@ int zkr_ledger_new(unsigned depth, int device, zkr_ledger **out) {
   if (rc) return rc;
   ZKR_HIP_CHECK(hipSetDevice(device));
   if ((rc = upload_mimc_constants(device))) return rc;
-  zkr_ledger *L = new zkr_ledger;
+  std::unique_ptr<zkr_ledger> L(new zkr_ledger);
   L->depth = depth, L->device = device;
   const size_t total = ((size_t)2 << depth) - 1;
-  if (hipMalloc((void **)&L->d_tree, total * 32) != hipSuccess) { delete L; set_error("out of device memory for a tree of depth %u", depth); return ZKR_ERR_HIP; }
+  if (L->d_tree.alloc(total)) { set_error("out of device memory for a tree of depth %u", depth); return ZKR_ERR_HIP; }
   uint8_t z[64] = {0};  // the empty tree: every node of a level is the hash of two empty nodes below (merkletree.ts:44-60)
   hipError_t e = hipSuccess;
   for (unsigned l = 0; l <= depth && e == hipSuccess; l++) {
@@ -660,23 +655,15 @@ int zkr_ledger_new(unsigned depth, int device, zkr_ledger **out) {
     zkr_mimcsponge_multihash(z, 2, z);
   }
   if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e != hipSuccess) { hipFree(L->d_tree); delete L; set_error("ledger tree fill failed: %s", hipGetErrorString(e)); return ZKR_ERR_HIP; }
-  *out = L;
+  if (e != hipSuccess) { set_error("ledger tree fill failed: %s", hipGetErrorString(e)); return ZKR_ERR_HIP; }
+  *out = L.release();
   return ZKR_OK;
 }
 
 void zkr_ledger_free(zkr_ledger *l) {
   if (!l) return;
-  if (hipSetDevice(l->device) == hipSuccess) {
-    if (l->d_tree) hipFree(l->d_tree);
-    if (l->arena.p) hipFree(l->arena.p);
-    if (l->d_joff) hipFree(l->d_joff);
-    if (l->d_jold) hipFree(l->d_jold);
-    if (l->d_jcount) hipFree(l->d_jcount);
-    book_free(l);
-  }
-  delete l->book;
-  delete l;
+  (void)hipSetDevice(l->device);
+  delete l;  // the tree, the arena, the journal and the book's tables go with their owners
 }
 
 int zkr_ledger_info(const zkr_ledger *l, uint64_t out[4]) {
@@ -749,8 +736,8 @@ int zkr_eddsa_verify_batch(const uint8_t *msgs, unsigned arity, const uint8_t *s
   ZKR_HIP_CHECK(hipSetDevice(device));
   if ((rc = upload_mimc_constants(device))) return rc;
   const size_t mb = DevArena::padded(n * arity * 32), sb = DevArena::padded(n * 96), pb = DevArena::padded(n * 64);
-  char *d = nullptr;
-  ZKR_HIP_CHECK(hipMalloc((void **)&d, mb + sb + pb + n));
+  Dev<char> d;
+  if ((rc = d.alloc(mb + sb + pb + n))) return rc;
   Fr *d_msgs = (Fr *)d, *d_sigs = (Fr *)(d + mb), *d_pubs = (Fr *)(d + mb + sb);
   uint8_t *d_v = (uint8_t *)(d + mb + sb + pb);
   hipError_t e = hipMemcpy(d_msgs, msgs, n * arity * 32, hipMemcpyHostToDevice);
@@ -761,7 +748,6 @@ int zkr_eddsa_verify_batch(const uint8_t *msgs, unsigned arity, const uint8_t *s
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpy(verdicts, d_v, n, hipMemcpyDeviceToHost);
-  hipFree(d);
   if (e != hipSuccess) { set_error("batch signature check failed: %s", hipGetErrorString(e)); return ZKR_ERR_HIP; }
   return ZKR_OK;
 }

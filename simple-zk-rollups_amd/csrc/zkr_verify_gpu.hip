@@ -212,32 +212,27 @@ struct zkr_vk {
   size_t n_public = 0;
   G1Affine ic0;
   DevBuf consts, win8, lines, f_alfa_beta;  // lines: beta | gamma | delta, N_LINES each
-  hipStream_t stream = nullptr;
-  hipEvent_t ev = nullptr;
+  OwnStream stream;
+  ScopedEvent ev;
   // per-batch buffers, for `cap` proofs: they grow to the largest piece seen
   size_t cap = 0;
   DevBuf proofs, pub, wptrs, a, b, c, vkx, f, verdict, degenerate;
-  uint32_t *h_verdict = nullptr;  // pinned
-  ~zkr_vk() {
-    if (stream) hipStreamDestroy(stream);
-    if (ev) hipEventDestroy(ev);
-    if (h_verdict) hipHostFree(h_verdict);
-  }
+  Pinned<uint32_t> h_verdict;
 };
 
 namespace {
 int vk_reserve(zkr_vk *vk, size_t n) {
   if (n <= vk->cap) return 0;
   for (DevBuf *d : {&vk->proofs, &vk->pub, &vk->wptrs, &vk->a, &vk->b, &vk->c, &vk->vkx, &vk->f, &vk->verdict, &vk->degenerate})
-    if (d->p) { ZKR_HIP_CHECK(hipFree(d->p)); d->p = nullptr; }
-  if (vk->h_verdict) { ZKR_HIP_CHECK(hipHostFree(vk->h_verdict)); vk->h_verdict = nullptr; }
+    d->reset();  // all of the old ones before any of the new
+  vk->h_verdict.reset();
   vk->cap = 0;
   int rc;
   if ((rc = vk->proofs.alloc(n * 256)) || (rc = vk->pub.alloc(n * vk->n_public * 32)) || (rc = vk->wptrs.alloc(n * sizeof(void *))) ||
       (rc = vk->a.alloc(n * sizeof(G1Affine))) || (rc = vk->b.alloc(n * sizeof(G2Affine))) || (rc = vk->c.alloc(n * sizeof(G1Affine))) ||
       (rc = vk->vkx.alloc(n * sizeof(G1Affine))) || (rc = vk->f.alloc(3 * n * sizeof(Fq12))) || (rc = vk->verdict.alloc(n * 4)) || (rc = vk->degenerate.alloc(n * 4)))
     return rc;
-  ZKR_HIP_CHECK(hipHostMalloc((void **)&vk->h_verdict, n * 4, hipHostMallocDefault));
+  if ((rc = vk->h_verdict.alloc(n))) return rc;
   vk->cap = n;
   return 0;
 }
@@ -331,8 +326,8 @@ int zkr_vk_load(const void *vk_bin, size_t vk_len, int device, zkr_vk **out) {
     if ((rc = upload(vk->consts, &k, sizeof(k))) || (rc = upload(vk->win8, win8.data(), win8.size() * sizeof(G1Affine))) ||
         (rc = upload(vk->lines, lines.data(), lines.size() * sizeof(Line))) || (rc = upload(vk->f_alfa_beta, &fab, sizeof(fab))))
       return rc;
-    ZKR_HIP_CHECK(hipStreamCreateWithFlags(&vk->stream, hipStreamNonBlocking));
-    ZKR_HIP_CHECK(hipEventCreateWithFlags(&vk->ev, hipEventDisableTiming));
+    if (int src = vk->stream.create()) return src;
+    if (int erc = vk->ev.create(hipEventDisableTiming)) return erc;
     return 0;
   };
   if ((rc = setup())) { delete vk; return rc; }

@@ -82,10 +82,6 @@ static __global__ __launch_bounds__(256) void withdraw_layout_kernel(const Fr *i
   wit[g] = v;
 }
 
-static int need_device(int device, const char *what) {
-  if (zkr_device_count() <= device || device < 0) { set_error("no HIP device %d; %s runs on the GPU and has no CPU fallback", device, what); return ZKR_ERR_NO_DEVICE; }
-  return ZKR_OK;
-}
 static inline unsigned blocks_of(size_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
 static void host_tables(std::vector<Fr> &tab, TxConsts &k) {
   tab.resize(2 * 253);
@@ -102,21 +98,15 @@ static size_t first_not_below_r(const uint8_t *p, size_t count) {
   return count;
 }
 // a device buffer that held secrets: zeroed, and the zeroing waited for, before it is freed -- however the call is left
-struct SecretBuf {
-  void *p = nullptr;
+struct SecretBuf : DevBuf {  // whose own destructor frees, after this one has run
   size_t bytes = 0;
   hipStream_t s = nullptr;
-  SecretBuf() = default;
-  SecretBuf(const SecretBuf &) = delete;
-  SecretBuf &operator=(const SecretBuf &) = delete;
   ~SecretBuf() {
     if (!p) return;
     (void)hipMemsetAsync(p, 0, bytes, s);
     (void)hipStreamSynchronize(s);
-    (void)hipFree(p);
   }
-  int alloc(size_t n) { ZKR_HIP_CHECK(hipMalloc(&p, n ? n : 1)); bytes = n; return 0; }
-  template <class T> T *as() const { return static_cast<T *>(p); }
+  int alloc(size_t n) { bytes = n; return DevBuf::alloc(n); }
 };
 enum : size_t { WALLET_PIECE = (size_t)1 << 20, WITHDRAW_PIECE = 4096 };  // items per launch: 32 MB of keys; 128 MB of chain workspace
 
