@@ -147,15 +147,13 @@ struct SetupScalars {
   std::vector<Fr> cpriv, ic, hx;      // (beta a + alfa b + c)/delta for s>p ; /gamma for s<=p ; t^i Z(t)/delta
 };
 
-Fr host_root_of_unity(unsigned k);
-
 template <class T> static void wipe_vector(std::vector<T> &v);
 static void setup_scalars(const Circuit &c, const Toxic &tx, SetupScalars &sc, bool secret) {
   uint32_t m = c.m, n = c.n, p = c.p;
   unsigned logm = 0;
   while ((1u << logm) < m) logm++;
   // L_c(t) = (t^m - 1) w^c / (m (t - w^c)) with one batch inversion
-  Fr w = host_root_of_unity(logm);
+  Fr w = fr_root_of_unity(logm);
   std::vector<Fr> wc(m), den(m), pref(m);
   Fr cur = Fr::one();
   for (uint32_t i = 0; i < m; i++) { wc[i] = cur; den[i] = sub(tx.t, cur); cur = mul(cur, w); }
@@ -352,7 +350,7 @@ static int key_build_eval_tables(zkr_key *k, const Generated &g, bool refuse) {
   const ArenaHeader &h = k->h;
   const Circuit &c = g.circ;
   const uint32_t n = h.n, m = h.m, p = h.p;
-  if (const char *e = getenv("ZKR_H_FORM"); e && !strcmp(e, "coefficients")) return 0;
+  if (h_form_forced_coefficients()) return 0;
   if (refuse || h.shard_parts != 1 || !h.npts[T_C] || h.npts[T_H] != m) return 0;
   ZKR_HIP_CHECK(hipSetDevice(k->device));
   struct Secret {  // scalars that reveal t or delta go the way the setup's own do

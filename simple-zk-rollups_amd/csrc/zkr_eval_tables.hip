@@ -154,7 +154,7 @@ int zkr_key_eval_tables(zkr_key *key, const void *r1cs_bin, size_t r1cs_len, uns
   std::lock_guard<std::mutex> lk(key->mu);  // no proof starts while the tables change
   if (int rc = refuse_in_flight(key, "zkr_key_eval_tables")) return rc;
   key_eval_tables_free(key);
-  if (const char *e = getenv("ZKR_H_FORM"); e && !strcmp(e, "coefficients")) { set_error("zkr_key_eval_tables: not built: ZKR_H_FORM=coefficients"); return 0; }
+  if (h_form_forced_coefficients()) { set_error("zkr_key_eval_tables: not built: ZKR_H_FORM=coefficients"); return 0; }
   if (!h.npts[T_C] || h.npts[T_H] != h.m) { set_error("zkr_key_eval_tables: not built: the key's H table dropped a point, or it has no C points"); return 0; }
   const char *why = nullptr;
   int rc = key_eval_rows(key, c);

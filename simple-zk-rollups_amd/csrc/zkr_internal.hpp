@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
 #include <time.h>
 #include <atomic>
 #include <condition_variable>
@@ -19,6 +21,8 @@ namespace zkr {
 
 struct Tw29;  // kernels_ntt.hpp: a butterfly twiddle as nine 29-bit limbs
 int os_random(void *out, size_t bytes);  // `bytes` from the OS CSPRNG (zkr_key.hip, beside set_error); ZKR_ERR_ARG with a message when it cannot be read
+// ZKR_H_FORM=coefficients: no side tables are built and every proof takes the coefficient form.  Read at every call, kept nowhere
+inline bool h_form_forced_coefficients() { const char *e = getenv("ZKR_H_FORM"); return e && !strcmp(e, "coefficients"); }
 // every entry point that needs a GPU refuses the same way when there is none
 inline int need_device(int device) {
   const int found = zkr_device_count();
@@ -250,17 +254,14 @@ struct Prof {  // where a launch helper records its timing spans (null key: stag
   zkr_key *k;
   ProofSlot *sl;
 };
+constexpr Prof NO_PROF{nullptr, nullptr};
 int prof_begin(Prof pf, hipStream_t s, const char *stage);
 void prof_end(Prof pf, hipStream_t s, int span);
 int prof_collect(zkr_key *k, ProofSlot &sl);
 struct NttTables { const Fr *tw; const Tw29 *tw29, *twl29; int tlog; };  // x 2^256 powers of w_{2m} (coset factors); x 2^261 powers for the butterflies (kernels_ntt.hpp)
 int ntt_lds_check(int device);  // ZKR_ERR_NO_DEVICE with a clear message when the device cannot hold an NTT tile in LDS
 int ntt_tables29_build(const Fr *tw, uint32_t n_tw, const Fr *twl, uint32_t n_twl, hipStream_t s, Dev<Tw29> &tw29, Dev<Tw29> &twl29);
-int run_ntt(hipStream_t s, const Fr *in0, const Fr *in1, Fr *out, const NttTables &tb, int L, bool dif, bool inverse, int pre, int nbat, Prof pf,
-            const Fr *in0_b = nullptr, const Fr *in1_b = nullptr, Fr *out_b = nullptr,  // in0_b / in1_b / out_b: a second transform of the same shape in the same launches
-            uint32_t want_lo = 0, uint32_t want_n = 0,   // DIF: only this range of the output is wanted (0, 0: all of it)
-            uint32_t coset_shift = 0, uint32_t coset_add = 0);  // PRE_COSET when the transform is one block of a larger one (NttPassArgs::pre_shift)
-int calc_h_device(zkr_key *k, ProofSlot &sl, hipStream_t s, int nbat = 1);  // sl.d_w -> sl.d_h (bit-reversed), nbat vectors end to end
+void ntt_twiddles_fill(Fr *tw, unsigned k, Fr *twl, hipStream_t s);  // tw[i] = w_{2^(k+1)}^i, 2^k entries; twl[i] = w_{2^(TWL_LOG+1)}^i, 2^TWL_LOG entries; launches only
 
 // ShardGroup (the shards of one proof running concurrently; barrier + abort): shard_group.hpp, no HIP in it
 // set by run_sharded's worker threads around zkr_prove_partial(_device): the proof this thread enqueues -- and collects -- is part

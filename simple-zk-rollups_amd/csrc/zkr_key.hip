@@ -10,7 +10,6 @@
 #include "kernels_ntt.hpp"
 #include "kernels_group.hpp"  // group_on_curve_launch for ZKR_CHECK_POINTS
 #include "hostops.hpp"
-#include "eval_h.hpp"  // fr_root_of_unity
 #include <map>
 #include "zkr_internal.hpp"
 
@@ -34,8 +33,6 @@ int os_random(void *out, size_t bytes) {
 }
 
 static inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
-
-Fr host_root_of_unity(unsigned k) { return fr_root_of_unity(k); }
 
 // The arena's layout: header, twiddles, the two QAP sides (CSR), then per table its K window levels and its rank map.
 // Everything that builds an arena -- key_build, the receiver of a compact arena, zkr_key_shard -- takes the offsets from here,
@@ -457,8 +454,7 @@ int key_build(int device, uint32_t n, uint32_t p, uint32_t m, const std::vector<
   }
   ZKR_HIP_CHECK(hipMemcpy(arena, &h, sizeof(h), hipMemcpyHostToDevice));  // again: rank_identity was filled in above
   // twiddles on device: T[k] = w_{2m}^k and w_2048^k
-  twiddle_table_kernel<<<(m + 255) / 256, 256>>>((Fr *)(arena + h.off_tw), m, fr_root_of_unity(h.logm + 1));
-  twiddle_table_kernel<<<((1u << TWL_LOG) + 255) / 256, 256>>>((Fr *)(arena + h.off_twl), 1u << TWL_LOG, fr_root_of_unity(TWL_LOG + 1));
+  ntt_twiddles_fill((Fr *)(arena + h.off_tw), h.logm, (Fr *)(arena + h.off_twl), nullptr);
   ZKR_HIP_CHECK(hipGetLastError());
   ZKR_HIP_CHECK(hipDeviceSynchronize());
 
@@ -811,8 +807,7 @@ int arena_from_base(const void *dev_ptr, size_t len, int device, Dev<unsigned ch
   if (int crc = key_arena_check(device, arena, h, 0, nullptr)) return crc;
   for (int t = 0; t < N_TABLES; t++)
     if (int rc = msm_precompute(device, t == T_B2, arena + h.off_pts[t], h.npts[t], plan[t])) return rc;
-  twiddle_table_kernel<<<(h.m + 255) / 256, 256>>>((Fr *)(arena + h.off_tw), h.m, fr_root_of_unity(h.logm + 1));
-  twiddle_table_kernel<<<((1u << TWL_LOG) + 255) / 256, 256>>>((Fr *)(arena + h.off_twl), 1u << TWL_LOG, fr_root_of_unity(TWL_LOG + 1));
+  ntt_twiddles_fill((Fr *)(arena + h.off_tw), h.logm, (Fr *)(arena + h.off_twl), nullptr);
   e = hipGetLastError();
   if (e == hipSuccess) e = hipDeviceSynchronize();
   if (e != hipSuccess) { set_error("rebuilding the window tables failed: %s", hipGetErrorString(e)); return ZKR_ERR_HIP; }

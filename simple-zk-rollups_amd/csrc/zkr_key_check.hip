@@ -16,6 +16,7 @@
 #include <memory>
 #include <map>
 #include <mutex>
+#include "eval_h.hpp"  // fr_root_of_unity
 #include "kernels_msm.hpp"
 #include "kernels_ntt.hpp"
 #include "hostops.hpp"
@@ -23,8 +24,6 @@
 #include "zkr_internal.hpp"
 
 namespace zkr {
-Fr host_root_of_unity(unsigned k);  // zkr_key.hip
-
 namespace {
 
 constexpr int N_SEC = ZKR_KEYSEC_CONSTS + 1;
@@ -329,9 +328,9 @@ int key_arena_check(int device, const unsigned char *arena, const ArenaHeader &h
       if (t == T_B2) points_check_kernel<Fq2><<<grid_for(count), CHECK_THREADS, 0, st>>>((const G2Affine *)(arena + h.off_pts[t]), count, b2, fc, ff);
       else points_check_kernel<Fq><<<grid_for(count), CHECK_THREADS, 0, st>>>((const G1Affine *)(arena + h.off_pts[t]), count, b1, fc, ff);
     }
-    twiddle_check_kernel<<<grid_for(h.m), CHECK_THREADS, 0, st>>>((const Fr *)(arena + h.off_tw), h.m, host_root_of_unity(h.logm + 1),
+    twiddle_check_kernel<<<grid_for(h.m), CHECK_THREADS, 0, st>>>((const Fr *)(arena + h.off_tw), h.m, fr_root_of_unity(h.logm + 1),
                                                                    &rec->count[ZKR_KEYSEC_TWIDDLES][0], &rec->first[ZKR_KEYSEC_TWIDDLES][0]);
-    twiddle_check_kernel<<<grid_for(1u << TWL_LOG), CHECK_THREADS, 0, st>>>((const Fr *)(arena + h.off_twl), 1u << TWL_LOG, host_root_of_unity(TWL_LOG + 1),
+    twiddle_check_kernel<<<grid_for(1u << TWL_LOG), CHECK_THREADS, 0, st>>>((const Fr *)(arena + h.off_twl), 1u << TWL_LOG, fr_root_of_unity(TWL_LOG + 1),
                                                                              &rec->count[ZKR_KEYSEC_TWIDDLES][1], &rec->first[ZKR_KEYSEC_TWIDDLES][1]);
     CoefArgs c;
     for (int s = 0; s < 2; s++) {

@@ -229,7 +229,7 @@ int shard_eval_tables(zkr_key *k, const zkr_key *src, uint32_t c_lo, const char 
   const EvalTables &sv = src->eval;
   EvalTables &ev = k->eval;
   if (!sv.ready) { *why = "the whole key has no side tables"; return 0; }
-  if (const char *e = getenv("ZKR_H_FORM"); e && !strcmp(e, "coefficients")) { *why = "ZKR_H_FORM=coefficients"; return 0; }
+  if (h_form_forced_coefficients()) { *why = "ZKR_H_FORM=coefficients"; return 0; }
   const int lt = src->layout.sort_src[T_C];
   if (k->layout.sort_src[T_C] != lt) { *why = "the shard's C table reads another digit sort than the whole key's"; return 0; }
   if (h.npts[T_H] != h.sc_n[1] || sh.npts[T_H] != sh.m) { *why = "the H table dropped a point"; return 0; }
@@ -533,7 +533,7 @@ int run_sharded(zkr_key *const *shards, size_t parts, const uint8_t *r32, const 
   // set.  A witness that leaves rows unsatisfied (the shards' counts, summed after their threads have joined) goes again on every
   // shard through the coefficient form, which is exact for every witness.
   bool eval_h = true;
-  if (const char *fe = getenv("ZKR_H_FORM"); fe && !strcmp(fe, "coefficients")) { eval_h = false; set_h_form(ZKR_H_COEFFICIENTS, "ZKR_H_FORM=coefficients"); }
+  if (h_form_forced_coefficients()) { eval_h = false; set_h_form(ZKR_H_COEFFICIENTS, "ZKR_H_FORM=coefficients"); }
   for (size_t i = 0; i < parts && eval_h; i++)
     if (!shards[i]->eval.ready) { eval_h = false; set_h_form(ZKR_H_COEFFICIENTS, "shard %zu has no side tables", i); }
   if (eval_h) set_h_form(ZKR_H_EVALUATION, "every shard has side tables");

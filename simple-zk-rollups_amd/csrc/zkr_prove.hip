@@ -12,12 +12,12 @@
 #include <time.h>
 #include <algorithm>
 #include <memory>
+#include "eval_h.hpp"  // fr_root_of_unity
 #include "kernels_msm.hpp"
 #include "kernels_ntt.hpp"
 #include "zkr_internal.hpp"
 
 namespace zkr {
-Fr host_root_of_unity(unsigned k);
 
 // ------------------------------------------------------------------ profiling (hipEvents on the launch stream)
 static const char *STAGES[] = {"ingest", "spmv", "ntt", "msm_sort", "msm_accum_g1", "msm_accum_g2", "msm_big", "msm_reduce", "total",
@@ -104,6 +104,26 @@ int ntt_tables29_build(const Fr *tw, uint32_t n_tw, const Fr *twl, uint32_t n_tw
   twl29 = std::move(b);
   return 0;
 }
+// the x 2^256 tables those are made from: tw[i] = w_{2^(k+1)}^i for i < 2^k, and the local table twl[i] = w_2048^i for i < 2^TWL_LOG
+void ntt_twiddles_fill(Fr *tw, unsigned k, Fr *twl, hipStream_t s) {
+  const uint32_t n = 1u << k, nl = 1u << TWL_LOG;
+  twiddle_table_kernel<<<(n + 255) / 256, 256, 0, s>>>(tw, n, fr_root_of_unity(k + 1));
+  twiddle_table_kernel<<<(nl + 255) / 256, 256, 0, s>>>(twl, nl, fr_root_of_unity(TWL_LOG + 1));
+}
+// The tables of a stage hook (zkr_ntt, zkr_selftest_ntt), which has no key to take them from: built for 2^tlog on the null stream
+struct HookNttTables {
+  DevBuf tw, twl;
+  Dev<Tw29> tw29, twl29;
+  int tlog = 0;
+  int build(unsigned log) {
+    tlog = (int)log;
+    int rc;
+    if ((rc = tw.alloc((size_t)32 << log)) || (rc = twl.alloc((size_t)32 << TWL_LOG))) return rc;
+    ntt_twiddles_fill(tw.as<Fr>(), log, twl.as<Fr>(), nullptr);
+    return ntt_tables29_build(tw.as<Fr>(), 1u << log, twl.as<Fr>(), 1u << TWL_LOG, nullptr, tw29, twl29);
+  }
+  NttTables view() const { return NttTables{tw.as<Fr>(), tw29, twl29, tlog}; }
+};
 
 // An NTT pass keeps a tile of 2^NTT_TILE_LOG elements x 9 limbs in LDS: 72 KB, above the 64 KB every target before gfx950
 // offers.  Asked once per device, so that another architecture (the Makefile's ARCH can be overridden) fails at key load / in
@@ -123,38 +143,76 @@ int ntt_lds_check(int device) {
 // tiles of 2048 is 64 workgroups, a quarter of the CUs -- were measured (512 / 1024 elements) and change nothing: the wavefront
 // count of a transform does not depend on the tile (a single tx proof 2.00 / 2.04 / 1.97-2.02 ms, profiles/r4_19_tx_single_ntt_tile.txt).
 
-// One transform, or TWO of the same shape in the same launches (in0_b / in1_b / out_b: gridDim.z = 2)
+// A transform call says what it passes by name.  The butterfly and the sign of the exponent are ONE choice out of four:
+enum NttDir { DIF_INVERSE, DIF_FORWARD, DIT_FORWARD, DIT_INVERSE };  // DIF: natural in, bit-reversed out; DIT: the other way round
+struct NttVecs { const Fr *in0 = nullptr, *in1 = nullptr; Fr *out = nullptr; };  // one transform's vectors; in1 with PRE_MUL only: the transform of in0 . in1
+static NttVecs ntt_in_place(Fr *v) { return NttVecs{v, nullptr, v}; }
+// One transform, or TWO of the same shape in the same launches (b: gridDim.z = 2)
 // want_lo / want_n (DIF only; 0, 0 = everything): only positions [want_lo, want_lo + want_n) of the output are wanted -- the
 // passes run on the aligned blocks that cover them (kernels_ntt.hpp NttPassArgs::blk_off); the rest of `out` is left half done
-int run_ntt(hipStream_t s, const Fr *in0, const Fr *in1, Fr *out, const NttTables &tb, int L, bool dif, bool inverse, int pre, int nbat, Prof pf,
-            const Fr *in0_b, const Fr *in1_b, Fr *out_b, uint32_t want_lo, uint32_t want_n, uint32_t coset_shift, uint32_t coset_add) {
-  if (want_n && (!dif || (uint64_t)want_lo + want_n > (1ull << L))) { set_error("run_ntt: an output range needs a DIF transform and must lie inside it"); return ZKR_ERR_ARG; }
+struct NttRun {
+  int L;
+  NttDir dir;
+  int pre = PRE_NONE, nbat = 1;  // nbat vectors end to end in every buffer
+  NttVecs a, b;                  // b.out null: one transform
+  uint32_t want_lo = 0, want_n = 0;
+  uint32_t coset_shift = 0, coset_add = 0;  // PRE_COSET when the transform is one block of a larger one (NttPassArgs::pre_shift; calc_h_split)
+};
+
+// what every pass of either driver is told
+static NttPassArgs ntt_pass_args(const NttTables &tb, int L) {
+  NttPassArgs a = {};
+  a.tw = tb.tw; a.tw29 = tb.tw29; a.twl29 = tb.twl29; a.tlog = tb.tlog; a.L = L;
+  // wave priority 1 for the NTT passes: with the 29-bit-limb accumulations the preparation chain (sorts + calcH) became
+  // the stream that paces two proofs in flight (its kernels starved behind the accumulation's wavefronts: 4.1 ms of NTT
+  // spans per proof at priority 0, 2.9 ms at 1; 120.9 -> 125.2 proofs/s; 2 and 3 measure the same as 1)
+  a.prio = 1;
+  return a;
+}
+template <int T, bool CROSS>
+static void ntt_pass_launch_dir(NttDir dir, dim3 grid, size_t lds, hipStream_t s, const NttPassArgs &a) {
+  switch (dir) {
+    case DIF_INVERSE: ntt_pass_kernel<true, true, T, CROSS><<<grid, T, lds, s>>>(a); break;
+    case DIF_FORWARD: ntt_pass_kernel<true, false, T, CROSS><<<grid, T, lds, s>>>(a); break;
+    case DIT_FORWARD: ntt_pass_kernel<false, false, T, CROSS><<<grid, T, lds, s>>>(a); break;
+    case DIT_INVERSE: ntt_pass_kernel<false, true, T, CROSS><<<grid, T, lds, s>>>(a); break;  // only zkr_selftest_ntt asks for it
+  }
+}
+// One pass inside its `ntt_pass` span: THE place that names the kernel's instantiations -- the four directions at either
+// workgroup size, and as CROSS passes at NTT_THREADS_LARGE only (whatever `threads` says)
+static void ntt_pass_launch(int threads, bool cross, NttDir dir, dim3 grid, size_t lds, hipStream_t s, const NttPassArgs &a, Prof pf) {
+  const int psp = prof_begin(pf, s, "ntt_pass");
+  if (cross) ntt_pass_launch_dir<NTT_THREADS_LARGE, true>(dir, grid, lds, s, a);
+  else if (threads == NTT_THREADS_SMALL) ntt_pass_launch_dir<NTT_THREADS_SMALL, false>(dir, grid, lds, s, a);
+  else ntt_pass_launch_dir<NTT_THREADS_LARGE, false>(dir, grid, lds, s, a);
+  prof_end(pf, s, psp);
+}
+
+static int run_ntt(hipStream_t s, const NttTables &tb, const NttRun &r, Prof pf) {
+  const int L = r.L;
+  const bool dif = r.dir == DIF_INVERSE || r.dir == DIF_FORWARD;
+  if (r.want_n && (!dif || (uint64_t)r.want_lo + r.want_n > (1ull << L))) { set_error("run_ntt: an output range needs a DIF transform and must lie inside it"); return ZKR_ERR_ARG; }
   std::vector<PassSpec> plan = ntt_plan(L, NTT_TILE_LOG);
   if (!dif) std::reverse(plan.begin(), plan.end());
   bool first = true;
   for (auto &ps : plan) {
-    NttPassArgs a = {};
-    a.pre_shift = coset_shift; a.pre_add = coset_add;  // PRE_COSET of a block of a larger transform (calc_h_split)
-    a.in0 = first ? in0 : out;
-    a.in1 = first ? in1 : nullptr;
-    a.out = out;
-    a.in0_b = first ? in0_b : out_b;
-    a.in1_b = first ? in1_b : nullptr;
-    a.out_b = out_b;
-    a.tw = tb.tw; a.tw29 = tb.tw29; a.twl29 = tb.twl29; a.tlog = tb.tlog; a.L = L;
+    NttPassArgs a = ntt_pass_args(tb, L);
+    a.pre_shift = r.coset_shift; a.pre_add = r.coset_add;
+    a.in0 = first ? r.a.in0 : r.a.out;
+    a.in1 = first ? r.a.in1 : nullptr;
+    a.out = r.a.out;
+    a.in0_b = first ? r.b.in0 : r.b.out;
+    a.in1_b = first ? r.b.in1 : nullptr;
+    a.out_b = r.b.out;
     a.lo = ps.lo; a.hi = ps.hi; a.wlog = ps.wlog;
-    a.pre = first ? pre : PRE_NONE;
+    a.pre = first ? r.pre : PRE_NONE;
     a.canon = &ps == &plan.back() ? 1 : 0;  // between passes values stay lazily reduced (below 3 r)
-    // wave priority 1 for the NTT passes: with the 29-bit-limb accumulations the preparation chain (sorts + calcH) became
-    // the stream that paces two proofs in flight (its kernels starved behind the accumulation's wavefronts: 4.1 ms of NTT
-    // spans per proof at priority 0, 2.9 ms at 1; 120.9 -> 125.2 proofs/s; 2 and 3 measure the same as 1)
-    a.prio = 1;
     uint32_t tile = 1u << (ps.hi - ps.lo + ps.wlog);
     uint32_t grid = (1u << L) / tile;
     a.blk_off = 0;
-    if (want_n) {  // the 2^hi-blocks that cover the range, 2^hi / tile workgroups each
+    if (r.want_n) {  // the 2^hi-blocks that cover the range, 2^hi / tile workgroups each
       const uint32_t per_block = (1u << ps.hi) / tile;
-      const uint32_t q0 = want_lo >> ps.hi, q1 = (uint32_t)(((uint64_t)want_lo + want_n + (1u << ps.hi) - 1) >> ps.hi);
+      const uint32_t q0 = r.want_lo >> ps.hi, q1 = (uint32_t)(((uint64_t)r.want_lo + r.want_n + (1u << ps.hi) - 1) >> ps.hi);
       a.blk_off = q0 * per_block;
       grid = (q1 - q0) * per_block;
     }
@@ -162,14 +220,7 @@ int run_ntt(hipStream_t s, const Fr *in0, const Fr *in1, Fr *out, const NttTable
     // workgroup size by transform size (kernels_ntt.hpp NTT_THREADS_*); a tile of 1024 elements has 256 four-element butterfly
     // groups per double stage: 256 threads
     const int threads = (L >= NTT_LARGE_LOG || tile <= 1024) ? NTT_THREADS_LARGE : NTT_THREADS_SMALL;
-#define ZKR_NTT_LAUNCH(DIF, INV, T) ntt_pass_kernel<DIF, INV, T><<<dim3(grid, nbat, out_b ? 2 : 1), T, lds, s>>>(a)
-#define ZKR_NTT_LAUNCH_T(T) do { if (dif) { if (inverse) ZKR_NTT_LAUNCH(true, true, T); else ZKR_NTT_LAUNCH(true, false, T); } \
-                                 else { if (inverse) ZKR_NTT_LAUNCH(false, true, T); else ZKR_NTT_LAUNCH(false, false, T); } } while (0)
-    const int psp = prof_begin(pf, s, "ntt_pass");
-    if (threads == NTT_THREADS_SMALL) ZKR_NTT_LAUNCH_T(NTT_THREADS_SMALL); else ZKR_NTT_LAUNCH_T(NTT_THREADS_LARGE);
-    prof_end(pf, s, psp);
-#undef ZKR_NTT_LAUNCH_T
-#undef ZKR_NTT_LAUNCH
+    ntt_pass_launch(threads, false, r.dir, dim3(grid, r.nbat, r.b.out ? 2 : 1), lds, s, a, pf);
     first = false;
   }
   ZKR_HIP_CHECK(hipGetLastError());
@@ -220,33 +271,44 @@ static void combine_h_consts(uint32_t m, Fr &c1v, Fr &c2v) {
   c2v = mul(mul(c1v, minv), minv);               // Montgomery(R/(2m^3)) = integer R^2/(2m^3)
 }
 
-// d_w (std, reduced) -> d_h (std, bit-reversed order).  See DESIGN.md "calcH on the GPU".
-int calc_h_device(zkr_key *k, ProofSlot &sl, hipStream_t s, int nbat) {
+static NttTables key_ntt_tables(const zkr_key *k) { return NttTables{(const Fr *)(k->arena + k->h.off_tw), k->tw29, k->twl29, (int)k->h.tlog}; }
+
+// What the two replicated forms do first after their QAP rows, nbat witnesses end to end: the `ntt` span opens (the caller closes
+// it), then two pairs of transforms of the same shape, each pair in ONE set of launches (gridDim.z = 2): the coefficients of a and
+// b (sl.va, sl.vb -> sl.ca, sl.cb; x m, bit-reversed), then their evaluations on the coset g*w^c in place (x m, natural)
+static int calc_h_open(zkr_key *k, ProofSlot &sl, hipStream_t s, int nbat, int *ntt_span) {
+  const Prof pf{k, &sl};
+  const NttTables tb = key_ntt_tables(k);
+  const int L = (int)k->h.logm;
+  *ntt_span = prof_begin(pf, s, "ntt");
+  if (int rc = run_ntt(s, tb, NttRun{.L = L, .dir = DIF_INVERSE, .nbat = nbat, .a = {.in0 = sl.va, .out = sl.ca}, .b = {.in0 = sl.vb, .out = sl.cb}}, pf)) return rc;
+  return run_ntt(s, tb, NttRun{.L = L, .dir = DIT_FORWARD, .pre = PRE_COSET, .nbat = nbat, .a = ntt_in_place(sl.ca), .b = ntt_in_place(sl.cb)}, pf);
+}
+
+// d_w (std, reduced) -> d_h (std, bit-reversed order), nbat vectors end to end.  See DESIGN.md "calcH on the GPU".
+static int calc_h_device(zkr_key *k, ProofSlot &sl, hipStream_t s, int nbat) {
   const Prof pf{k, &sl};
   const ArenaHeader &h = k->h;
-  const Fr *tw = (const Fr *)(k->arena + h.off_tw);
-  int L = (int)h.logm, tlog = (int)h.tlog;
-  const NttTables tb{tw, k->tw29, k->twl29, tlog};
+  const NttTables tb = key_ntt_tables(k);
+  const int L = (int)h.logm;
   uint32_t m = h.m;
   spmv_enqueue(k, sl, s, 0, m, nbat);
-  const int sp = prof_begin(pf, s, "ntt");
-  int rc;
-  // The six transforms come in three pairs of the same shape, each pair in ONE set of launches (gridDim.z = 2):
-  // coefficients of a and b (x m, bit-reversed), then their evaluations on the coset g*w^c (x m, natural),
+  int sp, rc;
+  // The six transforms come in three pairs of the same shape: the two of calc_h_open, then the pair of inverse transforms below.
   // A shard multiplies only positions [sc_lo, sc_lo + sc_n) of h (bit-reversed order, as the H table is laid out): the last pair of
   // transforms -- inverse DIF, whose passes below the top one stay inside aligned blocks -- and the combination run on the
   // blocks that cover that range only (at 2^22: 16 of 22 stages of two of the six transforms on 1/8 of the vector for 8 shards).
   const bool ranged = h.shard_parts > 1 && h.sc_n[1] < m;
   const uint32_t h_lo = ranged ? h.sc_lo[1] : 0, h_n = ranged ? h.sc_n[1] : 0;
-  if ((rc = run_ntt(s, sl.va, nullptr, sl.ca, tb, L, true, true, PRE_NONE, nbat, pf, sl.vb, nullptr, sl.cb))) return rc;
-  if ((rc = run_ntt(s, sl.ca, nullptr, sl.ca, tb, L, false, false, PRE_COSET, nbat, pf, sl.cb, nullptr, sl.cb))) return rc;
+  if ((rc = calc_h_open(k, sl, s, nbat, &sp))) return rc;
   // then D' = iNTT(A(gw^c).B(gw^c)) and S' = iNTT(a.b), both unscaled and bit-reversed
-  if ((rc = run_ntt(s, sl.ca, sl.cb, sl.ca, tb, L, true, true, PRE_MUL, nbat, pf, sl.va, sl.vb, sl.va, h_lo, h_n))) return rc;
+  if ((rc = run_ntt(s, tb, NttRun{.L = L, .dir = DIF_INVERSE, .pre = PRE_MUL, .nbat = nbat, .a = {.in0 = sl.ca, .in1 = sl.cb, .out = sl.ca},
+                                  .b = {.in0 = sl.va, .in1 = sl.vb, .out = sl.va}, .want_lo = h_lo, .want_n = h_n}, pf))) return rc;
   Fr c1v, c2v;
   combine_h_consts(m, c1v, c2v);
   const int csp = prof_begin(pf, s, "combine_h");
   const uint32_t pos0 = ranged ? h_lo : 0, pos1 = ranged ? h_lo + h_n : m;
-  combine_h_kernel<<<dim3((pos1 - pos0 + 255) / 256, nbat), 256, 0, s>>>(sl.va, sl.ca, sl.d_h, tw, tlog, L, c1v, c2v, sl.dig_h.rng, DIGIT_CLEAR_WORDS, pos0, pos1);  // + the counters of h's digit records
+  combine_h_kernel<<<dim3((pos1 - pos0 + 255) / 256, nbat), 256, 0, s>>>(sl.va, sl.ca, sl.d_h, tb.tw, tb.tlog, L, c1v, c2v, sl.dig_h.rng, DIGIT_CLEAR_WORDS, pos0, pos1);  // + the counters of h's digit records
   prof_end(pf, s, csp);
   prof_end(pf, s, sp);
   ZKR_HIP_CHECK(hipGetLastError());
@@ -264,17 +326,13 @@ int calc_h_device(zkr_key *k, ProofSlot &sl, hipStream_t s, int nbat) {
 static int calc_h_eval(zkr_key *k, ProofSlot &sl, hipStream_t s, int nbat) {
   const Prof pf{k, &sl};
   const ArenaHeader &h = k->h;
-  const int L = (int)h.logm;
-  const NttTables tb{(const Fr *)(k->arena + h.off_tw), k->tw29, k->twl29, (int)h.tlog};
   const uint32_t m = h.m;
   spmv_enqueue(k, sl, s, 0, m, nbat, true);
   eval_unsatisfied_kernel<<<dim3((m + 255) / 256, nbat), 256, 0, s>>>(sl.va, sl.vb, sl.d_h, m, sl.d_bad, 0, m);
   ZKR_HIP_CHECK(hipMemcpyAsync(sl.h_bad, sl.d_bad, (size_t)nbat * 4, hipMemcpyDeviceToHost, s));
   const uint32_t d0 = h.sc_lo[1], d1 = h.sc_lo[1] + h.sc_n[1];  // a whole key: 0 and m
-  const int sp = prof_begin(pf, s, "ntt");
-  int rc;
-  if ((rc = run_ntt(s, sl.va, nullptr, sl.ca, tb, L, true, true, PRE_NONE, nbat, pf, sl.vb, nullptr, sl.cb))) return rc;
-  if ((rc = run_ntt(s, sl.ca, nullptr, sl.ca, tb, L, false, false, PRE_COSET, nbat, pf, sl.cb, nullptr, sl.cb))) return rc;
+  int sp;
+  if (int rc = calc_h_open(k, sl, s, nbat, &sp)) return rc;
   const int csp = prof_begin(pf, s, "combine_h");  // the stage record keeps its keys: the product stands where the combination stood
   eval_product_kernel<<<dim3((d1 - d0 + 255) / 256, nbat), 256, 0, s>>>(sl.ca, sl.cb, sl.d_h, m, sl.dig_h.rng, DIGIT_CLEAR_WORDS, d0, d1);
   prof_end(pf, s, csp);
@@ -297,26 +355,28 @@ static int ntt_cross_wlog(int klog, uint32_t col_n) {
   while ((1u << wlog) > col_n) wlog--;
   return wlog;
 }
-static int run_ntt_cross(hipStream_t s, const NttTables &tb, int L, int klog, bool dif, bool inverse, int pre, bool canon, const Fr *const *rows_in0,
-                         const Fr *const *rows_in1, Fr *const *rows_out, uint32_t in_sub, uint32_t out_sub, uint32_t col_lo, uint32_t col_n, Prof pf) {
-  NttPassArgs a = {};
-  a.tw = tb.tw; a.tw29 = tb.tw29; a.twl29 = tb.twl29; a.tlog = tb.tlog; a.L = L;
-  a.lo = L - klog; a.hi = L;
-  const int wlog = ntt_cross_wlog(klog, col_n);
+struct NttCross {
+  int L, klog;
+  NttDir dir;
+  int pre = PRE_NONE;
+  bool canon = false;  // the transform's last pass: canonical stores
+  const Fr *const *rows_in0, *const *rows_in1 = nullptr;  // rows_in1 with PRE_MUL only
+  Fr *const *rows_out;
+  uint32_t in_sub = 0, out_sub = 0, col_lo, col_n;
+};
+static int run_ntt_cross(hipStream_t s, const NttTables &tb, const NttCross &c, Prof pf) {
+  NttPassArgs a = ntt_pass_args(tb, c.L);
+  a.lo = c.L - c.klog; a.hi = c.L;
+  const int wlog = ntt_cross_wlog(c.klog, c.col_n);
   a.wlog = wlog;
-  a.pre = pre;
-  a.canon = canon ? 1 : 0;
-  a.prio = 1;
-  for (int r = 0; r < (1 << klog); r++) { a.x_in0[r] = rows_in0[r]; a.x_in1[r] = rows_in1 ? rows_in1[r] : nullptr; a.x_out[r] = rows_out[r]; }
-  a.x_in_sub = in_sub; a.x_out_sub = out_sub;
-  const uint32_t tile = 1u << (klog + wlog);
-  a.blk_off = col_lo >> wlog;
-  const uint32_t grid = col_n >> wlog;
-  const size_t lds = (size_t)tile * 36;
-  const int psp = prof_begin(pf, s, "ntt_pass");
-  if (dif) { if (inverse) ntt_pass_kernel<true, true, NTT_THREADS_LARGE, true><<<grid, NTT_THREADS_LARGE, lds, s>>>(a); else ntt_pass_kernel<true, false, NTT_THREADS_LARGE, true><<<grid, NTT_THREADS_LARGE, lds, s>>>(a); }
-  else { if (inverse) ntt_pass_kernel<false, true, NTT_THREADS_LARGE, true><<<grid, NTT_THREADS_LARGE, lds, s>>>(a); else ntt_pass_kernel<false, false, NTT_THREADS_LARGE, true><<<grid, NTT_THREADS_LARGE, lds, s>>>(a); }
-  prof_end(pf, s, psp);
+  a.pre = c.pre;
+  a.canon = c.canon ? 1 : 0;
+  for (int r = 0; r < (1 << c.klog); r++) { a.x_in0[r] = c.rows_in0[r]; a.x_in1[r] = c.rows_in1 ? c.rows_in1[r] : nullptr; a.x_out[r] = c.rows_out[r]; }
+  a.x_in_sub = c.in_sub; a.x_out_sub = c.out_sub;
+  const uint32_t tile = 1u << (c.klog + wlog);
+  a.blk_off = c.col_lo >> wlog;
+  const uint32_t grid = c.col_n >> wlog;
+  ntt_pass_launch(NTT_THREADS_LARGE, true, c.dir, dim3(grid), (size_t)tile * 36, s, a, pf);
   ZKR_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -344,30 +404,31 @@ static int run_ntt_cross(hipStream_t s, const NttTables &tb, int L, int klog, bo
 //   4  CROSS top stages of the coset transforms, canonical, IN PLACE: this shard's columns of every block's ca, cb -- which no
 //      other shard touches -- so that after the barrier block j of ca, cb on shard j holds the evaluations in natural order
 //   5  d = their product on the block                                          -> d_h (block j)
-static int calc_h_split_phases(zkr_key *k, ProofSlot &sl, hipStream_t s, ShardGroup &g, unsigned part, std::unique_lock<std::mutex> &lock, bool eval);
 static int calc_h_split(zkr_key *k, ProofSlot &sl, hipStream_t s, ShardGroup &g, unsigned part, std::unique_lock<std::mutex> &lock, bool eval) {
-  const int rc = calc_h_split_phases(k, sl, s, g, part, lock, eval);
-  if (rc) g.abort();  // whoever waits for this shard (now or at a later barrier) gives up too
-  return rc;
-}
-static int calc_h_split_phases(zkr_key *k, ProofSlot &sl, hipStream_t s, ShardGroup &g, unsigned part, std::unique_lock<std::mutex> &lock, bool eval) {
+  struct AbortUnlessDone {  // on every return but the last: whoever waits for this shard (now or at a later barrier) gives up too
+    ShardGroup &g;
+    bool done = false;
+    ~AbortUnlessDone() { if (!done) g.abort(); }
+  } guard{g};
   const Prof pf{k, &sl};
   const ArenaHeader &h = k->h;
-  const Fr *tw = (const Fr *)(k->arena + h.off_tw);
-  const int L = (int)h.logm, tlog = (int)h.tlog, klog = g.klog, Lb = L - klog;
-  const NttTables tb{tw, k->tw29, k->twl29, tlog};
+  const NttTables tb = key_ntt_tables(k);
+  const int L = (int)h.logm, klog = g.klog, Lb = L - klog;
   const uint32_t m = h.m, P = g.parts, Bk = m >> klog, cols = Bk >> klog, col_lo = part * cols, blk = part * Bk;
   struct timespec t0;
   int phase = 0;
   auto phase_begin = [&] { clock_gettime(CLOCK_MONOTONIC, &t0); };
+  auto phase_stamp = [&] {  // host time since the phase began, into the group's record
+    struct timespec t1;
+    clock_gettime(CLOCK_MONOTONIC, &t1);
+    if (phase < 8) g.phase_ms[part][phase] = (t1.tv_sec - t0.tv_sec) * 1e3 + (t1.tv_nsec - t0.tv_nsec) * 1e-6;
+  };
   // end of a phase: this shard's part of it has run, then everybody's
   auto phase_end = [&]() -> int {
     hipError_t e = hipGetLastError();
     lock.unlock();
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    struct timespec t1;
-    clock_gettime(CLOCK_MONOTONIC, &t1);
-    if (phase < 8) g.phase_ms[part][phase] = (t1.tv_sec - t0.tv_sec) * 1e3 + (t1.tv_nsec - t0.tv_nsec) * 1e-6;
+    phase_stamp();
     phase++;
     int rc = 0;
     if (e != hipSuccess) { set_error("split calcH, phase %d: %s", phase, hipGetErrorString(e)); g.abort(); rc = ZKR_ERR_HIP; }
@@ -399,12 +460,14 @@ static int calc_h_split_phases(zkr_key *k, ProofSlot &sl, hipStream_t s, ShardGr
     r_ga[b] = w_ga[b] = sl.va + blk + (size_t)b * cols;  // this shard's columns of block b, kept in its own block of va / vb
     r_gb[b] = w_gb[b] = sl.vb + blk + (size_t)b * cols;
   }
+  // the top klog stages of a transform of the whole domain, on this shard's columns of every block: the call names the rest
+  auto top_stages = [&](NttCross c) { c.L = L; c.klog = klog; c.col_lo = col_lo; c.col_n = cols; return run_ntt_cross(s, tb, c, pf); };
   const int ntt_span = prof_begin(pf, s, "ntt");
   // 2: top stages of the three inverse transforms that start from the evaluations on the domain
   phase_begin();
-  if ((rc = run_ntt_cross(s, tb, L, klog, true, true, PRE_NONE, false, r_va, nullptr, w_ca, 0, 0, col_lo, cols, pf))) return rc;
-  if ((rc = run_ntt_cross(s, tb, L, klog, true, true, PRE_NONE, false, r_vb, nullptr, w_cb, 0, 0, col_lo, cols, pf))) return rc;
-  if (!eval && (rc = run_ntt_cross(s, tb, L, klog, true, true, PRE_MUL, false, r_va, r_vb, w_dh, 0, 0, col_lo, cols, pf))) return rc;
+  if ((rc = top_stages({.dir = DIF_INVERSE, .rows_in0 = r_va, .rows_out = w_ca}))) return rc;
+  if ((rc = top_stages({.dir = DIF_INVERSE, .rows_in0 = r_vb, .rows_out = w_cb}))) return rc;
+  if (!eval && (rc = top_stages({.dir = DIF_INVERSE, .pre = PRE_MUL, .rows_in0 = r_va, .rows_in1 = r_vb, .rows_out = w_dh}))) return rc;
   if ((rc = phase_end())) return rc;
   // 3: the block's own stages
   phase_begin();
@@ -412,46 +475,41 @@ static int calc_h_split_phases(zkr_key *k, ProofSlot &sl, hipStream_t s, ShardGr
     Fr *ca = sl.ca + blk, *cb = sl.cb + blk, *dh = sl.d_h + blk;
     uint32_t rev = 0;  // the block's index bit-reversed: low bits of its coefficients' indices
     for (int i = 0; i < klog; i++) rev |= ((part >> i) & 1u) << (klog - 1 - i);
-    if ((rc = run_ntt(s, ca, nullptr, ca, tb, Lb, true, true, PRE_NONE, 1, pf, cb, nullptr, cb))) return rc;              // coefficients of a, b (x m, bit-reversed)
-    if ((rc = run_ntt(s, ca, nullptr, ca, tb, Lb, false, false, PRE_COSET, 1, pf, cb, nullptr, cb, 0, 0, (uint32_t)klog, rev))) return rc;  // coset transforms below their top stages
-    if (!eval && (rc = run_ntt(s, dh, nullptr, dh, tb, Lb, true, true, PRE_NONE, 1, pf))) return rc;                    // S' on the block
+    // coefficients of a, b (x m, bit-reversed); coset transforms below their top stages; S' on the block
+    if ((rc = run_ntt(s, tb, NttRun{.L = Lb, .dir = DIF_INVERSE, .a = ntt_in_place(ca), .b = ntt_in_place(cb)}, pf))) return rc;
+    if ((rc = run_ntt(s, tb, NttRun{.L = Lb, .dir = DIT_FORWARD, .pre = PRE_COSET, .a = ntt_in_place(ca), .b = ntt_in_place(cb), .coset_shift = (uint32_t)klog, .coset_add = rev}, pf))) return rc;
+    if (!eval && (rc = run_ntt(s, tb, NttRun{.L = Lb, .dir = DIF_INVERSE, .a = ntt_in_place(dh)}, pf))) return rc;
   }
   if ((rc = phase_end())) return rc;
   // 4: top stages of the coset transforms into local columns, product, top stages of the last inverse transform
   phase_begin();
+  int csp;
   if (eval) {
-    if ((rc = run_ntt_cross(s, tb, L, klog, false, false, PRE_NONE, true, r_ca, nullptr, w_ca, 0, 0, col_lo, cols, pf))) return rc;
-    if ((rc = run_ntt_cross(s, tb, L, klog, false, false, PRE_NONE, true, r_cb, nullptr, w_cb, 0, 0, col_lo, cols, pf))) return rc;
+    if ((rc = top_stages({.dir = DIT_FORWARD, .canon = true, .rows_in0 = r_ca, .rows_out = w_ca}))) return rc;
+    if ((rc = top_stages({.dir = DIT_FORWARD, .canon = true, .rows_in0 = r_cb, .rows_out = w_cb}))) return rc;
     if ((rc = phase_end())) return rc;
     // 5: d on the block
     phase_begin();
-    const int psp = prof_begin(pf, s, "combine_h");  // as in calc_h_eval: the product stands where the combination stood
+    csp = prof_begin(pf, s, "combine_h");  // as in calc_h_eval: the product stands where the combination stood
     eval_product_kernel<<<dim3((Bk + 255) / 256, 1), 256, 0, s>>>(sl.ca, sl.cb, sl.d_h, m, sl.dig_h.rng, DIGIT_CLEAR_WORDS, blk, blk + Bk);
-    prof_end(pf, s, psp);
-    prof_end(pf, s, ntt_span);
-    ZKR_HIP_CHECK(hipGetLastError());
-    struct timespec t1;
-    clock_gettime(CLOCK_MONOTONIC, &t1);
-    if (phase < 8) g.phase_ms[part][phase] = (t1.tv_sec - t0.tv_sec) * 1e3 + (t1.tv_nsec - t0.tv_nsec) * 1e-6;  // enqueue time only: nothing waits here
-    return 0;
+  } else {
+    if ((rc = top_stages({.dir = DIT_FORWARD, .canon = true, .rows_in0 = r_ca, .rows_out = w_ga, .out_sub = col_lo}))) return rc;
+    if ((rc = top_stages({.dir = DIT_FORWARD, .canon = true, .rows_in0 = r_cb, .rows_out = w_gb, .out_sub = col_lo}))) return rc;
+    if ((rc = top_stages({.dir = DIF_INVERSE, .pre = PRE_MUL, .rows_in0 = r_ga, .rows_in1 = r_gb, .rows_out = w_ca, .in_sub = col_lo}))) return rc;
+    if ((rc = phase_end())) return rc;
+    // 5: D' on the block, then h
+    phase_begin();
+    if ((rc = run_ntt(s, tb, NttRun{.L = Lb, .dir = DIF_INVERSE, .a = ntt_in_place(sl.ca + blk)}, pf))) return rc;
+    Fr c1v, c2v;
+    combine_h_consts(m, c1v, c2v);
+    csp = prof_begin(pf, s, "combine_h");
+    combine_h_kernel<<<dim3((Bk + 255) / 256, 1), 256, 0, s>>>(sl.d_h, sl.ca, sl.d_h, tb.tw, tb.tlog, L, c1v, c2v, sl.dig_h.rng, DIGIT_CLEAR_WORDS, blk, blk + Bk);
   }
-  if ((rc = run_ntt_cross(s, tb, L, klog, false, false, PRE_NONE, true, r_ca, nullptr, w_ga, 0, col_lo, col_lo, cols, pf))) return rc;
-  if ((rc = run_ntt_cross(s, tb, L, klog, false, false, PRE_NONE, true, r_cb, nullptr, w_gb, 0, col_lo, col_lo, cols, pf))) return rc;
-  if ((rc = run_ntt_cross(s, tb, L, klog, true, true, PRE_MUL, false, r_ga, r_gb, w_ca, col_lo, 0, col_lo, cols, pf))) return rc;
-  if ((rc = phase_end())) return rc;
-  // 5: D' on the block, then h
-  phase_begin();
-  if ((rc = run_ntt(s, sl.ca + blk, nullptr, sl.ca + blk, tb, Lb, true, true, PRE_NONE, 1, pf))) return rc;
-  Fr c1v, c2v;
-  combine_h_consts(m, c1v, c2v);
-  const int csp = prof_begin(pf, s, "combine_h");
-  combine_h_kernel<<<dim3((Bk + 255) / 256, 1), 256, 0, s>>>(sl.d_h, sl.ca, sl.d_h, tw, tlog, L, c1v, c2v, sl.dig_h.rng, DIGIT_CLEAR_WORDS, blk, blk + Bk);
   prof_end(pf, s, csp);
   prof_end(pf, s, ntt_span);
   ZKR_HIP_CHECK(hipGetLastError());
-  struct timespec t1;
-  clock_gettime(CLOCK_MONOTONIC, &t1);
-  if (phase < 8) g.phase_ms[part][phase] = (t1.tv_sec - t0.tv_sec) * 1e3 + (t1.tv_nsec - t0.tv_nsec) * 1e-6;  // enqueue time only: nothing waits here
+  phase_stamp();  // enqueue time only: nothing waits here
+  guard.done = true;
   return 0;
 }
 
@@ -1329,17 +1387,15 @@ int zkr_ntt(void *data_std, unsigned logn, int inverse, int device) {
   ZKR_HIP_CHECK(hipSetDevice(device));
   if (int lrc = ntt_lds_check(device)) return lrc;
   size_t n = (size_t)1 << logn;
-  DevBuf bd, bd2, btw, btwl;
-  Dev<Tw29> tw29, twl29;
+  DevBuf bd, bd2;
+  HookNttTables tables;
   int rc;
-  if ((rc = bd.alloc(n * 32)) || (rc = bd2.alloc(n * 32)) || (rc = btw.alloc(n * 32)) || (rc = btwl.alloc((size_t)(1u << TWL_LOG) * 32))) return rc;
-  Fr *d = bd.as<Fr>(), *d2 = bd2.as<Fr>(), *tw = btw.as<Fr>(), *twl = btwl.as<Fr>();
+  if ((rc = bd.alloc(n * 32)) || (rc = bd2.alloc(n * 32))) return rc;
+  Fr *d = bd.as<Fr>(), *d2 = bd2.as<Fr>();
   ZKR_HIP_CHECK(hipMemcpy(d, data_std, n * 32, hipMemcpyHostToDevice));
   ingest_kernel<<<(unsigned)((n + 255) / 256), 256>>>(d, d, n);  // any 256-bit word -> below r, as the proving path does with witnesses: the passes state bounds on what they load
-  twiddle_table_kernel<<<(unsigned)((n + 255) / 256), 256>>>(tw, (uint32_t)n, host_root_of_unity(logn + 1));
-  twiddle_table_kernel<<<((1u << TWL_LOG) + 255) / 256, 256>>>(twl, 1u << TWL_LOG, host_root_of_unity(TWL_LOG + 1));
-  rc = ntt_tables29_build(tw, (uint32_t)n, twl, 1u << TWL_LOG, nullptr, tw29, twl29);
-  if (!rc) rc = run_ntt(nullptr, d, nullptr, d, NttTables{tw, tw29, twl29, (int)logn}, (int)logn, true, inverse != 0, PRE_NONE, 1, Prof{nullptr, nullptr});  // natural -> bit-reversed
+  rc = tables.build(logn);
+  if (!rc) rc = run_ntt(nullptr, tables.view(), NttRun{.L = (int)logn, .dir = inverse ? DIF_INVERSE : DIF_FORWARD, .a = ntt_in_place(d)}, NO_PROF);  // natural -> bit-reversed
   if (!rc) {
     bitrev_copy_kernel<<<(unsigned)((n + 255) / 256), 256>>>(d, d2, (int)logn);
     if (inverse) scale_kernel<<<(unsigned)((n + 255) / 256), 256>>>(d2, n, inv(to_mont(fr_from_u64(n))));
@@ -1420,18 +1476,10 @@ extern "C" int zkr_selftest_ntt(int device, const zkr_ntt_selftest_desc *desc, v
   ZKR_HIP_CHECK(hipSetDevice(device));
   if (int lrc = ntt_lds_check(device)) return lrc;
 
-  // the tables, as zkr_ntt builds them, for 2^tlog
-  const size_t nt = (size_t)1 << d.tlog;
-  DevBuf btw, btwl;
-  Dev<Tw29> tw29, twl29;
+  HookNttTables tables;
   int rc;
-  if ((rc = btw.alloc(nt * 32)) || (rc = btwl.alloc((size_t)(1u << TWL_LOG) * 32))) return rc;
-  Fr *tw = btw.as<Fr>(), *twl = btwl.as<Fr>();
-  twiddle_table_kernel<<<(unsigned)((nt + 255) / 256), 256>>>(tw, (uint32_t)nt, host_root_of_unity(d.tlog + 1));
-  twiddle_table_kernel<<<((1u << TWL_LOG) + 255) / 256, 256>>>(twl, 1u << TWL_LOG, host_root_of_unity(TWL_LOG + 1));
-  rc = ntt_tables29_build(tw, (uint32_t)nt, twl, 1u << TWL_LOG, nullptr, tw29, twl29);
-  if (rc) return rc;
-  const NttTables tb{tw, tw29, twl29, (int)d.tlog};
+  if ((rc = tables.build(d.tlog))) return rc;
+  const NttTables tb = tables.view();
 
   // the vectors: one allocation each (cross: one per row block), between guards
   const unsigned rows = d.cross ? 1u << d.klog : 1;
@@ -1458,12 +1506,24 @@ extern "C" int zkr_selftest_ntt(int device, const zkr_ntt_selftest_desc *desc, v
   ZKR_HIP_CHECK(hipGetLastError());
 
   // THE launch under test
+  const NttDir dir = d.dif ? (d.inverse ? DIF_INVERSE : DIF_FORWARD) : (d.inverse ? DIT_INVERSE : DIT_FORWARD);
   if (!d.cross) {
-    Fr *o = d.in_place ? v_in0[0]->data() : v_out[0]->data();
-    Fr *ob = !d.pair ? nullptr : d.in_place ? v_in0b[0]->data() : v_outb[0]->data();
-    rc = run_ntt(nullptr, v_in0[0]->data(), mul2 ? v_in1[0]->data() : nullptr, o, tb, (int)d.logn, d.dif != 0, d.inverse != 0, (int)d.pre, (int)d.nbat,
-                 Prof{nullptr, nullptr}, d.pair ? v_in0b[0]->data() : nullptr, d.pair && mul2 ? v_in1b[0]->data() : nullptr, ob, d.want_lo, d.want_n,
-                 d.coset_shift, d.coset_add);
+    NttRun run;
+    run.L = (int)d.logn;
+    run.dir = dir;
+    run.pre = (int)d.pre;
+    run.nbat = (int)d.nbat;
+    run.a.in0 = v_in0[0]->data();
+    run.a.in1 = mul2 ? v_in1[0]->data() : nullptr;
+    run.a.out = d.in_place ? v_in0[0]->data() : v_out[0]->data();
+    run.b.in0 = d.pair ? v_in0b[0]->data() : nullptr;
+    run.b.in1 = d.pair && mul2 ? v_in1b[0]->data() : nullptr;
+    run.b.out = !d.pair ? nullptr : d.in_place ? v_in0b[0]->data() : v_outb[0]->data();
+    run.want_lo = d.want_lo;
+    run.want_n = d.want_n;
+    run.coset_shift = d.coset_shift;
+    run.coset_add = d.coset_add;
+    rc = run_ntt(nullptr, tb, run, NO_PROF);
   } else {
     const Fr *r_in0[8], *r_in1[8];
     Fr *r_out[8];
@@ -1472,8 +1532,20 @@ extern "C" int zkr_selftest_ntt(int device, const zkr_ntt_selftest_desc *desc, v
       r_in1[r] = mul2 ? v_in1[r]->data() : nullptr;
       r_out[r] = d.in_place ? v_in0[r]->data() : v_out[r]->data();
     }
-    rc = run_ntt_cross(nullptr, tb, (int)d.logn, (int)d.klog, d.dif != 0, d.inverse != 0, (int)d.pre, d.canon != 0, r_in0, mul2 ? r_in1 : nullptr, r_out, d.in_sub,
-                       d.out_sub, d.col_lo, d.col_n, Prof{nullptr, nullptr});
+    NttCross cross;
+    cross.L = (int)d.logn;
+    cross.klog = (int)d.klog;
+    cross.dir = dir;
+    cross.pre = (int)d.pre;
+    cross.canon = d.canon != 0;
+    cross.rows_in0 = r_in0;
+    cross.rows_in1 = mul2 ? r_in1 : nullptr;
+    cross.rows_out = r_out;
+    cross.in_sub = d.in_sub;
+    cross.out_sub = d.out_sub;
+    cross.col_lo = d.col_lo;
+    cross.col_n = d.col_n;
+    rc = run_ntt_cross(nullptr, tb, cross, NO_PROF);
   }
   const hipError_t e = hipDeviceSynchronize();  // also after a refused run: the vectors go with this scope
   if (rc) return rc;
@@ -1518,7 +1590,7 @@ static int msm_hook(const void *points_mont, const void *scalars_std, size_t n, 
     ZKR_HIP_CHECK(hipMemcpy(d_sc, scalars_std, n * 32, hipMemcpyHostToDevice));
     if ((rc = msm_precompute(device, g2, d_pts, np, pl))) return rc;
     ingest_kernel<<<(unsigned)((n + 255) / 256), 256>>>(d_sc, d_sc2, n);
-    rc = msm_enqueue(Prof{nullptr, nullptr}, nullptr, g2, d_pts, d_rank, d_sc2, (uint32_t)n, np, pl, ms);
+    rc = msm_enqueue(NO_PROF, nullptr, g2, d_pts, d_rank, d_sc2, (uint32_t)n, np, pl, ms);
     hipError_t e = hipDeviceSynchronize();  // also after a failed enqueue: nothing may still run on buffers that are about to go
     if (!rc && e != hipSuccess) { set_error("msm failed: %s", hipGetErrorString(e)); rc = ZKR_ERR_HIP; }
     if (rc) return rc;
@@ -1544,7 +1616,7 @@ int key_table_msm(const zkr_key *k, int t, const Fr *d_scalars, G1XYZZ *out) {
   MsmScratch ms;
   int rc = msm_scratch_alloc(ms, rank_entries(h, t), h.npts[t], k->plan[t], false);
   if (rc) return rc;
-  rc = msm_enqueue(Prof{nullptr, nullptr}, nullptr, false, k->arena + h.off_pts[t], (const uint32_t *)(k->arena + h.off_rank[t]), d_scalars,
+  rc = msm_enqueue(NO_PROF, nullptr, false, k->arena + h.off_pts[t], (const uint32_t *)(k->arena + h.off_rank[t]), d_scalars,
                    rank_entries(h, t), h.npts[t], k->plan[t], ms);
   hipError_t e = hipDeviceSynchronize();  // also after a failed enqueue: the workspace goes with this scope
   if (!rc && e != hipSuccess) { set_error("msm over a key table failed: %s", hipGetErrorString(e)); rc = ZKR_ERR_HIP; }

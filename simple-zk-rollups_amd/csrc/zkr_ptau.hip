@@ -20,6 +20,7 @@
 #include <string.h>
 #include <algorithm>
 #include <vector>
+#include "eval_h.hpp"  // fr_root_of_unity
 #include "kernels_group.hpp"
 #include "hostops.hpp"
 #include "pairing.hpp"
@@ -27,8 +28,6 @@
 #include "zkr_internal.hpp"
 
 namespace zkr {
-
-Fr host_root_of_unity(unsigned k);  // zkr_key.hip
 
 // ---------------------------------------------------------------- kernels of the transcript's boundary
 // Standard-form coordinates -> the key's Montgomery form, in place; bad[0] counts the coordinates that are not below q (they are
@@ -121,7 +120,7 @@ int group_ntt_launch(Affine<typename C::W> *pts, Affine<typename C::W> *tmp, uns
   using W = typename C::W;
   const size_t n = (size_t)1 << logn;
   const uint32_t half_n = (uint32_t)(n / 2);
-  Fr g = host_root_of_unity(logn);
+  Fr g = fr_root_of_unity(logn);
   if (inverse) g = inv(g);
   twiddle_table_kernel<<<(half_n + 255) / 256, 256>>>(tw, half_n, g);
   fr_to_std_kernel<<<(half_n + 255) / 256, 256>>>(tw, half_n);

@@ -193,7 +193,7 @@ def run_cross(desc, want, x, y=None):
 def test_cross_passes_alone(klog, L, last_part):
     """run_ntt_cross with each of the 2^klog row blocks in a device allocation of its own, for the columns of the first and the last
     shard of a split calcH (col_n = 2^(L - 2 klog)): the narrow col_n of the small sizes lower the tile width, (2, 14) and (3, 17)
-    reach the 2^11 cap with several tiles per launch.  The five calls of calc_h_split_phases with its (in_sub, out_sub) -- whole
+    reach the 2^11 cap with several tiles per launch.  The five calls of calc_h_split with its (in_sub, out_sub) -- whole
     blocks both ways, local columns out, local columns in -- then the evaluation form's in-place pass and the two directions no
     proof runs."""
     ref = cross_reference(klog, L)
