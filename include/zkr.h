@@ -906,6 +906,49 @@ int zkr_book_withdraw_plan_host(const uint8_t *records, size_t n_accounts, const
                                 const uint8_t *proof_verdicts, size_t n, const uint32_t *resolved, uint8_t *verdicts,
                                 uint32_t *indices, uint8_t *events);
 
+/* ---- the operator's step: a signed queue in, verified proofs out, behind one handle (csrc/zkr_operator.hip).
+ * The loop around a proof (operator/src/routes/send.ts:72-135, pubsub.ts:19-66, snarks/common.ts:12-38) is zkr_ledger_sequence ->
+ * zkr_rollup_witness_batch_from_device -> zkr_r1cs_check_device -> zkr_prove_batch_device -> zkr_verify_each_device, and it hands
+ * DEVICE buffers from call to call.  An operator owns those buffers, so its caller passes host buffers only (what the Node binding
+ * can do), and it closes the gap a hand-written loop leaves: the sequencing advances the ledger before anything is proved, so a
+ * later failure leaves the ledger ahead of what can be published.  A step runs inside a ledger checkpoint of its own and the
+ * ledger moves only when every proof of the step is good.  No kernel of its own: the calls above launch what they launch alone.
+ *
+ * zkr_operator_new.  The four handles are BORROWED: the caller keeps them alive longer than the operator.  cs NULL: no constraint
+ * check; vk NULL: no acceptance check (zkr_verify_each_device takes about 50 ms whatever the batch size, profiles/verify_device.md:
+ * a caller that minds passes NULL and checks on the host with zkr_verify_batch).  opts: batch = transactions per proof;
+ * max_batches = the most proofs one step may produce (0: 256); flags and reserved 0.  Checked before anything is allocated, each
+ * failure ZKR_ERR_ARG with a message naming the mismatch: all handles on one device; zkr_rollup_info(batch, the ledger's depth)
+ * gives the key's nVars and nPublic; cs is the key's by zkr_r1cs_matches_key; vk has the key's nPublic.
+ * The handle owns, on that device: the circuit inputs and the witnesses of a step (n_batches x (nPublic - 1) x 32 B and n_batches x
+ * nVars x 32 B), the array of witness pointers (pinned host memory) and one stream.  They grow to the largest step seen, at most
+ * max_batches.  zkr_operator_info: out = batch, depth, nVars, nPublic, max_batches, device bytes held.
+ *
+ * zkr_operator_step.  txs (n_txs x 8 x 32 B) and status (n_txs bytes) as zkr_ledger_sequence takes and gives them; r32s / s32s as
+ * zkr_prove_batch_device: n_txs / batch x 32 B each, proof b takes row b, or both NULL (drawn per proof); proofs_out: room for
+ * n_txs / batch proofs of 256 B; publics_out: room for as many rows of nPublic x 32 B -- words 1..nPublic of each witness, one
+ * strided copy from the device.  Steps on one operator are serialised by a lock inside it.  In order: open a checkpoint, sequence
+ * on the operator's stream, build the witnesses from the device inputs, check them against cs, prove, zkr_verify_each_device
+ * against vk, read out, release the checkpoint.
+ *   n_txs / batch > max_batches: ZKR_ERR_ARG before the ledger or any buffer is touched.
+ *   No whole batch: ZKR_OK, *n_batches = 0, statuses and *consumed as zkr_ledger_sequence gives them, no checkpoint left open.
+ *   Any failure after the sequencing: the ledger is rolled back to the step's checkpoint, the checkpoint is released and the
+ *   status is returned -- ZKR_ERR_UNSATISFIED for inputs the circuit refuses or a violated constraint (the message names the
+ *   batch), the prover's own code for its errors, ZKR_ERR_BAD_KEY "batch b: proof rejected by the verifying key (verdict v)" for a
+ *   verdict other than 0.  Records, account count, every byte of the stored tree, applied and batches are then as before the call.
+ * Outputs are defined only on ZKR_OK.  The step's checkpoint nests inside the caller's: a later zkr_ledger_rollback to an older
+ * checkpoint still undoes a successful step.
+ * zkr_operator_stage_times: wall milliseconds of the last step's stages -- sequence, witness, check, prove, verify, read-out (every
+ * stage returns synchronised; 0 for a stage that did not run). ---- */
+typedef struct zkr_operator zkr_operator;
+typedef struct { uint32_t batch, max_batches, flags, reserved; } zkr_operator_opts;
+int zkr_operator_new(zkr_ledger *l, zkr_key *key, zkr_r1cs *cs, zkr_vk *vk, const zkr_operator_opts *opts, zkr_operator **out);
+void zkr_operator_free(zkr_operator *op);
+int zkr_operator_info(const zkr_operator *op, uint64_t out[6]);
+int zkr_operator_step(zkr_operator *op, const uint8_t *txs, size_t n_txs, const uint8_t *r32s, const uint8_t *s32s, uint8_t *status, uint8_t *proofs_out,
+                      void *publics_out, size_t *n_batches, size_t *consumed);
+int zkr_operator_stage_times(const zkr_operator *op, double ms[6]);
+
 /* Integer-ALU microbenchmark: sustained Fq Montgomery multiplications per second on `device` with the multiplier of the
  * hot path (9 x 29-bit limbs, 162 multiply-adds without carry words, csrc/field29.hpp); used for the secondary (VALU)
  * roofline.  _legacy: the 8 x 32-bit multiplier of csrc/field.hpp (136 multiply-adds + 136 carry additions), kept for

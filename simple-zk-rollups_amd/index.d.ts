@@ -89,6 +89,56 @@ export class WithdrawCircuit {
   publicSignals(witnessBin: ArrayBuffer): bigint[];
 }
 
+// ---- the operator's ledger and step on the GPU (send.ts:72-135, pubsub.ts:19-66, snarks/common.ts:12-38), host buffers only
+type Num = bigint | string | number;
+/** The txData row of one signed transaction: from to amount fee nonce R8x R8y S, 256 bytes. */
+export function txRow(from: Num, to: Num, amount: Num, fee: Num, nonce: Num, sig: Signature): Uint8Array;
+export type DepositRow = [number, [Num, Num], Num, Num?];
+/** Account records and the whole balance tree on the device. */
+export class Ledger {
+  constructor(depth: number, device?: number);
+  readonly depth: number; readonly device: number;
+  deposit(index: number, pub: [Num, Num], balance: Num, nonce?: Num): void;
+  deposit(rows: DepositRow[]): void;
+  root(): bigint;
+  account(index: number): { record: bigint[]; path: bigint[] };
+  info(): { depth: number; accounts: number; applied: number; batches: number };
+  /** The ZKRLEDG1 blob of the current state; restore checks it on the host and refuses records that do not rebuild to its root. */
+  snapshot(): Uint8Array;
+  static restore(blob: Uint8Array, device?: number): Ledger;
+  save(path: string): void;
+  static load(path: string, device?: number): Ledger;
+  /** Checkpoints nest; rollback(id) puts records, tree and counters back as they stood at checkpoint() and leaves id open. */
+  checkpoint(): number;
+  rollback(id: number): void;
+  release(id: number): void;
+  journalInfo(): { checkpoints: number; nodes: number };
+  /** Throws while a live Operator holds the ledger. */
+  close(): void;
+}
+export interface OperatorOptions {
+  ledger: Ledger;
+  /** A Bn128 that holds a key (setupR1cs, loadKeyFile, or a key the cache holds); terminate() throws while the operator lives. */
+  bn: Bn128;
+  /** The circuit's constraint system (RollupCircuit.r1cs()): every witness is checked against it before proving. */
+  r1csBin?: Uint8Array;
+  /** vk_bin bytes or the verifying key JSON: every proof is checked on the GPU before the step succeeds. */
+  vkBin?: Uint8Array | any;
+  batch?: number;
+  maxBatches?: number;
+}
+export interface OperatorBatch { proof: Groth16Proof; publicSignals: string[]; solidityProof: { a: string[]; b: string[][]; c: string[]; inputs: string[] }; }
+/** One operator step behind one handle: a signed queue in; statuses, proofs and public signals out; the ledger moves only when every proof is good. */
+export class Operator {
+  constructor(opts: OperatorOptions);
+  readonly batch: number; readonly nPublic: number;
+  /** Steps issued on one operator run in issue order; a library error rejects with its message and leaves the ledger as it was. */
+  step(queue: Uint8Array[] | Uint8Array, opts?: { rs?: Num[]; ss?: Num[] }): Promise<{ status: number[]; consumed: number; batches: OperatorBatch[] }>;
+  info(): { batch: number; depth: number; nVars: number; nPublic: number; maxBatches: number; deviceBytes: number };
+  stageTimes(): { sequence: number; witness: number; check: number; prove: number; verify: number; readOut: number };
+  close(): void;
+}
+
 // ---- process-level key cache (the reference builds a new Bn128 per proof: common.ts:23) and verifier constants
 /** Device keys loaded / found in the cache by groth16GenProof so far in this process. */
 export function keyCacheStats(): { loads: number; hits: number; replications: number; shardings?: number; entries: number; handles: number; shardedLastForm: ShardedForm };

@@ -312,7 +312,10 @@ class Bn128 {
     return { nVars: v[0], nPublic: v[1], domainSize: v[2], nnzA: v[3], nnzB: v[4] };
   }
 
-  terminate() { this._key = null; this._fp = null; this._replicas = null; }
+  terminate() {
+    if (this._operators > 0) throw new Error("this Bn128 is held by a live operator: close the operator first");
+    this._key = null; this._fp = null; this._replicas = null;
+  }
 }
 
 async function buildBn128(device) {
@@ -541,7 +544,121 @@ class WithdrawCircuit {
   publicSignals(witnessBin) { return leToBigInts(Buffer.from(witnessBin, 32, 96)); }
 }
 
+// ---- the operator's ledger and step (include/zkr.h zkr_ledger_*, zkr_operator_*; DESIGN.md 9k, INTEGRATION.md 6.6).  Host buffers
+// only: the device buffers of the loop belong to the library's operator handle.  Values are BigInt or decimal strings.
+
+// the txData row of batchprocesstx.circom for one signed transaction: from to amount fee nonce R8x R8y S, 256 bytes
+function txRow(from, to, amount, fee, nonce, sig) { return concatLe([from, to, amount, fee, nonce, sig.R8[0], sig.R8[1], sig.S]); }
+
+// The operator's state on the GPU: account records and the whole balance tree of `depth` levels (send.ts:72-135, pubsub.ts:19-66).
+class Ledger {
+  constructor(depth, device) { Ledger._adopt(native().ledgerNew(Number(depth), device || 0), device, this); }
+  static _adopt(handle, device, self) {
+    self = self || Object.create(Ledger.prototype);
+    self._h = handle; self.device = device || 0; self._operators = 0;
+    self.depth = native().ledgerRead(handle, 1)[0];
+    return self;
+  }
+  _handle() { if (!this._h) throw new Error("the ledger is closed"); return this._h; }
+  // onEventUpdateMerkleTree (pubsub.ts:19-66): one record, or deposit([[index, pub, balance, nonce], ...])
+  deposit(index, pub, balance, nonce) {
+    const rows = pub === undefined ? index : [[index, pub, balance, nonce]];
+    const idx = new Uint32Array(rows.length);
+    rows.forEach((r, i) => { idx[i] = Number(r[0]); });
+    native().ledgerDeposit(this._handle(), idx, concatLe([].concat(...rows.map((r) => [r[1][0], r[1][1], r[2], r[3] === undefined ? 0 : r[3]]))));
+  }
+  root() { return leToBigInts(native().ledgerRead(this._handle(), 0))[0]; }
+  // { record: [pubX, pubY, balance, nonce], path: getUpdatePath(index).pathElements }
+  account(index) {
+    const v = leToBigInts(native().ledgerRead(this._handle(), 2, Number(index), this.depth));
+    return { record: v.slice(0, 4), path: v.slice(4) };
+  }
+  info() { const v = native().ledgerRead(this._handle(), 1); return { depth: v[0], accounts: v[1], applied: v[2], batches: v[3] }; }
+  // the ZKRLEDG1 blob of the current state; restore checks it on the host and rebuilds the tree on the device
+  snapshot() { return native().ledgerRead(this._handle(), 3); }
+  static restore(blob, device) { return Ledger._adopt(native().ledgerOpen(Buffer.from(bytesOf(blob)), device || 0), device); }
+  save(path) { native().ledgerSave(this._handle(), String(path)); }
+  static load(path, device) { return Ledger._adopt(native().ledgerOpen(String(path), device || 0), device); }
+  // checkpoints nest; rollback(id) puts records, tree and counters back as they stood at checkpoint() and leaves `id` open
+  checkpoint() { return native().ledgerCheckpoint(this._handle(), 0); }
+  rollback(id) { native().ledgerCheckpoint(this._handle(), 1, Number(id)); }
+  release(id) { native().ledgerCheckpoint(this._handle(), 2, Number(id)); }
+  journalInfo() { const v = native().ledgerRead(this._handle(), 4); return { checkpoints: v[0], nodes: v[1] }; }
+  close() {
+    if (this._operators > 0) throw new Error("the ledger is held by a live operator: close the operator first");
+    if (this._h) native().ledgerClose(this._h);
+    this._h = null;
+  }
+}
+
+// One operator step behind one handle (zkr_operator_*): a queue of signed transactions in; statuses, proofs and public signals out;
+// the ledger moves only when every proof of the step is good.  opts: { ledger, bn (a Bn128 holding a key: setupR1cs, loadKeyFile or
+// one the cache holds), r1csBin (optional: the constraint check before proving), vkBin (optional: the acceptance check on the GPU,
+// about 50 ms a step whatever its size -- leave it out and use isValidBatch on the host where that matters; vk_bin bytes or the
+// verifying key JSON), batch (default 2), maxBatches (default 256) }.
+class Operator {
+  constructor(opts) {
+    const { ledger, bn } = opts || {};
+    if (!(ledger instanceof Ledger)) throw new Error("Operator: opts.ledger must be a Ledger");
+    if (!bn || !bn._key) throw new Error("Operator: opts.bn must be a Bn128 that holds a key (setupR1cs, loadKeyFile or a proof first)");
+    let vkBin = opts.vkBin === undefined ? null : opts.vkBin;
+    if (vkBin && vkBin.IC) vkBin = binarifyVerifyingKey(vkBin);
+    this._h = native().operatorNew(ledger._handle(), bn._key, opts.r1csBin || null, vkBin, opts.batch === undefined ? 2 : Number(opts.batch),
+      opts.maxBatches === undefined ? null : Number(opts.maxBatches));
+    // the handles this operator borrows stay referenced from here, so garbage collection cannot free them first
+    this._ledger = ledger; this._bn = bn; this._key = bn._key;
+    ledger._operators++; bn._operators = (bn._operators || 0) + 1;
+    const v = native().operatorInfo(this._h);
+    this.batch = v[0]; this.nPublic = v[3];
+    this._tail = Promise.resolve(); this._pending = 0;
+  }
+  // queue: txRow buffers (or their bytes back to back); opts.rs / opts.ss: one blinding scalar per batch the queue can fill
+  // (floor(queue length / batch)), or neither: drawn per proof.  Resolves to { status: one code per transaction as
+  // zkr_ledger_sequence gives them, consumed: resubmit queue.slice(consumed), batches: [{ proof, publicSignals, solidityProof }] };
+  // rejects with the library's message, the ledger as it was before the call.  Steps run in the order they were issued.
+  async step(queue, opts) {
+    if (!this._h) throw new Error("the operator is closed");
+    const txs = Array.isArray(queue) ? Buffer.concat(queue.map((t) => Buffer.from(bytesOf(t)))) : Buffer.from(bytesOf(queue));
+    if (txs.length % 256) throw new Error("Operator.step: the queue is 256 bytes per transaction (txRow)");
+    const room = Math.floor(txs.length / 256 / this.batch), rs = opts && opts.rs, ss = opts && opts.ss;
+    if ((rs == null) !== (ss == null)) throw new Error("Operator.step: pass both rs and ss or neither");
+    if (rs && (rs.length !== room || ss.length !== room)) throw new Error(`Operator.step: ${room} batches need ${room} blinding scalars of each kind, got ${rs.length} and ${ss.length}`);
+    const rb = rs ? concatLe(rs) : null, sb = rs ? concatLe(ss) : null;
+    const keep = [this._h, this._ledger._h, this._key];  // referenced by the addon until the step is done
+    const run = () => native().operatorStep(this._h, keep, txs, rb, sb);
+    const p = this._tail.then(run);
+    this._tail = p.then(() => {}, () => {});  // the next step starts when this one has settled, whichever way
+    this._pending++;
+    let res;
+    try { res = await p; } finally { this._pending--; }
+    const [status, consumed, proofs, publics] = res, row = 32 * this.nPublic, batches = [];
+    for (let b = 0; 256 * b < proofs.length; b++) {
+      const proof = proofFromBytes(proofs.subarray(256 * b, 256 * b + 256));
+      const publicSignals = leToBigInts(publics.subarray(row * b, row * b + row)).map((x) => x.toString());
+      batches.push({ proof, publicSignals, solidityProof: solidityProof(proof, publicSignals) });
+    }
+    return { status: Array.from(status), consumed, batches };
+  }
+  info() {
+    const v = native().operatorInfo(this._h);
+    return { batch: v[0], depth: v[1], nVars: v[2], nPublic: v[3], maxBatches: v[4], deviceBytes: v[5] };
+  }
+  // wall milliseconds of the last step's stages (0 for a stage that did not run)
+  stageTimes() {
+    const v = native().operatorStageTimes(this._h);
+    return { sequence: v[0], witness: v[1], check: v[2], prove: v[3], verify: v[4], readOut: v[5] };
+  }
+  close() {
+    if (!this._h) return;
+    if (this._pending > 0) throw new Error("the operator has a step in flight: await it first");
+    native().operatorClose(this._h);
+    this._h = null;
+    this._ledger._operators--; this._bn._operators--;
+  }
+}
+
 module.exports = {
+  Ledger, Operator, txRow,
   buildBn128, genProof, binarifyWitness, binarifyProvingKey, solidityProof, proofFromBytes, isValid, isValidBatch, binarifyVerifyingKey,
   contributionCheck, vkContribute,
   binarifyR1cs, verifyingKeyFromBytes, solidityVerifyingKey, solidityVerifyingKeySource,

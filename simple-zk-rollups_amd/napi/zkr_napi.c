@@ -13,6 +13,10 @@
 #include <string.h>
 
 typedef struct zkr_key zkr_key;
+typedef struct zkr_ledger zkr_ledger;
+typedef struct zkr_r1cs zkr_r1cs;
+typedef struct zkr_vk zkr_vk;
+typedef struct zkr_operator zkr_operator;
 static struct {
   void *handle;
   const char *(*last_error)(void);
@@ -57,6 +61,31 @@ static struct {
   int (*key_shard_opts)(const zkr_key *, unsigned, unsigned, int, unsigned, zkr_key **);
   int (*sharded_last_h_form)(int *, char *, size_t);
   int (*key_h_form)(const zkr_key *, int *, uint64_t *);
+  /* optional as a group (ledger_ok below): the ledger and the operator step, host buffers only */
+  int (*ledger_new)(unsigned, int, zkr_ledger **);
+  void (*ledger_free)(zkr_ledger *);
+  int (*ledger_deposit)(zkr_ledger *, const uint32_t *, const uint8_t *, size_t);
+  int (*ledger_info)(const zkr_ledger *, uint64_t *);
+  int (*ledger_root)(const zkr_ledger *, uint8_t *);
+  int (*ledger_account)(const zkr_ledger *, uint32_t, uint8_t *, uint8_t *);
+  int (*ledger_snapshot)(const zkr_ledger *, void **, size_t *);
+  int (*ledger_save)(const zkr_ledger *, const char *);
+  int (*ledger_restore)(const void *, size_t, int, zkr_ledger **);
+  int (*ledger_load_file)(const char *, int, zkr_ledger **);
+  int (*ledger_checkpoint)(zkr_ledger *, uint64_t *);
+  int (*ledger_rollback)(zkr_ledger *, uint64_t);
+  int (*ledger_release)(zkr_ledger *, uint64_t);
+  int (*ledger_journal_info)(const zkr_ledger *, uint64_t *);
+  int (*r1cs_load)(const void *, size_t, int, zkr_r1cs **);
+  void (*r1cs_free)(zkr_r1cs *);
+  int (*vk_load)(const void *, size_t, int, zkr_vk **);
+  void (*vk_free)(zkr_vk *);
+  int (*operator_new)(zkr_ledger *, zkr_key *, zkr_r1cs *, zkr_vk *, const uint32_t *, zkr_operator **);
+  void (*operator_free)(zkr_operator *);
+  int (*operator_info)(const zkr_operator *, uint64_t *);
+  int (*operator_step)(zkr_operator *, const uint8_t *, size_t, const uint8_t *, const uint8_t *, uint8_t *, uint8_t *, void *, size_t *, size_t *);
+  int (*operator_stage_times)(const zkr_operator *, double *);
+  int ledger_ok;
 } Z;
 /* which form the last sharded proof took (zkr_prove_sharded_last_form, read on the worker thread that ran it, published on the JS
  * thread when its promise settles) */
@@ -108,6 +137,17 @@ static napi_value js_load(napi_env env, napi_callback_info info) {
     *(void **)(&Z.key_shard_opts) = dlsym(h, "zkr_key_shard_opts");
     *(void **)(&Z.sharded_last_h_form) = dlsym(h, "zkr_prove_sharded_last_h_form");
     *(void **)(&Z.key_h_form) = dlsym(h, "zkr_key_h_form");
+    Z.ledger_ok = 1;
+#define OPT(field, name)                 \
+  *(void **)(&Z.field) = dlsym(h, name); \
+  if (!Z.field) Z.ledger_ok = 0;
+    OPT(ledger_new, "zkr_ledger_new") OPT(ledger_free, "zkr_ledger_free") OPT(ledger_deposit, "zkr_ledger_deposit") OPT(ledger_info, "zkr_ledger_info")
+    OPT(ledger_root, "zkr_ledger_root") OPT(ledger_account, "zkr_ledger_account") OPT(ledger_snapshot, "zkr_ledger_snapshot") OPT(ledger_save, "zkr_ledger_save")
+    OPT(ledger_restore, "zkr_ledger_restore") OPT(ledger_load_file, "zkr_ledger_load_file") OPT(ledger_checkpoint, "zkr_ledger_checkpoint")
+    OPT(ledger_rollback, "zkr_ledger_rollback") OPT(ledger_release, "zkr_ledger_release") OPT(ledger_journal_info, "zkr_ledger_journal_info")
+    OPT(r1cs_load, "zkr_r1cs_load") OPT(r1cs_free, "zkr_r1cs_free") OPT(vk_load, "zkr_vk_load") OPT(vk_free, "zkr_vk_free")
+    OPT(operator_new, "zkr_operator_new") OPT(operator_free, "zkr_operator_free") OPT(operator_info, "zkr_operator_info")
+    OPT(operator_step, "zkr_operator_step") OPT(operator_stage_times, "zkr_operator_stage_times")
     Z.handle = h;
   }
   napi_value out;
@@ -888,6 +928,349 @@ static napi_value js_verify_batch(napi_env env, napi_callback_info info) {
   return out;
 }
 
+/* ---- the operator's ledger and step (include/zkr.h zkr_ledger_*, zkr_operator_*; ../index.js class Ledger, class Operator).
+ * Host buffers only: the device buffers of the loop belong to the zkr_operator.  A handle is an external over a small box, so that
+ * close() can free the library object at once and leave the finalizer nothing to do. ---- */
+typedef struct { zkr_ledger *l; } ledger_box;
+typedef struct { zkr_operator *op; zkr_r1cs *cs; zkr_vk *vk; } operator_box;
+
+#define LEDGER_ARGS(n)                                                                        \
+  size_t argc = n;                                                                            \
+  napi_value argv[n];                                                                         \
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));                              \
+  if (!Z.handle) return throw_msg(env, "libzkr_hip.so not loaded");                           \
+  if (!Z.ledger_ok) return throw_msg(env, "this libzkr_hip.so has no ledger / operator calls")
+
+static void ledger_box_free(ledger_box *b) {
+  if (b->l) Z.ledger_free(b->l);
+  b->l = NULL;
+}
+static void ledger_finalize(napi_env env, void *data, void *hint) {
+  (void)env; (void)hint;
+  ledger_box_free((ledger_box *)data);
+  free(data);
+}
+static void operator_box_free(operator_box *b) {  /* the operator first: it borrows the other two */
+  if (b->op) Z.operator_free(b->op);
+  if (b->cs) Z.r1cs_free(b->cs);
+  if (b->vk) Z.vk_free(b->vk);
+  b->op = NULL; b->cs = NULL; b->vk = NULL;
+}
+static void operator_finalize(napi_env env, void *data, void *hint) {
+  (void)env; (void)hint;
+  operator_box_free((operator_box *)data);
+  free(data);
+}
+static napi_value wrap_ledger(napi_env env, zkr_ledger *l) {
+  ledger_box *b = (ledger_box *)calloc(1, sizeof(ledger_box));
+  napi_value ext;
+  if (!b || napi_create_external(env, b, ledger_finalize, NULL, &ext) != napi_ok) {
+    Z.ledger_free(l);
+    free(b);
+    return throw_msg(env, "zkr_napi: cannot wrap the ledger");
+  }
+  b->l = l;
+  return ext;
+}
+/* the open ledger behind a handle, or NULL with an exception pending */
+static zkr_ledger *open_ledger(napi_env env, napi_value v) {
+  ledger_box *b = NULL;
+  if (napi_get_value_external(env, v, (void **)&b) != napi_ok || !b) { throw_msg(env, "a ledger handle expected"); return NULL; }
+  if (!b->l) { throw_msg(env, "the ledger is closed"); return NULL; }
+  return b->l;
+}
+static zkr_operator *open_operator(napi_env env, napi_value v) {
+  operator_box *b = NULL;
+  if (napi_get_value_external(env, v, (void **)&b) != napi_ok || !b) { throw_msg(env, "an operator handle expected"); return NULL; }
+  if (!b->op) { throw_msg(env, "the operator is closed"); return NULL; }
+  return b->op;
+}
+static napi_value number_array(napi_env env, const double *v, uint32_t n) {
+  napi_value arr;
+  NAPI_OK(napi_create_array_with_length(env, n, &arr));
+  for (uint32_t i = 0; i < n; i++) {
+    napi_value x;
+    NAPI_OK(napi_create_double(env, v[i], &x));
+    NAPI_OK(napi_set_element(env, arr, i, x));
+  }
+  return arr;
+}
+static napi_value u64_array(napi_env env, const uint64_t *v, uint32_t n) {
+  double d[8];
+  for (uint32_t i = 0; i < n && i < 8; i++) d[i] = (double)v[i];
+  return number_array(env, d, n);
+}
+static napi_value copy_out(napi_env env, const void *p, size_t n) {
+  napi_value buf;
+  void *copy;
+  NAPI_OK(napi_create_buffer_copy(env, n, p, &copy, &buf));
+  return buf;
+}
+
+/* ledgerNew(depth, device) -> handle */
+static napi_value js_ledger_new(napi_env env, napi_callback_info info) {
+  LEDGER_ARGS(2);
+  uint32_t depth = 0;
+  int32_t dev = 0;
+  if (argc < 1 || napi_get_value_uint32(env, argv[0], &depth) != napi_ok) return throw_msg(env, "ledgerNew(depth, device)");
+  if (argc > 1) napi_get_value_int32(env, argv[1], &dev);
+  zkr_ledger *l = NULL;
+  if (Z.ledger_new(depth, dev, &l)) return throw_msg(env, Z.last_error());
+  return wrap_ledger(env, l);
+}
+/* ledgerOpen(blob | path, device) -> handle: zkr_ledger_restore of a ZKRLEDG1 blob, zkr_ledger_load_file of a path */
+static napi_value js_ledger_open(napi_env env, napi_callback_info info) {
+  LEDGER_ARGS(2);
+  int32_t dev = 0;
+  if (argc > 1) napi_get_value_int32(env, argv[1], &dev);
+  zkr_ledger *l = NULL;
+  const uint8_t *blob;
+  size_t len;
+  napi_valuetype t = napi_undefined;
+  if (argc > 0) napi_typeof(env, argv[0], &t);
+  if (t == napi_string) {
+    char path[4096];
+    NAPI_OK(napi_get_value_string_utf8(env, argv[0], path, sizeof(path), &len));
+    if (Z.ledger_load_file(path, dev, &l)) return throw_msg(env, Z.last_error());
+  } else if (argc > 0 && get_bytes(env, argv[0], &blob, &len)) {
+    if (Z.ledger_restore(blob, len, dev, &l)) return throw_msg(env, Z.last_error());
+  } else return throw_msg(env, "ledgerOpen(blob | path, device)");
+  return wrap_ledger(env, l);
+}
+/* ledgerClose(handle): frees the ledger now; every later call on the handle throws */
+static napi_value js_ledger_close(napi_env env, napi_callback_info info) {
+  LEDGER_ARGS(1);
+  ledger_box *b = NULL;
+  if (argc < 1 || napi_get_value_external(env, argv[0], (void **)&b) != napi_ok || !b) return throw_msg(env, "a ledger handle expected");
+  ledger_box_free(b);
+  return NULL;
+}
+/* ledgerDeposit(handle, indices (n x u32 LE), records (n x 128 B)) */
+static napi_value js_ledger_deposit(napi_env env, napi_callback_info info) {
+  LEDGER_ARGS(3);
+  zkr_ledger *l = argc < 3 ? NULL : open_ledger(env, argv[0]);
+  if (!l) return argc < 3 ? throw_msg(env, "ledgerDeposit(ledger, indices, records)") : NULL;
+  const uint8_t *idx, *rec;
+  size_t il, rl;
+  if (!get_bytes(env, argv[1], &idx, &il) || !get_bytes(env, argv[2], &rec, &rl) || il % 4 || rl != il / 4 * 128 || ((uintptr_t)idx & 3))
+    return throw_msg(env, "ledgerDeposit: 4 bytes of index and 128 bytes of record per row");
+  if (Z.ledger_deposit(l, (const uint32_t *)idx, rec, il / 4)) return throw_msg(env, Z.last_error());
+  return NULL;
+}
+/* ledgerRead(handle, what[, index, depth]): 0 root -> 32 B; 1 info -> [depth, accounts, applied, batches]; 2 account -> 128 B record
+ * then depth x 32 B of path; 3 snapshot -> the ZKRLEDG1 blob; 4 journalInfo -> [open checkpoints, journalled nodes] */
+static napi_value js_ledger_read(napi_env env, napi_callback_info info) {
+  LEDGER_ARGS(4);
+  zkr_ledger *l = argc < 2 ? NULL : open_ledger(env, argv[0]);
+  if (!l) return argc < 2 ? throw_msg(env, "ledgerRead(ledger, what)") : NULL;
+  int32_t what = -1;
+  napi_get_value_int32(env, argv[1], &what);
+  uint64_t v[4];
+  if (what == 0) {
+    uint8_t root[32];
+    if (Z.ledger_root(l, root)) return throw_msg(env, Z.last_error());
+    return copy_out(env, root, 32);
+  }
+  if (what == 1 || what == 4) {
+    if (what == 1 ? Z.ledger_info(l, v) : Z.ledger_journal_info(l, v)) return throw_msg(env, Z.last_error());
+    return u64_array(env, v, what == 1 ? 4 : 2);
+  }
+  if (what == 2) {
+    uint32_t index = 0, depth = 0;
+    if (argc < 4 || napi_get_value_uint32(env, argv[2], &index) != napi_ok || napi_get_value_uint32(env, argv[3], &depth) != napi_ok || depth > 24)
+      return throw_msg(env, "ledgerRead(ledger, 2, index, depth)");
+    uint8_t out[128 + 24 * 32];
+    if (Z.ledger_account(l, index, out, out + 128)) return throw_msg(env, Z.last_error());
+    return copy_out(env, out, 128 + 32 * (size_t)depth);
+  }
+  if (what == 3) {
+    void *blob = NULL;
+    size_t len = 0;
+    if (Z.ledger_snapshot(l, &blob, &len)) return throw_msg(env, Z.last_error());
+    napi_value buf = copy_out(env, blob, len);
+    Z.free_(blob);
+    return buf;
+  }
+  return throw_msg(env, "ledgerRead: unknown item");
+}
+/* ledgerSave(handle, path) */
+static napi_value js_ledger_save(napi_env env, napi_callback_info info) {
+  LEDGER_ARGS(2);
+  zkr_ledger *l = argc < 2 ? NULL : open_ledger(env, argv[0]);
+  if (!l) return argc < 2 ? throw_msg(env, "ledgerSave(ledger, path)") : NULL;
+  char path[4096];
+  size_t n = 0;
+  NAPI_OK(napi_get_value_string_utf8(env, argv[1], path, sizeof(path), &n));
+  if (Z.ledger_save(l, path)) return throw_msg(env, Z.last_error());
+  return NULL;
+}
+/* ledgerCheckpoint(handle, op[, id]): op 0 open -> id; 1 rollback(id); 2 release(id).  Ids are small counters: plain numbers. */
+static napi_value js_ledger_checkpoint(napi_env env, napi_callback_info info) {
+  LEDGER_ARGS(3);
+  zkr_ledger *l = argc < 2 ? NULL : open_ledger(env, argv[0]);
+  if (!l) return argc < 2 ? throw_msg(env, "ledgerCheckpoint(ledger, op, id)") : NULL;
+  int32_t op = -1;
+  napi_get_value_int32(env, argv[1], &op);
+  if (op == 0) {
+    uint64_t id = 0;
+    if (Z.ledger_checkpoint(l, &id)) return throw_msg(env, Z.last_error());
+    napi_value out;
+    NAPI_OK(napi_create_double(env, (double)id, &out));
+    return out;
+  }
+  double id = -1;
+  if (argc < 3 || napi_get_value_double(env, argv[2], &id) != napi_ok || id < 0 || id > 9007199254740992.0 || (op != 1 && op != 2))
+    return throw_msg(env, "ledgerCheckpoint(ledger, 1 | 2, id)");
+  if (op == 1 ? Z.ledger_rollback(l, (uint64_t)id) : Z.ledger_release(l, (uint64_t)id)) return throw_msg(env, Z.last_error());
+  return NULL;
+}
+
+/* operatorNew(ledger, key, r1csBin | null, vkBin | null, batch, maxBatches) -> handle.  The addon loads the constraint system and
+ * the verifying key on the key's device (zkr_r1cs_load, zkr_vk_load) and frees them with the operator.  Synchronous. */
+static napi_value js_operator_new(napi_env env, napi_callback_info info) {
+  LEDGER_ARGS(6);
+  zkr_ledger *l = argc < 5 ? NULL : open_ledger(env, argv[0]);
+  if (!l) return argc < 5 ? throw_msg(env, "operatorNew(ledger, key, r1csBin, vkBin, batch, maxBatches)") : NULL;
+  zkr_key *key = NULL;
+  uint32_t opts[4] = {0, 0, 0, 0};  /* zkr_operator_opts: batch, max_batches, flags, reserved */
+  if (napi_get_value_external(env, argv[1], (void **)&key) != napi_ok || !key || napi_get_value_uint32(env, argv[4], &opts[0]) != napi_ok)
+    return throw_msg(env, "operatorNew: a key handle and a batch size expected");
+  if (argc > 5 && !is_nullish(env, argv[5]) && napi_get_value_uint32(env, argv[5], &opts[1]) != napi_ok) return throw_msg(env, "operatorNew: maxBatches must be a number");
+  const uint8_t *r1cs = NULL, *vkb = NULL;
+  size_t r1cs_len = 0, vk_len = 0;
+  if (!is_nullish(env, argv[2]) && !get_bytes(env, argv[2], &r1cs, &r1cs_len)) return throw_msg(env, "operatorNew: r1csBin must be a byte buffer or null");
+  if (!is_nullish(env, argv[3]) && !get_bytes(env, argv[3], &vkb, &vk_len)) return throw_msg(env, "operatorNew: vkBin must be a byte buffer or null");
+  operator_box *b = (operator_box *)calloc(1, sizeof(operator_box));
+  if (!b) return throw_msg(env, "operatorNew: out of memory");
+  const int dev = Z.key_device(key);
+  if ((r1cs && Z.r1cs_load(r1cs, r1cs_len, dev, &b->cs)) || (vkb && Z.vk_load(vkb, vk_len, dev, &b->vk)) || Z.operator_new(l, key, b->cs, b->vk, opts, &b->op)) {
+    char msg[512];
+    strncpy(msg, Z.last_error(), sizeof(msg) - 1);
+    msg[sizeof(msg) - 1] = 0;
+    operator_box_free(b);
+    free(b);
+    return throw_msg(env, msg);
+  }
+  napi_value ext;
+  if (napi_create_external(env, b, operator_finalize, NULL, &ext) != napi_ok) {
+    operator_box_free(b);
+    free(b);
+    return throw_msg(env, "zkr_napi: cannot wrap the operator");
+  }
+  return ext;
+}
+static napi_value js_operator_close(napi_env env, napi_callback_info info) {
+  LEDGER_ARGS(1);
+  operator_box *b = NULL;
+  if (argc < 1 || napi_get_value_external(env, argv[0], (void **)&b) != napi_ok || !b) return throw_msg(env, "an operator handle expected");
+  operator_box_free(b);
+  return NULL;
+}
+/* operatorInfo(handle) -> [batch, depth, nVars, nPublic, maxBatches, device bytes held]; operatorStageTimes(handle) -> 6 x ms */
+static napi_value js_operator_info(napi_env env, napi_callback_info info) {
+  LEDGER_ARGS(1);
+  zkr_operator *op = argc < 1 ? NULL : open_operator(env, argv[0]);
+  if (!op) return argc < 1 ? throw_msg(env, "operatorInfo(operator)") : NULL;
+  uint64_t v[6];
+  if (Z.operator_info(op, v)) return throw_msg(env, Z.last_error());
+  return u64_array(env, v, 6);
+}
+static napi_value js_operator_stage_times(napi_env env, napi_callback_info info) {
+  LEDGER_ARGS(1);
+  zkr_operator *op = argc < 1 ? NULL : open_operator(env, argv[0]);
+  if (!op) return argc < 1 ? throw_msg(env, "operatorStageTimes(operator)") : NULL;
+  double ms[6];
+  if (Z.operator_stage_times(op, ms)) return throw_msg(env, Z.last_error());
+  return number_array(env, ms, 6);
+}
+
+typedef struct {
+  napi_async_work work;
+  napi_deferred deferred;
+  napi_ref keep;  /* the JS array of the operator, ledger and key handles: none is finalized under the job */
+  zkr_operator *op;
+  uint8_t *txs, *rs, *ss, *status, *proofs, *publics;  /* private copies and results: the worker touches no JS memory */
+  size_t n_txs, room, n_public, n_batches, consumed;
+  int rc;
+  char err[512];
+} step_job;
+static void step_free(napi_env env, step_job *j) {
+  if (!j) return;
+  if (j->keep) napi_delete_reference(env, j->keep);
+  if (j->work) napi_delete_async_work(env, j->work);
+  free(j->txs); free(j->rs); free(j->ss); free(j->status); free(j->proofs); free(j->publics); free(j);
+}
+static void step_execute(napi_env env, void *data) {  /* libuv worker thread */
+  (void)env;
+  step_job *j = (step_job *)data;
+  j->rc = Z.operator_step(j->op, j->txs, j->n_txs, j->rs, j->ss, j->status, j->proofs, j->publics, &j->n_batches, &j->consumed);
+  if (j->rc) { strncpy(j->err, Z.last_error(), sizeof(j->err) - 1); j->err[sizeof(j->err) - 1] = 0; }
+}
+static void step_complete(napi_env env, napi_status status, void *data) {
+  step_job *j = (step_job *)data;
+  napi_value v, msg, st, pr, pu, nc;
+  void *copy;
+  if (status == napi_ok && j->rc == 0 && napi_create_array_with_length(env, 4, &v) == napi_ok &&
+      napi_create_buffer_copy(env, j->n_txs, j->status, &copy, &st) == napi_ok && napi_create_double(env, (double)j->consumed, &nc) == napi_ok &&
+      napi_create_buffer_copy(env, 256 * j->n_batches, j->proofs, &copy, &pr) == napi_ok &&
+      napi_create_buffer_copy(env, 32 * j->n_public * j->n_batches, j->publics, &copy, &pu) == napi_ok && napi_set_element(env, v, 0, st) == napi_ok &&
+      napi_set_element(env, v, 1, nc) == napi_ok && napi_set_element(env, v, 2, pr) == napi_ok && napi_set_element(env, v, 3, pu) == napi_ok) {
+    napi_resolve_deferred(env, j->deferred, v);
+  } else {
+    napi_create_string_utf8(env, j->rc ? j->err : status == napi_ok ? "operator step: cannot build the result" : "operator step cancelled", NAPI_AUTO_LENGTH, &msg);
+    napi_create_error(env, NULL, msg, &v);
+    napi_reject_deferred(env, j->deferred, v);
+  }
+  step_free(env, j);
+}
+/* operatorStep(handle, keep, txs (n x 256 B), rs | null, ss | null) -> Promise<[status Buffer, consumed, proofs Buffer, publics Buffer]>:
+ * zkr_operator_step on a libuv worker, like prove.  The queue and the blinding are copied before the call returns. */
+static napi_value js_operator_step(napi_env env, napi_callback_info info) {
+  LEDGER_ARGS(5);
+  zkr_operator *op = argc < 3 ? NULL : open_operator(env, argv[0]);
+  if (!op) return argc < 3 ? throw_msg(env, "operatorStep(operator, keep, txs, rs, ss)") : NULL;
+  const uint8_t *txs, *pr = NULL, *ps = NULL;
+  size_t len, nr = 0, ns = 0;
+  uint64_t oi[6];
+  if (!get_bytes(env, argv[2], &txs, &len) || len % 256) return throw_msg(env, "operatorStep: the queue is 256 bytes per transaction (txRow)");
+  if (Z.operator_info(op, oi)) return throw_msg(env, Z.last_error());
+  step_job *j = (step_job *)calloc(1, sizeof(step_job));
+  if (!j) return throw_msg(env, "operatorStep: out of memory");
+  j->op = op;
+  j->n_txs = len / 256;
+  j->room = j->n_txs / (size_t)oi[0];
+  j->n_public = (size_t)oi[3];
+  const int have_rs = argc >= 4 && !is_nullish(env, argv[3]), have_ss = argc >= 5 && !is_nullish(env, argv[4]);
+  if (have_rs || have_ss) {  /* as proveBatch: a buffer of the wrong length must not silently turn into random blinding */
+    if (!have_rs || !have_ss || !get_bytes(env, argv[3], &pr, &nr) || !get_bytes(env, argv[4], &ps, &ns) || nr != 32 * j->room || ns != 32 * j->room) {
+      step_free(env, j);
+      return throw_msg(env, "operatorStep: rs and ss must both hold 32 bytes per batch the queue can fill (or both be null)");
+    }
+    j->rs = (uint8_t *)malloc(nr + 1);
+    j->ss = (uint8_t *)malloc(ns + 1);
+  }
+  j->txs = (uint8_t *)malloc(len + 1);
+  j->status = (uint8_t *)malloc(j->n_txs + 1);
+  j->proofs = (uint8_t *)malloc(256 * j->room + 1);
+  j->publics = (uint8_t *)malloc(32 * j->n_public * j->room + 1);
+  if (!j->txs || !j->status || !j->proofs || !j->publics || ((have_rs || have_ss) && (!j->rs || !j->ss))) { step_free(env, j); return throw_msg(env, "operatorStep: out of memory"); }
+  memcpy(j->txs, txs, len);
+  if (j->rs) { memcpy(j->rs, pr, nr); memcpy(j->ss, ps, ns); }
+  napi_value promise, name;
+  if (napi_create_promise(env, &j->deferred, &promise) != napi_ok || napi_create_reference(env, argv[1], 1, &j->keep) != napi_ok ||
+      napi_create_string_utf8(env, "zkr_operator_step", NAPI_AUTO_LENGTH, &name) != napi_ok ||
+      napi_create_async_work(env, NULL, name, step_execute, step_complete, j, &j->work) != napi_ok || napi_queue_async_work(env, j->work) != napi_ok) {
+    if (j->deferred) {  /* as in prove_common: a promise nobody will settle is rejected before the job goes */
+      napi_value msg, err;
+      if (napi_create_string_utf8(env, "operatorStep: could not queue the step", NAPI_AUTO_LENGTH, &msg) == napi_ok && napi_create_error(env, NULL, msg, &err) == napi_ok)
+        napi_reject_deferred(env, j->deferred, err);
+    }
+    step_free(env, j);
+    return throw_msg(env, "operatorStep: could not queue the step");
+  }
+  return promise;
+}
+
 static napi_value init(napi_env env, napi_value exports) {
   napi_property_descriptor props[] = {
       {"load", NULL, js_load, NULL, NULL, NULL, napi_default, NULL},       {"version", NULL, js_version, NULL, NULL, NULL, napi_default, NULL},
@@ -911,6 +1294,14 @@ static napi_value init(napi_env env, napi_value exports) {
       {"vkContribute", NULL, js_vk_contribute, NULL, NULL, NULL, napi_default, NULL},
       {"keyEvalTables", NULL, js_key_eval_tables, NULL, NULL, NULL, napi_default, NULL},
       {"keyHForm", NULL, js_key_h_form, NULL, NULL, NULL, napi_default, NULL},
+      {"ledgerNew", NULL, js_ledger_new, NULL, NULL, NULL, napi_default, NULL}, {"ledgerOpen", NULL, js_ledger_open, NULL, NULL, NULL, napi_default, NULL},
+      {"ledgerClose", NULL, js_ledger_close, NULL, NULL, NULL, napi_default, NULL}, {"ledgerDeposit", NULL, js_ledger_deposit, NULL, NULL, NULL, napi_default, NULL},
+      {"ledgerRead", NULL, js_ledger_read, NULL, NULL, NULL, napi_default, NULL}, {"ledgerSave", NULL, js_ledger_save, NULL, NULL, NULL, napi_default, NULL},
+      {"ledgerCheckpoint", NULL, js_ledger_checkpoint, NULL, NULL, NULL, napi_default, NULL},
+      {"operatorNew", NULL, js_operator_new, NULL, NULL, NULL, napi_default, NULL}, {"operatorClose", NULL, js_operator_close, NULL, NULL, NULL, napi_default, NULL},
+      {"operatorInfo", NULL, js_operator_info, NULL, NULL, NULL, napi_default, NULL},
+      {"operatorStageTimes", NULL, js_operator_stage_times, NULL, NULL, NULL, napi_default, NULL},
+      {"operatorStep", NULL, js_operator_step, NULL, NULL, NULL, napi_default, NULL},
   };
   napi_define_properties(env, exports, sizeof(props) / sizeof(props[0]), props);
   return exports;

@@ -20,6 +20,10 @@ class BookOpts(ctypes.Structure):   # zkr.h zkr_book_opts
     _fields_ = [("nullifier_cap_log2", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("salt", ctypes.c_uint64)]
 
 
+class OperatorOpts(ctypes.Structure):   # zkr.h zkr_operator_opts
+    _fields_ = [("batch", ctypes.c_uint32), ("max_batches", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
 class NttSelftestDesc(ctypes.Structure):   # zkr.h zkr_ntt_selftest_desc
     _fields_ = [(f, ctypes.c_uint32) for f in ("logn", "tlog", "dif", "inverse", "pre", "nbat", "pair", "in_place", "want_lo", "want_n", "coset_shift",
                                                "coset_add", "cross", "klog", "col_lo", "col_n", "in_sub", "out_sub", "canon", "reserved")]
@@ -207,6 +211,12 @@ def lib():
     L.zkr_book_blob_check.argtypes = [u8p, sz, u64p, c.POINTER(c.c_int)]
     L.zkr_book_deposit_plan_host.argtypes = [c.c_uint, u8p, sz, u8p, u8p, sz, u32p, u8p, u32p, u8p]
     L.zkr_book_withdraw_plan_host.argtypes = [u8p, sz, u8p, u8p, u8p, sz, u32p, u8p, u32p, u8p]
+    L.zkr_operator_new.argtypes = [vp, vp, vp, vp, c.POINTER(OperatorOpts), c.POINTER(vp)]
+    L.zkr_operator_free.argtypes = [vp]
+    L.zkr_operator_free.restype = None
+    L.zkr_operator_info.argtypes = [vp, u64p]
+    L.zkr_operator_step.argtypes = [vp, u8p, sz, u8p, u8p, u8p, u8p, vp, c.POINTER(sz), c.POINTER(sz)]
+    L.zkr_operator_stage_times.argtypes = [vp, c.POINTER(c.c_double)]
     _lib = L
     return L
 

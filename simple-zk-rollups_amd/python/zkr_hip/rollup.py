@@ -522,6 +522,78 @@ class Ledger:
         return {"nullifiers": info[0], "fees": int.from_bytes(blob[64:96], "little")}, None
 
 
+class Operator:
+    """One operator step behind one handle (zkr_operator_*): `step` takes a queue of signed transactions and returns
+    statuses, proofs and public signals -- Ledger.sequence, RollupCircuit.calculate_witness_batch_from_device,
+    ConstraintSystem.check_device, ProvingKey.prove_batch_device and VerifyingKey.verify_each_device in that order, over device
+    buffers the handle owns, inside a ledger checkpoint of its own: the ledger moves only when every proof of the step is good.
+    ledger, key, system (a ConstraintSystem, or None: no constraint check) and vk (a VerifyingKey, or None: no acceptance check --
+    verify_each_device takes about 50 ms whatever the batch size; check on the host with zkr_hip.verify_batch instead) are borrowed
+    and must outlive the operator, which keeps references to them.  A mismatch between them is ZkrError(-5) naming it."""
+    STAGES = ("sequence", "witness", "check", "prove", "verify", "read_out")
+
+    def __init__(self, ledger, key, system=None, vk=None, batch=2, max_batches=None):
+        from .binding import OperatorOpts
+        self._h = None
+        self._held = (ledger, key, system, vk)
+        self.batch = int(batch)
+        opts = OperatorOpts(self.batch, int(max_batches or 0), 0, 0)
+        h = ctypes.c_void_p()
+        _check(lib().zkr_operator_new(ledger._h, key._h, system._h if system is not None else None, vk._h if vk is not None else None,
+                                      ctypes.byref(opts), ctypes.byref(h)))
+        self._h = h
+        self.n_public = self.info()["n_public"]
+
+    def step(self, txs, rs=None, ss=None):
+        """txs = tx_row lists; rs / ss = one blinding scalar per batch the queue can fill (len(txs) // batch), or None: drawn per
+        proof.  -> {"status": one code per transaction as Ledger.sequence gives them, "consumed": the caller resubmits
+        txs[consumed:], "proofs": [256 bytes per batch], "publics": [the n_public signals of each batch]}.  Raises ZkrError with
+        the ledger as it was before the call when a witness, a constraint, a proof or the verifying key refuses a batch."""
+        from .binding import _blinding_bytes
+        n = len(txs)
+        room = n // self.batch
+        rb, sb = _blinding_bytes(rs, ss, room)   # a short list must not reach the C side
+        buf = b"".join(_le(v) for t in txs for v in t)
+        status = ctypes.create_string_buffer(max(n, 1))
+        proofs = ctypes.create_string_buffer(max(256 * room, 1))
+        publics = ctypes.create_string_buffer(max(32 * self.n_public * room, 1))
+        nb, consumed = ctypes.c_size_t(), ctypes.c_size_t()
+        _check(lib().zkr_operator_step(self._h, buf, n, rb, sb, status, proofs, publics, ctypes.byref(nb), ctypes.byref(consumed)))
+        row = 32 * self.n_public
+        return {"status": list(status.raw[:n]), "consumed": consumed.value,
+                "proofs": [proofs.raw[256 * b:256 * b + 256] for b in range(nb.value)],
+                "publics": [_ints(publics.raw[row * b:row * b + row]) for b in range(nb.value)]}
+
+    def info(self):
+        out = (ctypes.c_uint64 * 6)()
+        _check(lib().zkr_operator_info(self._h, out))
+        return dict(zip(("batch", "depth", "n_vars", "n_public", "max_batches", "device_bytes"), (int(v) for v in out)))
+
+    def stage_times(self):
+        """Wall milliseconds of the last step's stages (0 for a stage that did not run)."""
+        out = (ctypes.c_double * 6)()
+        _check(lib().zkr_operator_stage_times(self._h, out))
+        return dict(zip(self.STAGES, out))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().zkr_operator_free(self._h)
+            self._h = None
+        self._held = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _resolved_words(resolved):
     flat = [int(w) for r in resolved for w in r]
     return (ctypes.c_uint32 * max(1, len(flat)))(*flat)
