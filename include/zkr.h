@@ -419,6 +419,39 @@ int zkr_points_add_each(void *points_mont, const void *addends_mont, size_t n, i
 int zkr_setup_r1cs_websnark(const void *r1cs_bin, size_t r1cs_len, const uint8_t *toxic160, int device, void **pk_out, size_t *pk_len, void **vk_out,
                             size_t *vk_len);
 
+/* ---- a device key back in the reference's format (the way out that zkr_key_load_websnark is the way in of) ---------
+ * zkr_key_export_websnark: the same bytes (binarify.ts:143-206; malloc'ed, free with zkr_free) for ANY whole key -- loaded from
+ * websnark bytes or a key file, adopted, replicated in either mode, set up from scalars or from a transcript, contributed -- so a
+ * key no party can forge for (zkr_setup_r1cs_ptau + zkr_key_contribute) reaches groth16GenProof and the checkers.  n, p, m and the
+ * 448 constant bytes come from the arena header; polsA / polsB from the CSR sides: per signal by constraint index ascending, terms
+ * of one (signal, row) in their stored order, zero coefficients and duplicates as stored, the input-consistency rows like any
+ * other; the five point sections from level 0 of the window tables through the rank maps, on the GPU.  A scalar without a point
+ * (dropped at load, or the placeholder of a table laid out over a shared support) is the point at infinity as binarify.ts:92-102
+ * writes snarkjs's [0, 1, 0]: x = 0, y = Montgomery one; G2: x = (0, 0), y = (one, 0).  The side tables of the evaluation form
+ * are not part of the format.  ZKR_EXPORT_STANDARD: every field element in standard form instead of Montgomery -- not websnark
+ * bytes but the raw material of snarkjs's JSON key; infinity is (0, 1) and ((0, 0), (1, 0)).
+ * piece_points: output points per table converted and copied at a time (0: 2^20).  The call owns one device staging buffer of
+ * that many G2 points, one pinned buffer and one stream, and leaves nothing allocated; it only reads the arena, so proofs of the
+ * key may be in flight.  ZKR_ERR_ARG with a message: a null pointer, an unknown flag (both before any device call), a shard ("a
+ * shard holds a range of the tables"), a key past the format's 4 GiB (decided from the header before anything is allocated).
+ * zkr_key_export_last_times: this thread's last export -- [0] kernels, [1] copies, [2] host writer, [3] total, milliseconds,
+ * [4] the extra device bytes it held.
+ * Host only, the format's arithmetic and writer on their own: zkr_websnark_len is the length of a key with these sizes (nnz: the
+ * terms of a side, input-consistency rows included), ZKR_ERR_ARG past 2^32 - 1; zkr_websnark_render_host writes the bytes from the
+ * two sides in CSR by row (rowptr: domain + 1 entries from 0 to the side's term count; col: the signal; coef: 32 B, copied as they
+ * are) and the five full-length point sections in wire order A, B1, B2, C, hExps (n, n, n, n - p - 1, m points). */
+#define ZKR_EXPORT_STANDARD 1u
+typedef struct {
+  uint32_t flags;
+  uint32_t piece_points;
+} zkr_key_export_opts; /* NULL or zeros: defaults */
+int zkr_key_export_websnark(const zkr_key *key, const zkr_key_export_opts *opts, void **pk_out, size_t *pk_len);
+int zkr_key_export_last_times(double out[5]);
+int zkr_websnark_len(uint64_t n_vars, uint64_t n_public, uint64_t domain, uint64_t nnz_a, uint64_t nnz_b, uint64_t *len);
+int zkr_websnark_render_host(uint32_t n_vars, uint32_t n_public, uint32_t domain, const uint8_t *consts448, const uint32_t *rowptr_a, const uint32_t *col_a,
+                             const uint8_t *coef_a, const uint32_t *rowptr_b, const uint32_t *col_b, const uint8_t *coef_b, const uint8_t *const points[5],
+                             void **pk_out, size_t *pk_len);
+
 /* ---- does a witness satisfy its constraint system? (`snarkjs wtns check`, on the GPU) ----------------------------
  * zkr_prove proves whatever witness it is given: the key holds the A and B sides of the QAP and no C side, the quotient divides
  * exactly for every witness, and a witness that violates the circuit gives ZKR_OK and 256 bytes no verifier accepts.  The

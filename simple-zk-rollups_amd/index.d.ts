@@ -10,6 +10,17 @@ export interface Groth16Proof {
 export interface ProveOptions { r?: bigint | string; s?: bigint | string; device?: number; devices?: number[]; }
 /** devices: HIP ordinals of the GPUs a batch is sharded over (a device may be listed twice: two proof pipelines on it). */
 export interface BatchOptions { devices?: number[]; blinding?: ProveOptions[]; }
+/** piecePoints: output points per table converted and copied at a time (default 2^20). */
+export interface KeyExportOptions { piecePoints?: number; }
+/** A device key as a native handle (what keyEvalTables, keyHForm and keyReplication take). */
+export type KeyHandle = unknown;
+/** snarkjs 0.1.20 proving key, as the reference's `*_pk.json` holds it and binarifyProvingKey reads it: decimal strings. */
+export interface ProvingKeyJson {
+  protocol: "groth"; nVars: number; nPublic: number; domainBits: number; domainSize: number;
+  polsA: Array<{ [constraint: string]: string }>; polsB: Array<{ [constraint: string]: string }>;
+  A: string[][]; B1: string[][]; B2: string[][][]; C: Array<string[] | null>; hExps: string[][];
+  vk_alfa_1: string[]; vk_beta_1: string[]; vk_delta_1: string[]; vk_beta_2: string[][]; vk_delta_2: string[][];
+}
 export interface Bn128 {
   /** websnark-compatible: ArrayBuffers produced by binarifyWitness / binarifyProvingKey. */
   groth16GenProof(witnessBin: ArrayBuffer | Uint8Array, provingKeyBin: ArrayBuffer | Uint8Array, opts?: ProveOptions): Promise<Groth16Proof>;
@@ -30,6 +41,11 @@ export interface Bn128 {
    *  its proofs run four transforms instead of six from now on (the fused groups of proveBatch included).  contribute, saveKey / loadKeyFile and replicas carry no tables. */
   evalTables(r1csBin: Uint8Array): boolean;
   saveKey(path: string): void;
+  /** The held key as the provingKeyBin binarifyProvingKey writes (zkr_key_export_websnark), whatever it came from -- setupR1cs,
+   *  loadKeyFile, contribute(): what an unchanged groth16GenProof(witnessBin, provingKeyBin) takes. */
+  exportKey(opts?: KeyExportOptions): ArrayBuffer;
+  /** The same key as the snarkjs JSON: binarifyProvingKey(bn.exportKeyJson()) equals bn.exportKey(). */
+  exportKeyJson(): ProvingKeyJson;
   loadKeyFile(path: string): void;
   /** What the held key's arena contains (zkr_key_check): every index the kernels follow stays inside its section; with
    *  { deep: true } also the values (points on their curves at every window level, twiddles, coefficients, shared rank maps,
@@ -52,6 +68,10 @@ export function contributionCheck(record: Uint8Array): boolean;
 /** vkBin with vk_delta_2 replaced by the record's delta2_after; throws for a bad record or one that does not continue this key. */
 export function vkContribute(vkBin: Uint8Array, record: Uint8Array): Uint8Array;
 /** All proofs of a batch under one key with one merged pairing product (random linear combination). */
+/** exportKey for a key handle. */
+export function keyToWebsnark(key: KeyHandle, opts?: KeyExportOptions): ArrayBuffer;
+/** The JSON key from the standard-form export (zkr_key_export_websnark with ZKR_EXPORT_STANDARD), which exportKeyJson reads. */
+export function jsonKeyFromStandard(standardBytes: Uint8Array): ProvingKeyJson;
 export function isValidBatch(verifyingKey: any, proofs: Groth16Proof[], publicSignalsList: Array<Array<bigint | string>>): boolean;
 export function binarifyVerifyingKey(verifyingKey: any): Uint8Array;
 export function binarifyR1cs(circuitDef: any): Uint8Array;

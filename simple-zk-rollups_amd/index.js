@@ -27,6 +27,44 @@ function leBytesToDecimal(buf, off) {
   return v.toString();
 }
 
+// a key handle as websnark bytes (zkr_key_export_websnark); opts: { piecePoints, standard: field elements in standard form, the
+// layout jsonKeyFromStandard reads -- NOT websnark bytes }
+function keyToWebsnark(key, opts) {
+  return native().keyExport(key, opts && opts.standard ? 1 : 0, (opts && opts.piecePoints) || 0);
+}
+// the snarkjs 0.1.20 proving-key JSON (what binarify.ts:129-138,152-202 reads) from the standard-form export: decimal strings,
+// points [x, y, "1"] (infinity ["0", "1", "0"]), C null for the public signals, one {constraint: coefficient} object per signal
+// (terms a key stores twice for one constraint are added: an object holds one coefficient per constraint)
+function jsonKeyFromStandard(buf) {
+  const dv = new DataView(buf.buffer, buf.byteOffset, buf.byteLength);
+  const u32 = (o) => dv.getUint32(o, true);
+  const n = u32(0), p = u32(4), m = u32(8), ptr = [];
+  for (let i = 0; i < 7; i++) ptr.push(u32(12 + 4 * i));
+  const num = (o) => leBytesToDecimal(buf, o);
+  const g1 = (o) => { const x = num(o); return [x, num(o + 32), x === "0" ? "0" : "1"]; };
+  const g2 = (o) => { const x = [num(o), num(o + 32)]; return [x, [num(o + 64), num(o + 96)], x[0] === "0" && x[1] === "0" ? ["0", "0"] : ["1", "0"]]; };
+  const list = (o, count, size, f) => Array.from({ length: count }, (_, i) => f(o + size * i));
+  const pols = (o) => {
+    const out = [];
+    for (let s = 0; s < n; s++) {
+      const k = u32(o), d = {};
+      o += 4;
+      for (let e = 0; e < k; e++, o += 36) {
+        const c = u32(o), v = num(o + 4);
+        d[c] = c in d ? ((BigInt(d[c]) + BigInt(v)) % R).toString() : v;
+      }
+      out.push(d);
+    }
+    return out;
+  };
+  return {
+    protocol: "groth", nVars: n, nPublic: p, domainBits: 31 - Math.clz32(m), domainSize: m, polsA: pols(ptr[0]), polsB: pols(ptr[1]),
+    A: list(ptr[2], n, 64, g1), B1: list(ptr[3], n, 64, g1), B2: list(ptr[4], n, 128, g2),
+    C: new Array(p + 1).fill(null).concat(list(ptr[5], n - p - 1, 64, g1)), hExps: list(ptr[6], m, 64, g1),
+    vk_alfa_1: g1(40), vk_beta_1: g1(104), vk_delta_1: g1(168), vk_beta_2: g2(232), vk_delta_2: g2(360),
+  };
+}
+
 function proofFromBytes(pb) {
   const s = [];
   for (let i = 0; i < 8; i++) s.push(leBytesToDecimal(pb, 32 * i));
@@ -285,6 +323,12 @@ class Bn128 {
     this._key = key; this._fp = "contributed"; this._replicas = null;
     return { record: new Uint8Array(record) };
   }
+  // The held key as the provingKeyBin the reference's own prover takes (zkr_key_export_websnark): an ArrayBuffer, byte for byte what
+  // binarifyProvingKey writes for the snarkjs JSON of this key -- after setupR1cs, loadKeyFile or contribute() alike, which is how the
+  // key of a ceremony reaches an unchanged groth16GenProof(witnessBin, provingKeyBin).  opts.piecePoints: output points per table
+  // handled at a time (default 2^20).  exportKeyJson(): the same key as that JSON (`*_pk.json`; JSON.stringify writes the file).
+  exportKey(opts) { if (!this._key) throw new Error("no key loaded"); return keyToWebsnark(this._key, opts); }
+  exportKeyJson() { if (!this._key) throw new Error("no key loaded"); return jsonKeyFromStandard(new Uint8Array(keyToWebsnark(this._key, { standard: true }))); }
   // The evaluation-form side tables for the held key, whatever it came from, derived from its own points and the circuit's C side
   // (zkr_key_eval_tables; r1csBin: binarifyR1cs(circuitDef) or RollupCircuit.r1cs()).  true: its proofs run four transforms instead
   // of six from now on, the fused groups of proveBatch included; false: it keeps the coefficient form.  contribute, saveKey / loadKeyFile and replicas carry no tables: call again.
@@ -660,7 +704,7 @@ class Operator {
 module.exports = {
   Ledger, Operator, txRow,
   buildBn128, genProof, binarifyWitness, binarifyProvingKey, solidityProof, proofFromBytes, isValid, isValidBatch, binarifyVerifyingKey,
-  contributionCheck, vkContribute,
+  contributionCheck, vkContribute, keyToWebsnark, jsonKeyFromStandard,
   binarifyR1cs, verifyingKeyFromBytes, solidityVerifyingKey, solidityVerifyingKeySource,
   // which form the last sharded proof took and why ({form: "split" | "replicated" | "none", reason, hForm: "evaluation" | "coefficients" |
   // "none", hReason}); how a key handle came to its device

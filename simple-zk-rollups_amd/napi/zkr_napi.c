@@ -61,6 +61,7 @@ static struct {
   int (*key_shard_opts)(const zkr_key *, unsigned, unsigned, int, unsigned, zkr_key **);
   int (*sharded_last_h_form)(int *, char *, size_t);
   int (*key_h_form)(const zkr_key *, int *, uint64_t *);
+  int (*key_export)(const zkr_key *, const uint32_t *, void **, size_t *); /* optional; opts: zkr_key_export_opts = two u32 (flags, piece_points) */
   /* optional as a group (ledger_ok below): the ledger and the operator step, host buffers only */
   int (*ledger_new)(unsigned, int, zkr_ledger **);
   void (*ledger_free)(zkr_ledger *);
@@ -137,6 +138,7 @@ static napi_value js_load(napi_env env, napi_callback_info info) {
     *(void **)(&Z.key_shard_opts) = dlsym(h, "zkr_key_shard_opts");
     *(void **)(&Z.sharded_last_h_form) = dlsym(h, "zkr_prove_sharded_last_h_form");
     *(void **)(&Z.key_h_form) = dlsym(h, "zkr_key_h_form");
+    *(void **)(&Z.key_export) = dlsym(h, "zkr_key_export_websnark");
     Z.ledger_ok = 1;
 #define OPT(field, name)                 \
   *(void **)(&Z.field) = dlsym(h, name); \
@@ -314,6 +316,31 @@ static napi_value js_key_contribute(napi_env env, napi_callback_info info) {
   NAPI_OK(napi_set_element(env, arr, 0, ext));
   NAPI_OK(napi_set_element(env, arr, 1, recb));
   return arr;
+}
+/* keyExport(key, flags, piecePoints) -> ArrayBuffer: the key as binarifyProvingKey's bytes (zkr_key_export_websnark; flags 1 =
+ * ZKR_EXPORT_STANDARD: field elements in standard form, the raw material of the JSON key).  Synchronous, once per ceremony. */
+static napi_value js_key_export(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (!Z.handle) return throw_msg(env, "libzkr_hip.so not loaded");
+  if (!Z.key_export) return throw_msg(env, "libzkr_hip.so lacks symbol zkr_key_export_websnark");
+  zkr_key *key = NULL;
+  uint32_t opts[2] = {0, 0};
+  if (argc < 1 || napi_get_value_external(env, argv[0], (void **)&key) != napi_ok) return throw_msg(env, "keyExport(key, flags, piecePoints)");
+  if (argc > 1) napi_get_value_uint32(env, argv[1], &opts[0]);
+  if (argc > 2) napi_get_value_uint32(env, argv[2], &opts[1]);
+  void *pk = NULL, *data = NULL;
+  size_t len = 0;
+  if (Z.key_export(key, opts, &pk, &len)) return throw_msg(env, Z.last_error());
+  napi_value ab;
+  if (napi_create_arraybuffer(env, len, &data, &ab) != napi_ok) {
+    Z.free_(pk);
+    return throw_msg(env, "zkr_napi: no ArrayBuffer of the key's length");
+  }
+  memcpy(data, pk, len);
+  Z.free_(pk);
+  return ab;
 }
 static napi_value js_contribution_check(napi_env env, napi_callback_info info) {
   size_t argc = 1;
@@ -1290,6 +1317,7 @@ static napi_value init(napi_env env, napi_value exports) {
       {"shardedLastForm", NULL, js_sharded_last_form, NULL, NULL, NULL, napi_default, NULL},
       {"keyReplication", NULL, js_key_replication, NULL, NULL, NULL, napi_default, NULL},
       {"keyContribute", NULL, js_key_contribute, NULL, NULL, NULL, napi_default, NULL},
+      {"keyExport", NULL, js_key_export, NULL, NULL, NULL, napi_default, NULL},
       {"contributionCheck", NULL, js_contribution_check, NULL, NULL, NULL, napi_default, NULL},
       {"vkContribute", NULL, js_vk_contribute, NULL, NULL, NULL, napi_default, NULL},
       {"keyEvalTables", NULL, js_key_eval_tables, NULL, NULL, NULL, napi_default, NULL},

@@ -7,6 +7,7 @@ LIB_PATH = os.environ.get("ZKR_HIP_LIB") or os.path.normpath(os.path.join(_HERE,
 PROOF_BYTES = 256
 PARTIAL_BYTES = 640   # zkr.h ZKR_PARTIAL_BYTES
 SHARD_SIDE_TABLES = 1  # ZKR_SHARD_SIDE_TABLES
+EXPORT_STANDARD = 1  # ZKR_EXPORT_STANDARD
 CONTRIBUTION_BYTES = 352   # zkr.h ZKR_CONTRIBUTION_BYTES
 PTAU_RECORD_BYTES = 928   # zkr.h ZKR_PTAU_RECORD_BYTES
 REPLICATE_MODES = {"auto": 0, "full": 1, "base": 2}   # zkr.h ZKR_REPLICATE_*
@@ -22,6 +23,10 @@ class BookOpts(ctypes.Structure):   # zkr.h zkr_book_opts
 
 class OperatorOpts(ctypes.Structure):   # zkr.h zkr_operator_opts
     _fields_ = [("batch", ctypes.c_uint32), ("max_batches", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class KeyExportOpts(ctypes.Structure):   # zkr.h zkr_key_export_opts
+    _fields_ = [("flags", ctypes.c_uint32), ("piece_points", ctypes.c_uint32)]
 
 
 class NttSelftestDesc(ctypes.Structure):   # zkr.h zkr_ntt_selftest_desc
@@ -132,6 +137,10 @@ def lib():
     L.zkr_key_eval_tables_equal.argtypes = [vp, vp, c.POINTER(i)]
     L.zkr_points_add_each.argtypes = [u8p, u8p, sz, i, i]
     L.zkr_setup_r1cs_websnark.argtypes = [u8p, sz, u8p, i, c.POINTER(vp), c.POINTER(sz), c.POINTER(vp), c.POINTER(sz)]
+    L.zkr_key_export_websnark.argtypes = [vp, c.POINTER(KeyExportOpts), c.POINTER(vp), c.POINTER(sz)]
+    L.zkr_key_export_last_times.argtypes = [c.POINTER(c.c_double)]
+    L.zkr_websnark_len.argtypes = [c.c_uint64] * 5 + [c.POINTER(c.c_uint64)]
+    L.zkr_websnark_render_host.argtypes = [c.c_uint32, c.c_uint32, c.c_uint32, u8p, vp, vp, u8p, vp, vp, u8p, c.POINTER(c.c_char_p), c.POINTER(vp), c.POINTER(sz)]
     L.zkr_synth_vk.argtypes = [vp, u8p, sz, c.POINTER(vp), c.POINTER(sz)]
     L.zkr_synth_set_shape.argtypes = [c.c_uint]
     L.zkr_free.argtypes = [vp]
@@ -238,6 +247,68 @@ def device_pci_bus_id(device=0) -> str:
 
 def version():
     return lib().zkr_version().decode()
+
+
+def websnark_len(n_vars, n_public, domain, nnz_a, nnz_b) -> int:
+    """Length of a websnark proving key with these sizes (zkr_websnark_len, host only); ZkrError -5 past the format's 2^32 - 1."""
+    out = ctypes.c_uint64()
+    _check(lib().zkr_websnark_len(n_vars, n_public, domain, nnz_a, nnz_b, ctypes.byref(out)))
+    return int(out.value)
+
+
+def websnark_render_host(n_vars, n_public, domain, consts448, side_a, side_b, points) -> bytes:
+    """The websnark bytes from their parts (zkr_websnark_render_host, host only).  side_a / side_b: (rowptr, col, coefs) of a QAP
+    side in CSR by row -- two lists of ints and the coefficients as 32-byte strings end to end; points: the five sections A, B1,
+    B2, C, hExps as bytes."""
+    import struct
+    def side(sd):
+        rowptr, col, coef = sd
+        return struct.pack("<%dI" % len(rowptr), *rowptr), struct.pack("<%dI" % len(col), *col), bytes(coef)
+    ra, ca, fa = side(side_a)
+    rb, cb, fb = side(side_b)
+    pts = (ctypes.c_char_p * 5)(*[bytes(x) for x in points])
+    out, n = ctypes.c_void_p(), ctypes.c_size_t()
+    _check(lib().zkr_websnark_render_host(n_vars, n_public, domain, bytes(consts448), ra, ca, fa, rb, cb, fb, pts, ctypes.byref(out), ctypes.byref(n)))
+    return _take(out, n.value)
+
+
+def json_key_from_standard(buf: bytes) -> dict:
+    """The snarkjs JSON proving key from the standard-form export (ProvingKey.to_standard)."""
+    import struct
+    R = 21888242871839275222246405745257275088548364400416034343698204186575808495617
+    n, p, m = struct.unpack_from("<3I", buf, 0)
+    ptr = struct.unpack_from("<7I", buf, 12)
+    num = lambda o: str(int.from_bytes(buf[o:o + 32], "little"))
+
+    def g1(o):
+        x, y = num(o), num(o + 32)
+        return [x, y, "0" if x == "0" else "1"]
+
+    def g2(o):
+        x, y = [num(o), num(o + 32)], [num(o + 64), num(o + 96)]
+        return [x, y, ["0", "0"] if x == ["0", "0"] else ["1", "0"]]
+
+    def pols(o):
+        out = []
+        for _ in range(n):
+            (k,) = struct.unpack_from("<I", buf, o)
+            o += 4
+            d = {}
+            for _ in range(k):
+                (c,) = struct.unpack_from("<I", buf, o)
+                v = int.from_bytes(buf[o + 4:o + 36], "little")
+                d[c] = (d[c] + v) % R if c in d else v
+                o += 36
+            out.append({str(c): str(v) for c, v in d.items()})
+        return out
+
+    return {"protocol": "groth", "nVars": n, "nPublic": p, "domainBits": m.bit_length() - 1, "domainSize": m,
+            "polsA": pols(ptr[0]), "polsB": pols(ptr[1]),
+            "A": [g1(ptr[2] + 64 * i) for i in range(n)], "B1": [g1(ptr[3] + 64 * i) for i in range(n)],
+            "B2": [g2(ptr[4] + 128 * i) for i in range(n)],
+            "C": [None] * (p + 1) + [g1(ptr[5] + 64 * i) for i in range(n - p - 1)],
+            "hExps": [g1(ptr[6] + 64 * i) for i in range(m)],
+            "vk_alfa_1": g1(40), "vk_beta_1": g1(104), "vk_delta_1": g1(168), "vk_beta_2": g2(232), "vk_delta_2": g2(360)}
 
 
 def _take(ptr, n):
@@ -462,6 +533,36 @@ class ProvingKey:
         p, n = ctypes.c_void_p(), ctypes.c_size_t()
         _check(lib().zkr_key_base_arena(self._h, ctypes.byref(p), ctypes.byref(n)))
         return p.value, n.value
+
+    def _export(self, flags, piece_points):
+        opts = KeyExportOpts(flags, int(piece_points or 0))
+        out, n = ctypes.c_void_p(), ctypes.c_size_t()
+        _check(lib().zkr_key_export_websnark(self._h, ctypes.byref(opts), ctypes.byref(out), ctypes.byref(n)))
+        return _take(out, n.value)
+
+    def to_websnark(self, piece_points=None) -> bytes:
+        """This key as the provingKeyBin `binarifyProvingKey` writes (zkr_key_export_websnark): what load_websnark reads, what the
+        reference's groth16GenProof and the checkers take.  Any whole key: loaded, adopted, replicated, set up from scalars or
+        from a transcript, contributed.  piece_points: output points per table handled at a time (default 2^20)."""
+        return self._export(0, piece_points)
+
+    def to_standard(self, piece_points=None) -> bytes:
+        """The same layout with every field element in standard form (ZKR_EXPORT_STANDARD): what to_json_key() reads."""
+        return self._export(EXPORT_STANDARD, piece_points)
+
+    @staticmethod
+    def export_times():
+        """The calling thread's last export (zkr_key_export_last_times): milliseconds by part and the extra device bytes held."""
+        out = (ctypes.c_double * 5)()
+        _check(lib().zkr_key_export_last_times(out))
+        return {"kernels_ms": out[0], "copies_ms": out[1], "host_ms": out[2], "total_ms": out[3], "device_bytes": int(out[4])}
+
+    def to_json_key(self) -> dict:
+        """This key in the snarkjs 0.1.20 JSON shape binarify.ts:129-138,152-202 reads (the reference's `*_pk.json`): decimal
+        strings, points as [x, y, "1"] (infinity ["0", "1", "0"]), C None for the public signals, polsA / polsB one
+        {constraint: coefficient} object per signal.  An object holds one coefficient per constraint: terms a key stores twice
+        for one (signal, constraint) are added."""
+        return json_key_from_standard(self.to_standard())
 
     def prove(self, witness: bytes, r=None, s=None, stream=None) -> bytes:
         out = ctypes.create_string_buffer(PROOF_BYTES)
