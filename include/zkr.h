@@ -494,7 +494,7 @@ int zkr_r1cs_check(zkr_r1cs *cs, const void *const *witnesses_std, size_t witnes
  * on a random v with probability 1/r; term order inside a row does not matter.
  * WHAT THIS BINDS: the A and B sides only.  A key has no C side to compare -- C reaches a key only through the C-query points of
  * its setup -- so a system that differs from the key's in C alone is reported as the same.  The call catches the wrong or stale
- * circuit file; it is no statement about the key's C query.
+ * circuit file; it is no statement about the key's C query (zkr_key_audit makes that one, against the transcript the key came from).
  * A shard key is accepted (it holds the whole QAP).  Key and system on different devices: ZKR_ERR_ARG.  A mismatch is ZKR_OK with
  * *same = 0 and a zkr_last_error line naming the geometry, or the side and the first differing row. */
 int zkr_r1cs_matches_key(zkr_r1cs *cs, const zkr_key *key, int *same);
@@ -609,6 +609,56 @@ int zkr_setup_r1cs_ptau(const void *r1cs_bin, size_t r1cs_len, const void *ptau,
  * includes the factor 1 / n, so the inverse transform of tau^i G is the Lagrange-basis points L_j(tau) G of the domain. */
 int zkr_points_scale_each(void *points_mont, const void *scalars_std, size_t n, int g2, int device);
 int zkr_group_ntt(void *points_mont, unsigned logn, int inverse, int g2, int device);
+
+/* ---- anybody: audit the finished key against circuit, transcript and records alone (snarkjs users: `zkey verify`) ----------
+ * Host only.  For delta records what zkr_ptau_record_check is for phase-1 records: records = n_records x ZKR_CONTRIBUTION_BYTES
+ * in the order the contributions were made; *valid = 1 iff every record passes zkr_contribution_check, record 0's delta1_before
+ * is the G1 generator (a key from a transcript starts at delta = 1) and record j + 1's delta1_before is record j's delta1_after.
+ * zkr_last_error names the record and the check.  n_records == 0 is valid.  An error status only for a null pointer. */
+int zkr_contribution_chain_check(const uint8_t *records, size_t n_records, int *valid);
+/* What a depositor, an exchange or whoever deploys the verifier runs.  It holds the public artefacts only -- the circuit (cs), the
+ * phase-1 transcript with its records, the delta records, the proving key and vk_bin -- no intermediate key, and it repeats
+ * nothing of the setup's derivation: the setup goes through NTTs over points, the audit through random combinations on the scalar
+ * side.  Notation: n, p, m the key's nVars, nPublic and domain; polsA / polsB the key's QAP sides with the p + 1
+ * rows the setup appends to A, polsC the system's third side (zero on those rows); for a vector v over the signals
+ * x(v) = iNTT_m(j -> sum_s polsX[s][j] v_s), so that sum_s v_s X_s(tau) = sum_i x(v)_i tau^i; T(v) = sum_i a(v)_i betaTauG1[i] +
+ * b(v)_i alfaTauG1[i] + c(v)_i tauG1[i].  rho_s (s < n), sigma_i (i < m): 128 bits each from the OS CSPRNG; rho_pub / rho_priv:
+ * rho on the signals 0..p / above p, zero elsewhere.  A wrong entry slips through with probability 2^-128.  Every sum runs on the
+ * device through the MSM path the prover uses; the pairings on the host.
+ * Steps, in order; the first failure ends the call:
+ *   1. the transcript passes zkr_ptau_verify's steps 2-6 with ptau_records;
+ *   2. m <= 2^K, and zkr_r1cs_matches_key(cs, key);
+ *   3. zkr_contribution_chain_check(delta_records), and the key's delta1 / delta2 are the last record's delta1_after /
+ *      delta2_after -- with no records, the generators;
+ *   4. the key's alfa1 == alfaTauG1[0], beta1 == betaTauG1[0], beta2 == betaG2; vk_alfa_1 and vk_beta_2 are the same transcript
+ *      entries; vk_gamma_2 == G2; vk_delta_2 == the key's delta2;
+ *   5. the key's two twiddle sections are the tables of its domain, and the window levels of all five tables are the multiples
+ *      of their own base points: each rebuilt and compared byte for byte, one table at a time (as step 4 of
+ *      zkr_key_contribution_verify does for C and H).  The sums below read those levels.  The twiddles are bytes of the key
+ *      file, which a load does not check (zkr_key_check level 1 does): the audit's own transforms use tables built for the call;
+ *   6. E1 sum_s rho_s A[s] == sum_i a(rho)_i tauG1[i];  E2 sum_s rho_s B1[s] == sum_i b(rho)_i tauG1[i];
+ *      E3 sum_s rho_s B2[s] == sum_i b(rho)_i tauG2[i];
+ *   7. E4 sum_{s<=p} rho_s IC[s] == T(rho_pub): the verifying key's IC points, which go on chain (gamma = 1);
+ *   8. E5 e(sum_{s>p} rho_s C[s], delta2) == e(T(rho_priv), G2) and E6 e(sum_i sigma_i hExps[i], delta2) ==
+ *      e(sum_i sigma_i (tauG1[i+m] - tauG1[i]), G2), in one pairing product.  A table entry the key dropped because it is the
+ *      point at infinity adds nothing on the left; the right side must then agree by itself.  This is the statement about the
+ *      key's C query that zkr_r1cs_matches_key cannot make.
+ * report (may be null): [0] the first failed step (0: none); [1] a detail -- the record's index for step 3; for steps 5 and 6 the
+ * first table that differs (0 A, 1 B1, 2 B2, 3 C, 4 hExps; 5 at step 5: the twiddles); else 0; [2] the number of phase-1 records;
+ * [3] the number of delta records.
+ * A KEY WITH report[3] == 0 IS CONSISTENT AND NOT SOUND: delta = 1 is public, and whoever knows delta forges proofs.  A key is
+ * sound if one phase-1 contributor and one delta contributor forgot their secrets; the audit says that the records are about this
+ * key, not who the contributors were.
+ * The key's evaluation-form side tables (zkr_key_eval_tables) are not part of the audit: whoever proves derives them locally from
+ * the points audited here.
+ * A key that fails is ZKR_OK with *valid = 0 and a zkr_last_error line that says "step N".  A status below zero only for bad
+ * arguments or a HIP failure: a null pointer, a shard, key and system on different devices are ZKR_ERR_ARG; so are -- before any
+ * device call -- a malformed transcript header or length, a vk_len that does not match its IC count, and an IC count other than
+ * p + 1.  The key is only read: nothing is cached on it.  Working memory above the key: the transcript's body; 18 m + 3 n scalars;
+ * one table at a time -- in step 5 a copy of the key's largest table, in the sums one vector's window levels with one MSM
+ * workspace. */
+int zkr_key_audit(const zkr_key *key, zkr_r1cs *cs, const void *ptau, size_t ptau_len, const uint8_t *ptau_records, size_t n_ptau_records,
+                  const uint8_t *delta_records, size_t n_delta_records, const void *vk_bin, size_t vk_len, int *valid, uint64_t report[4]);
 
 /* Circuit shape drawn by the zkr_synth_* calls of the CALLING THREAD (thread-local, default 0): 0 = rollup-shaped (default; 1-3 terms
  * per row, 3 % boolean and 2 % small signals, a third of the signals absent from B), 1 = dense random (BASELINE.json

@@ -313,4 +313,43 @@ int digit_lists_alloc(DigitLists &dl, size_t n_scalars, const MsmPlan &pl);
 int msm_scratch_alloc(MsmScratch &m, size_t n_scalars, size_t n_points, const MsmPlan &pl, bool g2);  // for one proof of one table
 int msm_precompute(int device, bool g2, void *d_table, uint32_t n, const MsmPlan &pl);  // fills levels 1..K-1 of a table whose level 0 is in place, then converts the table to the hot path's radix
 int radix_convert(int device, bool g2, void *d_points, size_t count, bool to261);
+
+// ---- what the audit of a finished key (zkr_key_audit.hip) takes from the other units
+// zkr_ptau.hip: a verified transcript left on the device -- the body as Montgomery affine points, as ptau_upload leaves it -- with
+// the byte offsets of its vectors in the host transcript
+struct PtauOnDevice {
+  unsigned power = 0;
+  size_t M = 0;
+  size_t off_tau1 = 0, off_tau2 = 0, off_alfa1 = 0, off_beta1 = 0, off_beta2 = 0;
+  DevBuf body;
+  const G1Affine *tau1 = nullptr, *alfa1 = nullptr, *beta1 = nullptr;  // 2 M, M, M points
+  const G2Affine *tau2 = nullptr, *beta2 = nullptr;                    // M points, 1 point
+};
+const char *ptau_shape_fault(const void *ptau, size_t len, unsigned *power);  // null when header and length agree (step 1 of zkr_ptau_verify); host only
+// zkr_ptau_verify itself; keep != null: the device form stays with the caller when the transcript verifies
+int ptau_verify_keep(const void *ptau, size_t len, const uint8_t *records, size_t n_records, int device, int *valid, uint64_t rep[2], PtauOnDevice *keep);
+// zkr_prove.hip: key_table_msm for the G2 table
+int key_table_msm_g2(const zkr_key *k, const Fr *d_scalars, XYZZ<Fq2> *out);
+// zkr_prove.hip: *same = the key's two twiddle sections are, byte for byte, the tables ntt_twiddles_fill makes for its domain (they
+// are bytes of the key file otherwise: level 0 of zkr_key_check, which a load runs, does not look at them)
+int key_twiddles_fresh_equal(const zkr_key *k, bool *same);
+// zkr_prove.hip: nvec vectors of 2^logm words end to end, values on the domain -> coefficients: the prover's inverse transform
+// with twiddle tables built FOR THIS CALL (nothing a key supplies), then natural order and the factor 1 / m; in: canonical,
+// overwritten; out: nvec x m words; null stream, synchronised on return
+int fresh_scalar_intt(int device, unsigned logm, Fr *d_in, Fr *d_out, int nvec);
+// zkr_prove.hip: out[j] = sum_i scalars[j][i] pts[i], j < n_sums, over ONE vector of n finite points in device memory (Montgomery
+// affine, left as it is): its window levels are built once, into a table that goes with the call, and every sum runs msm_enqueue
+// over it with the identity rank map.  scalars: n words each, standard form below r.  out: n_sums XYZZ points of the group
+int device_points_msm(int device, bool g2, const void *d_points, uint32_t n, const Fr *const *d_scalars, int n_sums, void *out_xyzz);
+// zkr_r1cs.hip: the system as its kernels read it -- shape, the three CSR sides (0 A, 1 B, 2 C) on its device: row pointers
+// (nC + 1), signals, Montgomery coefficients -- and the list of constraints with a side of more than wide_terms terms
+struct R1csView {
+  int device;
+  uint32_t n, p, nC, m;
+  const uint32_t *row_ptr[3], *col[3];
+  const Fr *coef[3];
+  const uint32_t *wide;
+  uint32_t n_wide, wide_terms;
+};
+void r1cs_view(const zkr_r1cs *cs, R1csView *v);
 }  // namespace zkr

@@ -1607,21 +1607,79 @@ static int msm_hook(const void *points_mont, const void *scalars_std, size_t n, 
 }
 
 namespace zkr {
-int key_table_msm(const zkr_key *k, int t, const Fr *d_scalars, G1XYZZ *out) {
-  if (t == T_B2) { set_error("key_table_msm: G1 tables only"); return ZKR_ERR_ARG; }
+// one table of the key, either group: *out = the XYZZ sum as the chain's pinned result holds it
+template <class F>
+static int key_table_msm_any(const zkr_key *k, int t, const Fr *d_scalars, XYZZ<F> *out) {
+  constexpr bool g2 = sizeof(F) != 32;
   ZKR_HIP_CHECK(hipSetDevice(k->device));
   const ArenaHeader &h = k->h;
-  *out = G1XYZZ::inf();
+  *out = XYZZ<F>::inf();
   if (!h.npts[t]) return 0;
   MsmScratch ms;
-  int rc = msm_scratch_alloc(ms, rank_entries(h, t), h.npts[t], k->plan[t], false);
+  int rc = msm_scratch_alloc(ms, rank_entries(h, t), h.npts[t], k->plan[t], g2);
   if (rc) return rc;
-  rc = msm_enqueue(NO_PROF, nullptr, false, k->arena + h.off_pts[t], (const uint32_t *)(k->arena + h.off_rank[t]), d_scalars,
+  rc = msm_enqueue(NO_PROF, nullptr, g2, k->arena + h.off_pts[t], (const uint32_t *)(k->arena + h.off_rank[t]), d_scalars,
                    rank_entries(h, t), h.npts[t], k->plan[t], ms);
   hipError_t e = hipDeviceSynchronize();  // also after a failed enqueue: the workspace goes with this scope
   if (!rc && e != hipSuccess) { set_error("msm over a key table failed: %s", hipGetErrorString(e)); rc = ZKR_ERR_HIP; }
   if (rc) return rc;
-  *out = *(const G1XYZZ *)ms.chain.h_result;
+  *out = *(const XYZZ<F> *)ms.chain.h_result;
+  return 0;
+}
+int key_table_msm(const zkr_key *k, int t, const Fr *d_scalars, G1XYZZ *out) {
+  if (t == T_B2) { set_error("key_table_msm: G1 tables only"); return ZKR_ERR_ARG; }
+  return key_table_msm_any<Fq>(k, t, d_scalars, out);
+}
+int key_table_msm_g2(const zkr_key *k, const Fr *d_scalars, G2XYZZ *out) { return key_table_msm_any<Fq2>(k, T_B2, d_scalars, out); }
+
+// The audit's transforms run with tables built for the call, never with the key's: the twiddle sections of an arena are bytes of
+// whatever file the key was loaded from.
+int key_twiddles_fresh_equal(const zkr_key *k, bool *same) {
+  ZKR_HIP_CHECK(hipSetDevice(k->device));
+  const ArenaHeader &h = k->h;
+  *same = false;
+  if (h.tlog != h.logm) return 0;
+  DevBuf tw, twl;
+  int rc;
+  if ((rc = tw.alloc((size_t)32 << h.logm)) || (rc = twl.alloc((size_t)32 << TWL_LOG))) return rc;
+  ntt_twiddles_fill(tw.as<Fr>(), h.logm, twl.as<Fr>(), nullptr);  // as key_build and arena_from_base fill them
+  ZKR_HIP_CHECK(hipGetLastError());
+  ZKR_HIP_CHECK(hipDeviceSynchronize());
+  bool a = false, b = false;
+  if ((rc = device_bytes_equal(k->device, k->arena + h.off_tw, tw.p, (size_t)32 << h.logm, &a)) || (rc = device_bytes_equal(k->device, k->arena + h.off_twl, twl.p, (size_t)32 << TWL_LOG, &b))) return rc;
+  *same = a && b;
+  return 0;
+}
+int fresh_scalar_intt(int device, unsigned logm, Fr *d_in, Fr *d_out, int nvec) {
+  ZKR_HIP_CHECK(hipSetDevice(device));
+  const size_t m = (size_t)1 << logm;
+  HookNttTables tables;
+  if (int rc = tables.build(logm)) return rc;
+  if (int rc = run_ntt(nullptr, tables.view(), NttRun{.L = (int)logm, .dir = DIF_INVERSE, .nbat = nvec, .a = ntt_in_place(d_in)}, NO_PROF)) return rc;  // natural -> bit-reversed, unscaled
+  for (int j = 0; j < nvec; j++) bitrev_copy_kernel<<<(unsigned)((m + 255) / 256), 256>>>(d_in + (size_t)j * m, d_out + (size_t)j * m, (int)logm);
+  scale_kernel<<<(unsigned)((m * (size_t)nvec + 255) / 256), 256>>>(d_out, m * (size_t)nvec, inv(to_mont(fr_from_u64(m))));
+  ZKR_HIP_CHECK(hipGetLastError());
+  ZKR_HIP_CHECK(hipDeviceSynchronize());  // the tables go with this scope
+  return 0;
+}
+
+int device_points_msm(int device, bool g2, const void *d_points, uint32_t n, const Fr *const *d_scalars, int n_sums, void *out_xyzz) {
+  ZKR_HIP_CHECK(hipSetDevice(device));
+  const size_t pb = g2 ? sizeof(G2Affine) : sizeof(G1Affine), ob = g2 ? sizeof(G2XYZZ) : sizeof(G1XYZZ);
+  const MsmPlan pl = msm_plan(n, n);
+  MsmScratch ms;
+  DevBuf tbl;
+  int rc;
+  if ((rc = msm_scratch_alloc(ms, n, n, pl, g2)) || (rc = tbl.alloc((size_t)n * pb * pl.K))) return rc;
+  ZKR_HIP_CHECK(hipMemcpy(tbl.p, d_points, (size_t)n * pb, hipMemcpyDeviceToDevice));
+  if ((rc = msm_precompute(device, g2, tbl.p, n, pl))) return rc;
+  for (int j = 0; j < n_sums; j++) {
+    rc = msm_enqueue(NO_PROF, nullptr, g2, tbl.p, nullptr, d_scalars[j], n, n, pl, ms);
+    hipError_t e = hipDeviceSynchronize();  // also after a failed enqueue: table and workspace go with this scope
+    if (!rc && e != hipSuccess) { set_error("msm over a vector of points failed: %s", hipGetErrorString(e)); rc = ZKR_ERR_HIP; }
+    if (rc) return rc;
+    memcpy((uint8_t *)out_xyzz + (size_t)j * ob, ms.chain.h_result, ob);
+  }
   return 0;
 }
 }  // namespace zkr

@@ -653,6 +653,65 @@ int g1_combine_columns(uint32_t n, const QapColumns &cols, const G1Affine *pts, 
   return rc;
 }
 
+const char *ptau_shape_fault(const void *ptau, size_t len, unsigned *power) {
+  PtauLayout l;
+  const char *f = ptau_header_fault(ptau, len, l);
+  if (!f && power) *power = l.power;
+  return f;
+}
+
+// zkr_ptau_verify (include/zkr.h has the steps); keep: where the device form of a transcript that verified goes
+int ptau_verify_keep(const void *ptau, size_t len, const uint8_t *records, size_t n_records, int device, int *valid, uint64_t report[2], PtauOnDevice *keep) {
+  if (!ptau || !valid || (n_records && !records)) { set_error("null argument"); return ZKR_ERR_ARG; }
+  *valid = 0;
+  uint64_t rep_local[2];
+  uint64_t *rep = report ? report : rep_local;
+  rep[0] = rep[1] = 0;
+  PtauLayout l;
+  if (const char *f = ptau_header_fault(ptau, len, l)) { rep[0] = 1; set_error("ptau verify: step 1 failed: %s", f); return ZKR_ERR_ARG; }
+  if (int rc = need_device(device)) return rc;
+  ZKR_HIP_CHECK(hipSetDevice(device));
+  DevicePtau d;
+  PtauVerdict v;
+  if (int rc = ptau_check(ptau, l, device, d, v)) return rc;
+  if (v.step) {
+    rep[0] = v.step; rep[1] = v.vector;
+    set_error("ptau verify: %s", v.why);
+    return 0;
+  }
+  // 6. the records verify, chain from the generators, and end at THIS transcript
+  auto fail6 = [&](uint64_t vector, const char *what) {
+    rep[0] = 6; rep[1] = vector;
+    set_error("ptau verify: step 6 failed: %s", what);
+    return 0;
+  };
+  char why[256];
+  if (!ptau_records_valid(records, n_records, why, sizeof(why))) return fail6(0, why);
+  const uint8_t *b = (const uint8_t *)ptau;
+  uint8_t g1[64], g2[128];
+  store_g1_std(g1, g1_generator());
+  store_g2_std(g2, g2_generator());
+  const uint8_t *last = n_records ? records + (n_records - 1) * ZKR_PTAU_RECORD_BYTES : nullptr;
+  const struct { int vec; size_t at; const uint8_t *want; size_t bytes; } ends[5] = {
+      {V_TAU1, l.off[V_TAU1] + 64, last ? last + PREC_AFTER[0] : g1, 64},   {V_ALFA1, l.off[V_ALFA1], last ? last + PREC_AFTER[1] : g1, 64},
+      {V_BETA1, l.off[V_BETA1], last ? last + PREC_AFTER[2] : g1, 64},      {V_TAU2, l.off[V_TAU2] + 128, last ? last + PREC_G2[0] : g2, 128},
+      {V_BETA2, l.off[V_BETA2], last ? last + PREC_G2[2] : g2, 128}};
+  for (const auto &e : ends)
+    if (memcmp(b + e.at, e.want, e.bytes) != 0) {
+      snprintf(why, sizeof(why), last ? "the last record does not end at this transcript's %s" : "no records, but %s is not the all-generators transcript's", VECTOR_NAME[e.vec]);
+      return fail6((uint64_t)e.vec, why);
+    }
+  *valid = 1;
+  if (keep) {
+    keep->power = l.power; keep->M = l.M;
+    keep->off_tau1 = l.off[V_TAU1]; keep->off_tau2 = l.off[V_TAU2]; keep->off_alfa1 = l.off[V_ALFA1]; keep->off_beta1 = l.off[V_BETA1]; keep->off_beta2 = l.off[V_BETA2];
+    keep->tau1 = d.vec<G1Affine>(V_TAU1); keep->alfa1 = d.vec<G1Affine>(V_ALFA1); keep->beta1 = d.vec<G1Affine>(V_BETA1);
+    keep->tau2 = d.vec<G2Affine>(V_TAU2); keep->beta2 = d.vec<G2Affine>(V_BETA2);
+    keep->body = std::move(d.body);
+  }
+  return 0;
+}
+
 }  // namespace zkr
 
 using namespace zkr;
@@ -706,47 +765,7 @@ int zkr_ptau_record_check(const uint8_t *records, size_t n_records, int *valid) 
 }
 
 int zkr_ptau_verify(const void *ptau, size_t len, const uint8_t *records, size_t n_records, int device, int *valid, uint64_t report[2]) {
-  if (!ptau || !valid || (n_records && !records)) { set_error("null argument"); return ZKR_ERR_ARG; }
-  *valid = 0;
-  uint64_t rep_local[2];
-  uint64_t *rep = report ? report : rep_local;
-  rep[0] = rep[1] = 0;
-  PtauLayout l;
-  if (const char *f = ptau_header_fault(ptau, len, l)) { rep[0] = 1; set_error("ptau verify: step 1 failed: %s", f); return ZKR_ERR_ARG; }
-  if (int rc = need_device(device)) return rc;
-  ZKR_HIP_CHECK(hipSetDevice(device));
-  DevicePtau d;
-  PtauVerdict v;
-  if (int rc = ptau_check(ptau, l, device, d, v)) return rc;
-  if (v.step) {
-    rep[0] = v.step; rep[1] = v.vector;
-    set_error("ptau verify: %s", v.why);
-    return 0;
-  }
-  // 6. the records verify, chain from the generators, and end at THIS transcript
-  auto fail6 = [&](uint64_t vector, const char *what) {
-    rep[0] = 6; rep[1] = vector;
-    set_error("ptau verify: step 6 failed: %s", what);
-    return 0;
-  };
-  char why[256];
-  if (!ptau_records_valid(records, n_records, why, sizeof(why))) return fail6(0, why);
-  const uint8_t *b = (const uint8_t *)ptau;
-  uint8_t g1[64], g2[128];
-  store_g1_std(g1, g1_generator());
-  store_g2_std(g2, g2_generator());
-  const uint8_t *last = n_records ? records + (n_records - 1) * ZKR_PTAU_RECORD_BYTES : nullptr;
-  const struct { int vec; size_t at; const uint8_t *want; size_t bytes; } ends[5] = {
-      {V_TAU1, l.off[V_TAU1] + 64, last ? last + PREC_AFTER[0] : g1, 64},   {V_ALFA1, l.off[V_ALFA1], last ? last + PREC_AFTER[1] : g1, 64},
-      {V_BETA1, l.off[V_BETA1], last ? last + PREC_AFTER[2] : g1, 64},      {V_TAU2, l.off[V_TAU2] + 128, last ? last + PREC_G2[0] : g2, 128},
-      {V_BETA2, l.off[V_BETA2], last ? last + PREC_G2[2] : g2, 128}};
-  for (const auto &e : ends)
-    if (memcmp(b + e.at, e.want, e.bytes) != 0) {
-      snprintf(why, sizeof(why), last ? "the last record does not end at this transcript's %s" : "no records, but %s is not the all-generators transcript's", VECTOR_NAME[e.vec]);
-      return fail6((uint64_t)e.vec, why);
-    }
-  *valid = 1;
-  return 0;
+  return ptau_verify_keep(ptau, len, records, n_records, device, valid, report, nullptr);
 }
 
 int zkr_ptau_contribute(const void *ptau, size_t len, const uint8_t *secrets96, int device, void **ptau_out, size_t *out_len, uint8_t record_out[ZKR_PTAU_RECORD_BYTES]) {

@@ -217,6 +217,14 @@ static int r1cs_upload(zkr_r1cs *cs, const Circuit &c) {
   return cs->ev.create(hipEventDisableTiming);
 }
 
+namespace zkr {
+void r1cs_view(const zkr_r1cs *cs, R1csView *v) {
+  v->device = cs->device; v->n = cs->n; v->p = cs->p; v->nC = cs->nC; v->m = cs->m;
+  for (int s = 0; s < 3; s++) { v->row_ptr[s] = cs->rowptr[s].as<uint32_t>(); v->col[s] = cs->col[s].as<uint32_t>(); v->coef[s] = cs->coef[s].as<Fr>(); }
+  v->wide = cs->wide.as<uint32_t>(); v->n_wide = cs->n_wide; v->wide_terms = R1CS_WIDE;
+}
+}  // namespace zkr
+
 extern "C" {
 
 int zkr_r1cs_load(const void *r1cs_bin, size_t r1cs_len, int device, zkr_r1cs **out) {

@@ -1,4 +1,5 @@
 """ctypes binding of libzkr_hip.so (declarations follow include/zkr.h one to one)."""
+import collections
 import ctypes
 import os
 
@@ -9,6 +10,7 @@ PARTIAL_BYTES = 640   # zkr.h ZKR_PARTIAL_BYTES
 SHARD_SIDE_TABLES = 1  # ZKR_SHARD_SIDE_TABLES
 EXPORT_STANDARD = 1  # ZKR_EXPORT_STANDARD
 CONTRIBUTION_BYTES = 352   # zkr.h ZKR_CONTRIBUTION_BYTES
+KeyAudit = collections.namedtuple("KeyAudit", "valid step detail phase1_contributions delta_contributions")   # ProvingKey.audit
 PTAU_RECORD_BYTES = 928   # zkr.h ZKR_PTAU_RECORD_BYTES
 REPLICATE_MODES = {"auto": 0, "full": 1, "base": 2}   # zkr.h ZKR_REPLICATE_*
 KEY_SECTIONS = ("none", "rowptr", "col", "wide", "rank", "header", "points", "twiddles", "coef", "shared rank", "consts")   # zkr.h ZKR_KEYSEC_*
@@ -82,6 +84,8 @@ def lib():
     L.zkr_contribution_check.argtypes = [u8p, c.POINTER(i)]
     L.zkr_key_contribution_verify.argtypes = [vp, vp, u8p, c.POINTER(i), c.POINTER(c.c_uint64)]
     L.zkr_vk_contribute.argtypes = [u8p, sz, u8p, c.POINTER(vp), c.POINTER(sz)]
+    L.zkr_contribution_chain_check.argtypes = [u8p, sz, c.POINTER(i)]
+    L.zkr_key_audit.argtypes = [vp, vp, u8p, sz, u8p, sz, u8p, sz, u8p, sz, c.POINTER(i), c.POINTER(c.c_uint64)]
     L.zkr_ptau_new.argtypes = [c.c_uint, c.POINTER(vp), c.POINTER(sz)]
     L.zkr_ptau_contribute.argtypes = [u8p, sz, u8p, i, c.POINTER(vp), c.POINTER(sz), u8p]
     L.zkr_ptau_record_check.argtypes = [u8p, sz, c.POINTER(i)]
@@ -429,6 +433,20 @@ class ProvingKey:
         rep = (ctypes.c_uint64 * 2)()
         _check(lib().zkr_key_contribution_verify(self._h, after._h, bytes(record), ctypes.byref(ok), rep))
         return bool(ok.value), int(rep[0]), int(rep[1])
+
+    def audit(self, system, ptau, ptau_records=(), delta_records=(), vk_bin=b""):
+        """What somebody who took no part in the ceremony runs on the finished key (zkr_key_audit): are this proving key and
+        `vk_bin` the ones `system` (a ConstraintSystem on this key's device) and the transcript `ptau` give, with delta moved only by the
+        contributors of `delta_records`?  Records: lists of records or their concatenation, in the order they were made.
+        -> KeyAudit(valid, step, detail, phase1_contributions, delta_contributions); step = the first failed step (0: none),
+        detail = the record's index (step 3) or the table (steps 5 and 6: 0 A, 1 B1, 2 B2, 3 C, 4 hExps; 5: the twiddles);
+        zkr_hip.lib().zkr_last_error() names what failed.  A key with delta_contributions == 0 is consistent and NOT sound."""
+        pr, dr = _records(ptau_records, PTAU_RECORD_BYTES), _records(delta_records, CONTRIBUTION_BYTES)
+        ok = ctypes.c_int(0)
+        rep = (ctypes.c_uint64 * 4)()
+        _check(lib().zkr_key_audit(self._h, system._h, bytes(ptau), len(ptau), pr if pr else None, len(pr) // PTAU_RECORD_BYTES, dr if dr else None,
+                                   len(dr) // CONTRIBUTION_BYTES, bytes(vk_bin), len(vk_bin), ctypes.byref(ok), rep))
+        return KeyAudit(bool(ok.value), int(rep[0]), int(rep[1]), int(rep[2]), int(rep[3]))
 
     def replication(self):
         """How this key came to its device (zkr_key_replication): {"mode": "none" | "full" | "base", "peer_direct": bool}."""
@@ -943,6 +961,21 @@ def contribution_check(record: bytes) -> bool:
     assert len(record) == CONTRIBUTION_BYTES
     ok = ctypes.c_int(0)
     _check(lib().zkr_contribution_check(bytes(record), ctypes.byref(ok)))
+    return bool(ok.value)
+
+
+def _records(records, size) -> bytes:
+    rb = bytes(records) if isinstance(records, (bytes, bytearray)) else b"".join(bytes(r) for r in records)
+    assert len(rb) % size == 0
+    return rb
+
+
+def contribution_chain_check(records) -> bool:
+    """zkr_contribution_chain_check: a chain of delta records (a list of 352-byte records, or their concatenation) from the
+    generator on, host only; zkr_hip.lib().zkr_last_error() names the record and the check that failed."""
+    rb = _records(records, CONTRIBUTION_BYTES)
+    ok = ctypes.c_int(0)
+    _check(lib().zkr_contribution_chain_check(rb if rb else None, len(rb) // CONTRIBUTION_BYTES, ctypes.byref(ok)))
     return bool(ok.value)
 
 
