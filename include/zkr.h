@@ -499,6 +499,77 @@ int zkr_r1cs_check(zkr_r1cs *cs, const void *const *witnesses_std, size_t witnes
  * *same = 0 and a zkr_last_error line naming the geometry, or the side and the first differing row. */
 int zkr_r1cs_matches_key(zkr_r1cs *cs, const zkr_key *key, int *same);
 
+/* ---- witness programs: batch witnesses for ANY circuit on the GPU (csrc/zkr_wprog.hip over csrc/wprog.hpp) ----
+ * zkr_setup_r1cs, zkr_r1cs_check, zkr_prove* and zkr_verify_each take any circuit; the witness builders of this library
+ * (zkr_rollup_witness*, zkr_withdraw_witness*) are device programs written by hand for its own two.  A witness program is the
+ * same thing as DATA: r1cs_bin carries a circuit's constraints, wprog_bin carries how its values are computed, and a front end
+ * emits the two from one description (python/zkr_hip/circuit.py is one; a converter from circom's output would be another).
+ *
+ * wprog_bin.  All integers little-endian u32.  The program is straight-line -- no control flow -- over a store of WIRES, which
+ * are Fr values numbered implicitly: wire 0 is the constant 1, wires 1..n_inputs are the instance's inputs in order, and every
+ * value-producing instruction defines the next wire.  Every wire an instruction names must be an EARLIER wire.
+ *   header   u32 magic 0x50574b5a ("ZKWP") | u32 version = 1 | u32 n_inputs | u32 n_consts | u32 n_instr |
+ *            u32 n_vars | u32 n_public | u32 n_statements
+ *   consts   n_consts x 32 B, standard form LE, below r
+ *   code     n_instr x 16 B:  u32 op | u32 a | u32 b | u32 c     (a field an opcode does not use is 0)
+ *   map      n_vars x u32: witness signal s of an instance is the value of wire map[s]; map[0] = 0
+ * and nothing after it.  Opcodes:
+ *   1 CONST k        the value of constant-pool entry a = k
+ *   2 ADD a b   3 SUB a b   4 MUL a b     field arithmetic on wires a and b
+ *   5 INV0 a         0 for 0, the inverse otherwise
+ *   6 BIT a i        bit b = i < 254 of the canonical standard-form value of wire a, as 0 or 1
+ *   7 ASSERT_ZERO a stmt     defines no wire: the first such instruction in program order whose wire a is not zero sets the
+ *                    instance's statement to b = stmt < n_statements
+ * Division is MUL with INV0; comparators, selectors and hashes are compositions: the front end's business.  n_public and
+ * n_statements are carried for the caller (the circuit's nPublic; how many statement texts the front end keeps).
+ * THE VALIDATOR runs before any device call, so a malformed program is ZKR_ERR_ARG with a message naming the field on a machine
+ * without a GPU too: magic, version, the exact length the counts give; every count at most 2^28 and 1 + n_inputs + n_instr at
+ * most 2^28; n_public < n_vars; every constant below r; per instruction a known opcode, every wire operand below the wire the
+ * instruction would define, a constant index below n_consts, a bit index below 254, a statement below n_statements, unused
+ * fields 0; every map entry below the wire count, entry 0 = wire 0.  The kernels index device memory with the program's numbers
+ * and check none of them: this validation is why they cannot read or write out of bounds.
+ *
+ * zkr_wprog_load: parse and validate, then the device (ZKR_ERR_NO_DEVICE without one: no CPU fallback); uploads the code, the
+ * constants in Montgomery form and the map, and allocates the handle's one workspace: the wire store, n_wires x piece x 32 B, and
+ * piece x 8 B of reports.  A batch is processed in pieces of `piece` instances.  zkr_wprog_load_opts: opts->piece = 0 (and
+ * zkr_wprog_load) takes the DEFAULT: the largest multiple of 64 whose store fits 1 GiB, at least 64 and at most 16384; any
+ * other value up to 2^20 is taken as it is (a store that cannot be allocated is ZKR_ERR_HIP).  reserved must be 0.
+ * One zkr_wprog serves ONE call at a time (it owns one stream and one workspace, as a zkr_r1cs does).
+ * zkr_wprog_info: out[0..7] = n_inputs, wires, instructions, n_vars, n_public, workspace bytes held, piece, n_statements.
+ * zkr_wprog_shape: the same from the bytes alone, host only (out[5] = out[6] = 0).
+ * zkr_wprog_witness_batch_device: d_inputs_std = n x n_inputs x 32 B, standard form, in device memory; d_witnesses = device
+ * memory for n x n_vars x 32 B, standard form -- exactly what zkr_prove_batch_device, zkr_r1cs_check_device and
+ * zkr_verify_each_device take.  Both 16-byte aligned.  `stream` as for zkr_prove_device: the work starts after what is queued
+ * there (the producer of the inputs) and runs on the handle's own stream; the call returns when the witnesses are complete.
+ * reports (may be NULL): n x 2 words: [0] 0 ok, 1 an input is not below r ([1] = the first such input), 2 an assertion failed
+ * ([1] = its statement).  When an instance fails the status is ZKR_ERR_UNSATISFIED and zkr_last_error names the FIRST failing
+ * instance, "instance 64 violates statement 3" or "instance 0: input 2 is not below r"; the witnesses of the instances that did
+ * not fail are complete and correct all the same, those of the failing ones are all zero.  n = 0 is ZKR_OK, nothing launched.
+ * zkr_wprog_witness_batch: the same with the inputs in host memory; their range check then happens on the host before the device
+ * is looked at: ZKR_ERR_ARG naming the first element not below r, nothing launched (as zkr_babyjub_pubkey_batch).
+ * zkr_wprog_stage_times: milliseconds the last batch call spent in the interpreter kernel and in the layout kernel (events on the
+ * handle's stream, summed over the pieces).
+ * zkr_wprog_run_host: test hook -- ONE instance on the host through the same interpreter step, no device.  witness_out: n_vars x
+ * 32 B (all zero unless *code = 0); wires_out (may be NULL): every wire, standard form (all zero for code 1).  ZKR_OK whatever
+ * the instance's *code; ZKR_ERR_ARG for a malformed program.
+ * zkr_mimcsponge_round_constants: the 220 round constants of zkr_mimcsponge_multihash (220 x 32 B, standard form), for front ends
+ * that compose the hash.  The Node binding does not carry these calls. */
+typedef struct zkr_wprog zkr_wprog;
+typedef struct zkr_wprog_opts {
+  uint32_t piece;     /* instances per pass over the wire store; 0: the default */
+  uint32_t reserved;  /* 0 */
+} zkr_wprog_opts;
+int zkr_wprog_load(const void *wprog_bin, size_t len, int device, zkr_wprog **out);
+int zkr_wprog_load_opts(const void *wprog_bin, size_t len, int device, const zkr_wprog_opts *opts, zkr_wprog **out);
+void zkr_wprog_free(zkr_wprog *prog);
+int zkr_wprog_info(const zkr_wprog *prog, uint64_t out[8]);
+int zkr_wprog_shape(const void *wprog_bin, size_t len, uint64_t out[8]);
+int zkr_wprog_witness_batch_device(zkr_wprog *prog, const void *d_inputs_std, size_t n, void *d_witnesses, uint32_t *reports, void *stream);
+int zkr_wprog_witness_batch(zkr_wprog *prog, const uint8_t *inputs_std, size_t n, void *d_witnesses, uint32_t *reports);
+int zkr_wprog_stage_times(const zkr_wprog *prog, double out_ms[2]);
+int zkr_wprog_run_host(const void *wprog_bin, size_t len, const uint8_t *inputs_std, uint8_t *witness_out, uint8_t *wires_out, uint32_t *code, uint32_t *stmt);
+int zkr_mimcsponge_round_constants(uint8_t *out);
+
 /* ---- a further party's contribution to a key's delta (what makes a key somebody else can trust) ------
  * Whoever ran a setup saw (or chose) delta, and delta forges proofs (a key from a transcript has delta = 1).  A contributor
  * re-randomises delta with a secret d of its own and none of the toxic values:

@@ -31,6 +31,10 @@ class KeyExportOpts(ctypes.Structure):   # zkr.h zkr_key_export_opts
     _fields_ = [("flags", ctypes.c_uint32), ("piece_points", ctypes.c_uint32)]
 
 
+class WprogOpts(ctypes.Structure):   # zkr.h zkr_wprog_opts
+    _fields_ = [("piece", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
 class NttSelftestDesc(ctypes.Structure):   # zkr.h zkr_ntt_selftest_desc
     _fields_ = [(f, ctypes.c_uint32) for f in ("logn", "tlog", "dif", "inverse", "pre", "nbat", "pair", "in_place", "want_lo", "want_n", "coset_shift",
                                                "coset_add", "cross", "klog", "col_lo", "col_n", "in_sub", "out_sub", "canon", "reserved")]
@@ -79,6 +83,17 @@ def lib():
     L.zkr_r1cs_check_device.argtypes = [vp, c.POINTER(vp), sz, vp, c.POINTER(c.c_uint64), c.POINTER(i)]
     L.zkr_r1cs_check.argtypes = [vp, c.POINTER(c.c_char_p), sz, sz, c.POINTER(c.c_uint64), c.POINTER(i)]
     L.zkr_r1cs_matches_key.argtypes = [vp, vp, c.POINTER(i)]
+    L.zkr_wprog_load.argtypes = [u8p, sz, i, c.POINTER(vp)]
+    L.zkr_wprog_load_opts.argtypes = [u8p, sz, i, c.POINTER(WprogOpts), c.POINTER(vp)]
+    L.zkr_wprog_free.argtypes = [vp]
+    L.zkr_wprog_free.restype = None
+    L.zkr_wprog_info.argtypes = [vp, c.POINTER(c.c_uint64)]
+    L.zkr_wprog_shape.argtypes = [u8p, sz, c.POINTER(c.c_uint64)]
+    L.zkr_wprog_witness_batch_device.argtypes = [vp, vp, sz, vp, c.POINTER(c.c_uint32), vp]
+    L.zkr_wprog_witness_batch.argtypes = [vp, u8p, sz, vp, c.POINTER(c.c_uint32)]
+    L.zkr_wprog_stage_times.argtypes = [vp, c.POINTER(c.c_double)]
+    L.zkr_wprog_run_host.argtypes = [u8p, sz, u8p, u8p, u8p, c.POINTER(c.c_uint32), c.POINTER(c.c_uint32)]
+    L.zkr_mimcsponge_round_constants.argtypes = [u8p]
     L.zkr_key_replicate.argtypes = [vp, i, i, c.POINTER(vp)]
     L.zkr_key_contribute.argtypes = [vp, u8p, c.POINTER(vp), u8p]
     L.zkr_contribution_check.argtypes = [u8p, c.POINTER(i)]
@@ -754,6 +769,136 @@ class ConstraintSystem:
     def close(self):
         if self._h:
             lib().zkr_r1cs_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+WPROG_INFO = ("nInputs", "nWires", "nInstructions", "nVars", "nPublic", "workspaceBytes", "piece", "nStatements")   # zkr_wprog_info
+WPROG_CODES = ("ok", "an input is not below r", "an assertion failed")   # reports[0] of zkr_wprog_witness_batch_device
+WitnessRun = collections.namedtuple("WitnessRun", "code statement witness wires")   # WitnessProgram.run_host
+
+
+def mimcsponge_round_constants():
+    """The 220 round constants of multi_hash as integers (zkr_mimcsponge_round_constants, host only)."""
+    out = ctypes.create_string_buffer(220 * 32)
+    _check(lib().zkr_mimcsponge_round_constants(out))
+    return [int.from_bytes(out.raw[32 * k:32 * k + 32], "little") for k in range(220)]
+
+
+def wprog_shape(wprog_bin: bytes) -> dict:
+    """Counts of a witness program from its bytes (zkr_wprog_shape: the validator, host only); ZkrError -5 names what is malformed."""
+    out = (ctypes.c_uint64 * 8)()
+    _check(lib().zkr_wprog_shape(bytes(wprog_bin), len(wprog_bin), out))
+    return {k: int(v) for k, v in zip(WPROG_INFO, out) if k not in ("workspaceBytes", "piece")}
+
+
+def wprog_run_host(wprog_bin: bytes, row, want_wires=False) -> WitnessRun:
+    """zkr_wprog_run_host: ONE instance on the host through the interpreter step the kernel runs; no device.  row: n_inputs ints
+    below 2^256.  -> WitnessRun(code, statement, witness bytes (n_vars x 32, zeros unless code == 0), wires bytes or None)."""
+    shape = wprog_shape(wprog_bin)
+    if len(row) != shape["nInputs"]:
+        raise ValueError("the program takes %d inputs, got %d" % (shape["nInputs"], len(row)))
+    ins = b"".join(int(v).to_bytes(32, "little") for v in row)
+    wit = ctypes.create_string_buffer(32 * shape["nVars"])
+    wires = ctypes.create_string_buffer(32 * shape["nWires"]) if want_wires else None
+    code, stmt = ctypes.c_uint32(), ctypes.c_uint32()
+    _check(lib().zkr_wprog_run_host(bytes(wprog_bin), len(wprog_bin), ins, wit, wires, ctypes.byref(code), ctypes.byref(stmt)))
+    return WitnessRun(code.value, stmt.value, wit.raw, wires.raw if want_wires else None)
+
+
+class WitnessProgram:
+    """A witness program resident on the device (zkr_wprog*): witnesses of a whole batch of instances of ANY circuit, one GPU lane
+    per instance, laid out as ProvingKey.prove_batch_device and ConstraintSystem.check_device take them.  wprog_bin comes from a
+    front end (zkr_hip.circuit.Circuit.program()); statements: its statement texts, used in error messages.  piece: instances
+    per pass over the wire store (None: the library's default).  One WitnessProgram serves one call at a time."""
+
+    def __init__(self, wprog_bin: bytes, device=0, piece=None, statements=None):
+        self._h = None
+        self.bin = bytes(wprog_bin)
+        self.statements = list(statements) if statements is not None else []
+        self.device = device
+        self.reports = []
+        h = ctypes.c_void_p()
+        opts = WprogOpts(int(piece or 0), 0)
+        _check(lib().zkr_wprog_load_opts(self.bin, len(self.bin), device, ctypes.byref(opts), ctypes.byref(h)))
+        self._h = h
+
+    def info(self):
+        out = (ctypes.c_uint64 * 8)()
+        _check(lib().zkr_wprog_info(self._h, out))
+        return dict(zip(WPROG_INFO, [int(x) for x in out]))
+
+    def statement_text(self, stmt):
+        return self.statements[stmt] if stmt < len(self.statements) else "statement %d" % stmt
+
+    def _raise(self, err, reports):
+        """The library's error with the failing instance's statement in the front end's words."""
+        if err.code != -7:
+            raise err
+        j = next(k for k, r in enumerate(reports) if r[0])
+        code, stmt = reports[j]
+        what = "input %d is not below r" % stmt if code == 1 else "violates: %s" % self.statement_text(stmt)
+        e = ZkrError(err.code, "instance %d %s" % (j, what))
+        e.reports = reports
+        raise e from None
+
+    def witness_batch_device(self, inputs, stream=None):
+        """zkr_wprog_witness_batch_device / zkr_wprog_witness_batch.  inputs: a torch.uint8 tensor on the program's device holding
+        n x n_inputs x 32 B (standard form), or a list of rows of ints, which are checked against r on the host and uploaded.
+        stream: the stream (a torch stream or a raw handle) the inputs were written on.  -> torch.uint8 [n, n_vars * 32] on the
+        device; row j's data_ptr() is witness j.  self.reports: [(code, statement)] of the call.  An instance that fails raises
+        ZkrError -7 naming the first one with its statement text; e.reports has every instance's, and the witnesses of the
+        others are complete (self.last holds the tensor)."""
+        import torch
+        info = self.info()
+        ni, nv = info["nInputs"], info["nVars"]
+        dev = torch.device("cuda", self.device)
+        raw = getattr(stream, "cuda_stream", stream) or 0
+        if isinstance(inputs, torch.Tensor):
+            if inputs.dtype != torch.uint8 or not inputs.is_cuda or inputs.device.index != self.device or not inputs.is_contiguous():
+                raise ValueError("inputs must be a contiguous torch.uint8 tensor on cuda:%d" % self.device)
+            if inputs.numel() % (32 * ni or 32):
+                raise ValueError("inputs hold %d bytes, not a multiple of n_inputs x 32 = %d" % (inputs.numel(), 32 * ni))
+            n = inputs.numel() // (32 * ni) if ni else int(inputs.shape[0])
+            host = None
+        else:
+            rows = [list(r) for r in inputs]
+            if any(len(r) != ni for r in rows):
+                raise ValueError("every row must hold the program's %d inputs" % ni)
+            n = len(rows)
+            host = b"".join(int(v).to_bytes(32, "little") for r in rows for v in r)
+        out = torch.empty((n, nv * 32), dtype=torch.uint8, device=dev)
+        rep = (ctypes.c_uint32 * (2 * n or 1))()
+        self.last = out
+        try:
+            if host is None:
+                _check(lib().zkr_wprog_witness_batch_device(self._h, ctypes.c_void_p(inputs.data_ptr()), n, ctypes.c_void_p(out.data_ptr()), rep, ctypes.c_void_p(raw)))
+            else:
+                _check(lib().zkr_wprog_witness_batch(self._h, host, n, ctypes.c_void_p(out.data_ptr()), rep))
+        except ZkrError as e:
+            self.reports = [(int(rep[2 * j]), int(rep[2 * j + 1])) for j in range(n)]
+            self._raise(e, self.reports)
+        self.reports = [(int(rep[2 * j]), int(rep[2 * j + 1])) for j in range(n)]
+        return out
+
+    def stage_times(self):
+        """Milliseconds of the last batch call in the interpreter kernel and in the layout kernel (zkr_wprog_stage_times)."""
+        out = (ctypes.c_double * 2)()
+        _check(lib().zkr_wprog_stage_times(self._h, out))
+        return {"run_ms": out[0], "layout_ms": out[1]}
+
+    def run_host(self, row, want_wires=False) -> WitnessRun:
+        """One instance on the host (wprog_run_host); raises nothing for a failing instance: look at .code and .statement."""
+        return wprog_run_host(self.bin, row, want_wires)
+
+    def close(self):
+        if self._h:
+            lib().zkr_wprog_free(self._h)
             self._h = None
 
     def __del__(self):
