@@ -1,5 +1,5 @@
 // eval_h.hpp -- the scalars of a key's evaluation-form side tables (DESIGN.md 3.1 "H in evaluation form").  Nothing of HIP in it:
-// the setups (workload.hip) call it where they hold the key's scalars, the host shim compiles it for the CPU tests.
+// the setups (zkr_setup.hip) call it where they hold the key's scalars, the host shim compiles it for the CPU tests.
 //
 // The H multiexp is linear in h, and h = (P - Q)/2 in coefficients, where P interpolates c_j = a_j b_j on the domain w^j and Q
 // interpolates d_j = A(g w^j) B(g w^j) on the coset (g = w_2m, so x^m = -1 there).  Moving both inverse transforms from the

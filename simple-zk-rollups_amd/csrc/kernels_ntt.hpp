@@ -19,6 +19,7 @@
 #include <type_traits>
 #include "curve.hpp"
 #include "field29.hpp"
+#include "qap_forms.hpp"
 
 namespace zkr {
 
@@ -340,7 +341,7 @@ static __global__ void ingest_kernel(const Fr *in, Fr *out, size_t n, uint32_t *
 // coef Montgomery, w standard -> out standard.  One thread per constraint row: rows are 1-3 terms, except for the
 // occasional wide row (64-term bit-packing rows, a handful per few thousand), which would leave 63 lanes of its
 // wavefront waiting for one; rows wider than SPMV_WIDE are left to spmv_wide_kernel (one wavefront per row).
-constexpr uint32_t SPMV_WIDE = 8;
+constexpr uint32_t SPMV_WIDE = WIDE_ROW_TERMS;  // qap_forms.hpp: the host lists the wide rows with the same number
 // blockIdx.z = 1: the B side of the QAP in the same launch (its CSR arrays and output vector); 2: the C side of a key that proves
 // with H in evaluation form (gridDim.z = 3; everybody else passes an empty third side and gridDim.z = 2)
 struct SpmvSide { const uint32_t *row_ptr, *col; const Fr *coef; Fr *out; const uint32_t *wide; uint32_t n_wide; };

@@ -35,7 +35,27 @@ inline bool read_g2(const uint8_t *p, G2Affine &out) {
   return !out.is_inf() && pairing::g2_on_curve(out) && pairing::g2_in_subgroup(out);
 }
 
-constexpr size_t VK_FIXED_BYTES = 64 + 3 * 128 + 4;  // alfa1, beta2, gamma2, delta2, the IC count
+// vk_bin: alfa1 | beta2 | gamma2 | delta2 | u32 IC count | the IC points, standard form
+constexpr size_t VK_OFF_BETA2 = 64, VK_OFF_GAMMA2 = VK_OFF_BETA2 + 128, VK_OFF_DELTA2 = VK_OFF_GAMMA2 + 128, VK_OFF_N_IC = VK_OFF_DELTA2 + 128;
+constexpr size_t VK_FIXED_BYTES = VK_OFF_N_IC + 4;
+// the IC count a buffer long enough for the fixed part claims
+inline uint32_t vk_ic_count(const void *vk_bin) {
+  uint32_t n_ic;
+  memcpy(&n_ic, (const uint8_t *)vk_bin + VK_OFF_N_IC, 4);
+  return n_ic;
+}
+// THE writer: alfa1, beta2, delta2 as a key header holds them (Montgomery affine), gamma2 and the n_ic IC points in standard form
+inline void write_vk(std::vector<uint8_t> &vk, const uint8_t *alfa1_mont, const uint8_t *beta2_mont, const uint8_t *gamma2_std, const uint8_t *delta2_mont,
+                     const uint8_t *ic_std, size_t n_ic) {
+  vk.resize(VK_FIXED_BYTES + 64 * n_ic);
+  store_g1_std(vk.data(), load_g1(alfa1_mont));
+  store_g2_std(vk.data() + VK_OFF_BETA2, load_g2(beta2_mont));
+  memcpy(vk.data() + VK_OFF_GAMMA2, gamma2_std, 128);
+  store_g2_std(vk.data() + VK_OFF_DELTA2, load_g2(delta2_mont));
+  const uint32_t n_ic32 = (uint32_t)n_ic;
+  memcpy(vk.data() + VK_OFF_N_IC, &n_ic32, 4);
+  memcpy(vk.data() + VK_FIXED_BYTES, ic_std, 64 * n_ic);
+}
 struct ParsedVk {
   G1Affine alfa1, ic0;
   G2Affine beta2, gamma2, delta2;
@@ -46,11 +66,10 @@ inline int parse_vk(const void *vk_bin, size_t vk_len, size_t n_public, ParsedVk
   const uint8_t *vk = (const uint8_t *)vk_bin;
   const size_t fixed = VK_FIXED_BYTES;
   if (vk_len < fixed) { set_error("verifying key shorter than its fixed part (%zu bytes)", fixed); return ZKR_ERR_BAD_KEY; }
-  uint32_t n_ic;
-  memcpy(&n_ic, vk + 64 + 3 * 128, 4);
+  const uint32_t n_ic = vk_ic_count(vk);
   if (vk_len != fixed + 64ull * n_ic) { set_error("verifying key length %zu does not match %u IC points", vk_len, n_ic); return ZKR_ERR_BAD_KEY; }
   if (n_ic != n_public + 1) { set_error("%zu public signals for a key with %u IC points (needs nPublic + 1, TxVerifier.sol:261)", n_public, n_ic); return ZKR_ERR_ARG; }
-  if (!read_g1(vk, k.alfa1) || !read_g2(vk + 64, k.beta2) || !read_g2(vk + 192, k.gamma2) || !read_g2(vk + 320, k.delta2) || !read_g1(vk + fixed, k.ic0)) {
+  if (!read_g1(vk, k.alfa1) || !read_g2(vk + VK_OFF_BETA2, k.beta2) || !read_g2(vk + VK_OFF_GAMMA2, k.gamma2) || !read_g2(vk + VK_OFF_DELTA2, k.delta2) || !read_g1(vk + fixed, k.ic0)) {
     set_error("verifying key holds a point that is not on the curve (or a G2 point outside the order-r subgroup)");
     return ZKR_ERR_BAD_KEY;
   }

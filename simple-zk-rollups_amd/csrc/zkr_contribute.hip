@@ -20,6 +20,7 @@
 #include "hostops.hpp"
 #include "pairing.hpp"
 #include "record_util.hpp"
+#include "verify_key.hpp"
 #include "zkr_internal.hpp"
 
 namespace zkr {
@@ -149,23 +150,18 @@ int zkr_contribution_check(const uint8_t record[ZKR_CONTRIBUTION_BYTES], int *va
 int zkr_vk_contribute(const void *vk_bin, size_t vk_len, const uint8_t record[ZKR_CONTRIBUTION_BYTES], void **vk_out, size_t *vk_out_len) {
   if (!vk_bin || !record || !vk_out || !vk_out_len) { set_error("null argument"); return ZKR_ERR_ARG; }
   const uint8_t *vk = (const uint8_t *)vk_bin;
-  const size_t fixed = 64 + 3 * 128 + 4;
-  uint32_t n_ic = 0;
-  if (vk_len >= fixed) memcpy(&n_ic, vk + 64 + 3 * 128, 4);
+  const size_t fixed = VK_FIXED_BYTES;
+  const uint32_t n_ic = vk_len >= fixed ? vk_ic_count(vk) : 0;
   if (vk_len < fixed || vk_len != fixed + 64ull * n_ic) { set_error("verifying key length %zu does not match its IC count", vk_len); return ZKR_ERR_ARG; }
   Parsed p;
   const char *why = "";
   if (!record_valid(record, p, &why)) { set_error("contribution record: %s", why); return ZKR_ERR_ARG; }
   G2Affine vk_delta2;
-  if (!read_g2_std(vk + 320, vk_delta2)) { set_error("vk_delta_2 is not a member of G2"); return ZKR_ERR_ARG; }
+  if (!read_g2_std(vk + VK_OFF_DELTA2, vk_delta2)) { set_error("vk_delta_2 is not a member of G2"); return ZKR_ERR_ARG; }
   if (!pairings_equal(p.d1b, g2_generator(), g1_generator(), vk_delta2)) { set_error("the record does not continue this verifying key (its delta1_before is not this key's delta)"); return ZKR_ERR_ARG; }
-  uint8_t *out = (uint8_t *)malloc(vk_len);
-  if (!out) { set_error("out of memory"); return ZKR_ERR_ARG; }
-  memcpy(out, vk, vk_len);
-  memcpy(out + 320, record + REC_D2A, 128);
-  *vk_out = out;
-  *vk_out_len = vk_len;
-  return 0;
+  std::vector<uint8_t> next(vk, vk + vk_len);
+  memcpy(next.data() + VK_OFF_DELTA2, record + REC_D2A, 128);
+  return give_bytes(next, vk_out, vk_out_len);
 }
 
 int zkr_key_contribute(const zkr_key *key, const uint8_t *d32, zkr_key **out, uint8_t record_out[ZKR_CONTRIBUTION_BYTES]) {

@@ -1,5 +1,5 @@
 // zkr_eval_tables.hip -- the side tables of H in evaluation form (zkr_internal.hpp EvalTables; the algebra: eval_h.hpp) for ANY
-// whole key, derived from the key's own points.  workload.hip key_build_eval_tables makes them from the setup's scalars, which only
+// whole key, derived from the key's own points.  zkr_setup.hip key_build_eval_tables makes them from the setup's scalars, which only
 // a test or benchmark setup knows; a key loaded from websnark bytes or a file, a transcript key and every contributed key hold the
 // same information as points, and both tables are linear images of those:
 //     E'_j = ke 1/m sum_i (g w^j)^(-i) H_i      ke = -1/2 R / m^2 (eval_h.hpp eprime), H_i the key's hExps, g = w_2m

@@ -15,6 +15,7 @@
 #include "hostops.hpp"
 #include "zkr_owners.hpp"
 #include "msm_plan.hpp"
+#include "qap_forms.hpp"
 #include "shard_group.hpp"
 
 namespace zkr {
@@ -86,6 +87,24 @@ static_assert(sizeof(ArenaHeader) <= 1024, "header fits its slot");
 constexpr size_t ARENA_HEADER_BYTES = 1024;
 constexpr uint64_t ARENA_MAGIC = 0x343059454b524b5aull;  // "ZKRKEY04" (03: point tables in the radix-2^261 form of field29.hpp; 04: scalar sub-ranges of shard keys): bump with every change of ArenaHeader or of a section layout (packed key files carry it)
 inline uint32_t rank_entries(const ArenaHeader &h, int t) { return h.sc_n[t == T_H ? 1 : 0]; }  // entries of table t's rank map = scalars the key multiplies with it
+// the 448 bytes of constants in a websnark key's header <-> the header's fields
+inline void header_set_consts(ArenaHeader &h, const uint8_t *consts448) {
+  memcpy(h.alfa1, consts448, 64); memcpy(h.beta1, consts448 + 64, 64); memcpy(h.delta1, consts448 + 128, 64);
+  memcpy(h.beta2, consts448 + 192, 128); memcpy(h.delta2, consts448 + 320, 128);
+}
+inline void header_get_consts(const ArenaHeader &h, uint8_t *consts448) {
+  memcpy(consts448, h.alfa1, 64); memcpy(consts448 + 64, h.beta1, 64); memcpy(consts448 + 128, h.delta1, 64);
+  memcpy(consts448 + 192, h.beta2, 128); memcpy(consts448 + 320, h.delta2, 128);
+}
+// bytes the caller frees with zkr_free: a malloc'ed copy of v.  ZKR_ERR_ARG with the out-pointers null when there is no memory
+inline int give_bytes(const std::vector<uint8_t> &v, void **out, size_t *len) {
+  *out = malloc(v.size() ? v.size() : 1);
+  *len = 0;
+  if (!*out) { set_error("out of memory"); return ZKR_ERR_ARG; }
+  if (!v.empty()) memcpy(*out, v.data(), v.size());
+  *len = v.size();
+  return 0;
+}
 
 // digit records of one scalar vector, split by bucket range (kernels_msm.hpp "digit sort", stage 1)
 struct DigitLists {
@@ -174,7 +193,7 @@ struct ProofSlot {
 }  // namespace zkr
 
 namespace zkr {
-// Side tables of the evaluation form (eval_h.hpp has the algebra), made from the scalars by a builder that knew them (workload.hip
+// Side tables of the evaluation form (eval_h.hpp has the algebra), made from the scalars by a builder that knew them (zkr_setup.hip
 // key_build_eval_tables) or from the key's own points for any whole key (zkr_eval_tables.hip zkr_key_eval_tables): the H
 // multiexp over E' = -1/2 E with the coset products d_j as scalars, the C multiexp over C' = C + 1/2 C^T F.  Outside the arena: key
 // files, replicas and contributed keys do not carry them and prove through the coefficient form until they are derived
@@ -242,10 +261,20 @@ inline void key_streams_sync(zkr_key *k) {
   for (hipStream_t s : {k->stream, k->prep_stream, k->g2_stream, k->g1_stream, k->aux_stream}) (void)hipStreamSynchronize(s);
 }
 // zkr_key.hip
-int key_build(int device, uint32_t n, uint32_t p, uint32_t m, const std::vector<uint32_t> rowptr[2], const std::vector<uint32_t> col[2],
-              const std::vector<uint8_t> coef[2], const void *const tbl_src[N_TABLES], const bool tbl_src_on_device[N_TABLES],
-              const std::vector<uint32_t> tbl_srcidx[N_TABLES], const std::vector<uint32_t> tbl_sidx[N_TABLES], const uint8_t *consts448,
-              zkr_key **out);
+// What key_build makes a key from.  A table's source holds every point of its vector (affine Montgomery, 64 / 128 B per point);
+// kept point j is source entry srcidx[j] and multiplies scalar sidx[j]
+struct KeyTableSource {
+  const void *src = nullptr;
+  bool on_device = false;
+  std::vector<uint32_t> srcidx, sidx;
+};
+struct KeySource {
+  uint32_t n = 0, p = 0, m = 0;
+  KeyRows side[2];  // A and B as the key holds them (qap_forms.hpp), Montgomery coefficients
+  KeyTableSource tbl[N_TABLES];
+  const uint8_t *consts448 = nullptr;  // alfa1 beta1 delta1 beta2 delta2 as the websnark header has them
+};
+int key_build(int device, const KeySource &src, zkr_key **out);
 int key_alloc_workspace(zkr_key *k);
 int fixed_base_points(int device, bool g2, const uint8_t *scalars_std, size_t n, DevBuf &out, bool wipe_scalars = false);  // out: device array of affine Montgomery points
 int key_from_arena(int device, Dev<unsigned char> &&arena, const ArenaHeader &h, zkr_key **out);  // the key that owns `arena` from here on, with its workspace
@@ -282,11 +311,6 @@ int key_table_msm(const zkr_key *k, int t, const Fr *d_scalars, XYZZ<Fq> *out);
 // zkr_key_check.hip: what an arena whose header passed arena_header_fault CONTAINS (zkr_key_check; level 0 structure, 1 values)
 int key_arena_check(int device, const unsigned char *arena, const ArenaHeader &h, int level, uint64_t report[4]);
 // zkr_ptau.hip: the group elements of a key from a powers-of-tau transcript (zkr_setup_r1cs_ptau; delta = gamma = 1).
-// One QAP matrix by signal: column s = the terms [colptr[s], colptr[s + 1]), term e = coef[32 e ..] (standard form) x L_row[e]
-struct QapColumns {
-  std::vector<uint32_t> colptr, row;
-  std::vector<uint8_t> coef;
-};
 // cols: A (with the input-consistency rows), B, C over the domain m.  Steps 1-5 of zkr_ptau_verify run on the transcript first
 // (ZKR_ERR_BAD_KEY).  d_tbl (device, Montgomery affine, infinity where a signal's polynomial vanishes):
 // [T_A], [T_B1], [T_B2]: n points; [T_C]: the n points K[s] = beta A_s + alfa B_s + C_s (IC for s <= nPublic, C above); [T_H]: m
@@ -297,18 +321,8 @@ int g1_scale_each(G1Affine *pts, size_t n, const Fr *d_scalars, uint32_t sc_stri
 int g1_group_ntt(G1Affine *pts, G1Affine *tmp, unsigned logn, bool inverse, Fr *tw, void *ztmp);  // natural order in and out, the inverse with 1 / n; tmp: n points, tw: n / 2 + 1 scalars
 // out: point s < n = sum over column s of coefficient x pts[row]; partial sums lie behind
 int g1_combine_columns(uint32_t n, const QapColumns &cols, const G1Affine *pts, DevBuf &out);
-// workload.hip: a rank-1 constraint system as the setups and zkr_r1cs.hip take it, rows in CSR
-struct Term { uint32_t sig; Fr coef; };  // coef Montgomery
-struct Circuit {
-  uint32_t n = 0, p = 0, nC = 0, m = 0;
-  std::vector<uint32_t> rowA, rowB, rowC;  // CSR row pointers (nC+1)
-  std::vector<Term> tA, tB, tC;
-  std::vector<Fr> w;  // Montgomery
-};
-int parse_r1cs(const void *r1cs_bin, size_t r1cs_len, Circuit &c);  // r1cs_bin (include/zkr.h) -> the circuit, with its domain; host only; ZKR_ERR_ARG with a message
 int device_bytes_equal(int device, const void *a, const void *b, size_t bytes, bool *same);  // zkr_contribute.hip: its compare kernel over one range; bytes a multiple of 16
-void qap_columns(const Circuit &c, int side, QapColumns &q);  // one side of the QAP (0 = A with its input-consistency rows, 1 = B, 2 = C) by signal
-int key_eval_rows(zkr_key *k, const Circuit &c);  // room for a whole key's side tables (eval_tables_alloc), C by row filled in; above zero: an allocation failed
+int key_eval_rows(zkr_key *k, const Circuit &c);  // zkr_setup.hip: room for a whole key's side tables (eval_tables_alloc), C by row filled in; above zero: an allocation failed
 int digit_lists_alloc(DigitLists &dl, size_t n_scalars, const MsmPlan &pl);
 int msm_scratch_alloc(MsmScratch &m, size_t n_scalars, size_t n_points, const MsmPlan &pl, bool g2);  // for one proof of one table
 int msm_precompute(int device, bool g2, void *d_table, uint32_t n, const MsmPlan &pl);  // fills levels 1..K-1 of a table whose level 0 is in place, then converts the table to the hot path's radix

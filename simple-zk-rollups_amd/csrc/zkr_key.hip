@@ -346,47 +346,41 @@ int key_from_arena(int device, Dev<unsigned char> &&arena, const ArenaHeader &h,
   return 0;
 }
 
-// Builds the arena.  tbl_src[t]: full source table (host or device memory, affine Montgomery, 64/128 B
-// per point); tbl_srcidx[t][j]: source index of kept point j; tbl_sidx[t][j]: index of its scalar.
-int key_build(int device, uint32_t n, uint32_t p, uint32_t m, const std::vector<uint32_t> rowptr[2], const std::vector<uint32_t> col[2],
-              const std::vector<uint8_t> coef[2], const void *const tbl_src[N_TABLES], const bool tbl_src_on_device[N_TABLES],
-              const std::vector<uint32_t> tbl_srcidx[N_TABLES], const std::vector<uint32_t> tbl_sidx[N_TABLES], const uint8_t *consts448,
-              zkr_key **out) {
+// Builds the arena from the rows and the kept points of `ks` (zkr_internal.hpp KeySource).
+int key_build(int device, const KeySource &ks, zkr_key **out) {
+  const uint32_t n = ks.n, m = ks.m;
   ZKR_HIP_CHECK(hipSetDevice(device));
   ArenaHeader h;
   memset(&h, 0, sizeof(h));
   h.magic = ARENA_MAGIC;
-  h.n = n; h.p = p; h.m = m;
-  h.logm = 0;
-  while ((1u << h.logm) < m) h.logm++;
+  h.n = n; h.p = ks.p; h.m = m;
+  h.logm = domain_log2(m);
   h.tlog = h.logm;
-  h.nnzA = (uint32_t)col[0].size();
-  h.nnzB = (uint32_t)col[1].size();
-  memcpy(h.alfa1, consts448, 64); memcpy(h.beta1, consts448 + 64, 64); memcpy(h.delta1, consts448 + 128, 64);
-  memcpy(h.beta2, consts448 + 192, 128); memcpy(h.delta2, consts448 + 320, 128);
+  h.nnzA = (uint32_t)ks.side[0].col.size();
+  h.nnzB = (uint32_t)ks.side[1].col.size();
+  header_set_consts(h, ks.consts448);
   h.sc_lo[0] = h.sc_lo[1] = 0; h.sc_n[0] = n; h.sc_n[1] = m;
   h.shard_part = 0; h.shard_parts = 1;
-  std::vector<uint32_t> wide_rows[2];
+  std::vector<uint32_t> wide[2];
   for (int s = 0; s < 2; s++) {
-    for (uint32_t r = 0; r < m; r++)
-      if (rowptr[s][r + 1] - rowptr[s][r] > SPMV_WIDE) wide_rows[s].push_back(r);
-    h.n_wide[s] = (uint32_t)wide_rows[s].size();
+    wide[s] = wide_rows(ks.side[s].rowptr.data(), m);
+    h.n_wide[s] = (uint32_t)wide[s].size();
   }
   // A and C multiply the same scalars and nearly the same signals (C lacks the public ones): when their supports
   // overlap by >= 90 % both tables are laid out over the UNION of the supports (a missing point is stored as
   // infinity, x = 0, and skipped by the accumulation), so one digit sort serves both (h.share_ac).
   const std::vector<uint32_t> *srcidx_eff[N_TABLES], *sidx_eff[N_TABLES];
-  for (int t = 0; t < N_TABLES; t++) { srcidx_eff[t] = &tbl_srcidx[t]; sidx_eff[t] = &tbl_sidx[t]; }
+  for (int t = 0; t < N_TABLES; t++) { srcidx_eff[t] = &ks.tbl[t].srcidx; sidx_eff[t] = &ks.tbl[t].sidx; }
   std::vector<uint32_t> u_sidx, uA_src, uC_src;
   {
-    const std::vector<uint32_t> &sa = tbl_sidx[T_A], &sc = tbl_sidx[T_C];
+    const std::vector<uint32_t> &sa = ks.tbl[T_A].sidx, &sc = ks.tbl[T_C].sidx;
     size_t i = 0, j = 0, both = 0;
     while (i < sa.size() || j < sc.size()) {
       uint32_t a = i < sa.size() ? sa[i] : 0xffffffffu, c = j < sc.size() ? sc[j] : 0xffffffffu;
       uint32_t s = a < c ? a : c;
       u_sidx.push_back(s);
-      uA_src.push_back(a == s ? tbl_srcidx[T_A][i] : RANK_NONE);
-      uC_src.push_back(c == s ? tbl_srcidx[T_C][j] : RANK_NONE);
+      uA_src.push_back(a == s ? ks.tbl[T_A].srcidx[i] : RANK_NONE);
+      uC_src.push_back(c == s ? ks.tbl[T_C].srcidx[j] : RANK_NONE);
       both += (a == s && c == s);
       if (a == s) i++;
       if (c == s) j++;
@@ -403,7 +397,7 @@ int key_build(int device, uint32_t n, uint32_t p, uint32_t m, const std::vector<
     plan[t] = msm_plan(t == T_H ? m : n, h.npts[t]);
     h.win_c[t] = (uint32_t)plan[t].c;
   }
-  h.share_b = tbl_sidx[T_B1] == tbl_sidx[T_B2] ? 1 : 0;
+  h.share_b = ks.tbl[T_B1].sidx == ks.tbl[T_B2].sidx ? 1 : 0;
   arena_layout(h);
   const size_t off = h.total_len;
 
@@ -412,12 +406,13 @@ int key_build(int device, uint32_t n, uint32_t p, uint32_t m, const std::vector<
   ZKR_HIP_CHECK(hipMemset(arena, 0, off));  // alignment gaps and slack bytes are part of the arena's bytes (replicas, packed key files): defined, not stale
   ZKR_HIP_CHECK(hipMemcpy(arena, &h, sizeof(h), hipMemcpyHostToDevice));
   for (int s = 0; s < 2; s++) {
-    ZKR_HIP_CHECK(hipMemcpy(arena + h.off_rowptr[s], rowptr[s].data(), rowptr[s].size() * 4, hipMemcpyHostToDevice));
-    if (!col[s].empty()) {
-      ZKR_HIP_CHECK(hipMemcpy(arena + h.off_col[s], col[s].data(), col[s].size() * 4, hipMemcpyHostToDevice));
-      ZKR_HIP_CHECK(hipMemcpy(arena + h.off_coef[s], coef[s].data(), coef[s].size(), hipMemcpyHostToDevice));
+    const KeyRows &q = ks.side[s];
+    ZKR_HIP_CHECK(hipMemcpy(arena + h.off_rowptr[s], q.rowptr.data(), q.rowptr.size() * 4, hipMemcpyHostToDevice));
+    if (!q.col.empty()) {
+      ZKR_HIP_CHECK(hipMemcpy(arena + h.off_col[s], q.col.data(), q.col.size() * 4, hipMemcpyHostToDevice));
+      ZKR_HIP_CHECK(hipMemcpy(arena + h.off_coef[s], q.coef.data(), q.coef.size(), hipMemcpyHostToDevice));
     }
-    if (!wide_rows[s].empty()) ZKR_HIP_CHECK(hipMemcpy(arena + h.off_wide[s], wide_rows[s].data(), wide_rows[s].size() * 4, hipMemcpyHostToDevice));
+    if (!wide[s].empty()) ZKR_HIP_CHECK(hipMemcpy(arena + h.off_wide[s], wide[s].data(), wide[s].size() * 4, hipMemcpyHostToDevice));
   }
   for (int t = 0; t < N_TABLES; t++) {
     size_t np = h.npts[t], pb = t == T_B2 ? 128 : 64;
@@ -430,20 +425,20 @@ int key_build(int device, uint32_t n, uint32_t p, uint32_t m, const std::vector<
       h.rank_identity[t] = ident ? 1 : 0;
       ZKR_HIP_CHECK(hipMemcpy(arena + h.off_rank[t], rank.data(), rank.size() * 4, hipMemcpyHostToDevice));
     }
-    if (tbl_src_on_device[t]) {
+    if (ks.tbl[t].on_device) {
       Dev<uint32_t> d_idx;
       if (int irc = d_idx.alloc(np)) return irc;
       ZKR_HIP_CHECK(hipMemcpy(d_idx, srcidx_eff[t]->data(), np * 4, hipMemcpyHostToDevice));
       unsigned grid = (unsigned)((np * (pb / 16) + 255) / 256);  // one 16-byte piece per thread
       if (t == T_B2)
-        gather_kernel<G2Affine><<<grid, 256>>>((const G2Affine *)tbl_src[t], d_idx, np, (G2Affine *)(arena + h.off_pts[t]));
+        gather_kernel<G2Affine><<<grid, 256>>>((const G2Affine *)ks.tbl[t].src, d_idx, np, (G2Affine *)(arena + h.off_pts[t]));
       else
-        gather_kernel<G1Affine><<<grid, 256>>>((const G1Affine *)tbl_src[t], d_idx, np, (G1Affine *)(arena + h.off_pts[t]));
+        gather_kernel<G1Affine><<<grid, 256>>>((const G1Affine *)ks.tbl[t].src, d_idx, np, (G1Affine *)(arena + h.off_pts[t]));
       ZKR_HIP_CHECK(hipGetLastError());
       ZKR_HIP_CHECK(hipDeviceSynchronize());
     } else {
       std::vector<uint8_t> stage(np * pb);
-      const uint8_t *src = (const uint8_t *)tbl_src[t];
+      const uint8_t *src = (const uint8_t *)ks.tbl[t].src;
       for (size_t j = 0; j < np; j++) {
         uint32_t si = (*srcidx_eff[t])[j];
         if (si != RANK_NONE) memcpy(&stage[j * pb], src + (size_t)si * pb, pb);  // else: stays all-zero = infinity (x = 0)
@@ -557,61 +552,27 @@ int zkr_key_load_websnark(const void *pk_bin, size_t pk_len, int device, zkr_key
     set_error("section pointers/length inconsistent with nVars=%u nPublic=%u domainSize=%u (len %zu)", n, p, m, pk_len);
     return ZKR_ERR_BAD_KEY;
   }
-  // column-major sparse pols -> CSR rows
-  std::vector<uint32_t> rowptr[2], col[2];
-  std::vector<uint8_t> coef[2];
-  for (int s = 0; s < 2; s++) {
-    size_t o = ptr[s], end = ptr[s + 1];
-    std::vector<uint32_t> cnt(m + 1, 0);
-    size_t nnz = 0;
-    for (uint32_t sig = 0; sig < n; sig++) {
-      if (o + 4 > end) { set_error("pols section %d truncated", s); return ZKR_ERR_BAD_KEY; }
-      uint32_t kk = rd32(pk + o);
-      o += 4;
-      if (o + 36ull * kk > end) { set_error("pols section %d truncated", s); return ZKR_ERR_BAD_KEY; }
-      for (uint32_t e = 0; e < kk; e++, o += 36) {
-        uint32_t c = rd32(pk + o);
-        if (c >= m) { set_error("constraint index %u >= domainSize %u", c, m); return ZKR_ERR_BAD_KEY; }
-        cnt[c + 1]++;
-      }
-      nnz += kk;
-    }
-    if (o != end) { set_error("pols section %d has trailing bytes", s); return ZKR_ERR_BAD_KEY; }
-    rowptr[s].assign(m + 1, 0);
-    for (uint32_t c = 0; c < m; c++) rowptr[s][c + 1] = rowptr[s][c] + cnt[c + 1];
-    col[s].resize(nnz);
-    coef[s].resize(nnz * 32);
-    std::vector<uint32_t> cur(rowptr[s].begin(), rowptr[s].end() - 1);
-    o = ptr[s];
-    for (uint32_t sig = 0; sig < n; sig++) {
-      uint32_t kk = rd32(pk + o);
-      o += 4;
-      for (uint32_t e = 0; e < kk; e++, o += 36) {
-        uint32_t c = rd32(pk + o), pos = cur[c]++;
-        col[s][pos] = sig;
-        memcpy(&coef[s][(size_t)pos * 32], pk + o + 4, 32);
-      }
-    }
-  }
+  KeySource ks;
+  ks.n = n; ks.p = p; ks.m = m;
+  ks.consts448 = pk + 40;
+  for (int s = 0; s < 2; s++)
+    if (int rc = pols_to_rows(pk, ptr[s], ptr[s + 1], s, n, m, ks.side[s])) return rc;
   // point tables: drop points at infinity (x == 0), remember which scalar each kept point multiplies
-  const void *src[N_TABLES] = {pk + ptr[2], pk + ptr[3], pk + ptr[4], pk + ptr[5], pk + ptr[6]};
-  const bool on_dev[N_TABLES] = {false, false, false, false, false};
-  std::vector<uint32_t> srcidx[N_TABLES], sidx[N_TABLES];
+  for (int t = 0; t < N_TABLES; t++) ks.tbl[t].src = pk + ptr[2 + t];
+  auto keep = [&](int t, uint32_t src, uint32_t scalar) { ks.tbl[t].srcidx.push_back(src); ks.tbl[t].sidx.push_back(scalar); };
   for (uint32_t i = 0; i < n; i++) {
-    if (!all_zero(pk + ptr[2] + 64ull * i, 32)) { srcidx[T_A].push_back(i); sidx[T_A].push_back(i); }
-    if (!all_zero(pk + ptr[3] + 64ull * i, 32)) { srcidx[T_B1].push_back(i); sidx[T_B1].push_back(i); }
-    if (!all_zero(pk + ptr[4] + 128ull * i, 64)) { srcidx[T_B2].push_back(i); sidx[T_B2].push_back(i); }
+    if (!all_zero(pk + ptr[2] + 64ull * i, 32)) keep(T_A, i, i);
+    if (!all_zero(pk + ptr[3] + 64ull * i, 32)) keep(T_B1, i, i);
+    if (!all_zero(pk + ptr[4] + 128ull * i, 64)) keep(T_B2, i, i);
   }
   for (uint32_t i = 0; i + p + 1 < n; i++)
-    if (!all_zero(pk + ptr[5] + 64ull * i, 32)) { srcidx[T_C].push_back(i); sidx[T_C].push_back(i + p + 1); }
-  uint32_t logm = 0;
-  while ((1u << logm) < m) logm++;
+    if (!all_zero(pk + ptr[5] + 64ull * i, 32)) keep(T_C, i, i + p + 1);
+  const unsigned logm = domain_log2(m);
   for (uint32_t j = 0; j < m; j++) {  // h is produced in bit-reversed order: pair position j with hExps[bitrev(j)]
-    uint32_t i = 0;
-    for (uint32_t b = 0; b < logm; b++) i |= ((j >> b) & 1) << (logm - 1 - b);
-    if (!all_zero(pk + ptr[6] + 64ull * i, 32)) { srcidx[T_H].push_back(i); sidx[T_H].push_back(j); }
+    const uint32_t i = bitrev32(j, logm);
+    if (!all_zero(pk + ptr[6] + 64ull * i, 32)) keep(T_H, i, j);
   }
-  return key_build(device, n, p, m, rowptr, col, coef, src, on_dev, srcidx, sidx, pk + 40, out);
+  return key_build(device, ks, out);
 }
 
 void zkr_key_free(zkr_key *k) {

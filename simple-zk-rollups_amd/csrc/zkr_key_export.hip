@@ -142,8 +142,7 @@ static int key_export(const zkr_key *k, uint32_t flags, uint32_t piece_points, v
     }
     const auto t0 = Clock::now();
     uint8_t consts[448];
-    memcpy(consts, h.alfa1, 64); memcpy(consts + 64, h.beta1, 64); memcpy(consts + 128, h.delta1, 64);
-    memcpy(consts + 192, h.beta2, 128); memcpy(consts + 320, h.delta2, 128);
+    header_get_consts(h, consts);
     if (standard) {  // x 2^-256: the 14 coordinates of the header, every coefficient
       for (int c = 0; c < 14; c++) {
         Fq v;

@@ -7,7 +7,7 @@
 // Here: the transcript's layout, the all-generators start, a contribution with its record (three Schnorr proofs, as the delta
 // record's one), the check of a chain of records (host, pairings), the verification of a transcript (curve and order checks on
 // the device, the progressions by random combinations through the library's MSM path), and the group elements of a key derived
-// from a transcript (zkr_setup_r1cs_ptau, workload.hip): Lagrange-basis points by the inverse NTT over points, the per-signal
+// from a transcript (zkr_setup_r1cs_ptau, zkr_setup.hip): Lagrange-basis points by the inverse NTT over points, the per-signal
 // sparse combinations of them, the hExps differences.  The kernels are in kernels_group.hpp; two of them are reachable on their
 // own as stage hooks (zkr_points_scale_each, zkr_group_ntt).
 //
@@ -573,8 +573,7 @@ int ptau_key_tables(const void *ptau, size_t len, int device, uint32_t m, uint32
   int rc;
   if ((rc = ptau_check(ptau, l, device, d, v))) return rc;
   if (v.step) { set_error("zkr_setup_r1cs_ptau: the transcript does not verify: %s", v.why); return ZKR_ERR_BAD_KEY; }
-  unsigned logm = 0;
-  while ((1u << logm) < m) logm++;
+  const unsigned logm = domain_log2(m);
 
   // the plans of the three combinations: A over Lag1; B over Lag1 and Lag2; K over [Lag1 | LagAlfa | LagBeta] with A's rows in
   // the beta slice, B's in the alfa slice, C's in the first

@@ -6,7 +6,7 @@
 // `groth.isValid` after every proof (operator/src/snarks/common.ts:30-38), which says "invalid" and never where; its witness comes
 // from `Circuit.calculateWitness` (common.ts:15-17), which checks the circuit it was compiled from and nothing a key was set up for.
 //
-// The system is the r1cs_bin of zkr_setup_r1cs (parse_r1cs, workload.hip): three CSR sides -- row pointers, signals, Montgomery
+// The system is the r1cs_bin of zkr_setup_r1cs (parse_r1cs, qap_forms.cpp): three CSR sides -- row pointers, signals, Montgomery
 // coefficients as spmv_kernel takes them -- and the list of constraints with a side wider than R1CS_WIDE terms.  One launch
 // evaluates the three sides of a constraint and compares a b with c in registers: no m-sized vectors exist.  The grid is
 // constraints x witnesses (blockIdx.y, as spmv_kernel's fused batch).  Narrow constraints get one thread each, wide ones one
@@ -25,7 +25,7 @@
 namespace zkr {
 namespace {
 
-constexpr uint32_t R1CS_WIDE = 8;  // a constraint with a side of more terms goes to a wavefront (the key's SPMV_WIDE)
+constexpr uint32_t R1CS_WIDE = WIDE_ROW_TERMS;  // a constraint with a side of more terms goes to a wavefront (the key's SPMV_WIDE)
 constexpr int R1CS_THREADS = 256;
 constexpr size_t R1CS_CHUNK = 1024;  // witnesses per launch (gridDim.y; the limit is 65535)
 constexpr unsigned long long NONE64 = ~0ull;
@@ -191,23 +191,15 @@ static int upload(DevBuf &d, const void *src, size_t bytes) {
 
 static int r1cs_upload(zkr_r1cs *cs, const Circuit &c) {
   ZKR_HIP_CHECK(hipSetDevice(cs->device));
-  const std::vector<uint32_t> *rp[3] = {&c.rowA, &c.rowB, &c.rowC};
-  const std::vector<Term> *tt[3] = {&c.tA, &c.tB, &c.tC};
-  std::vector<uint32_t> cols;
-  std::vector<Fr> coefs;
   for (int s = 0; s < 3; s++) {
-    cs->nnz[s] = tt[s]->size();
-    cols.resize(tt[s]->size());
-    coefs.resize(tt[s]->size());
-    for (size_t k = 0; k < tt[s]->size(); k++) { cols[k] = (*tt[s])[k].sig; coefs[k] = (*tt[s])[k].coef; }
+    const QapRows &q = c.side[s];
+    cs->nnz[s] = q.sig.size();
     int rc;
-    if ((rc = upload(cs->rowptr[s], rp[s]->data(), rp[s]->size() * 4)) || (rc = upload(cs->col[s], cols.data(), cols.size() * 4)) ||
-        (rc = upload(cs->coef[s], coefs.data(), coefs.size() * sizeof(Fr))))
+    if ((rc = upload(cs->rowptr[s], q.rowptr.data(), q.rowptr.size() * 4)) || (rc = upload(cs->col[s], q.sig.data(), q.sig.size() * 4)) ||
+        (rc = upload(cs->coef[s], q.coef.data(), q.coef.size() * sizeof(Fr))))
       return rc;
   }
-  std::vector<uint32_t> wide;
-  for (uint32_t r = 0; r < c.nC; r++)
-    if (c.rowA[r + 1] - c.rowA[r] > R1CS_WIDE || c.rowB[r + 1] - c.rowB[r] > R1CS_WIDE || c.rowC[r + 1] - c.rowC[r] > R1CS_WIDE) wide.push_back(r);
+  const std::vector<uint32_t> wide = wide_rows({c.side[0].rowptr.data(), c.side[1].rowptr.data(), c.side[2].rowptr.data()}, c.nC, R1CS_WIDE);
   cs->n_wide = (uint32_t)wide.size();
   if (int rc = upload(cs->wide, wide.data(), wide.size() * 4)) return rc;
   int rc;

@@ -294,8 +294,7 @@ int zkr_vk_load(const void *vk_bin, size_t vk_len, int device, zkr_vk **out) {
   // nPublic from the key's own IC count; everything else is parse_vk's business, before any device call
   size_t n_public = 0;
   if (vk_len >= VK_FIXED_BYTES) {
-    uint32_t n_ic;
-    memcpy(&n_ic, (const uint8_t *)vk_bin + 64 + 3 * 128, 4);
+    const uint32_t n_ic = vk_ic_count(vk_bin);
     if (n_ic) n_public = n_ic - 1;
   }
   ParsedVk pk;

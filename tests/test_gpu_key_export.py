@@ -2,8 +2,8 @@
 comes to exist.
 
 Everything is compared EXACTLY, as bytes.  The expected bytes never come from the export: they are the oracle's key
-(groth16.setup + binarify_proving_key), the bytes zkr_setup_r1cs_websnark renders from the setup's own scalars, a patched copy of
-the oracle's key, or -- for the key of a ceremony, which no scalar-knowing writer can produce -- the proofs of the C oracle over
+(groth16.setup + binarify_proving_key), the bytes zkr_setup_r1cs_websnark renders from the setup's own scalars (their pols sections, which
+that writer and the export lay out with the same code, rebuilt here from the r1cs_bin), a patched copy of the oracle's key, or -- for the key of a ceremony, which no scalar-knowing writer can produce -- the proofs of the C oracle over
 the exported bytes against the proofs of the key on the GPU.
 
 Sizes: the export has ONE code path per group (a kernel thread per output point, in pieces of piece_points), so the cases are
@@ -97,9 +97,33 @@ def _pols_shape(pkb, s):
     return per_sig, per_row
 
 
+def _pols_from_r1cs(r1cs):
+    """polsA | polsB of the key of this r1cs_bin, rebuilt here: per signal its terms by row ascending (a row's in stored order,
+    nothing merged or dropped), coefficient x 2^256 mod r, and on A the rows nConstraints + i that tie public signal i to itself"""
+    n, p, n_c = struct.unpack_from("<3I", r1cs, 0)
+    cols = [[[] for _ in range(n)] for _ in range(2)]
+    o = 12
+    for row in range(n_c):
+        for s in range(3):
+            (k,) = struct.unpack_from("<I", r1cs, o)
+            o += 4
+            for _ in range(k):
+                if s < 2:
+                    (sig,) = struct.unpack_from("<I", r1cs, o)
+                    coef = int.from_bytes(r1cs[o + 4:o + 36], "little") * MONT % R
+                    cols[s][sig].append(struct.pack("<I", row) + coef.to_bytes(32, "little"))
+                o += 36
+    assert o == len(r1cs)
+    for i in range(p + 1):
+        cols[0][i].append(struct.pack("<I", n_c + i) + (MONT % R).to_bytes(32, "little"))
+    return b"".join(struct.pack("<I", len(terms)) + b"".join(terms) for side in cols for terms in side)
+
+
 def _against_the_scalar_knowing_writer(r1cs, toxic):
     import zkr_hip
     want = zkr_hip.setup_r1cs_websnark(r1cs, toxic)[0]
+    ptr = _sections(want)[3]
+    assert want[ptr[0]:ptr[2]] == _pols_from_r1cs(bytes(r1cs))  # the setup's writer shares its front with the export: the pols are pinned here
     for side_tables in (True, False):
         key, _ = zkr_hip.ProvingKey.setup_r1cs(r1cs, toxic=toxic, side_tables=side_tables)
         try:
