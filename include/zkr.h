@@ -820,6 +820,37 @@ int zkr_withdraw_witness_program_host(const uint8_t private_key[32], const uint8
 const char *zkr_withdraw_statement_text(uint32_t stmt);
 uint32_t zkr_withdraw_n_vars(void);
 
+/* ---- the rest of crypto.ts: key agreement and the MiMC7 cipher (csrc/zkr_crypto.hip over csrc/crypto_program.hpp).
+ * All values 32 B little-endian standard form.  One item on the host, no device needed:
+ *   zkr_mimc7_round_constants  circomlib mimc7.js getConstants("mimc", 91): 91 x 32 B, c_0 = 0
+ *   zkr_mimc7_hash             mimc7.hash(x, k)
+ *   zkr_mimc7_multihash        mimc7.multiHash(in[0..n), key)
+ *   zkr_babyjub_ecdh           ecdh(priv, pub) (crypto.ts:86-93): the x coordinate of formatPrivKeyForBabyJub(priv) * pub
+ *   zkr_mimc7_encrypt          encrypt(msg, key) (crypto.ts:95-110): *iv = multiHash(msg, 0), out[i] = msg[i] + hash(key, iv + i) --
+ *                              the INTEGER sum, below 2r, as the reference's BigInt `+` leaves it [DEP-KNOWLEDGE]
+ *   zkr_mimc7_decrypt          decrypt({iv, msg}, key) (crypto.ts:112-123): (enc[i] - hash(key, iv + i)) mod r for enc[i] < 2r
+ * ecdhEncrypt / ecdhDecrypt (crypto.ts:125-141) are zkr_babyjub_ecdh followed by zkr_mimc7_encrypt / zkr_mimc7_decrypt.
+ * ZKR_ERR_ARG, naming the item (0 for these calls) and the element: a key, message element, iv or public-key coordinate not below
+ * r; a ciphertext element not below 2r; a public key that is not on the curve (the reference multiplies whatever it is given:
+ * a stated deviation); an arity outside 1..65536.  The identity and the low-order points are accepted, as in the reference. */
+int zkr_mimc7_round_constants(uint8_t *out);
+int zkr_mimc7_hash(const uint8_t x[32], const uint8_t k[32], uint8_t out[32]);
+int zkr_mimc7_multihash(const uint8_t *in, size_t n, const uint8_t key[32], uint8_t out[32]);
+int zkr_babyjub_ecdh(const uint8_t priv[32], const uint8_t pub[64], uint8_t shared[32]);
+int zkr_mimc7_encrypt(const uint8_t key[32], const uint8_t *msg, unsigned arity, uint8_t iv[32], uint8_t *out);
+int zkr_mimc7_decrypt(const uint8_t key[32], const uint8_t iv[32], const uint8_t *enc, unsigned arity, uint8_t *out);
+/* The same for whole lists ON THE GPU, each item equal to the host call's bit for bit: one thread per key pair (ecdh), per message
+ * (the iv) and per message ELEMENT (the keystream).  privs, keys, ivs, shared: n x 32 B; pubs: n x 64 B; msgs, encs, out: n x arity
+ * x 32 B, one arity for the whole call.  In the ecdh_* calls the shared keys never leave the device.  The refusals above come
+ * first and without a device, naming the first offending item; then no CPU fallback (ZKR_ERR_NO_DEVICE).  n = 0 is ZKR_OK with
+ * nothing launched.  On an error return the outputs are untouched.  Every device buffer that held a key or a plaintext is zeroed
+ * before it is freed.  The kernels are NOT constant time. */
+int zkr_babyjub_ecdh_batch(const uint8_t *privs, const uint8_t *pubs, size_t n, uint8_t *shared, int device);
+int zkr_mimc7_encrypt_batch(const uint8_t *keys, const uint8_t *msgs, unsigned arity, size_t n, uint8_t *ivs, uint8_t *out, int device);
+int zkr_mimc7_decrypt_batch(const uint8_t *keys, const uint8_t *ivs, const uint8_t *encs, unsigned arity, size_t n, uint8_t *out, int device);
+int zkr_ecdh_encrypt_batch(const uint8_t *privs, const uint8_t *pubs, const uint8_t *msgs, unsigned arity, size_t n, uint8_t *ivs, uint8_t *out, int device);
+int zkr_ecdh_decrypt_batch(const uint8_t *privs, const uint8_t *pubs, const uint8_t *ivs, const uint8_t *encs, unsigned arity, size_t n, uint8_t *out, int device);
+
 /* ---- the operator's ledger on the GPU: a queue of signed transactions -> a status each and the circuit inputs of every whole
  * batch, in device memory (csrc/zkr_sequencer.hip).  Stands in for the per-transaction loop of
  * operator/src/routes/send.ts:72-135 and the tree updates of operator/src/routes/pubsub.ts:19-66.  The ledger holds the account

@@ -160,6 +160,21 @@ static const MimcConstants &mimc() {
   static const MimcConstants k;
   return k;
 }
+// MiMC7-91 (circomlib mimc7.js getConstants("mimc", 91), what crypto.ts:95-123 encrypts with): c_0 = 0, c_i = the i-th link of
+// the keccak chain from keccak256("mimc"), read big-endian mod r; pinned by tests/golden/mimc7_kat.json
+constexpr int MIMC7_NROUNDS = 91;
+struct Mimc7Constants {
+  Fr c[MIMC7_NROUNDS];
+  Mimc7Constants() {
+    uint8_t h[32];
+    keccak256((const uint8_t *)"mimc", 4, h);
+    c[0] = Fr::zero();
+    for (int i = 1; i < MIMC7_NROUNDS; i++) {
+      keccak256(h, 32, h);
+      c[i] = fr_from_be(h, 32);
+    }
+  }
+};
 static inline Fr pow5(const Fr &t) {
   Fr t2 = sqr(t);
   return mul(sqr(t2), t);
@@ -955,6 +970,11 @@ static void *dup_bytes(const void *p, size_t n) {
 namespace zkr {
 // the 220 round constants (Montgomery form) for the device kernels of rollup_gpu.hip
 const Fr *mimc_round_constants() { return mimc().c; }
+// the 91 round constants of MiMC7 (Montgomery form) for crypto_program.hpp's host calls and the kernels of zkr_crypto.hip
+const Fr *mimc7_round_constants() {
+  static const Mimc7Constants k;
+  return k.c;
+}
 // what the device witness builder (rollup_gpu.hip) shares with the gadget program above: curve constants, the fixed-base
 // table of scalar_mul_base8, and the geometry of the signal vector
 void rollup_device_constants(Fr *a, Fr *d, uint32_t suborder_m1[8], Fr *b8x253, Fr *b8y253) {

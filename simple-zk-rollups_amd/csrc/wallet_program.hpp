@@ -11,9 +11,18 @@
 // NOT constant time: the loops over text lengths, the zero tests and the memory the witness program touches depend on the
 // secrets.  These programs are for a machine whose operator holds the keys anyway.
 #pragma once
+#include <vector>
 #include "rollup_witness.hpp"
 
 namespace zkr {
+void rollup_device_constants(Fr *a, Fr *d, uint32_t suborder_m1[8], Fr *b8x253, Fr *b8y253);  // rollup.cpp
+const Fr *mimc_round_constants();                                                                // rollup.cpp
+// the programs' constants in HOST memory, for the host calls and the test hooks: `tab` owns the table k points into
+static inline void wl_host_tables(std::vector<Fr> &tab, TxConsts &k) {
+  tab.resize(2 * 253);
+  rollup_device_constants(&k.a, &k.d, k.suborder_m1, tab.data(), tab.data() + 253);
+  k.b8x = tab.data(), k.b8y = tab.data() + 253, k.mimc = mimc_round_constants();
+}
 // Withdraw(): signal 0 = 1, 1..2 = publicKey, 3 = nullifier, 4 = privateKey, then Num2Bits(253), 252 additions of six signals each
 // (scalar_mul_base8) and the three-input sponge (three signals per round)
 constexpr uint32_t WD_PUBLIC = 5;  // signals in front of the private ones

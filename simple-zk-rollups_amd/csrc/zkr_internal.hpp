@@ -31,6 +31,7 @@ inline int need_device(int device) {
   return 0;
 }
 // the same for a call that has a name of its own: `what`, with the host call that does the same job where there is one
+inline unsigned blocks_of(size_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }  // of a one-thread-per-item launch
 inline int need_device(int device, const char *what) {
   if (zkr_device_count() <= device || device < 0) { set_error("no HIP device %d; %s runs on the GPU and has no CPU fallback", device, what); return ZKR_ERR_NO_DEVICE; }
   return 0;

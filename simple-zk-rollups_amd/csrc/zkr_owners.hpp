@@ -53,6 +53,17 @@ struct MemBuf : Owner<void *, Free> {
 struct DevBuf : MemBuf<FreeDevice> {
   int alloc(size_t bytes) { reset(); ZKR_HIP_CHECK(hipMalloc(&p, bytes ? bytes : 1)); return 0; }
 };
+// a device buffer that held secrets: zeroed, and the zeroing waited for, before it is freed -- however the call is left
+struct SecretBuf : DevBuf {  // whose own destructor frees, after this one has run
+  size_t bytes = 0;
+  hipStream_t s = nullptr;
+  ~SecretBuf() {
+    if (!p) return;
+    (void)hipMemsetAsync(p, 0, bytes, s);
+    (void)hipStreamSynchronize(s);
+  }
+  int alloc(size_t n) { bytes = n; return DevBuf::alloc(n); }
+};
 struct PinnedBuf : MemBuf<FreePinned> {
   int alloc(size_t bytes) { reset(); ZKR_HIP_CHECK(hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocDefault)); return 0; }
 };

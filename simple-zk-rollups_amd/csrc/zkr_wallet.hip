@@ -13,8 +13,6 @@
 #include "wallet_program.hpp"
 
 namespace zkr {
-void rollup_device_constants(Fr *a, Fr *d, uint32_t suborder_m1[8], Fr *b8x253, Fr *b8y253);  // rollup.cpp
-const Fr *mimc_round_constants();                                                                // rollup.cpp
 int rollup_device_tables(int device, TxConsts *k);                                               // rollup_gpu.hip
 
 // out[t] = formatPrivKeyForBabyJub(privs[t])
@@ -82,12 +80,6 @@ static __global__ __launch_bounds__(256) void withdraw_layout_kernel(const Fr *i
   wit[g] = v;
 }
 
-static inline unsigned blocks_of(size_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
-static void host_tables(std::vector<Fr> &tab, TxConsts &k) {
-  tab.resize(2 * 253);
-  rollup_device_constants(&k.a, &k.d, k.suborder_m1, tab.data(), tab.data() + 253);
-  k.b8x = tab.data(), k.b8y = tab.data() + 253, k.mimc = mimc_round_constants();
-}
 // index of the first of `count` elements (32 B, standard form) that is not below r, or `count`
 static size_t first_not_below_r(const uint8_t *p, size_t count) {
   for (size_t i = 0; i < count; i++) {
@@ -97,17 +89,6 @@ static size_t first_not_below_r(const uint8_t *p, size_t count) {
   }
   return count;
 }
-// a device buffer that held secrets: zeroed, and the zeroing waited for, before it is freed -- however the call is left
-struct SecretBuf : DevBuf {  // whose own destructor frees, after this one has run
-  size_t bytes = 0;
-  hipStream_t s = nullptr;
-  ~SecretBuf() {
-    if (!p) return;
-    (void)hipMemsetAsync(p, 0, bytes, s);
-    (void)hipStreamSynchronize(s);
-  }
-  int alloc(size_t n) { bytes = n; return DevBuf::alloc(n); }
-};
 enum : size_t { WALLET_PIECE = (size_t)1 << 20, WITHDRAW_PIECE = 4096 };  // items per launch: 32 MB of keys; 128 MB of chain workspace
 
 enum WalletOp { OP_FORMAT, OP_PUBKEY, OP_SIGN };
@@ -210,7 +191,7 @@ int zkr_wallet_pubkey_program_host(const uint8_t priv[32], uint8_t formatted[32]
   if (first_not_below_r(priv, 1) < 1) { set_error("private key >= r"); return ZKR_ERR_ARG; }
   std::vector<Fr> tab;
   TxConsts k;
-  host_tables(tab, k);
+  wl_host_tables(tab, k);
   Fr ps, p, ax, ay;
   memcpy(ps.v, priv, 32);
   wl_read(&ps, p);
@@ -233,7 +214,7 @@ int zkr_wallet_sign_program_host(const uint8_t priv[32], const uint8_t *msg, uns
   }
   std::vector<Fr> tab, m(arity);
   TxConsts k;
-  host_tables(tab, k);
+  wl_host_tables(tab, k);
   memcpy(m.data(), msg, (size_t)arity * 32);
   Fr ps, p, r8x, r8y;
   memcpy(ps.v, priv, 32);
@@ -250,7 +231,7 @@ int zkr_withdraw_witness_program_host(const uint8_t private_key[32], const uint8
   if (!private_key || !nullifier || !witness_out || !stmt) { set_error("null argument"); return ZKR_ERR_ARG; }
   std::vector<Fr> tab, w(WD_NVARS), ws(WD_WS_ELEMS);
   TxConsts k;
-  host_tables(tab, k);
+  wl_host_tables(tab, k);
   Fr key, nul;
   memcpy(key.v, private_key, 32);
   memcpy(nul.v, nullifier, 32);

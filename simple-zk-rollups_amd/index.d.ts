@@ -92,6 +92,14 @@ export function genPublicKey(privKey: bigint): [bigint, bigint];
 export function formatPrivKeyForBabyJub(privKey: bigint): bigint;
 export function sign(privKey: bigint, msg: Array<bigint | string | number>): Signature;
 export function verify(msg: Array<bigint | string | number>, sig: Signature, pubKey: [bigint, bigint]): boolean;
+/** types/primitives.ts:40.  Each element is the integer msg[i] + mimc7.hash(key, iv + i), below 2r. */
+export interface EncryptedMessage { iv: bigint; msg: bigint[]; }
+/** ecdh (crypto.ts:86-93).  Throws for a public key that is not on the curve. */
+export function ecdh(privKey: bigint, pubKey: [bigint, bigint]): bigint;
+export function encrypt(msg: Array<bigint | string | number>, key: bigint): EncryptedMessage;
+export function decrypt(encryptedMsg: EncryptedMessage, key: bigint): bigint[];
+export function ecdhEncrypt(msg: Array<bigint | string | number>, privKey: bigint, pubKey: [bigint, bigint]): EncryptedMessage;
+export function ecdhDecrypt(encryptedMsg: EncryptedMessage, privKey: bigint, pubKey: [bigint, bigint]): bigint[];
 /** BatchProcessTx(batch, depth) (tx.circom = (2, 6)) as constraint system + witness builder. */
 export class RollupCircuit {
   constructor(batch?: number, depth?: number);

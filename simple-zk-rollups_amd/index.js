@@ -543,6 +543,17 @@ function sign(priv, msg) {
   const v = leToBigInts(native().rollupCrypto(2, bigintToLe32(priv), concatLe(msg)));
   return { R8: [v[0], v[1]], S: v[2] };
 }
+// ecdh(priv, pub) (crypto.ts:86-93); a public key that is not on the curve is refused (the reference multiplies whatever it is given)
+function ecdh(priv, pub) { return leToBigInts(native().rollupCrypto(5, bigintToLe32(priv), concatLe(pub)))[0]; }
+// encrypt(msg, key) -> { iv, msg } (crypto.ts:95-110): each element the INTEGER msg[i] + mimc7.hash(key, iv + i), below 2r;
+// decrypt({ iv, msg }, key) (:112-123); ecdhEncrypt / ecdhDecrypt (:125-141)
+function encrypt(msg, key) {
+  const v = leToBigInts(native().rollupCrypto(6, bigintToLe32(key), concatLe(msg)));
+  return { iv: v[0], msg: v.slice(1) };
+}
+function decrypt(enc, key) { return leToBigInts(native().rollupCrypto(7, bigintToLe32(key), bigintToLe32(enc.iv), concatLe(enc.msg))); }
+const ecdhEncrypt = (msg, priv, pub) => encrypt(msg, ecdh(priv, pub));
+const ecdhDecrypt = (enc, priv, pub) => decrypt(enc, ecdh(priv, pub));
 function verify(msg, sig, pub) {
   if ([sig.R8[0], sig.R8[1], sig.S, pub[0], pub[1]].some((v) => BigInt(v) < 0n || BigInt(v) >= MONT)) return false;
   return native().rollupCrypto(3, concatLe(msg), concatLe([sig.R8[0], sig.R8[1], sig.S]), concatLe(pub));
@@ -715,7 +726,7 @@ module.exports = {
   keyHForm: (key) => native().keyHForm(key),
   keyCacheStats: () => Object.assign({ shardedLastForm: addon ? native().shardedLastForm() : { form: "none", reason: "", hForm: "none", hReason: "" } }, { entries: keyCache.size, handles: Array.from(keyCache.values()).reduce((a, e) => a + Array.from(e.entries()).reduce((b, [k, v]) => b + (k === "ref" || k === "src" ? 0 : Array.isArray(v) ? v.length : 1), 0), 0) }, keyCacheStats), clearKeyCache, keyFingerprint,
   _cacheEntry: cacheEntry,  // the cache's lookup alone (no device involved): tests/test_node_host.py
-  multiHash, multiHashBatch, buildBalanceTree, hashLeftRight, genPublicKey, formatPrivKeyForBabyJub, sign, verify, RollupCircuit, WithdrawCircuit,
+  multiHash, multiHashBatch, buildBalanceTree, hashLeftRight, genPublicKey, formatPrivKeyForBabyJub, sign, verify, ecdh, encrypt, decrypt, ecdhEncrypt, ecdhDecrypt, RollupCircuit, WithdrawCircuit,
   deviceCount: () => { native(); return deviceCount; },
   version: () => native().version(),
 };

@@ -44,6 +44,9 @@ static struct {
   int (*eddsa_sign)(const uint8_t *, const uint8_t *, size_t, uint8_t *);
   int (*eddsa_verify)(const uint8_t *, size_t, const uint8_t *, const uint8_t *, int *);
   int (*format_privkey)(const uint8_t *, uint8_t *);
+  int (*ecdh)(const uint8_t *, const uint8_t *, uint8_t *);
+  int (*mimc7_encrypt)(const uint8_t *, const uint8_t *, unsigned, uint8_t *, uint8_t *);
+  int (*mimc7_decrypt)(const uint8_t *, const uint8_t *, const uint8_t *, unsigned, uint8_t *);
   int (*multihash_batch)(const void *, size_t, unsigned, void *, int);
   int (*tree_build)(const void *, unsigned, void *, int);
   int (*withdraw_r1cs)(void **, size_t *);
@@ -130,7 +133,8 @@ static napi_value js_load(napi_env env, napi_callback_info info) {
     SYM(setup_r1cs, "zkr_setup_r1cs") SYM(key_save, "zkr_key_save") SYM(key_load_file, "zkr_key_load_file") SYM(key_check, "zkr_key_check") SYM(free_, "zkr_free")
     SYM(multihash, "zkr_mimcsponge_multihash") SYM(pubkey, "zkr_babyjub_pubkey") SYM(eddsa_sign, "zkr_eddsa_sign") SYM(eddsa_verify, "zkr_eddsa_verify")
     SYM(multihash_batch, "zkr_mimcsponge_multihash_batch") SYM(tree_build, "zkr_balance_tree_build")
-    SYM(format_privkey, "zkr_babyjub_format_privkey") SYM(withdraw_r1cs, "zkr_withdraw_r1cs") SYM(withdraw_witness, "zkr_withdraw_witness")
+    SYM(format_privkey, "zkr_babyjub_format_privkey") SYM(ecdh, "zkr_babyjub_ecdh") SYM(mimc7_encrypt, "zkr_mimc7_encrypt") SYM(mimc7_decrypt, "zkr_mimc7_decrypt")
+    SYM(withdraw_r1cs, "zkr_withdraw_r1cs") SYM(withdraw_witness, "zkr_withdraw_witness")
     SYM(rollup_info, "zkr_rollup_info") SYM(rollup_r1cs, "zkr_rollup_r1cs") SYM(rollup_witness, "zkr_rollup_witness")
     SYM(sharded_last_form, "zkr_prove_sharded_last_form") SYM(key_replication, "zkr_key_replication")
     SYM(key_contribute, "zkr_key_contribute") SYM(contribution_check, "zkr_contribution_check") SYM(vk_contribute, "zkr_vk_contribute")
@@ -786,7 +790,9 @@ static napi_value js_verify(napi_env env, napi_callback_info info) {
 
 /* ---- the rollup circuit without circom / snarkjs (include/zkr.h); all synchronous host work ---- */
 /* rollupCrypto(op, a, b, c): op 0 multiHash(values) -> 32 B; 1 pubKey(priv32) -> 64 B; 2 sign(priv32, msg) -> 96 B;
- * 3 verify(msg, sig96, pub64) -> boolean; 4 formatPrivKeyForBabyJub(priv32) -> 32 B.  Field elements are 32 B little-endian (operator/src/utils/crypto.ts). */
+ * 3 verify(msg, sig96, pub64) -> boolean; 4 formatPrivKeyForBabyJub(priv32) -> 32 B; 5 ecdh(priv32, pub64) -> 32 B;
+ * 6 encrypt(key32, msg) -> iv, then the elements (32 B each, integers below 2r); 7 decrypt(key32, iv32, elements) -> msg.
+ * Field elements are 32 B little-endian (operator/src/utils/crypto.ts). */
 static napi_value js_rollup_crypto(napi_env env, napi_callback_info info) {
   size_t argc = 4;
   napi_value argv[4];
@@ -825,6 +831,26 @@ static napi_value js_rollup_crypto(napi_env env, napi_callback_info info) {
       if (al != 32) return throw_msg(env, "formatPrivKeyForBabyJub: the private key is 32 bytes");
       rc = Z.format_privkey(a, out), out_len = 32;
       break;
+    case 5:
+      if (al != 32 || bl != 64) return throw_msg(env, "ecdh: 32-byte private key, 64-byte public key");
+      rc = Z.ecdh(a, b, out), out_len = 32;
+      break;
+    case 6:
+    case 7: {  /* as long as the message: the result goes into a buffer of its own */
+      const uint8_t *elems = op == 6 ? b : c;
+      const size_t el = op == 6 ? bl : cl;
+      if (al != 32 || el % 32 || el / 32 > 65536 || (op == 7 && bl != 32)) return throw_msg(env, "encrypt / decrypt: 32-byte key (and iv), up to 65536 elements of 32 bytes");
+      const size_t head = op == 6 ? 32 : 0;
+      uint8_t *big = (uint8_t *)malloc(head + el + 1);
+      if (!big) return throw_msg(env, "out of memory");
+      rc = op == 6 ? Z.mimc7_encrypt(a, elems, (unsigned)(el / 32), big, big + 32) : Z.mimc7_decrypt(a, b, elems, (unsigned)(el / 32), big);
+      if (rc) { free(big); return throw_msg(env, Z.last_error()); }
+      void *big_copy;
+      napi_status st = napi_create_buffer_copy(env, head + el, big, &big_copy, &res);
+      free(big);
+      NAPI_OK(st);
+      return res;
+    }
     default:
       return throw_msg(env, "rollupCrypto: unknown operation");
   }

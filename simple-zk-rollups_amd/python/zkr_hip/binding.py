@@ -197,6 +197,17 @@ def lib():
     L.zkr_withdraw_statement_text.argtypes = [c.c_uint32]
     L.zkr_withdraw_statement_text.restype = c.c_char_p
     L.zkr_withdraw_n_vars.argtypes = []
+    L.zkr_mimc7_round_constants.argtypes = [u8p]
+    L.zkr_mimc7_hash.argtypes = [u8p, u8p, u8p]
+    L.zkr_mimc7_multihash.argtypes = [u8p, sz, u8p, u8p]
+    L.zkr_babyjub_ecdh.argtypes = [u8p, u8p, u8p]
+    L.zkr_mimc7_encrypt.argtypes = [u8p, u8p, c.c_uint, u8p, u8p]
+    L.zkr_mimc7_decrypt.argtypes = [u8p, u8p, u8p, c.c_uint, u8p]
+    L.zkr_babyjub_ecdh_batch.argtypes = [u8p, u8p, sz, u8p, i]
+    L.zkr_mimc7_encrypt_batch.argtypes = [u8p, u8p, c.c_uint, sz, u8p, u8p, i]
+    L.zkr_mimc7_decrypt_batch.argtypes = [u8p, u8p, u8p, c.c_uint, sz, u8p, i]
+    L.zkr_ecdh_encrypt_batch.argtypes = [u8p, u8p, u8p, c.c_uint, sz, u8p, u8p, i]
+    L.zkr_ecdh_decrypt_batch.argtypes = [u8p, u8p, u8p, u8p, c.c_uint, sz, u8p, i]
     L.zkr_withdraw_n_vars.restype = c.c_uint32
     L.zkr_ledger_new.argtypes = [c.c_uint, i, c.POINTER(vp)]
     L.zkr_ledger_free.argtypes = [vp]

@@ -21,6 +21,7 @@ R = 2188824287183927522224640574525727508854836440041603434369820418657580849561
 WPROG_MAGIC, WPROG_VERSION = 0x50574B5A, 1
 OP_CONST, OP_ADD, OP_SUB, OP_MUL, OP_INV0, OP_BIT, OP_ASSERT_ZERO = 1, 2, 3, 4, 5, 6, 7
 MIMC_ROUNDS = 220   # hasher.circom:8
+BJ_A, BJ_D = 168700, 168696   # BabyJub: a x^2 + y^2 = 1 + d x^2 y^2
 
 
 class Signal:
@@ -75,6 +76,48 @@ class LC:
 
     def key(self):
         return tuple(sorted((s.uid, v) for s, v in self.terms.items()))
+
+
+class Hint:
+    """A value that lives on a wire of the program and is NO signal: what circom computes with `<--` before it names the result.
+    Lifted from a linear combination (Circuit.hint), it combines with +, -, * and inv() -- ADD, SUB, MUL and INV0 on the program
+    side, nothing on the constraint side -- and Circuit.witness makes it a signal.  Immutable."""
+    __slots__ = ("c", "wire")
+
+    def __init__(self, circuit, wire):
+        self.c, self.wire = circuit, wire
+
+    def _lift(self, o):
+        if isinstance(o, Hint):
+            if o.c is not self.c:
+                raise ValueError("hint values of two circuits")
+            return o
+        return self.c.hint(o)
+
+    def _op(self, op, a, b):
+        return Hint(self.c, self.c._emit(op, a.wire, b.wire))
+
+    def __add__(self, o):
+        return self._op(OP_ADD, self, self._lift(o))
+
+    def __radd__(self, o):
+        return self._op(OP_ADD, self._lift(o), self)
+
+    def __sub__(self, o):
+        return self._op(OP_SUB, self, self._lift(o))
+
+    def __rsub__(self, o):
+        return self._op(OP_SUB, self._lift(o), self)
+
+    def __mul__(self, o):
+        return self._op(OP_MUL, self, self._lift(o))
+
+    def __rmul__(self, o):
+        return self._op(OP_MUL, self._lift(o), self)
+
+    def inv(self):
+        """0 for 0, the inverse otherwise (INV0)"""
+        return Hint(self.c, self.c._emit(OP_INV0, self.wire))
 
 
 class Circuit:
@@ -210,6 +253,18 @@ class Circuit:
     def hint_inv0(self, a, name=None):
         """a new signal: 0 for 0, the inverse of a otherwise.  No constraint: the caller adds them (gadgets.is_zero)."""
         return self._internal(self._emit(OP_INV0, self._wire(self.const(0) + a)), name)
+
+    def hint(self, lc):
+        """the value of a linear combination (or a number) as a Hint: computed by the program, unknown to the constraints"""
+        if isinstance(lc, Hint):
+            return lc
+        return Hint(self, self._wire(self.const(0) + lc))
+
+    def witness(self, value, name=None):
+        """a new signal that takes a Hint's value, with no constraint (circom's `<--`): the caller adds them"""
+        if not isinstance(value, Hint) or value.c is not self:
+            raise ValueError("witness takes a hint value of this circuit")
+        return self._internal(value.wire, name)
 
     def _statement(self, text):
         self.statements.append(text)
@@ -371,6 +426,109 @@ class gadgets:
         c.assert_zero(root - gadgets.merkle_root(c, leaf, path_elements, path_index_bits), "the leaf is in the tree with this root")
 
 
+    # ---- BabyJub (circomlib babyjub.circom, escalarmulany.circom)
+    @staticmethod
+    def babyjub_check(c, p, text):
+        """BabyCheck: a x^2 + y^2 = 1 + d x^2 y^2, a statement the program checks and reports with `text`"""
+        x, y = p
+        x2, y2 = c.mul(x, x), c.mul(y, y)
+        c.constrain(x2 * BJ_D, y2, x2 * BJ_A + y2 - 1, text=text)
+
+    @staticmethod
+    def babyjub_add(c, p, q, known=None):
+        """BabyAdd's six constraints: beta = x1 y2, gamma = y1 x2, delta = (-a x1 + y1)(x2 + y2), tau = beta gamma,
+        (1 + d tau) x3 = beta + gamma, (1 - d tau) y3 = delta + a beta - gamma.  The law is complete on the curve: no exceptional
+        cases.  x3 and y3 are values the program computes: `known` = their Hints where the caller has them already (a chain that
+        inverts once for all its points); otherwise one INV0 here for the two denominators."""
+        (x1, y1), (x2, y2) = p, q
+        beta, gamma = c.mul(x1, y2), c.mul(y1, x2)
+        delta = c.mul(y1 - (c.const(0) + x1) * BJ_A, (c.const(0) + x2) + y2)
+        tau = c.mul(beta, gamma)
+        dx, dy = tau * BJ_D + 1, 1 - tau * BJ_D
+        nx, ny = beta + gamma, delta + beta * BJ_A - gamma
+        if known is None:
+            hx, hy = c.hint(dx), c.hint(dy)
+            i = (hx * hy).inv()
+            known = (c.hint(nx) * (i * hy), c.hint(ny) * (i * hx))
+        x3, y3 = c.witness(known[0]), c.witness(known[1])
+        c.constrain(dx, x3, nx)
+        c.constrain(dy, y3, ny)
+        return x3, y3
+
+    @staticmethod
+    def babyjub_dbl(c, p, known=None):
+        return gadgets.babyjub_add(c, p, p, known)
+
+    @staticmethod
+    def _proj_add(p, q):
+        """add-2008-bbjlp on hint values (X : Y : Z)"""
+        (x1, y1, z1), (x2, y2, z2) = p, q
+        a = z1 * z2
+        b, cc, d = a * a, x1 * x2, y1 * y2
+        e = (cc * d) * BJ_D
+        f, g = b - e, b + e
+        return (a * f) * ((x1 + y1) * (x2 + y2) - cc - d), (a * g) * (d - cc * BJ_A), f * g
+
+    @staticmethod
+    def _proj_dbl(p):
+        """dbl-2008-bbjlp on hint values"""
+        x, y, z = p
+        s = x + y
+        b, cc, d = s * s, x * x, y * y
+        e = cc * BJ_A
+        f, h = e + d, z * z
+        j = f - (h + h)
+        return (b - cc - d) * j, f * (e - d), f * j
+
+    @staticmethod
+    def _affine_all(c, pts):
+        """affine Hints of projective hint points with ONE inversion (Montgomery's trick): prefix products, INV0, the walk back"""
+        prefix, run = [], c.hint(1)
+        for _, _, z in pts:
+            prefix.append(run)
+            run = run * z
+        ia, out = run.inv(), [None] * len(pts)
+        for k in range(len(pts) - 1, -1, -1):
+            x, y, z = pts[k]
+            zi = ia * prefix[k]
+            ia = ia * z
+            out[k] = (x * zi, y * zi)
+        return out
+
+    @staticmethod
+    def escalar_mul_any(c, bits, p, text="the point is on the curve"):
+        """e * p for e = sum of bits[i] 2^i (bits: boolean signals, least significant first) and any point p of the curve:
+        babyjub_check on p first (an off-curve p is a reported statement), then double-and-add -- per bit a doubling of 2^i p, an
+        addition to the running sum and an arithmetic select of the two coordinates, 14 constraints.  The witness side never
+        divides per step: it walks the same points in projective coordinates on hint values and inverts all their Z at once.  On
+        the curve no Z is 0; off it the instance has failed its statement and is zeroed whatever the hints hold."""
+        p = (c.const(0) + p[0], c.const(0) + p[1])
+        gadgets.babyjub_check(c, p, text)
+        n = len(bits)
+        # the program's own walk: Q_i = 2^i p, S_i = A_{i-1} + Q_i, A_i = bits[i] ? S_i : A_{i-1}
+        one = c.hint(1)
+        q = (c.hint(p[0]), c.hint(p[1]), one)
+        b0 = c.hint(bits[0])
+        acc = (b0 * q[0], b0 * (q[1] - 1) + 1, one)
+        doubles, sums = [], []
+        for i in range(1, n):
+            q = gadgets._proj_dbl(q)
+            s = gadgets._proj_add(acc, q)
+            b = c.hint(bits[i])
+            acc = tuple(b * (sv - av) + av for sv, av in zip(s, acc))
+            doubles.append(q)
+            sums.append(s)
+        aff = gadgets._affine_all(c, doubles + sums)
+        # the constraints, over signals that take those values
+        qa = p
+        ax, ay = c.mul(bits[0], p[0]), c.mul(bits[0], p[1] - 1, add=1)
+        for i in range(1, n):
+            qa = gadgets.babyjub_dbl(c, qa, known=aff[i - 1])
+            sx, sy = gadgets.babyjub_add(c, (ax, ay), qa, known=aff[n - 1 + i - 1])
+            ax, ay = gadgets.select(c, bits[i], sx, ax), gadgets.select(c, bits[i], sy, ay)
+        return ax, ay
+
+
 # ---- the reference's wrapper circuits (prover/__tests__/circuits/*_test.circom), as this builder states them
 def Hasher(length):
     """inputs in[length], key; output hash"""
@@ -408,4 +566,17 @@ def MerkleTreeLeafExists(depth):
     pes = [c.private_input("pathElements[%d]" % i) for i in range(depth)]
     idx = [c.private_input("pathIndexes[%d]" % i) for i in range(depth)]
     gadgets.leaf_exists(c, leaf, pes, idx, root)
+    return c
+
+
+def Ecdh():
+    """prover/circuits/ecdh.circom:6-27: inputs publicKey[0..1] | privateKey (private, the FORMATTED key); output sharedKey, the x
+    coordinate of privateKey * publicKey"""
+    c = Circuit()
+    out = c.output("sharedKey")
+    pub = [c.public_input("publicKey[%d]" % i) for i in range(2)]
+    priv = c.private_input("privateKey")
+    bits = gadgets.num2bits(c, priv, 253, "private key fits 253 bits")
+    x, _ = gadgets.escalar_mul_any(c, bits, pub, "public key is on the curve")
+    c.assign(out, x)
     return c

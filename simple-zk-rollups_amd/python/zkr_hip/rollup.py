@@ -169,6 +169,160 @@ def wallet_sign_program_host(priv, msg):
     return {"R8": (v[0], v[1]), "S": v[2]}
 
 
+# ---- ecdh and the MiMC7 cipher (crypto.ts:86-141; csrc/zkr_crypto.hip over csrc/crypto_program.hpp)
+def _les(values):
+    """32-byte little-endian forms of integers in 0 .. 2^256 - 1 (what the C side then range-checks), joined."""
+    values = [int(v) for v in values]
+    if any(v < 0 or v >> 256 for v in values):
+        raise ZkrError(-5, "a value outside 0 .. 2^256 - 1")
+    return b"".join(_le(v) for v in values)
+
+
+def _pubs_bytes(pubs, n):
+    pubs = [tuple(p) for p in pubs]
+    if len(pubs) != n or any(len(p) != 2 for p in pubs):
+        raise ZkrError(-5, "%d public keys of two coordinates for %d private keys" % (len(pubs), n))
+    return _les(v for p in pubs for v in p)
+
+
+def _rows_bytes(rows, n, what):
+    """n equally long, non-empty rows of elements -> (arity, bytes); anything else is ZkrError(-5) before a launch."""
+    rows = [list(r) for r in rows]
+    if len(rows) != n:
+        raise ZkrError(-5, "%d %s for %d keys" % (len(rows), what, n))
+    arity = len(rows[0]) if rows else 0
+    for t, r in enumerate(rows):
+        if len(r) != arity:
+            raise ZkrError(-5, "item %d: %d elements where item 0 has %d (one arity per call)" % (t, len(r), arity))
+    return arity, _les(v for r in rows for v in r)
+
+
+def _encrypted_rows(ivs, buf, arity):
+    v = _ints(buf)
+    return [{"iv": iv, "msg": v[t * arity:(t + 1) * arity]} for t, iv in enumerate(ivs)]
+
+
+def mimc7_round_constants():
+    """The 91 round constants of MiMC7 as integers (zkr_mimc7_round_constants, host only); c_0 = 0."""
+    out = ctypes.create_string_buffer(32 * 91)
+    _check(lib().zkr_mimc7_round_constants(out))
+    return _ints(out.raw)
+
+
+def mimc7_hash(x, k) -> int:
+    """circomlib mimc7.hash(x, k): 91 rounds of x -> x^7.  Operands not below r are ZkrError(-5)."""
+    out = ctypes.create_string_buffer(32)
+    _check(lib().zkr_mimc7_hash(_les([x]), _les([k]), out))
+    return int.from_bytes(out.raw, "little")
+
+
+def mimc7_multi_hash(values, key=0) -> int:
+    """circomlib mimc7.multiHash(arr, key)."""
+    values = list(values)
+    out = ctypes.create_string_buffer(32)
+    _check(lib().zkr_mimc7_multihash(_les(values), len(values), _les([key]), out))
+    return int.from_bytes(out.raw, "little")
+
+
+def ecdh(priv, pub) -> int:
+    """ecdh(priv, pub) (crypto.ts:86-93): the x coordinate of formatPrivKeyForBabyJub(priv) * pub.  A public key that is not
+    on the curve is ZkrError(-5): the reference multiplies whatever it is given."""
+    out = ctypes.create_string_buffer(32)
+    _check(lib().zkr_babyjub_ecdh(_les([priv]), _pubs_bytes([pub], 1), out))
+    return int.from_bytes(out.raw, "little")
+
+
+def encrypt(msg, key):
+    """encrypt(msg, key) (crypto.ts:95-110) -> {"iv": int, "msg": [int, ...]}, the shape of EncryptedMessage
+    (types/primitives.ts:40).  Each element is the INTEGER msg[i] + hash(key, iv + i), below 2r."""
+    arity, mb = _rows_bytes([msg], 1, "messages")
+    iv, out = ctypes.create_string_buffer(32), ctypes.create_string_buffer(32 * max(arity, 1))
+    _check(lib().zkr_mimc7_encrypt(_les([key]), mb, arity, iv, out))
+    return _encrypted_rows(_ints(iv.raw), out.raw, arity)[0]
+
+
+def decrypt(enc, key):
+    """decrypt({iv, msg}, key) (crypto.ts:112-123) -> the message; ciphertext elements below 2r."""
+    arity, eb = _rows_bytes([enc["msg"]], 1, "messages")
+    out = ctypes.create_string_buffer(32 * max(arity, 1))
+    _check(lib().zkr_mimc7_decrypt(_les([key]), _les([enc["iv"]]), eb, arity, out))
+    return _ints(out.raw)[:arity]
+
+
+def ecdh_encrypt(msg, priv, pub):   # crypto.ts:125-132
+    return encrypt(msg, ecdh(priv, pub))
+
+
+def ecdh_decrypt(enc, priv, pub):   # crypto.ts:134-141
+    return decrypt(enc, ecdh(priv, pub))
+
+
+def ecdh_batch(privs, pubs, device=0):
+    """ecdh for many (private key, public key) pairs on the GPU, one thread each (zkr_babyjub_ecdh_batch): the shared keys,
+    each what `ecdh` returns.  Refusals as `ecdh`'s, naming the first offending item, before anything is launched."""
+    privs = list(privs)
+    kb, pb = _les(privs), _pubs_bytes(pubs, len(privs))
+    if not privs:
+        return []
+    out = ctypes.create_string_buffer(32 * len(privs))
+    _check(lib().zkr_babyjub_ecdh_batch(kb, pb, len(privs), out, device))
+    return _ints(out.raw)
+
+
+def encrypt_batch(keys, msgs, device=0):
+    """encrypt for many (key, message) pairs of ONE arity on the GPU (zkr_mimc7_encrypt_batch): one thread per message for the
+    iv, one per message element for the keystream.  A list of {"iv", "msg"}, each what `encrypt` returns."""
+    keys = list(keys)
+    kb = _les(keys)
+    arity, mb = _rows_bytes(msgs, len(keys), "messages")
+    if not keys:
+        return []
+    ivs, out = ctypes.create_string_buffer(32 * len(keys)), ctypes.create_string_buffer(32 * len(keys) * max(arity, 1))
+    _check(lib().zkr_mimc7_encrypt_batch(kb, mb, arity, len(keys), ivs, out, device))
+    return _encrypted_rows(_ints(ivs.raw), out.raw, arity)
+
+
+def decrypt_batch(keys, encs, device=0):
+    """decrypt for many (key, {"iv", "msg"}) pairs of one arity on the GPU (zkr_mimc7_decrypt_batch): the messages."""
+    keys, encs = list(keys), list(encs)
+    kb = _les(keys)
+    arity, eb = _rows_bytes([e["msg"] for e in encs], len(keys), "messages")
+    ib = _les(e["iv"] for e in encs)
+    if not keys:
+        return []
+    out = ctypes.create_string_buffer(32 * len(keys) * max(arity, 1))
+    _check(lib().zkr_mimc7_decrypt_batch(kb, ib, eb, arity, len(keys), out, device))
+    v = _ints(out.raw)
+    return [v[t * arity:(t + 1) * arity] for t in range(len(keys))]
+
+
+def ecdh_encrypt_batch(privs, pubs, msgs, device=0):
+    """ecdhEncrypt (crypto.ts:125-132) for many items on the GPU (zkr_ecdh_encrypt_batch): the shared keys are computed and used
+    on the device and never reach the host."""
+    privs = list(privs)
+    kb, pb = _les(privs), _pubs_bytes(pubs, len(privs))
+    arity, mb = _rows_bytes(msgs, len(privs), "messages")
+    if not privs:
+        return []
+    ivs, out = ctypes.create_string_buffer(32 * len(privs)), ctypes.create_string_buffer(32 * len(privs) * max(arity, 1))
+    _check(lib().zkr_ecdh_encrypt_batch(kb, pb, mb, arity, len(privs), ivs, out, device))
+    return _encrypted_rows(_ints(ivs.raw), out.raw, arity)
+
+
+def ecdh_decrypt_batch(privs, pubs, encs, device=0):
+    """ecdhDecrypt (crypto.ts:134-141) for many items on the GPU (zkr_ecdh_decrypt_batch): the messages."""
+    privs, encs = list(privs), list(encs)
+    kb, pb = _les(privs), _pubs_bytes(pubs, len(privs))
+    arity, eb = _rows_bytes([e["msg"] for e in encs], len(privs), "messages")
+    ib = _les(e["iv"] for e in encs)
+    if not privs:
+        return []
+    out = ctypes.create_string_buffer(32 * len(privs) * max(arity, 1))
+    _check(lib().zkr_ecdh_decrypt_batch(kb, pb, ib, eb, arity, len(privs), out, device))
+    v = _ints(out.raw)
+    return [v[t * arity:(t + 1) * arity] for t in range(len(privs))]
+
+
 def tx_row(frm, to, amount, fee, nonce, sig):
     """The txData row of batchprocesstx.circom for one signed transaction: from to amount fee nonce R8x R8y S."""
     return [frm, to, amount, fee, nonce, sig["R8"][0], sig["R8"][1], sig["S"]]
